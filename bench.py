@@ -23,6 +23,18 @@ solves the whole problem (dp_policy "replicate": the SMO iteration is a latency
 chain and sharding adds a cross-device hop to each of its ~10^5 iterations);
 then one untimed sharded solve runs first and its time, iterations and b are
 reported as "shard_check" (docs/DESIGN.md, Multi-GPU).
+
+A plain run (--gpus 1 --steps K --warmup W) does what the headline figure
+needs and no more: setup, W warmup solves, the K timed solves, the JSON line
+(ms_per_step = milliseconds per timed solve).  --full adds everything else the
+record can carry, untimed, after the timed solves: the training accuracy of
+the timed model, the pair-at-a-time engine's solve of the same problem
+("reference_check") and the structured mnist-parity problem ("secondary");
+--reference-check off / --secondary off / --no-accuracy drop single parts of
+it.  (N > 1: the policy measurement above picks the timed path, so it stays.)
+--dump-outputs DIR writes what the last timed solve returned (alpha, b) as
+DIR/<name>.npy; the inputs are seeded, so two builds given the same arguments
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -59,6 +71,11 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed extras: training accuracy, the "
+                         "reference_check solve and the secondary problem (a plain run skips them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (alpha, b) as DIR/<name>.npy")
     ap.add_argument("--config", default="mnist", choices=sorted(PRESETS),
                     help="preset (BASELINE.json configs; explicit flags override)")
     ap.add_argument("--data", default=None, help="synthetic generator (mnist = BASELINE headline shape)")
@@ -91,7 +108,7 @@ def parse(argv=None):
                          "policies are timed once on this node and the timed runs use the faster; measure: "
                          "that measured choice whatever the shape-based policy says)")
     ap.add_argument("--secondary", default="auto", choices=["auto", "off"],
-                    help="headline config at N=1: also record the structured mnist-parity problem (untimed for the headline)")
+                    help="--full, headline config at N=1: also record the structured mnist-parity problem (untimed for the headline)")
     ap.add_argument("--shard-check", default="auto", choices=["auto", "off"],
                     help="N > 1 with a replicated timed solve: one untimed sharded solve first (cross-device "
                          "exchange evidence: its time, iterations and b go into the JSON line)")
@@ -100,7 +117,7 @@ def parse(argv=None):
                          "(the reference's pair rule on q-row sub-problems in LDS, the reference's stop test on "
                          "the exact gradient), else the pair-at-a-time engines; ws / smo force one of them")
     ap.add_argument("--reference-check", default="auto", choices=["auto", "off"],
-                    help="auto: when the timed solve ran ws-dense, one untimed solve by the pair-at-a-time engine (the reference's "
+                    help="--full: when the timed solve ran ws-dense, one untimed solve by the pair-at-a-time engine (the reference's "
                          "trajectory) after the timed runs; its time, iterations, b, support vectors and the "
                          "decision agreement with the timed model go into the JSON line")
     ap.add_argument("--ws-size", type=int, default=192)
@@ -140,7 +157,7 @@ def parse(argv=None):
     ap.add_argument("--xch-mem", default="auto", choices=["auto", "uncached", "coarse"])
     ap.add_argument("--xch-timeout", type=float, default=None,
                     help="give-up bound of one in-kernel exchange poll (default 30 s at N > 1, else 120 s)")
-    ap.add_argument("--no-accuracy", action="store_true")
+    ap.add_argument("--no-accuracy", action="store_true", help="--full without the training accuracy")
     ap.add_argument("--log-every", type=int, default=0,
                     help="rank 0 prints b_hi / b_lo / gap every N pair steps (long big-config runs)")
     ap.add_argument("--verbose", action="store_true", help="solver diagnostics on stderr (engine, shrink phases)")
@@ -237,6 +254,30 @@ def spawn_ranks(a, argv) -> int:
     return 0
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, arrays) -> None:
+    """Write each array as <dirname>/<name>.npy in float32 (float64 stays
+    float64).  Past DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded
+    sample of its flattened elements (the same indices for the same shapes)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        arrs[name] = np.ascontiguousarray(v if v.dtype == np.float64 else v.astype(np.float32))
+    total = sum(v.nbytes for v in arrs.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrs)  # room for the .npy headers
+    for name, v in arrs.items():
+        if total > budget:
+            keep = max(1, int(v.size * (budget / total)))
+            idx = np.sort(np.random.default_rng(0).choice(v.size, size=keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
 def main(argv=None) -> int:
     raw_argv = list(sys.argv[1:] if argv is None else argv)
     a = parse(raw_argv)
@@ -244,6 +285,8 @@ def main(argv=None) -> int:
         return spawn_ranks(a, raw_argv)
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -418,7 +461,7 @@ def main(argv=None) -> int:
     sync()
     barrier()
     elapsed = time.perf_counter() - t0
-    per_run = elapsed / max(1, a.steps)
+    per_run = elapsed / a.steps
     solve_s = [r[1]["t_solve"] for r in results]
     t = torch.tensor([per_run, max(solve_s), min(solve_s)], dtype=torch.float64)
     if n_ranks > 1:
@@ -427,12 +470,14 @@ def main(argv=None) -> int:
         t[2] = -t[2]
     per_run, solve_max, solve_min = t.tolist()
     alpha, res = results[-1]
+    if a.dump_outputs and ctx.rank == 0:
+        dump_outputs(a.dump_outputs, {"alpha": alpha, "b": [res["b"]]})
     acc = None
-    if not a.no_accuracy and on_gpu and solver is not None:
+    if a.full and not a.no_accuracy and on_gpu and solver is not None:
         acc = float(solver.train_accuracy(alpha, res["b"]))
     nsv = int((alpha > 0).sum())
     ref_check = None
-    if (on_gpu and a.solver != "smo" and a.reference_check == "auto" and info.get("iteration") == "ws-dense"
+    if (a.full and on_gpu and a.solver != "smo" and a.reference_check == "auto" and info.get("iteration") == "ws-dense"
             and (n_ranks == 1 or info.get("dp_policy") == "replicate")):
         rows = np.arange(0, X.shape[0], max(1, X.shape[0] // 4096))
         d_ws = np.asarray(solver.decision(alpha, res["b"], X[rows]))
@@ -457,7 +502,7 @@ def main(argv=None) -> int:
 
     secondary = None
     headline_cfg = a.config == "mnist" and a.data == "mnist" and a.samples == 60000 and a.features == 784
-    if on_gpu and n_ranks == 1 and headline_cfg and a.secondary == "auto" and ctx.rank == 0:
+    if a.full and on_gpu and n_ranks == 1 and headline_cfg and a.secondary == "auto" and ctx.rank == 0:
         # the headline data is degenerate (K ~ I: every row a support vector); the
         # structured MNIST-shape problem of the same size and parameters
         # (mnist-parity: digit-like prototypes, label = parity) rides along in the
@@ -522,6 +567,7 @@ def main(argv=None) -> int:
             "n_gpus": n_ranks,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": round(per_run * 1000.0, 3),
             "higher_is_better": False,
             "scaling": "strong",

@@ -21,7 +21,7 @@ while IFS='|' read -r label args envs; do
   case "$label" in \#*) continue ;; esac
   log="gpurun_out/ab_${TAG}_${label}.log"
   # shellcheck disable=SC2086
-  timeout -k 10 "$LIMIT" env $envs python -u bench.py $args > "$log" 2>&1
+  timeout -k 10 "$LIMIT" env $envs python -u bench.py --full $args > "$log" 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then
     echo "$label FAILED rc=$rc" | tee -a "$out"

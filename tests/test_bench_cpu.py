@@ -21,6 +21,50 @@ def test_bench_json_contract():
     assert out["vs_baseline"] is None and "1500x" in out["metric"]
 
 
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """--dump-outputs DIR: the last timed solve's alpha and b as float .npy
+    files, identical from run to run (seeded inputs); --steps sets the number
+    of timed solves and ms_per_step is the time of one; --full is recorded."""
+    import numpy as np
+
+    outs = []
+    for tag, steps, extra in (("a", 1, []), ("b", 3, ["--full"])):
+        d = str(tmp_path / tag)
+        r = run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu", "--samples", "600",
+                 "--steps", str(steps), "--warmup", "0", "--dump-outputs", d] + extra)
+        assert r.returncode == 0, r.stderr
+        out = json.loads([l for l in r.stdout.strip().split("\n") if l.startswith("{")][-1])
+        assert out["steps"] == steps and out["full"] is bool(extra)
+        assert out["unit"] == "s" and abs(out["ms_per_step"] - 1000.0 * out["value"]) < 1e-3
+        assert sorted(os.listdir(d)) == ["alpha.npy", "b.npy"]
+        alpha, b = np.load(os.path.join(d, "alpha.npy")), np.load(os.path.join(d, "b.npy"))
+        assert alpha.dtype in (np.float32, np.float64) and alpha.shape == (600,)
+        assert b.dtype in (np.float32, np.float64) and b.shape == (1,) and float(b[0]) == out["b"]
+        assert int((alpha > 0).sum()) == out["n_sv"]
+        outs.append((alpha, b))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """Past the size limit every array keeps the same seeded sample."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.DUMP_LIMIT_BYTES = 1 << 16
+    big = np.arange(100000, dtype=np.float32)
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), {"alpha": big, "b": [0.5]})
+    files = [tmp_path / t / n for t in ("a", "b") for n in ("alpha.npy", "b.npy")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= 1 << 16
+    a, b = np.load(files[0]), np.load(files[2])
+    assert a.dtype == np.float32 and 1 < a.size < big.size and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.load(files[1]).dtype == np.float64
+
+
 def test_graft_entry_build():
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge

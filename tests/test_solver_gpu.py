@@ -151,7 +151,7 @@ def test_bench_gpu_small():
     import subprocess
 
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--samples", "8000", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr
     out = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])
     assert out["converged"] and out["n_gpus"] == 1 and out["train_accuracy"] > 0.99

@@ -130,15 +130,34 @@ void split_rows_f16(const float* x, int64_t rows, int dp, int ldx, void* out, in
 // 4 persistent LDS-DMA
 int split_gemm_variant();
 void set_split_gemm_variant(int v);
-// diagnostics: per-workgroup s_memtime stamps of the wide-wave Gram kernel (nullptr: off)
+// diagnostics: per-workgroup s_memtime stamps of the wide-wave Gram kernel (nullptr: off; 8 words a tile).  The
+// adaptive Gram stamps its one-product pass instead: 16 words a tile of the pass (bench/gram_overlap_stamps.py)
 void set_gram_stamps(uint64_t* p);
 void set_rows_stamps(uint64_t* p);  // diagnostics: the LDS-DMA rows kernel's per-workgroup stamps (0: off)
 // cold_tau > 0: the adaptive Gram (docs/DESIGN.md §13) — a one-product pass, then the tiles holding an element
 // split_cold rejects recomputed with all three products; every stored value within cold_tau of the three-product
 // one.  Falls back to the three-product kernel where the persistent wide-wave path does not apply.
+// The symmetric adaptive Gram's operand prep that depends on the rows alone (h planes, R = log2 |x|) and its
+// hot-tile buffer, built once for rows that stay put (a solver's X) instead of by every call: gram_adapt_prep
+// allocates and fills it from split rows A / |x|^2 Asq (stream-ordered; false and nothing allocated where the
+// adaptive pass cannot take the shape), gram_adapt_prep_free releases it.
+struct GramAdaptPrep {
+  const void* A = nullptr;  // the split rows it was built from
+  int64_t M = 0;
+  int dp = 0;
+  void* planes = nullptr;   // h planes of the 256-row tiles' rows
+  float* r = nullptr;       // log2 |x| [M]
+  uint32_t* hot = nullptr;  // [2 ntiles + 1]: per-tile reports, the hot list's length, its entries
+  int64_t ntiles = 0;
+  size_t bytes = 0;
+};
+bool gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, hipStream_t s, GramAdaptPrep* prep);
+void gram_adapt_prep_free(GramAdaptPrep* prep);
+// prep (symmetric adaptive Grams of prep's own rows only; else ignored): skip the per-call operand prep
 void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, int64_t M, const void* B,
                           const int32_t* Bsh, const float* Bsq, int64_t N, int dp, float gamma, float* out,
-                          int64_t ldo, hipStream_t s, bool symmetric = false, float cold_tau = 0.f);
+                          int64_t ldo, hipStream_t s, bool symmetric = false, float cold_tau = 0.f,
+                          const GramAdaptPrep* prep = nullptr);
 // split_cold's constants c0, c1 for gamma, tau (host; docs/DESIGN.md §13)
 void split_cold_consts(float gamma, float tau, float* c0, float* c1);
 // the calling thread's last adaptive Gram: tiles of the one-product pass and the hot ones recomputed (valid once

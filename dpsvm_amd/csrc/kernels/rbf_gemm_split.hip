@@ -1932,14 +1932,24 @@ __device__ __forceinline__ void h1_store_block(const f16v& v, int i, int j, int 
   }
 }
 
+__device__ __forceinline__ uint32_t clock_lo_v() {  // s_memtime's low word, in a vector register
+  uint32_t c = (uint32_t)__builtin_amdgcn_s_memtime();
+  asm volatile("" : "+v"(c));
+  return c;
+}
+
 // the h1s kernel's DMA waves (a function of its own: its uniform addressing
-// does not share the compute waves' scalar registers)
+// does not share the compute waves' scalar registers).  ST (diagnostics):
+// per tile, stamps[16 L + 8 ..] = the first wave's cycles at the barrier of
+// the tile's stage 0 (where it waits out the previous tile's epilogue), at
+// the other stages' barriers, waiting for its own DMA to land, and in all
+template <bool ST>
 __device__ __noinline__ void h1s_dma(const u4* __restrict__ A, const int32_t* __restrict__ Ash,
                                      const float* __restrict__ Asq, const float* __restrict__ Ar, int M,
                                      const u4* __restrict__ B, const int32_t* __restrict__ Bsh,
                                      const float* __restrict__ Bsq, const float* __restrict__ Br, int N, int nst,
                                      const uint32_t* __restrict__ tiles, int ntiles, int L, int dwave, int lane,
-                                     u4* lds, uint32_t* s_rows) {
+                                     u4* lds, uint32_t* s_rows, uint64_t* stamps) {
   constexpr int TM = 256, TN = 128, ROWS = TM + TN, NB = 3, RD = 1536;
   const int G = gridDim.x;
   const uint32_t rs = (uint32_t)nst * 8;
@@ -1990,18 +2000,39 @@ __device__ __noinline__ void h1s_dma(const u4* __restrict__ A, const int32_t* __
       const int m0 = (int)(t >> 16) * TM, n0 = (int)(t & 0xffffu) * TN;
       const uint32_t tp = has_next ? tn_next : t;
       const int nm0 = (int)(tp >> 16) * TM, nn0 = (int)(tp & 0xffffu) * TN;
+      uint32_t c_bar0 = 0, c_bar = 0, c_land = 0, c_t0 = 0;  // (the clock's low word)
+      if constexpr (ST) c_t0 = clock_lo_v();
 #pragma clang loop unroll(disable)
       for (int s = 0; s < nst; ++s) {
+        uint32_t ca = 0, cb = 0;
+        if constexpr (ST) ca = clock_lo_v();
         // stage s landed: younger are stage s + 1 (12 pieces) and, at s == 1, the next tile's row data (6)
         if (s == 1) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        if constexpr (ST) cb = clock_lo_v();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
+        if constexpr (ST) {
+          const uint32_t cc = clock_lo_v();
+          c_land += cb - ca;
+          if (s == 0) c_bar0 = cc - cb;
+          else c_bar += cc - cb;
+        }
         const bool own = s + 2 < nst;
         stage(own ? m0 : nm0, own ? n0 : nn0, own ? s + 2 : s + 2 - nst, (int)((g + 2) % NB));
         // the next tile's row data (the last tile reloads its own into the unused parity: the count stays 6)
         if (s == 0) rowdata(nm0, nn0, par ^ 1);
         ++g;
+      }
+      if constexpr (ST) {
+        const uint32_t c_t1 = clock_lo_v();
+        if (dw == 0 && lane == 0) {
+          uint64_t* o = stamps + (size_t)L * 16 + 8;
+          o[0] = c_bar0;
+          o[1] = c_bar;
+          o[2] = c_land;
+          o[3] = c_t1 - c_t0;
+        }
       }
       if (!has_next) break;
       L = Ln;
@@ -2014,13 +2045,15 @@ __device__ __noinline__ void h1s_dma(const u4* __restrict__ A, const int32_t* __
 }
 
 constexpr int kH1sThreads = 768;  // 8 compute waves + 4 DMA waves
-template <int ABL = 0>
+// ST (diagnostics, set_gram_stamps): 16 words a tile — the first compute wave's s_memtime at the tile's start,
+// stage 0 landed, k loop done, values done, stores issued, s_memrealtime at start / end, the tile; then h1s_dma's
+template <int ABL = 0, bool ST = false>
 __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
     const float* __restrict__ Ar, int M, const u4* __restrict__ B, const int32_t* __restrict__ Bsh,
     const float* __restrict__ Bsq, const float* __restrict__ Br, int N, int nkb, float gamma, float c0, float c1,
     float* __restrict__ out, int ldo, int sym, const uint32_t* __restrict__ tiles, int ntiles,
-    uint32_t* __restrict__ tile_hot, uint32_t* __restrict__ hot) {
+    uint32_t* __restrict__ tile_hot, uint32_t* __restrict__ hot, uint64_t* __restrict__ stamps) {
   constexpr int WN = 2, TM = 256, TN = 128, ROWS = TM + TN, CPR = 8, BUF = ROWS * CPR, NB = 3, RD = 1536;
   __shared__ u4 lds[NB * BUF + 2 * RD / 4];  // 3 operand buffers, then row data [2][RD]
   uint32_t* const s_rows = (uint32_t*)(lds + NB * BUF);
@@ -2030,7 +2063,7 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nst = (nkb + 1) >> 1;  // ring stages a tile (launcher: nkb >= 5)
   if (__builtin_amdgcn_readfirstlane(wave) >= 8) {
-    h1s_dma(A, Ash, Asq, Ar, M, B, Bsh, Bsq, Br, N, nst, tiles, ntiles, L, wave - 8, lane, lds, s_rows);
+    h1s_dma<ST>(A, Ash, Asq, Ar, M, B, Bsh, Bsq, Br, N, nst, tiles, ntiles, L, wave - 8, lane, lds, s_rows, stamps);
     return;
   }
   // ---- compute waves: the h1 kernel's 64 x 64 waves; never a load, so their stores drain unwaited ----
@@ -2043,10 +2076,18 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
   const int ra0 = (wm * 64 + (lane & 31)) * CPR;
   const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR;
   int par = 0;
+  // (stamps: the clocks' low words, each stored as it is read — none stays live over the k loop)
+  auto stamp = [&](int i, uint32_t v) {
+    if (tid == 0) stamps[(size_t)L * 16 + i] = v;
+  };
   while (true) {
     const bool has_next = Ln < ntiles;  // uniform
     const int tx = (int)(t >> 16), ty = (int)(t & 0xffffu);
     const int m0 = tx * TM, n0 = ty * TN;
+    if constexpr (ST) {
+      stamp(0, (uint32_t)__builtin_amdgcn_s_memtime());
+      stamp(5, (uint32_t)__builtin_amdgcn_s_memrealtime());
+    }
     f16v H[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -2054,11 +2095,12 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) H[i][j][r] = 0.f;
-#pragma clang loop unroll(disable)
-    for (int s = 0; s < nst; ++s) {
+    // FS: the tile's first stage (stamps)
+    auto stage = [&]<bool FS = false>() {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
+      if constexpr (ST && FS) stamp(1, (uint32_t)__builtin_amdgcn_s_memtime());
       const u4* buf = lds + (g % NB) * BUF;
       const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
       auto rd = [&](int q, h8& a0, h8& a1, h8& b0, h8& b1) {
@@ -2091,11 +2133,16 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3));
       mma(y0, y1, y2, y3);
       ++g;
-    }
+    };
+    if constexpr (ST) stage.template operator()<true>();
+#pragma clang loop unroll(disable)
+    for (int s = ST ? 1 : 0; s < nst; ++s) stage();
+    if constexpr (ST) stamp(2, (uint32_t)__builtin_amdgcn_s_memtime());
     int el = lane;
     asm volatile("" : "+v"(el));
     const float* rows = (const float*)(s_rows + par * RD);
     const bool hotw = h1_values(H, rows, (const int32_t*)(rows + ROWS), rows + 2 * ROWS, el, wm, wn, gamma, c0, c1);
+    if constexpr (ST) stamp(3, (uint32_t)__builtin_amdgcn_s_memtime());
     const bool mirror = sym && ty > 2 * tx + (wm >> 1);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -2109,6 +2156,11 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
         const uint32_t k = atomicAdd(hot, 1u);
         hot[1 + k] = t;
       }
+    }
+    if constexpr (ST) {
+      stamp(4, (uint32_t)__builtin_amdgcn_s_memtime());
+      stamp(6, (uint32_t)__builtin_amdgcn_s_memrealtime());
+      stamp(7, t);
     }
     if (!has_next) break;
     L = Ln;
@@ -2661,9 +2713,41 @@ void gram_adapt_last(int64_t* tiles, int64_t* hot) {
   *hot = t_adapt_tiles >= 0 && t_adapt_hot ? (int64_t)*(volatile uint32_t*)t_adapt_hot : -1;
 }
 
+bool gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, hipStream_t s, GramAdaptPrep* prep) {
+  *prep = GramAdaptPrep{};
+  const int nkb = (dp + 31) / 32;
+  const int64_t tm2 = (M + 255) / 256, tn = (M + 127) / 128;
+  // (rbf_gemm_store_split's conditions on the shape for the adaptive pass)
+  if (M <= 0 || nkb < 5 || tm2 >= 65536 || tn >= 65536 || (M + 512) * (int64_t)nkb * 8 >= (1ll << 31)) return false;
+  const int64_t ntiles = sym_tile_table(tm2, tn, s, true).count;
+  const int64_t nq = (int64_t)((nkb + 1) / 2) * 8, ra = tm2 * 256;
+  const size_t pb = (size_t)ra * nq * 16, rb = (size_t)M * 4, hb = (size_t)(2 * ntiles + 1) * 4;
+  HIP_CHECK(hipMalloc(&prep->planes, pb));
+  HIP_CHECK(hipMalloc((void**)&prep->r, rb));
+  HIP_CHECK(hipMalloc((void**)&prep->hot, hb));
+  prep->bytes = pb + rb + hb;
+  dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)A, ra, nkb,
+                                                                                    (dev::u4*)prep->planes);
+  post_launch("split_hplane", s);
+  dev::split_log2norm_kernel<<<dim3((unsigned)((M + 255) / 256)), 256, 0, s>>>(Asq, (int)M, prep->r);
+  post_launch("split_log2norm", s);
+  prep->A = A;
+  prep->M = M;
+  prep->dp = dp;
+  prep->ntiles = ntiles;
+  return true;
+}
+
+void gram_adapt_prep_free(GramAdaptPrep* prep) {
+  if (prep->planes) (void)hipFree(prep->planes);
+  if (prep->r) (void)hipFree(prep->r);
+  if (prep->hot) (void)hipFree(prep->hot);
+  *prep = GramAdaptPrep{};
+}
+
 void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, int64_t M, const void* B,
                           const int32_t* Bsh, const float* Bsq, int64_t N, int dp, float gamma, float* out,
-                          int64_t ldo, hipStream_t s, bool symmetric, float cold_tau) {
+                          int64_t ldo, hipStream_t s, bool symmetric, float cold_tau, const GramAdaptPrep* prep) {
   t_adapt_tiles = -1;
   if (M <= 0 || N <= 0) return;
   DPSVM_CHECK(!symmetric || (A == B && Asq == Bsq && Ash == Bsh && M == N && ldo % 4 == 0),
@@ -2735,7 +2819,7 @@ void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, i
     // 32 bits: they also take Grams of more than 2^32 elements (200k rows: 160 GB)
     const bool idx_adapt = (M + 512) * (int64_t)nkb * 8 < (1ll << 31) && (N + 512) * (int64_t)nkb * 8 < (1ll << 31) &&
                            ldo < (1ll << 22);
-    const bool adapt = pe && cold_tau > 0.f && gamma > 0.f && nkb >= 5 && !g_gram_stamps && nt == 0 && idx_adapt &&
+    const bool adapt = pe && cold_tau > 0.f && gamma > 0.f && nkb >= 5 && nt == 0 && idx_adapt &&
                        tm2 < 65536 && tn < 65536 && (!symmetric || compact) &&
                        (variant == 0 || variant == 7 || variant == 12);
     if (persist || adapt) {
@@ -2757,26 +2841,35 @@ void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, i
         // adaptive: pass 1 one-product over every tile, pass 2 three products over the reported ones
         float c0 = 0.f, c1 = 0.f;
         split_cold_consts(gamma, cold_tau, &c0, &c1);
+        // a solver's prep of these very rows: the h planes and R are there, the hot buffer is re-zeroed
+        const bool pre = prep && symmetric && prep->planes && prep->A == A && prep->M == M && prep->dp == dp &&
+                         prep->ntiles == ntiles;
         const int64_t nr = symmetric ? M : M + N;
-        float* r = nullptr;
-        uint32_t* hb = nullptr;  // [ntiles] per-tile reports, then the list's length and entries
-        HIP_CHECK(hipMallocAsync((void**)&r, (size_t)nr * 4, s));
-        HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * ntiles + 1) * 4, s));
-        HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(ntiles + 1) * 4, s));
-        dev::split_log2norm_kernel<<<dim3((unsigned)((M + 255) / 256)), 256, 0, s>>>(Asq, (int)M, r);
-        float* br = r;
-        if (!symmetric) {
-          br = r + M;
-          dev::split_log2norm_kernel<<<dim3((unsigned)((N + 255) / 256)), 256, 0, s>>>(Bsq, (int)N, br);
+        float* r = pre ? prep->r : nullptr;
+        uint32_t* hb = pre ? prep->hot : nullptr;  // [ntiles] per-tile reports, then the list's length and entries
+        if (!pre) {
+          HIP_CHECK(hipMallocAsync((void**)&r, (size_t)nr * 4, s));
+          HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * ntiles + 1) * 4, s));
         }
-        post_launch("split_log2norm", s);
+        HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(ntiles + 1) * 4, s));
+        float* br = r;
+        if (!pre) {
+          dev::split_log2norm_kernel<<<dim3((unsigned)((M + 255) / 256)), 256, 0, s>>>(Asq, (int)M, r);
+          if (!symmetric) {
+            br = r + M;
+            dev::split_log2norm_kernel<<<dim3((unsigned)((N + 255) / 256)), 256, 0, s>>>(Bsq, (int)N, br);
+          }
+          post_launch("split_log2norm", s);
+        }
         static const int h1_abl = [] {  // diagnostics (bench/gram_adapt_probe.py): h1 pass ablations
           const char* e = std::getenv("DPSVM_H1_ABLATE");
           return e ? atoi(e) : 0;
         }();
         const void *hA = A, *hB = B;
         dev::u4* planes = nullptr;
-        {  // the h planes of the rows the tiles read (whole 256 / 128-row tiles)
+        if (pre) {
+          hA = hB = prep->planes;
+        } else {  // the h planes of the rows the tiles read (whole 256 / 128-row tiles)
           const int64_t nq = (int64_t)((nkb + 1) / 2) * 8, ra = tm2 * 256, rb = symmetric ? 0 : tn * 128;
           HIP_CHECK(hipMallocAsync((void**)&planes, (size_t)(ra + rb) * nq * 16, s));
           dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)A, ra,
@@ -2789,14 +2882,16 @@ void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, i
           }
           post_launch("split_hplane", s);
         }
-        auto h1k = h1_abl == 1   ? dev::rbf_gemm_split_h1s_kernel<1>
+        // (stamps, set_gram_stamps: the one-product pass's 16 words a tile; pass 2 runs unstamped)
+        auto h1k = g_gram_stamps ? dev::rbf_gemm_split_h1s_kernel<0, true>
+                   : h1_abl == 1 ? dev::rbf_gemm_split_h1s_kernel<1>
                    : h1_abl == 2 ? dev::rbf_gemm_split_h1s_kernel<2>
                    : h1_abl == 3 ? dev::rbf_gemm_split_h1s_kernel<3>
                    : h1_abl == 4 ? dev::rbf_gemm_split_h1s_kernel<4>
                                  : dev::rbf_gemm_split_h1s_kernel<0>;
         h1k<<<dim3((unsigned)grid), dev::kH1sThreads, 0, s>>>(
             (const dev::u4*)hA, Ash, Asq, r, (int)M, (const dev::u4*)hB, Bsh, Bsq, br, (int)N, nkb, gamma, c0, c1, out,
-            (int)ldo, symmetric ? 1 : 0, t1.dev, (int)ntiles, hb, hb + ntiles);
+            (int)ldo, symmetric ? 1 : 0, t1.dev, (int)ntiles, hb, hb + ntiles, g_gram_stamps);
         if (planes) HIP_CHECK(hipFreeAsync(planes, s));
         post_launch("rbf_gemm_split_h1", s);
         dev::rbf_gemm_split_w64p_kernel<0, true, true><<<dim3((unsigned)grid), dev::kW64Threads, 0, s>>>(
@@ -2806,8 +2901,10 @@ void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, i
         if (!t_adapt_hot) HIP_CHECK(hipHostMalloc((void**)&t_adapt_hot, 4, hipHostMallocDefault));
         HIP_CHECK(hipMemcpyAsync(t_adapt_hot, hb + ntiles, 4, hipMemcpyDeviceToHost, s));
         t_adapt_tiles = ntiles;
-        HIP_CHECK(hipFreeAsync(r, s));
-        HIP_CHECK(hipFreeAsync(hb, s));
+        if (!pre) {
+          HIP_CHECK(hipFreeAsync(r, s));
+          HIP_CHECK(hipFreeAsync(hb, s));
+        }
         return;
       }
       auto pk = g_gram_stamps ? (pe ? dev::rbf_gemm_split_w64p_kernel<3, true> : dev::rbf_gemm_split_w64p_kernel<3>)

@@ -63,6 +63,7 @@ namespace {
 // The split GEMMs' fp16 operands of every x row this rank holds (part of the
 // Gram / first-round work, so inside the timed region of every solve).
 void split_x(GpuSolver::Impl& m) {
+  if (m.gram_prep.planes) return;  // setup split them with the adaptive Gram's other X-only operands
   if (m.gram_split) launch::split_rows_f16(m.x, m.x_rows, m.dp, m.dp, m.xs, m.xsh, m.stream);
 }
 
@@ -81,7 +82,7 @@ struct DenseBase : Engine {
       const size_t ru = (size_t)launch::split_row_u4(m.dp) * 16;
       launch::rbf_gemm_store_split(m.xs, m.xsh, m.xsq, m.n, (const uint8_t*)m.xs + (size_t)m.off * ru, m.xsh + m.off,
                                    m.xsq + m.off, m.nl, m.dp, m.gamma, m.lines, m.ldl, m.stream, sym,
-                                   m.gram_cold_tau);
+                                   m.gram_cold_tau, &m.gram_prep);
     } else {
       // one rank holds the whole (symmetric) Gram: compute half, mirror the rest
       const bool sym = m.off == 0 && m.nl == m.n;

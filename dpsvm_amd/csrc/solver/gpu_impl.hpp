@@ -106,13 +106,17 @@ struct GpuSolver::Impl {
   int32_t* wsiota = nullptr;                  //   (their GEMM row indices: 0..q_max-1)
   // fp16 split operands of the GEMMs (rbf_gemm_split.hip), rebuilt by every
   // solve inside the timed region: xs / xsh = the x_rows rows of x; wsxs /
-  // wsxsh = the packed misses of partitioned ws-cache rounds
+  // wsxsh = the packed misses of partitioned ws-cache rounds.  One rank's
+  // resident adaptive Gram (gram_prep.planes set): xs / xsh and the one-product
+  // pass's h planes / log2 |x| depend on X and gamma alone and are built once
+  // by setup, like the X upload and |x|^2
   bool gram_split = false;
   float gram_cold_tau = 0.f;  // > 0: the resident split Gram is adaptive (gram_adapt, docs/DESIGN.md §13)
   void* xs = nullptr;
   int32_t* xsh = nullptr;
   void* wsxs = nullptr;
   int32_t* wsxsh = nullptr;
+  launch::GramAdaptPrep gram_prep;
   std::vector<uint8_t> h_wscand;   // host staging of the per-round collectives (host communicators)
   std::vector<float> h_wssub, h_wsxq;
   std::vector<uint8_t> h_wspart;

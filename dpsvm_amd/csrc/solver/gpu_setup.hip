@@ -32,6 +32,7 @@ GpuSolver::Impl::~Impl() {
   if (xpeer_d) (void)hipFree(xpeer_d);
   if (gexec) (void)hipGraphExecDestroy(gexec);
   if (graph) (void)hipGraphDestroy(graph);
+  launch::gram_adapt_prep_free(&gram_prep);
   if (gexec1) (void)hipGraphExecDestroy(gexec1);
   if (graph1) (void)hipGraphDestroy(graph1);
   for (void* ptr : {(void*)x, (void*)xsq, (void*)y, (void*)alpha, (void*)f, (void*)lines, (void*)slot_of,
@@ -829,6 +830,12 @@ GpuSetupInfo GpuSolver::setup(const float* xh, int64_t n_x_rows, int64_t n, int 
     const bool ok = cand && (mode == 1 || gram_cold_sample_ok(xh, n_x_rows, d, m.gamma, m.p.gram_cold_tau));
     m.gram_cold_tau = m.all_agree(ok, m.comm, m.world) ? m.p.gram_cold_tau : 0.f;
     if (m.gram_cold_tau > 0.f) m.info.gram = "split-f16-adaptive";
+    // one rank's whole symmetric Gram: the split rows and the one-product pass's operands once, here
+    if (m.gram_cold_tau > 0.f && m.replicated && m.off == 0 && m.nl == n) {
+      launch::split_rows_f16(m.x, m.x_rows, m.dp, m.dp, m.xs, m.xsh, m.stream);
+      if (launch::gram_adapt_prep(m.xs, m.xsq, n, m.dp, m.stream, &m.gram_prep)) m.bytes += m.gram_prep.bytes;
+      HIP_CHECK(hipStreamSynchronize(m.stream));
+    }
   }
   if (m.working_set()) {
     WsArgs& w = m.wsa;

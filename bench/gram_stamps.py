@@ -64,7 +64,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=60000)
     ap.add_argument("--slab", type=int, default=0, help="P: also the n x n/P slab")
-    ap.add_argument("--variant", type=int, default=0, help="split GEMM variant (6 w64 tiles, 7 persistent)")
+    ap.add_argument("--variant", type=int, default=0, help="split GEMM variant (0 auto, 11 w64 tiles, 12 persistent)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     C = load()

@@ -8,7 +8,7 @@ median / min per variant and whether each variant's output is bit-identical to
 the first one's (the split kernels must agree bit for bit: operand-swap
 symmetry, docs/DESIGN.md §8b).
 
-    python bench/gram_variants.py --variants 5,6 --rounds 7 [--slab 8]
+    python bench/gram_variants.py --variants 12,11 --rounds 7 [--slab 8]
 """
 import argparse
 import json
@@ -26,7 +26,7 @@ from dpsvm_amd.utils.datasets import synthetic  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=60000)
-    ap.add_argument("--variants", default="5,6")
+    ap.add_argument("--variants", default="12,11")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--slab", type=int, default=0, help="P: also time the n x n/P slab (0: symmetric only)")
     ap.add_argument("--out", default="")

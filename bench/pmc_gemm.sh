@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes over one GEMM, one counter group per run (rocprofv3 does not split
 # counters over passes):
-#   bench/pmc_gemm.sh TAG gram   the headline split Gram GEMM (bench/gram_ab.py; DPSVM_SPLIT_GEMM picks the variant)
+#   bench/pmc_gemm.sh TAG gram   the headline split Gram GEMM (bench/gram_ab.py; DPSVM_SPLIT_GEMM forces a path: 1, 3, 11, 12)
 #   bench/pmc_gemm.sh TAG rows   the ws-cache miss-row GEMM at the synthetic-2m shape (bench/rows_probe.py)
 # then: python3 bench/pmc_summary.py gpurun_out/pmc_TAG_*
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

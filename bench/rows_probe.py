@@ -5,7 +5,6 @@ B panel (8.2 GB of split operands) is streamed from HBM once per launch; the
 report gives ms, the B stream's TB/s and the share of the split MFMA peak
 (3 products x 2 m n d flops at 2.5 PFLOP/s dense f16).
 
-    DPSVM_ROWS_BRING=3 python bench/rows_probe.py   # the round-5 B ring depth
     python bench/rows_probe.py [--n 2000000] [--d 1024] [--m 189] [--reps 7]
 """
 import argparse
@@ -56,7 +55,7 @@ def main():
     cols = torch.arange(0, n, max(1, n // 4096), device="cuda")[:4096]
     ref = torch.exp(-(1.0 / d) * torch.cdist(xr[sel].double(), xr[cols].double()) ** 2)
     err = float((out[:4, cols].double() - ref).abs().max())
-    res = {"n": n, "d": d, "m": m, "ring": os.environ.get("DPSVM_ROWS_BRING", "3"), "persist": os.environ.get("DPSVM_ROWS_PERSIST", "1"), "ms_median": round(med, 4),
+    res = {"n": n, "d": d, "m": m, "ms_median": round(med, 4),
            "ms_min": round(float(min(ms)), 4), "b_stream_TBps": round(b_bytes / med / 1e9, 2),
            "split_peak_share": round(flops / (med * 1e-3) / 2.5e15, 3), "max_abs_err_vs_f64": err}
     if a.stamps:

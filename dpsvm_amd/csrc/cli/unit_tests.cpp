@@ -11,6 +11,7 @@
 #include "dpsvm/common.hpp"
 #include "dpsvm/io.hpp"
 #include "dpsvm/solver.hpp"
+#include "kernels/kernels.hpp"
 
 using namespace dpsvm;
 
@@ -197,6 +198,49 @@ static void test_cpu_checkpoint_resume() {
   unlink(path);
 }
 
+// launch::split_gram_path: the split Gram's launch plan (kernels.hpp), shape by shape
+static void test_gram_path() {
+  using launch::GramPath;
+  auto path = [](int64_t M, int64_t N, int64_t ldo, int dp, bool sym, bool cold, int variant = 0) {
+    return launch::split_gram_path(launch::GramShape{M, N, ldo, dp, sym, cold}, variant);
+  };
+  // the headline: persistent wide-wave, adaptive when cold
+  EXPECT(path(60000, 60000, 60032, 784, true, false) == GramPath::W64Persist);
+  EXPECT(path(60000, 60000, 60032, 784, true, true) == GramPath::Adaptive);
+  // 4 k blocks a row: no wide-wave path
+  EXPECT(path(60000, 60000, 60032, 128, true, false) == GramPath::Glds);
+  EXPECT(path(60000, 60000, 60032, 128, true, true) == GramPath::Glds);
+  // more than 2^32 elements: the persistent three-product kernel indexes the output in 32 bits
+  EXPECT(path(66000, 66000, 66048, 784, true, false) == GramPath::W64Grid);
+  EXPECT(path(66000, 66000, 66048, 784, true, true) == GramPath::Adaptive);
+  // the packed epilogue's bound: a 256-row tile of ldo floats below 2^31 bytes
+  const int64_t wide = (1ll << 21) - 128;
+  EXPECT(path(256, wide, wide, 784, false, false) == GramPath::W64Grid);
+  EXPECT(path(256, wide, wide, 784, false, true) == GramPath::Adaptive);
+  EXPECT(path(256, 1ll << 21, 1ll << 21, 784, false, false) == GramPath::Glds);
+  EXPECT(path(256, 1ll << 21, 1ll << 21, 784, false, true) == GramPath::Glds);
+  // operand rows beyond 32 bits: the first M with (M + 512) x 25 x 8 >= 2^31
+  const int64_t m32 = ((1ll << 31) + 199) / 200 - 512;
+  EXPECT((m32 + 512) * 200 >= (1ll << 31) && (m32 + 511) * 200 < (1ll << 31));
+  EXPECT(path(m32, 256, 256, 784, false, false) == GramPath::W64Grid);
+  EXPECT(path(m32, 256, 256, 784, false, true) == GramPath::W64Grid);
+  EXPECT(path(m32 - 1, 256, 256, 784, false, true) == GramPath::Adaptive);
+  // tile tables hold 16-bit tile coordinates
+  EXPECT(path(65535ll * 256, 256, 256, 160, false, true) == GramPath::Adaptive);
+  EXPECT(path(65535ll * 256 + 1, 256, 256, 160, false, true) == GramPath::W64Grid);
+  // forced variants (the tests' hook), and one the shape cannot take
+  EXPECT(path(1000, 777, 896, 784, false, false, 1) == GramPath::Tile);
+  EXPECT(path(1000, 777, 896, 784, false, false, 3) == GramPath::Glds);
+  EXPECT(path(1000, 777, 896, 784, false, false, 11) == GramPath::W64Grid);
+  EXPECT(path(1000, 777, 896, 784, false, false, 12) == GramPath::W64Persist);
+  EXPECT(path(1000, 777, 896, 784, false, true, 11) == GramPath::W64Grid);
+  EXPECT(path(1000, 777, 896, 784, false, true, 12) == GramPath::Adaptive);
+  EXPECT(path(1000, 777, 896, 784, false, true, 3) == GramPath::Glds);
+  EXPECT(path(1000, 777, 896, 100, false, false, 12) == GramPath::Glds);
+  EXPECT(path(1000, 777, 896, 100, false, false, 11) == GramPath::Glds);
+  EXPECT(path(1000, 777, 896, 100, false, false, 1) == GramPath::Tile);
+}
+
 static void test_gpu() {
   if (device_count() == 0) {
     printf("  (no GPU: device tests skipped)\n");
@@ -236,6 +280,7 @@ int main(int argc, char** argv) {
       {"io", test_io},
       {"cpu_solver_ranks", test_cpu_solver_ranks},
       {"cpu_checkpoint_resume", test_cpu_checkpoint_resume},
+      {"gram_path", test_gram_path},
   };
   if (gpu) tests.push_back({"gpu", test_gpu});
   for (auto& [name, fn] : tests) {

@@ -126,8 +126,24 @@ void rbf_rows_indexed(const float* X, const float* Xsq, const int32_t* a_rows, c
 int64_t split_row_u4(int dp);
 int64_t split_pad_rows(int64_t rows);
 void split_rows_f16(const float* x, int64_t rows, int dp, int ldx, void* out, int32_t* shift, hipStream_t s);
-// split STORE GEMM variant: 0 auto (4 when dp > 128, else 3), 1 register-staged tile per workgroup, 3 LDS-DMA,
-// 4 persistent LDS-DMA
+// The split STORE GEMM's launch plan (host only: no HIP call, no environment, no state).
+//   Adaptive    one-product pass + three-product hot tiles: cold, >= 5 k blocks, ldo < 2^21, rows / tiles in 32 bits
+//   W64Persist  persistent wide-wave kernel: the same without cold, and M ldo, N ldo < 2^32 (the headline Gram)
+//   W64Grid     wide-wave kernel, a tile per workgroup: >= 5 k blocks, ldo < 2^21 (Grams of more than 2^32 elements)
+//   Glds        LDS-DMA 128 x 128 tiles, 64-bit indexing: everything else
+//   Tile        register-staged tile kernel: forced only (the tests' bit-identity reference)
+// First eligible wins, in that order.  variant (split_gemm_variant(), a test hook; DPSVM_SPLIT_GEMM): 0 auto,
+// 1 Tile, 3 Glds, 11 W64Grid, 12 W64Persist (Adaptive when cold, as auto); a forced path the shape cannot take
+// falls through to the next eligible one.
+enum class GramPath { Tile, Glds, W64Grid, W64Persist, Adaptive };
+struct GramShape {
+  int64_t M, N, ldo;
+  int dp;
+  bool symmetric;
+  bool cold;  // cold_tau > 0 && gamma > 0
+};
+GramPath split_gram_path(const GramShape& g, int variant);
+const char* gram_path_name(GramPath p);
 int split_gemm_variant();
 void set_split_gemm_variant(int v);
 // diagnostics: per-workgroup s_memtime stamps of the wide-wave Gram kernel (nullptr: off; 8 words a tile).  The
@@ -136,11 +152,12 @@ void set_gram_stamps(uint64_t* p);
 void set_rows_stamps(uint64_t* p);  // diagnostics: the LDS-DMA rows kernel's per-workgroup stamps (0: off)
 // cold_tau > 0: the adaptive Gram (docs/DESIGN.md §13) — a one-product pass, then the tiles holding an element
 // split_cold rejects recomputed with all three products; every stored value within cold_tau of the three-product
-// one.  Falls back to the three-product kernel where the persistent wide-wave path does not apply.
+// one.  Runs the three-product kernels where split_gram_path does not say Adaptive.
 // The symmetric adaptive Gram's operand prep that depends on the rows alone (h planes, R = log2 |x|) and its
 // hot-tile buffer, built once for rows that stay put (a solver's X) instead of by every call: gram_adapt_prep
-// allocates and fills it from split rows A / |x|^2 Asq (stream-ordered; false and nothing allocated where the
-// adaptive pass cannot take the shape), gram_adapt_prep_free releases it.
+// allocates and fills it from split rows A / |x|^2 Asq for the symmetric M x M Gram into rows of ldo floats
+// (stream-ordered; the caller has asked split_gram_path: an error where that Gram is not Adaptive),
+// gram_adapt_prep_free releases it.
 struct GramAdaptPrep {
   const void* A = nullptr;  // the split rows it was built from
   int64_t M = 0;
@@ -151,7 +168,8 @@ struct GramAdaptPrep {
   int64_t ntiles = 0;
   size_t bytes = 0;
 };
-bool gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, hipStream_t s, GramAdaptPrep* prep);
+void gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, int64_t ldo, hipStream_t s,
+                     GramAdaptPrep* prep);
 void gram_adapt_prep_free(GramAdaptPrep* prep);
 // prep (symmetric adaptive Grams of prep's own rows only; else ignored): skip the per-call operand prep
 void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, int64_t M, const void* B,

@@ -25,13 +25,28 @@
 // of 128 B, each 32 h values then the 32 l values of k = 32 b .. 32 b + 31, so
 // one 128-B line per row per k-stage (a whole line per load group of 8 lanes).
 //
-// Tiling: 8 waves, each 32 rows x 64 columns (2 MFMA 32x32 tiles, three
-// accumulators each: 96 accumulator registers).  STORE: waves 4 x 2 = 128 x 128
-// block tiles; ROWS (a working set's cache misses): 2 x 4 = 64 x 256 (short row
-// sets).  BK = 32 per stage (two k16 MFMA steps), LDS double buffered through
-// registers; LDS rows are the 128-B row blocks with the 16-B chunk index XORed
-// by (row >> 1) & 7, which makes every ds_read_b128 lane group of the operand
-// reads (16 rows, one chunk) hit 16 distinct bank quads.
+// Tiling of the first kernel (rbf_gemm_split_kernel, now the tests' reference):
+// 8 waves, each 32 rows x 64 columns (2 MFMA 32x32 tiles, three accumulators
+// each: 96 accumulator registers), 4 x 2 = 128 x 128 block tiles, LDS double
+// buffered through registers; LDS rows are the row blocks with the 16-B chunk
+// index XORed so that every ds_read_b128 lane group of the operand reads (16
+// rows, one chunk) hits 16 distinct bank quads.  The kernels after it keep its
+// per-element MFMA sequence (bit-identical values) and stage by LDS-DMA.
+//
+// Which kernel a Gram runs: launch::split_gram_path (kernels.hpp), first
+// eligible of
+//   Adaptive    h1s one-product pass + w64p over the hot tiles: cold_tau > 0,
+//               >= 5 k blocks, ldo < 2^21, rows / tile tables in 32 bits (the
+//               solver's resident Gram and its slabs)
+//   W64Persist  w64p: the same without cold_tau, and M ldo, N ldo < 2^32
+//   W64Grid     w64, a tile per workgroup: >= 5 k blocks, ldo < 2^21 (three-
+//               product Grams of more than 2^32 elements)
+//   Glds        128 x 128 LDS-DMA tiles, 64-bit indexing: everything else
+//   Tile        forced only
+// The working-set row GEMM (rbf_rows_indexed_split): the persistent small-K
+// kernel up to 2 k blocks, else the LDS-DMA rows kernel, persistent over the
+// column tiles for one tile row.  Variants that lost their A/B are not
+// compiled; their measurements are in profiles/.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -155,33 +170,27 @@ __device__ __forceinline__ void xcd_tile(int64_t& tx, int64_t& ty) {
   xcd_tile_of(blockIdx.x + (int64_t)blockIdx.y * gridDim.x, gridDim.x, gridDim.y, tx, ty);
 }
 
-enum SplitEpi { SPLIT_STORE = 0, SPLIT_ROWS = 1 };
-
-// KB: 32-wide k blocks per LDS stage (1: 128-B LDS rows, chunk index XOR
-// (row >> 1) & 7; 2: 256-B rows, XOR row & 15 — both leave every ds_read_b128
-// lane group of the operand reads on 16 distinct bank quads).
-// ABL (diagnostics only, DPSVM_SPLIT_ABLATE): 1 = no global stores (a runtime
-// condition never true, gamma < 0, keeps the epilogue's math), 2 = no mirrored stores
-// WM x WN waves (default 8 waves); a workgroup tile of 32 WM rows x 64 WN columns.
-template <int EPI, int WM, int KB, int ABL = 0, int WN = 8 / WM>
-__global__ __launch_bounds__(64 * WM * WN, 1) void rbf_gemm_split_kernel(
+// The register-staged tile kernel: the first split STORE GEMM, kept as the
+// tests' bit-identity reference for the LDS-DMA kernels below (GramPath::Tile,
+// forced only).  WM x WN = 4 x 2 waves, a 128 x 128 workgroup tile; KB = 2
+// 32-wide k blocks per LDS stage (256-B LDS rows, chunk index XOR row & 15:
+// every ds_read_b128 lane group of the operand reads on 16 distinct bank quads).
+__global__ __launch_bounds__(kSplitThreads, 1) void rbf_gemm_split_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq, int64_t M,
     const u4* __restrict__ B, const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq, int64_t N, int nkb,
-    float gamma, float* __restrict__ out, int64_t ldo, int sym, const int32_t* __restrict__ a_rows,
-    const int32_t* __restrict__ out_rows, const int32_t* __restrict__ m_dev) {
+    float gamma, float* __restrict__ out, int64_t ldo, int sym) {
+  constexpr int WM = 4, WN = 2, KB = 2;
   constexpr int THREADS = 64 * WM * WN, TM = 32 * WM, TN = 64 * WN, ROWS = TM + TN;
   constexpr int CPR = 8 * KB;                    // 16-B chunks per row and stage
   constexpr int CH = ROWS * CPR;                 // chunks per stage
   constexpr int NL = (CH + THREADS - 1) / THREADS;  // chunks per thread (the last one: a spare LDS slot)
-  static_assert((KB == 1 || KB == 2) && THREADS >= TM, "stage geometry");
+  static_assert(THREADS == kSplitThreads && THREADS >= TM, "stage geometry");
   int64_t tx, ty;
   xcd_tile(tx, ty);
-  if (EPI == SPLIT_ROWS) M = *m_dev;
-  if (EPI == SPLIT_STORE && sym && ty < tx) return;
-  if (EPI == SPLIT_ROWS && tx * TM >= M) return;  // uniform: no barrier reached
+  if (sym && ty < tx) return;
   __shared__ u4 lds[2][CH + 1];  // + a spare slot for the staging remainder
   __shared__ float s_asq[TM];
-  __shared__ int32_t s_ash[TM], s_orow[TM];
+  __shared__ int32_t s_ash[TM];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -190,11 +199,9 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void rbf_gemm_split_kernel(
   const int nst = (nkb + KB - 1) / KB;       // stages
 
   if (tid < TM) {
-    const int64_t row = m0 + tid;
-    const int64_t ar = EPI == SPLIT_ROWS ? (int64_t)a_rows[min(row, M - 1)] : min(row, M - 1);
+    const int64_t ar = min(m0 + tid, M - 1);
     s_asq[tid] = Asq[ar];
     s_ash[tid] = Ash[ar];
-    s_orow[tid] = EPI == SPLIT_ROWS ? (row < M ? out_rows[row] : -1) : 0;
   }
 
   // staging: chunk id = tid + THREADS i -> stage row id / CPR (A rows, then B
@@ -207,15 +214,14 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void rbf_gemm_split_kernel(
     int64_t grow;
     const u4* base;
     if (r < TM) {
-      const int64_t row = m0 + r;  // rows past M: read a valid row (never stored)
-      grow = EPI == SPLIT_ROWS ? (int64_t)a_rows[min(row, M - 1)] : row;
+      grow = m0 + r;  // rows past M: read a valid row (never stored)
       base = A;
     } else {
       grow = n0 + (r - TM);
       base = B;
     }
     src[i] = base + grow * rstride + c;
-    dst[i] = spare ? CH : r * CPR + (c ^ (KB == 1 ? (r >> 1) & 7 : r & 15));
+    dst[i] = spare ? CH : r * CPR + (c ^ (r & 15));
   }
   // chunk i of a stage belongs to k block (i % CPR) / 8 of it: the last stage
   // of an odd block count computes its first block only, and its chunks of the
@@ -225,7 +231,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void rbf_gemm_split_kernel(
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int blk = ((tid + THREADS * i) % CPR) >> 3;
-      const int64_t o = (int64_t)kt * CPR - ((KB > 1 && kt * KB + blk >= nkb) ? 8 : 0);
+      const int64_t o = (int64_t)kt * CPR - (kt * KB + blk >= nkb ? 8 : 0);
       st[i] = src[i][o];
     }
   };
@@ -242,34 +248,31 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void rbf_gemm_split_kernel(
     for (int r = 0; r < 16; ++r) H[j][r] = P[j][r] = Q[j][r] = 0.f;
 
   // operand rows of this lane: A row wm*32 + (lane&31), B rows TM + wn*64 + 32 j + (lane&31)
-  const int sw = KB == 1 ? ((lane & 31) >> 1) & 7 : lane & 15, hl = lane >> 5;
+  const int sw = lane & 15, hl = lane >> 5;
   const int ra = (wm * 32 + (lane & 31)) * CPR;
   const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR, rb1 = rb0 + 32 * CPR;
-  const bool live = EPI != SPLIT_ROWS || m0 + wm * 32 < M;  // ROWS: a wave whose rows all lie past M only stages
   int cur = 0;
   for (int kt = 0; kt < nst; ++kt) {
     const bool more = kt + 1 < nst;
     if (more) load(st, kt + 1);
-    if (live) {
 #pragma unroll
-      for (int blk = 0; blk < KB; ++blk) {
-        if (KB > 1 && kt * KB + blk >= nkb) break;  // uniform
+    for (int blk = 0; blk < KB; ++blk) {
+      if (kt * KB + blk >= nkb) break;  // uniform
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const int ch = (8 * blk + 2 * ks + hl) ^ sw, cl = (8 * blk + 4 + 2 * ks + hl) ^ sw;
-          const h8 ah = __builtin_bit_cast(h8, lds[cur][ra + ch]);
-          const h8 al = __builtin_bit_cast(h8, lds[cur][ra + cl]);
-          const h8 bh0 = __builtin_bit_cast(h8, lds[cur][rb0 + ch]);
-          const h8 bl0 = __builtin_bit_cast(h8, lds[cur][rb0 + cl]);
-          const h8 bh1 = __builtin_bit_cast(h8, lds[cur][rb1 + ch]);
-          const h8 bl1 = __builtin_bit_cast(h8, lds[cur][rb1 + cl]);
-          H[0] = mfma32_f16(ah, bh0, H[0]);
-          H[1] = mfma32_f16(ah, bh1, H[1]);
-          P[0] = mfma32_f16(ah, bl0, P[0]);
-          P[1] = mfma32_f16(ah, bl1, P[1]);
-          Q[0] = mfma32_f16(al, bh0, Q[0]);
-          Q[1] = mfma32_f16(al, bh1, Q[1]);
-        }
+      for (int ks = 0; ks < 2; ++ks) {
+        const int ch = (8 * blk + 2 * ks + hl) ^ sw, cl = (8 * blk + 4 + 2 * ks + hl) ^ sw;
+        const h8 ah = __builtin_bit_cast(h8, lds[cur][ra + ch]);
+        const h8 al = __builtin_bit_cast(h8, lds[cur][ra + cl]);
+        const h8 bh0 = __builtin_bit_cast(h8, lds[cur][rb0 + ch]);
+        const h8 bl0 = __builtin_bit_cast(h8, lds[cur][rb0 + cl]);
+        const h8 bh1 = __builtin_bit_cast(h8, lds[cur][rb1 + ch]);
+        const h8 bl1 = __builtin_bit_cast(h8, lds[cur][rb1 + cl]);
+        H[0] = mfma32_f16(ah, bh0, H[0]);
+        H[1] = mfma32_f16(ah, bh1, H[1]);
+        P[0] = mfma32_f16(ah, bl0, P[0]);
+        P[1] = mfma32_f16(ah, bl1, P[1]);
+        Q[0] = mfma32_f16(al, bh0, Q[0]);
+        Q[1] = mfma32_f16(al, bh1, Q[1]);
       }
     }
     if (more) {
@@ -279,7 +282,6 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void rbf_gemm_split_kernel(
     __syncthreads();
     cur ^= 1;
   }
-  if (!live) return;
 
   // ---- epilogue: K = exp(-g max(|a|^2 + |b|^2 - 2 dot, 0)), dot = 2^-(sa+sb) (H + (P + Q)) ----
   // (all values first, into H; then the stores: unpredicated for interior tiles)
@@ -304,30 +306,16 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void rbf_gemm_split_kernel(
     }
   }
   const bool interior = m0 + TM <= M && n0 + TN <= N;
-  if (EPI == SPLIT_ROWS) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int32_t orow = s_orow[wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl];
+  for (int r = 0; r < 16; ++r) {
+    const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-        if (orow >= 0 && (interior || col < N)) out[(int64_t)orow * ldo + col] = H[j][r];
-      }
-    }
-    return;
-  }
-  if (ABL != 1 || gamma < 0.f) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-        if (interior || (row < M && col < N)) out[row * ldo + col] = H[j][r];
-      }
+    for (int j = 0; j < 2; ++j) {
+      const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
+      if (interior || (row < M && col < N)) out[row * ldo + col] = H[j][r];
     }
   }
-  if (EPI == SPLIT_STORE && sym && ty != tx && ABL == 0) {
+  if (sym && ty != tx) {
     // transposed tile: a lane holds 4 consecutive rows per group -> 16-B stores out[col][row .. row+3]
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -514,31 +502,33 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 // ---------------------------------------------------------------------------
 // LDS-DMA ROWS GEMM: a working-set round's cache misses (up to 192 indexed A
 // rows, a_rows[0 .. *m_dev)) against all of this rank's B rows, K written to
-// the misses' cache lines.  The register-staged ROWS kernel above waits for
-// each 32-k stage's loads before the next can start, so on synthetic-2m
-// (K = 1024, 2M B rows: the 8 GB split X panel per round) it ran at 2.3 TB/s of
-// B bytes and 3.5 ms per round (profiles/r4_big_inputs).  Here the operands of
+// the misses' cache lines.  The register-staged form of it (the tile kernel
+// above with indexed rows, since removed) waited for each 32-k stage's loads
+// before the next could start, so on synthetic-2m (K = 1024, 2M B rows: the
+// 8 GB split X panel per round) it ran at 2.3 TB/s of B bytes and 3.5 ms per
+// round (profiles/r4_big_inputs).  Here the operands of
 // a 192 x 128 tile go through three 32-k LDS buffers by global_load_lds_dwordx4
 // (40 KiB each; the row data after them in the same array), the next block's
-// DMA in flight while a block is multiplied; the waves are the ROWS kernel's
-// (6 x 2, 32 x 64 each) with its MFMA sequence and epilogue, so the rows are
-// bit-identical to it (and to the Gram kernels').  Ten waves issue the DMA: 40
+// DMA in flight while a block is multiplied; the waves (6 x 2, 32 x 64 each)
+// run the tile kernel's MFMA sequence and epilogue per element, so the rows are
+// bit-identical to the Gram kernels'.  Ten waves issue the DMA: 40
 // wave instructions of 8 rows x 128 B per block, 4 per wave.
 // ---------------------------------------------------------------------------
 constexpr int kRowsGldsThreads = 768;
-// BAUX: cache policy of the B operand's DMA (2 = nt: streamed once per round,
-// kept from evicting the A rows every tile re-reads from L2)
+// kRowsBAux: cache policy of the B operand's DMA (2 = nt: streamed once per
+// round, kept from evicting the A rows every tile re-reads from L2)
 // NBR: B ring depth.  A and B have separate rings: A three deep (block kb + 2
 // issued at block kb), B NBR deep (block kb + NBR - 1 issued at kb); the waves
 // that stage A (0-5) and B (6-9) wait on their own DMA counts.  Measured at the
 // synthetic-2m round shape (bench/rows_probe.py, profiles/r6_rows_kernel.txt):
-// NBR 5 does not beat 3, B read from L2 instead of HBM saves only ~10%, and
-// the operand reads one MFMA group ahead (the Gram's SP 2) change nothing —
-// the k loop runs at ~46% MFMA with the chip at ~1.57 GHz.
+// a B ring 5 deep does not beat 3, B read from L2 instead of HBM saves only
+// ~10%, and the operand reads one MFMA group ahead (the Gram's read-ahead)
+// change nothing — the k loop runs at ~46% MFMA with the chip at ~1.57 GHz.
 // ST: diagnostics build with per-workgroup stamps (entry, first block landed,
 // k loop done, stores issued, stores done; s_memrealtime at entry / end) at
 // stamps[8 (blockIdx.y gridDim.x + blockIdx.x) ..] (bench/rows_probe.py --stamps)
-template <int BAUX, int NBR = 3, bool ST = false>
+constexpr int kRowsBAux = 2;
+template <bool ST>
 __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
     const int32_t* __restrict__ a_rows, const int32_t* __restrict__ m_dev, const u4* __restrict__ B,
@@ -549,7 +539,7 @@ __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_kerne
     st[0] = __builtin_amdgcn_s_memtime();
     rt0 = __builtin_amdgcn_s_memrealtime();
   }
-  constexpr int WN = 2, TM = 192, TN = 128, CPR = 8, NA = 3;
+  constexpr int WN = 2, TM = 192, TN = 128, CPR = 8, NA = 3, NBR = 3;
   constexpr int BUFA = TM * CPR, BUFB = TN * CPR;
   constexpr int DMA_WAVES = (TM + TN) / 32;  // 10: each fills 32 rows (4 instructions of 8 rows)
   static_assert(NA * BUFA * 16 + NBR * BUFB * 16 + (3 * TM + 2 * TN) * 4 <= 160 * 1024, "LDS");
@@ -602,7 +592,7 @@ __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_kerne
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         __builtin_amdgcn_global_load_lds((const void*)(src[i] + (int64_t)kb * 8),
-                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, BAUX);
+                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, kRowsBAux);
     } else {
       u4* dst = ldsA + (kb % NA) * BUFA + 32 * wave * CPR;
 #pragma unroll
@@ -667,7 +657,7 @@ __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_kerne
   if (!live) return;
   if constexpr (ST) st[2] = __builtin_amdgcn_s_memtime();
 
-  // ---- epilogue (the ROWS kernel's): K = exp(-g max(|a|^2 + |b|^2 - 2 dot, 0)) ----
+  // ---- epilogue: K = exp(-g max(|a|^2 + |b|^2 - 2 dot, 0)) ----
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int cb = wn * 64 + 32 * j + (lane & 31);
@@ -724,7 +714,6 @@ __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_kerne
 // each epilogue ends with vmcnt(0).  Same MFMA sequence and epilogue per tile:
 // bit-identical to the kernel above.
 // ---------------------------------------------------------------------------
-template <int BAUX>
 __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_persist_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
     const int32_t* __restrict__ a_rows, const int32_t* __restrict__ m_dev, const u4* __restrict__ B,
@@ -781,7 +770,7 @@ __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_persi
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         __builtin_amdgcn_global_load_lds((const void*)(base + off[i]),
-                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, BAUX);
+                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, kRowsBAux);
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -913,7 +902,7 @@ __global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_persi
 // (its 16 stores of the tile before are younger than that DMA), so the stores
 // drain under the next tile instead of being waited for (every live lane
 // stores exactly 16 values: rows past M and columns past N go to a scratch
-// line).  MFMA sequence and epilogue as the ROWS kernels: bit-identical rows.
+// line).  MFMA sequence and epilogue as the rows kernels above: bit-identical rows.
 // ---------------------------------------------------------------------------
 constexpr int kRowsPersistThreads = 768;
 template <int NKB>
@@ -1047,15 +1036,15 @@ __global__ __launch_bounds__(kRowsPersistThreads, 1) void rbf_rows_split_persist
   }
 }
 
-// The w64 kernels' epilogue (PE, the default): the values two at a time in
+// The w64 kernels' epilogue: the values two at a time in
 // packed f32 (v_pk_add / v_pk_mul; the same IEEE operations per value, so the
 // same bits as rbf_split_value), stores through buffer descriptors: a lane
 // outside the tile's columns gets an out-of-range offset and rows past M fall
 // beyond the descriptor's size, so the hardware drops them — one address add
 // per store and no exec-mask branch.  The scalar epilogue was ~20 VALU and ~13
 // SALU per value, VALU-issue-bound: 13.4k -> 10.0k cycles a tile
-// (profiles/r6_gram_lds_readahead_ab.json).  Host: the last row tile's
-// (M - m0) x ldo floats < 2^31 bytes.  lane: the caller's (laundered) lane id.
+// (profiles/r6_gram_lds_readahead_ab.json).  Host (split_gram_path): a tile's
+// 256 x ldo floats < 2^31 bytes.  lane: the caller's (laundered) lane id.
 // AD: the adaptive Gram's hot-tile pass — every element takes the one-product
 // value where split_cold allows it (R = log2 |x| from Ar / Br, global loads:
 // this pass runs only the few tiles the one-product pass reported).
@@ -1176,7 +1165,7 @@ __device__ __forceinline__ void w64_epilogue_pe(f16v (&H)[2][2], const f16v (&P)
 }
 
 // ---------------------------------------------------------------------------
-// Wide-wave LDS-DMA STORE GEMM (variant 5): 256 x 128 tiles, 8 waves of
+// Wide-wave LDS-DMA STORE GEMM (variant 11): 256 x 128 tiles, 8 waves of
 // 64 x 64 (2 x 2 MFMA tiles, three accumulators each: 192 accumulator
 // registers at two waves per SIMD).  The 32 x 64 waves of the kernels above
 // read 6 KiB of LDS operands per 6 MFMAs; with the DMA's 32 KiB of LDS writes
@@ -1191,23 +1180,19 @@ __device__ __forceinline__ void w64_epilogue_pe(f16v (&H)[2][2], const f16v (&P)
 // in flight while one is multiplied.
 // ---------------------------------------------------------------------------
 constexpr int kW64Threads = 512;
-// NT 1: non-temporal Gram stores (measured slower, profiles/r4_gram_nt_store_ab.txt);
-// NT 2: diagnostics only — stores skipped unless a value is NaN (the store-free time);
-// NT 3: diagnostics only — plain stores plus per-workgroup s_memtime stamps
+// ST: diagnostics only — per-workgroup s_memtime stamps
 // (entry, first k block landed, k loop done, stores issued, stores done) and
 // s_memrealtime at entry / end into stamps[8 blockIdx.x ..] (bench/gram_stamps.py)
 // tiles: nullptr = the whole tm x tn grid in the XCD order; else a compact
 // table of the tiles to compute (the symmetric Gram's upper tiles, host-built
 // in the XCD order: no workgroup is launched only to exit)
-// SP 1: the next-but-one block's six LDS-DMA pieces are issued one after each
+// Spread: the next-but-one block's six LDS-DMA pieces are issued one after each
 // group of four MFMAs instead of all six right after the k-block barrier (all
-// eight waves then stall on the load path at once while the MFMA pipe idles)
-// SP 2 (default): SP 1 plus the operand fragments read from LDS one MFMA group
+// eight waves then stall on the load path at once while the MFMA pipe idles).
+// Read-ahead: the operand fragments are read from LDS one MFMA group
 // ahead with counted lgkmcnt waits, so only the block's first group waits on
 // LDS latency (k loop 63.8k -> 59.1k cycles a tile, bench/gram_stamps.py)
-
-
-template <int NT, int SP = 0, bool PE = false>
+template <bool ST>
 __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq, int64_t M,
     const u4* __restrict__ B, const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq, int64_t N, int nkb,
@@ -1215,7 +1200,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
     uint64_t* __restrict__ stamps) {
   constexpr int WN = 2, TM = 256, TN = 128, ROWS = TM + TN, CPR = 8, BUF = ROWS * CPR, NB = 3;
   uint64_t st[5] = {0, 0, 0, 0, 0}, rt0 = 0;
-  if constexpr (NT == 3) {
+  if constexpr (ST) {
     st[0] = __builtin_amdgcn_s_memtime();
     rt0 = __builtin_amdgcn_s_memrealtime();
   }
@@ -1286,12 +1271,11 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if constexpr (NT == 3) {
+    if constexpr (ST) {
       if (kb == 0) st[1] = __builtin_amdgcn_s_memtime();
     }
     // block kb + 2 goes into the buffer of block kb - 1 (every wave is past it)
-    if (SP == 0 && kb + 2 < nkb) dma(kb + 2);
-    const bool spread = SP != 0 && kb + 2 < nkb;  // uniform
+    const bool spread = kb + 2 < nkb;  // uniform
     auto piece = [&](int i) {
       if (spread) {
         __builtin_amdgcn_sched_barrier(0);
@@ -1300,162 +1284,73 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
       }
     };
     const u4* buf = lds + (kb % NB) * BUF;
-    if constexpr (SP == 2) {
-      // LDS reads issued one MFMA group ahead, in asm with counted waits (the
-      // compiler drains lgkmcnt to 0 around the LDS-DMA): a group's fragments
-      // land while the previous group's MFMAs run, except the block's first.
-      // Eight fragments live at most.  A wait names the fragments it retires
-      // ("+v"), so no MFMA can move above it
-      const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
-      auto rd2 = [&](uint32_t base, int c, h8& x0, h8& x1) {
-        const uint32_t a0 = base + 16u * (uint32_t)c;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(x0) : "v"(a0) : "memory");
-        asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(x1) : "v"(a0) : "memory");  // + 32 rows
-      };
-      const int ch0 = hl ^ sw, cl0 = (4 + hl) ^ sw, ch1 = (2 + hl) ^ sw, cl1 = (6 + hl) ^ sw;
-      h8 ah0, ah1, bh0, bh1, bl0, bl1, al0, al1, bh0n, bh1n;
-      rd2(abase, ch0, ah0, ah1);
-      rd2(bbase, ch0, bh0, bh1);
-      rd2(bbase, cl0, bl0, bl1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0), "+v"(bh1));
-      H[0][0] = mfma32_f16(ah0, bh0, H[0][0]);
-      H[0][1] = mfma32_f16(ah0, bh1, H[0][1]);
-      H[1][0] = mfma32_f16(ah1, bh0, H[1][0]);
-      H[1][1] = mfma32_f16(ah1, bh1, H[1][1]);
-      piece(0);
-      rd2(abase, cl0, al0, al1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
-      P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
-      P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
-      P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
-      P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
-      piece(1);
-      rd2(abase, ch1, ah0, ah1);  // k step 1 (A hi of step 0 is dead)
-      rd2(bbase, ch1, bh0n, bh1n);
-      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(al0), "+v"(al1));
-      Q[0][0] = mfma32_f16(al0, bh0, Q[0][0]);
-      Q[0][1] = mfma32_f16(al0, bh1, Q[0][1]);
-      Q[1][0] = mfma32_f16(al1, bh0, Q[1][0]);
-      Q[1][1] = mfma32_f16(al1, bh1, Q[1][1]);
-      piece(2);
-      rd2(bbase, cl1, bl0, bl1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0n), "+v"(bh1n));
-      H[0][0] = mfma32_f16(ah0, bh0n, H[0][0]);
-      H[0][1] = mfma32_f16(ah0, bh1n, H[0][1]);
-      H[1][0] = mfma32_f16(ah1, bh0n, H[1][0]);
-      H[1][1] = mfma32_f16(ah1, bh1n, H[1][1]);
-      piece(3);
-      rd2(abase, cl1, al0, al1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
-      P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
-      P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
-      P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
-      P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
-      piece(4);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al0), "+v"(al1));
-      Q[0][0] = mfma32_f16(al0, bh0n, Q[0][0]);
-      Q[0][1] = mfma32_f16(al0, bh1n, Q[0][1]);
-      Q[1][0] = mfma32_f16(al1, bh0n, Q[1][0]);
-      Q[1][1] = mfma32_f16(al1, bh1n, Q[1][1]);
-      piece(5);
-      continue;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int ch = (2 * ks + hl) ^ sw, cl = (4 + 2 * ks + hl) ^ sw;
-      // hi x hi, then hi x lo (the A hi fragments die), then lo x hi: at most
-      // six operand fragments live
-      const h8 ah0 = __builtin_bit_cast(h8, buf[ra0 + ch]);
-      const h8 ah1 = __builtin_bit_cast(h8, buf[ra0 + 32 * CPR + ch]);
-      const h8 bh0 = __builtin_bit_cast(h8, buf[rb0 + ch]);
-      const h8 bh1 = __builtin_bit_cast(h8, buf[rb0 + 32 * CPR + ch]);
-      H[0][0] = mfma32_f16(ah0, bh0, H[0][0]);
-      H[0][1] = mfma32_f16(ah0, bh1, H[0][1]);
-      H[1][0] = mfma32_f16(ah1, bh0, H[1][0]);
-      H[1][1] = mfma32_f16(ah1, bh1, H[1][1]);
-      piece(3 * ks);
-      const h8 bl0 = __builtin_bit_cast(h8, buf[rb0 + cl]);
-      const h8 bl1 = __builtin_bit_cast(h8, buf[rb0 + 32 * CPR + cl]);
-      P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
-      P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
-      P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
-      P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
-      piece(3 * ks + 1);
-      const h8 al0 = __builtin_bit_cast(h8, buf[ra0 + cl]);
-      const h8 al1 = __builtin_bit_cast(h8, buf[ra0 + 32 * CPR + cl]);
-      Q[0][0] = mfma32_f16(al0, bh0, Q[0][0]);
-      Q[0][1] = mfma32_f16(al0, bh1, Q[0][1]);
-      Q[1][0] = mfma32_f16(al1, bh0, Q[1][0]);
-      Q[1][1] = mfma32_f16(al1, bh1, Q[1][1]);
-      piece(3 * ks + 2);
-    }
+    // LDS reads issued one MFMA group ahead, in asm with counted waits (the
+    // compiler drains lgkmcnt to 0 around the LDS-DMA): a group's fragments
+    // land while the previous group's MFMAs run, except the block's first.
+    // Eight fragments live at most.  A wait names the fragments it retires
+    // ("+v"), so no MFMA can move above it
+    const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
+    auto rd2 = [&](uint32_t base, int c, h8& x0, h8& x1) {
+      const uint32_t a0 = base + 16u * (uint32_t)c;
+      asm volatile("ds_read_b128 %0, %1" : "=v"(x0) : "v"(a0) : "memory");
+      asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(x1) : "v"(a0) : "memory");  // + 32 rows
+    };
+    const int ch0 = hl ^ sw, cl0 = (4 + hl) ^ sw, ch1 = (2 + hl) ^ sw, cl1 = (6 + hl) ^ sw;
+    h8 ah0, ah1, bh0, bh1, bl0, bl1, al0, al1, bh0n, bh1n;
+    rd2(abase, ch0, ah0, ah1);
+    rd2(bbase, ch0, bh0, bh1);
+    rd2(bbase, cl0, bl0, bl1);
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0), "+v"(bh1));
+    H[0][0] = mfma32_f16(ah0, bh0, H[0][0]);
+    H[0][1] = mfma32_f16(ah0, bh1, H[0][1]);
+    H[1][0] = mfma32_f16(ah1, bh0, H[1][0]);
+    H[1][1] = mfma32_f16(ah1, bh1, H[1][1]);
+    piece(0);
+    rd2(abase, cl0, al0, al1);
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
+    P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
+    P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
+    P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
+    P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
+    piece(1);
+    rd2(abase, ch1, ah0, ah1);  // k step 1 (A hi of step 0 is dead)
+    rd2(bbase, ch1, bh0n, bh1n);
+    asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(al0), "+v"(al1));
+    Q[0][0] = mfma32_f16(al0, bh0, Q[0][0]);
+    Q[0][1] = mfma32_f16(al0, bh1, Q[0][1]);
+    Q[1][0] = mfma32_f16(al1, bh0, Q[1][0]);
+    Q[1][1] = mfma32_f16(al1, bh1, Q[1][1]);
+    piece(2);
+    rd2(bbase, cl1, bl0, bl1);
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0n), "+v"(bh1n));
+    H[0][0] = mfma32_f16(ah0, bh0n, H[0][0]);
+    H[0][1] = mfma32_f16(ah0, bh1n, H[0][1]);
+    H[1][0] = mfma32_f16(ah1, bh0n, H[1][0]);
+    H[1][1] = mfma32_f16(ah1, bh1n, H[1][1]);
+    piece(3);
+    rd2(abase, cl1, al0, al1);
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
+    P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
+    P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
+    P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
+    P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
+    piece(4);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al0), "+v"(al1));
+    Q[0][0] = mfma32_f16(al0, bh0n, Q[0][0]);
+    Q[0][1] = mfma32_f16(al0, bh1n, Q[0][1]);
+    Q[1][0] = mfma32_f16(al1, bh0n, Q[1][0]);
+    Q[1][1] = mfma32_f16(al1, bh1n, Q[1][1]);
+    piece(5);
   }
 
-  if constexpr (NT == 3) st[2] = __builtin_amdgcn_s_memtime();
+  if constexpr (ST) st[2] = __builtin_amdgcn_s_memtime();
   // ---- epilogue, one 32 x 32 MFMA tile at a time: values, direct stores,
   // transposed stores.  ONE code path for interior and edge tiles: a second,
   // interior-only copy (round 4) made the compiler spill 396 B of the live
-  // accumulators to scratch (175 scratch instructions).  |x|^2 and shifts are
-  // read as 4-row vectors (one LDS round trip per 4 values), stores go to
-  // 32-bit offsets from uniform tile bases (host: ldo < 2^24) under a row /
-  // column mask that is all-true on interior tiles ----
-  typedef int i4v __attribute__((ext_vector_type(4)));
+  // accumulators to scratch (175 scratch instructions) ----
   const bool mirror = sym && ty > 2 * tx + (wm >> 1);  // this wave's 64 rows lie in 128-row block 2 tx + (wm >> 1)
-  float* const ob = out + m0 * ldo + n0;  // direct block
-  float* const mb = out + n0 * ldo + m0;  // mirrored block (symmetric: M == N)
-  const uint32_t ld = (uint32_t)ldo;
-  const int rlim = (int)min<int64_t>(M - m0, TM);  // tile rows inside [0, M)
-  const int clim = (int)min<int64_t>(N - n0, TN);  // tile columns inside [0, N)
-  if constexpr (PE) w64_epilogue_pe(H, P, Q, s_sq, s_sh, lane, wm, wn, mirror, out, m0, n0, M, N, ldo, gamma);
-#pragma unroll
-  for (int j = 0; j < (PE ? 0 : 2); ++j) {
-    const int cl = wn * 64 + 32 * j + (lane & 31);
-    const bool okc = cl < clim;
-    const float bsq = s_sq[TM + cl];
-    const int bsh = s_sh[TM + cl];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int lr0 = wm * 64 + 32 * i + 4 * hl;  // value r sits on row lr0 + 8 (r >> 2) + (r & 3)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f4 asq = *(const f4*)(s_sq + lr0 + 8 * g);
-        const i4v ash = *(const i4v*)(s_sh + lr0 + 8 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e, lr = lr0 + 8 * g + e;
-          const float dot = ldexpf(H[i][j][r] + (P[i][j][r] + Q[i][j][r]), -(ash[e] + bsh));
-          H[i][j][r] = rbf_split_value(asq[e], bsq, dot, gamma);
-          if (NT == 2 && !(H[i][j][r] != H[i][j][r])) continue;
-          if (okc && lr < rlim) {
-            float* dst = ob + ((uint32_t)lr * ld + (uint32_t)cl);
-            if constexpr (NT == 1) __builtin_nontemporal_store(H[i][j][r], dst);
-            else *dst = H[i][j][r];
-          }
-        }
-      }
-      if (mirror && NT != 2) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int lr = lr0 + 8 * q;
-          float* dst = mb + ((uint32_t)cl * ld + (uint32_t)lr);
-          f4 v;
-          v.x = H[i][j][4 * q + 0];
-          v.y = H[i][j][4 * q + 1];
-          v.z = H[i][j][4 * q + 2];
-          v.w = H[i][j][4 * q + 3];
-          if (okc && lr + 3 < rlim) {
-            if constexpr (NT == 1) __builtin_nontemporal_store(v, (f4*)dst);
-            else *(f4*)dst = v;
-          } else if (okc) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-              if (lr + c < rlim) dst[c] = v[c];
-          }
-        }
-      }
-    }
-  }
-  if constexpr (NT == 3) {
+  w64_epilogue_pe(H, P, Q, s_sq, s_sh, lane, wm, wn, mirror, out, m0, n0, M, N, ldo, gamma);
+  if constexpr (ST) {
     st[3] = __builtin_amdgcn_s_memtime();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     st[4] = __builtin_amdgcn_s_memtime();
@@ -1472,10 +1367,8 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Persistent wide-wave STORE GEMM (the default; PE: the packed epilogue,
-// variant 12; variant 7 without it; DPSVM_GRAM_PERSIST=0 for the tile-per-
-// workgroup kernel): the w64 kernel's tile, k loop (with SP 2's read-ahead)
-// and epilogue, one workgroup per CU walking tiles L = b, b + G, ... of the
+// Persistent wide-wave STORE GEMM (the default; variant 12): the w64 kernel's
+// tile, k loop and epilogue, one workgroup per CU walking tiles L = b, b + G, ... of the
 // same table.  The w64 kernel's stamps put ~12% of a tile in its prologue (row
 // data, then the first LDS-DMA block's latency) with the MFMA pipe idle, and
 // ~7% of the CU time between workgroups (237.5 of 256 in flight).  Here the
@@ -1488,7 +1381,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
 // epilogue: 8.86 vs 9.01 ms symmetric, 2.30 vs 2.47 ms for the P = 8 slab
 // against the w64 kernel (profiles/r6_gram_lds_readahead_ab.json).  Same MFMA
 // sequence per output: bit-identical to the w64 kernel.
-// NT 3: per-tile stamps (first wait, first block landed, k loop done, stores
+// ST: per-tile stamps (first wait, first block landed, k loop done, stores
 // issued) and s_memrealtime at the tile's start / end into stamps[8 L ..].
 // ---------------------------------------------------------------------------
 // LDS-DMA piece of a k block into ring buffer buf.  The persistent kernel
@@ -1535,10 +1428,10 @@ __device__ __forceinline__ void w64p_row_dma(const float* __restrict__ Asq, cons
   }
 }
 
-// AD (with PE): the adaptive Gram's hot-tile pass — the tile count is read from
+// AD: the adaptive Gram's hot-tile pass — the tile count is read from
 // ntiles_dev (written by the one-product pass) and the epilogue applies
 // split_cold with Ar / Br, c0, c1.
-template <int NT, bool PE = false, bool AD = false>
+template <bool ST, bool AD = false>
 __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq, int M,
     const u4* __restrict__ B, const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq, int N, int nkb,
@@ -1595,7 +1488,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
   const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR;
   while (true) {
     uint64_t st[4] = {0, 0, 0, 0}, rt0 = 0;
-    if constexpr (NT == 3) {
+    if constexpr (ST) {
       st[0] = __builtin_amdgcn_s_memtime();
       rt0 = __builtin_amdgcn_s_memrealtime();
     }
@@ -1622,7 +1515,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if constexpr (NT == 3) {
+      if constexpr (ST) {
         if (kb == 0) st[1] = __builtin_amdgcn_s_memtime();
       }
       // the prefetch slot: block kb + 2 of this tile, or block kb + 2 - nkb of
@@ -1639,7 +1532,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
         else PIECE_A(uA, pbuf, j < 2 ? j : j - 1);
         __builtin_amdgcn_sched_barrier(0);
       };
-      // operand fragments read one MFMA group ahead (the w64 kernel's SP 2)
+      // operand fragments read one MFMA group ahead (as in the w64 kernel)
       const u4* buf = lds + (g % NB) * BUF;
       const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
       auto rd2 = [&](uint32_t base, int c, h8& x0, h8& x1) {
@@ -1695,81 +1588,24 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
       piece(5);
       ++g;
     }
-    if constexpr (NT == 3) st[2] = __builtin_amdgcn_s_memtime();
+    if constexpr (ST) st[2] = __builtin_amdgcn_s_memtime();
     // the next tile's row data into the other parity (last read by the previous
     // tile's epilogue, before this tile's first barrier)
     if (has_next) ROW_DMA(nm0, nn0, par ^ 1);
 
     // ---- epilogue of the w64 kernel (row data from parity `par`) ----
-    if constexpr (PE) {
-      int el = lane;
-      asm volatile("" : "+v"(el));
-      w64_epilogue_pe<AD>(H, P, Q, (const float*)(s_rows + par * RD), (const int32_t*)(s_rows + par * RD + ROWS),
-                          el, wm, wn, sym && ty > 2 * tx + (wm >> 1), out, m0, n0, M, N, ldo, gamma, Ar, Br, c0,
-                          c1);
-    }
     // (the per-lane epilogue addresses are recomputed per tile from a
     // laundered lane id: hoisted out of the tile loop they would hold ~64
     // registers across the k loop)
     int el = lane;
     asm volatile("" : "+v"(el));
-    const int ewn = wn, ewm = wm, ehl = el >> 5;
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const float* s_sq = (const float*)(s_rows + par * RD);
-    const int32_t* s_sh = (const int32_t*)(s_rows + par * RD + ROWS);
-    const bool mirror = sym && ty > 2 * tx + (ewm >> 1);
-    float* const ob = out + ((uint32_t)m0 * (uint32_t)ldo + (uint32_t)n0);
-    float* const mb = out + ((uint32_t)n0 * (uint32_t)ldo + (uint32_t)m0);
-    const uint32_t ld = (uint32_t)ldo;
-    const int rlim = min(M - m0, TM);
-    const int clim = min(N - n0, TN);
-#pragma unroll
-    for (int j = 0; j < (PE ? 0 : 2); ++j) {
-      const int cl = ewn * 64 + 32 * j + (el & 31);
-      const bool okc = cl < clim;
-      const float bsq = s_sq[TM + cl];
-      const int bsh = s_sh[TM + cl];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int lr0 = ewm * 64 + 32 * i + 4 * ehl;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const f4 asq = *(const f4*)(s_sq + lr0 + 8 * q4);
-          const i4v ash = *(const i4v*)(s_sh + lr0 + 8 * q4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = 4 * q4 + e, lr = lr0 + 8 * q4 + e;
-            const float dot = ldexpf(H[i][j][r] + (P[i][j][r] + Q[i][j][r]), -(ash[e] + bsh));
-            H[i][j][r] = rbf_split_value(asq[e], bsq, dot, gamma);
-            if (okc && lr < rlim) ob[(uint32_t)lr * ld + (uint32_t)cl] = H[i][j][r];
-          }
-        }
-        if (mirror) {
-#pragma unroll
-          for (int q4 = 0; q4 < 4; ++q4) {
-            const int lr = lr0 + 8 * q4;
-            float* dst = mb + ((uint32_t)cl * ld + (uint32_t)lr);
-            f4 v;
-            v.x = H[i][j][4 * q4 + 0];
-            v.y = H[i][j][4 * q4 + 1];
-            v.z = H[i][j][4 * q4 + 2];
-            v.w = H[i][j][4 * q4 + 3];
-            if (okc && lr + 3 < rlim) {
-              *(f4*)dst = v;
-            } else if (okc) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c)
-                if (lr + c < rlim) dst[c] = v[c];
-            }
-          }
-        }
-      }
-    }
+    w64_epilogue_pe<AD>(H, P, Q, (const float*)(s_rows + par * RD), (const int32_t*)(s_rows + par * RD + ROWS), el,
+                        wm, wn, sym && ty > 2 * tx + (wm >> 1), out, m0, n0, M, N, ldo, gamma, Ar, Br, c0, c1);
     // the stores, the next tile's blocks 0 / 1 and its row data retired here:
     // the loop's uniform vmcnt(6) then holds at the next tile's first block (and
     // no DMA is in flight when the kernel ends)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (NT == 3) {
+    if constexpr (ST) {
       st[3] = __builtin_amdgcn_s_memtime();
       const uint64_t rt1 = __builtin_amdgcn_s_memrealtime();
       if (tid == 0) {
@@ -1878,10 +1714,7 @@ __device__ __forceinline__ bool h1_values(f16v (&H)[2][2], const float* s_sq, co
 // the stores of one 32 x 32 MFMA block (i, j) of a wave's values v: 16 direct
 // 4-B stores per lane, and for a mirroring wave 4 transposed 16-B ones (plus,
 // on the last row tile, a partial quad's values one at a time); out-of-range
-// offsets where a value has no place (the hardware drops those).  ABL
-// (diagnostics): 1 every store dropped, 2 the mirrored ones; 4 (A/B): every
-// store with the non-temporal cache policy.
-template <int ABL = 0>
+// offsets where a value has no place (the hardware drops those).
 __device__ __forceinline__ void h1_store_block(const f16v& v, int i, int j, int lane, int wm, int wn, bool mirror,
                                                bool valid, float* out, int m0, int n0, int M, int N, int ldo) {
   constexpr int TM = 256, TN = 128;
@@ -1898,8 +1731,8 @@ __device__ __forceinline__ void h1_store_block(const f16v& v, int i, int j, int 
   const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(ob, 0, (int)ob_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(mb, 0, (int)mb_bytes, 0x00020000);
   const int cl = wn * 64 + 32 * j + (lane & 31);
-  const bool okc = valid && cl < clim && ABL != 1;
-  constexpr int CP = ABL == 4 ? 2 : 0;  // buffer-store cache policy: nt
+  const bool okc = valid && cl < clim;
+  constexpr int CP = 0;  // buffer-store cache policy (non-temporal measured slower: profiles/r6_late)
   const int lr0 = wm * 64 + 32 * i + 4 * hl;
   const uint32_t vo = okc ? ((uint32_t)lr0 * ld + (uint32_t)cl) * 4u : OOB;
 #pragma unroll
@@ -1908,7 +1741,7 @@ __device__ __forceinline__ void h1_store_block(const f16v& v, int i, int j, int 
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv), rs_o,
                                           (int)(vo + (uint32_t)(8 * (r >> 2) + (r & 3)) * ld * 4u), 0, CP);
   }
-  if (!(mirror && valid) || ABL == 2) return;  // uniform
+  if (!(mirror && valid)) return;  // uniform
   const bool okm = okc;
   const uint32_t vm = okm ? ((uint32_t)cl * ld + (uint32_t)lr0) * 4u : OOB;
 #pragma unroll
@@ -2047,7 +1880,7 @@ __device__ __noinline__ void h1s_dma(const u4* __restrict__ A, const int32_t* __
 constexpr int kH1sThreads = 768;  // 8 compute waves + 4 DMA waves
 // ST (diagnostics, set_gram_stamps): 16 words a tile — the first compute wave's s_memtime at the tile's start,
 // stage 0 landed, k loop done, values done, stores issued, s_memrealtime at start / end, the tile; then h1s_dma's
-template <int ABL = 0, bool ST = false>
+template <bool ST>
 __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
     const float* __restrict__ Ar, int M, const u4* __restrict__ B, const int32_t* __restrict__ Bsh,
@@ -2112,7 +1945,6 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
         asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(b1) : "v"(pb) : "memory");
       };
       auto mma = [&](const h8& a0, const h8& a1, const h8& b0, const h8& b1) {
-        if (ABL == 3) return;
         H[0][0] = mfma32_f16(a0, b0, H[0][0]);
         H[0][1] = mfma32_f16(a0, b1, H[0][1]);
         H[1][0] = mfma32_f16(a1, b0, H[1][0]);
@@ -2149,7 +1981,7 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         __builtin_amdgcn_sched_barrier(0);
-        h1_store_block<ABL>(H[i][j], i, j, el, wm, wn, mirror, true, out, m0, n0, M, N, ldo);
+        h1_store_block(H[i][j], i, j, el, wm, wn, mirror, true, out, m0, n0, M, N, ldo);
       }
     if (hotw && lane == 0) {  // the tile's first report appends it to the list
       if (atomicAdd(tile_hot + L, 1u) == 0u) {
@@ -2189,231 +2021,6 @@ __global__ __launch_bounds__(256) void split_log2norm_kernel(const float* __rest
                                                              float* __restrict__ r) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) r[i] = split_log2norm(sq[i]);
-}
-
-// ---------------------------------------------------------------------------
-// Persistent LDS-DMA STORE GEMM: the LDS-DMA kernel's k loop, one 512-thread
-// workgroup per CU walking tiles as the persistent kernel does, so that a
-// tile's Gram stores (128 KiB per tile with the mirror: 4.2 of the tile
-// kernel's 13.6 ms, profiles/r3_split_gemm_headline_ab.txt) drain while the
-// next tile multiplies.  Order at a tile boundary: the next tile's row data
-// (plain loads, issued while no DMA is in flight), the epilogue math, a
-// barrier, the next tile's first three DMAs, THEN this tile's stores — so the
-// next tile's first three waits count the stores as younger than their DMA:
-// vmcnt(8 + S) with S the store instructions each lane issued (interior tiles:
-// exactly 32 direct + 8 mirrored, unpredicated; edge tiles store predicated and
-// drain with vmcnt(0)).  From block 3 on the stores are older than the block's
-// DMA and vmcnt(8) retires them too.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kGldsThreads, 1) void rbf_gemm_split_glds_persist_kernel(
-    const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq, int64_t M,
-    const u4* __restrict__ B, const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq, int64_t N, int nkb,
-    float gamma, float* __restrict__ out, int64_t ldo, int sym, int tm, int tn) {
-  constexpr int WN = 2, TM = 128, TN = 128, ROWS = TM + TN, CPR = 8, BUF = ROWS * CPR, NB = 4;
-  __shared__ u4 lds[NB * BUF + 4 * ROWS / 4];  // 4 operand buffers, then per tile parity |x|^2 [ROWS], shifts [ROWS]
-  float* s_sq0 = (float*)(lds + NB * BUF);
-  int32_t* s_sh0 = (int32_t*)(lds + NB * BUF) + 2 * ROWS;
-
-  const int total = tm * tn, G = gridDim.x;
-  auto valid = [&](int L, int& x, int& y) {
-    xcd_tile_of32(L, tm, tn, x, y);
-    return !(sym && y < x);
-  };
-  int tx = 0, ty = 0, L = blockIdx.x;
-  while (L < total && !valid(L, tx, ty)) L += G;
-  if (L >= total) return;  // uniform: no barrier reached
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
-  const int64_t rstride = (int64_t)nkb * 8;
-  int64_t m0 = (int64_t)tx * TM, n0 = (int64_t)ty * TN;
-
-  // DMA geometry (as rbf_gemm_split_glds_kernel): row 32 w + 8 i + (lane >> 3)
-  int srow[4], schunk[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    srow[i] = 32 * wave + 8 * i + (lane >> 3);
-    schunk[i] = (lane & 7) ^ ((srow[i] >> 1) & 7);
-  }
-  const u4* src[4];
-  auto set_src = [&](int64_t a0, int64_t b0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      src[i] = srow[i] < TM ? A + (a0 + srow[i]) * rstride + schunk[i] : B + (b0 + (srow[i] - TM)) * rstride + schunk[i];
-  };
-  auto dma = [&](int kb) {
-    u4* dst = lds + (kb & (NB - 1)) * BUF + 32 * wave * CPR;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const void*)(src[i] + (int64_t)kb * 8),
-                                       (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, 0);
-  };
-  auto row_data = [&](int64_t a0, int64_t b0, float& q, int32_t& h) {
-    if (tid < ROWS) {
-      const int64_t ri = tid < TM ? min(a0 + tid, M - 1) : min(b0 + (tid - TM), N - 1);
-      q = tid < TM ? Asq[ri] : Bsq[ri];
-      h = tid < TM ? Ash[ri] : Bsh[ri];
-    }
-  };
-  {
-    float q = 0.f;
-    int32_t h = 0;
-    row_data(m0, n0, q, h);
-    if (tid < ROWS) {
-      s_sq0[tid] = q;
-      s_sh0[tid] = h;
-    }
-  }
-  __syncthreads();  // row data of tile 0 (no DMA in flight yet)
-  set_src(m0, n0);
-  dma(0);
-  if (nkb > 1) dma(1);
-  if (nkb > 2) dma(2);
-
-  const int sw = ((lane & 31) >> 1) & 7;
-  const int ra = (wm * 32 + (lane & 31)) * CPR;
-  const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR, rb1 = rb0 + 32 * CPR;
-  int par = 0;
-  int pend = 0;  // store instructions each lane issued after the current tile's first DMAs (0, 32 or 40)
-  f16v H[2], P[2], Q[2];
-  while (true) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) H[j][r] = P[j][r] = Q[j][r] = 0.f;
-    for (int kb = 0; kb < nkb; ++kb) {
-      const int ahead = min(2, nkb - 1 - kb);
-      // the previous tile's stores sit between the DMAs of blocks 2 and 3
-      const int st = kb < 3 ? pend : 0;
-      if (ahead == 2) {
-        if (st == 40) asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
-        else if (st == 32) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      } else if (ahead == 1) {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // never with pending stores: nkb >= 5 (launcher)
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (kb + 3 < nkb) dma(kb + 3);
-      const u4* buf = lds + (kb & (NB - 1)) * BUF;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int ch = (2 * ks + hl) ^ sw, cl = (4 + 2 * ks + hl) ^ sw;
-        const h8 ah = __builtin_bit_cast(h8, buf[ra + ch]);
-        const h8 al = __builtin_bit_cast(h8, buf[ra + cl]);
-        const h8 bh0 = __builtin_bit_cast(h8, buf[rb0 + ch]);
-        const h8 bl0 = __builtin_bit_cast(h8, buf[rb0 + cl]);
-        const h8 bh1 = __builtin_bit_cast(h8, buf[rb1 + ch]);
-        const h8 bl1 = __builtin_bit_cast(h8, buf[rb1 + cl]);
-        H[0] = mfma32_f16(ah, bh0, H[0]);
-        H[1] = mfma32_f16(ah, bh1, H[1]);
-        P[0] = mfma32_f16(ah, bl0, P[0]);
-        P[1] = mfma32_f16(ah, bl1, P[1]);
-        Q[0] = mfma32_f16(al, bh0, Q[0]);
-        Q[1] = mfma32_f16(al, bh1, Q[1]);
-      }
-    }
-    // ---- tile boundary (no DMA in flight: the last block waited vmcnt(0)) ----
-    int nL = L + G, ntx = tx, nty = ty;
-    while (nL < total && !valid(nL, ntx, nty)) nL += G;
-    const bool has_next = nL < total;
-    const int64_t nm0 = (int64_t)ntx * TM, nn0 = (int64_t)nty * TN;
-    float nq = 0.f;
-    int32_t nh = 0;
-    if (has_next) row_data(nm0, nn0, nq, nh);
-    const float* s_sq = s_sq0 + par * ROWS;
-    const int32_t* s_sh = s_sh0 + par * ROWS;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int cb = TM + wn * 64 + 32 * j + (lane & 31);
-      const float bsq = s_sq[cb];
-      const int bsh = s_sh[cb];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-        const float dot = ldexpf(H[j][r] + (P[j][r] + Q[j][r]), -(s_sh[lr] + bsh));
-        H[j][r] = rbf_split_value(s_sq[lr], bsq, dot, gamma);
-      }
-    }
-    if (has_next && tid < ROWS) {
-      s_sq0[(par ^ 1) * ROWS + tid] = nq;
-      s_sh0[(par ^ 1) * ROWS + tid] = nh;
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // every wave is done with the operand buffers of this tile
-    asm volatile("" ::: "memory");
-    if (has_next) {
-      set_src(nm0, nn0);
-      dma(0);
-      dma(1);
-      dma(2);
-    }
-    asm volatile("" ::: "memory");  // the stores stay behind the DMAs
-    const bool interior = m0 + TM <= M && n0 + TN <= N;
-    const bool mirror = sym && ty != tx;
-    if (interior) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) out[row * ldo + n0 + wn * 64 + 32 * j + (lane & 31)] = H[j][r];
-      }
-      if (mirror) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            f4 v;
-            v.x = H[j][4 * q + 0];
-            v.y = H[j][4 * q + 1];
-            v.z = H[j][4 * q + 2];
-            v.w = H[j][4 * q + 3];
-            *(f4*)(out + col * ldo + m0 + wm * 32 + 8 * q + 4 * hl) = v;
-          }
-        }
-      }
-      pend = mirror ? 40 : 32;
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-          if (row < M && col < N) out[row * ldo + col] = H[j][r];
-        }
-      }
-      if (mirror) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int64_t row = m0 + wm * 32 + 8 * q + 4 * hl;
-            float* dst = out + col * ldo + row;
-            if (col < M) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c)
-                if (row + c < N) dst[c] = H[j][4 * q + c];
-            }
-          }
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // predicated stores: drained here
-      pend = 0;
-    }
-    if (!has_next) break;
-    L = nL;
-    tx = ntx;
-    ty = nty;
-    m0 = nm0;
-    n0 = nn0;
-    par ^= 1;
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2566,13 +2173,47 @@ int g_split_variant = -1;
 
 int split_gemm_variant() {
   if (g_split_variant < 0) {
-    const char* e = std::getenv("DPSVM_SPLIT_GEMM");  // A/B: 1 tile kernel, 3 LDS-DMA, 4 persistent LDS-DMA, 5 wide-wave
+    const char* e = std::getenv("DPSVM_SPLIT_GEMM");  // test hook: the values of split_gram_path's `variant`
     g_split_variant = e ? atoi(e) : 0;
   }
   return g_split_variant;
 }
 
 void set_split_gemm_variant(int v) { g_split_variant = v; }
+
+// The split STORE GEMM's launch plan, the one place its shape conditions live
+// (rbf_gemm_store_split, the solver's setup and gram_adapt_prep all ask here).
+// First eligible of Adaptive, W64Persist, W64Grid, Glds; a forced variant only
+// removes candidates, so a shape it cannot take falls through to the next.
+GramPath split_gram_path(const GramShape& g, int variant) {
+  if (variant == 1) return GramPath::Tile;
+  const bool any = variant != 3 && variant != 11 && variant != 12;  // 0 and unknown numbers: auto
+  const int64_t nkb = (g.dp + 31) / 32, tm2 = (g.M + 255) / 256, tn = (g.N + 127) / 128;
+  // The wide-wave kernels' packed epilogue (w64_epilogue_pe, h1_store_block)
+  // stores through a buffer descriptor of at most 2^31 bytes at 32-bit byte
+  // offsets from the tile's first element: the last of a tile's 256 rows starts
+  // 255 ldo floats in, so 256 x ldo x 4 B < 2^31, ldo < 2^21.  (Beyond that the
+  // hardware range check drops the late rows' stores without an error.)
+  const bool wide = (any || variant == 11 || variant == 12) && nkb >= 5 && g.ldo < (1ll << 21);
+  if (!wide) return GramPath::Glds;
+  // persistent kernels: split operand rows ((rows + 512) x nkb x 8 u4) and tile tables in 32 bits
+  const bool persist_ok = (any || variant == 12) && (g.M + 512) * nkb * 8 < (1ll << 31) &&
+                          (g.N + 512) * nkb * 8 < (1ll << 31) && tm2 < 65536 && tn < 65536;
+  if (persist_ok && g.cold) return GramPath::Adaptive;  // 64-bit tile bases: also Grams of more than 2^32 elements
+  if (persist_ok && g.M * g.ldo < (1ll << 32) && g.N * g.ldo < (1ll << 32)) return GramPath::W64Persist;
+  return GramPath::W64Grid;
+}
+
+const char* gram_path_name(GramPath p) {
+  switch (p) {
+    case GramPath::Tile: return "Tile";
+    case GramPath::Glds: return "Glds";
+    case GramPath::W64Grid: return "W64Grid";
+    case GramPath::W64Persist: return "W64Persist";
+    case GramPath::Adaptive: return "Adaptive";
+  }
+  return "?";
+}
 
 // diagnostics: non-null = the wide-wave Gram kernel writes per-workgroup stamps here
 uint64_t* g_gram_stamps = nullptr;
@@ -2640,34 +2281,24 @@ struct TileTable {
   uint32_t* dev = nullptr;
   int64_t count = 0;
 };
-// Keyed by (device, tm, tn): the table lives in the memory of the device that
+// Keyed by (device, tm, tn, sym, one_product): the table lives in the memory of the device that
 // launches the GEMM (svmTrain -p N: one rank per device, threads of one process).
-// gm / ch > 0: that grouping instead of the default (the one-product pass: 8 / 64,
-// 6.73-6.93 vs 7.03-7.10 ms for 4 / 32, profiles/r6_gram_adapt/h1_tile_order_sweep.txt)
-const TileTable& sym_tile_table(int64_t tm, int64_t tn, hipStream_t s, bool sym = true, int gm = 0, int ch = 0) {
+const TileTable& sym_tile_table(int64_t tm, int64_t tn, hipStream_t s, bool sym = true, bool one_product = false) {
   static std::mutex mu;
-  static std::map<std::tuple<int, int64_t, int64_t, bool, int, int>, TileTable> cache;
+  static std::map<std::tuple<int, int64_t, int64_t, bool, bool>, TileTable> cache;
   const int device = current_device();
   std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find({device, tm, tn, sym, gm, ch});
+  auto it = cache.find({device, tm, tn, sym, one_product});
   if (it != cache.end()) return it->second;
   // the needed tiles in groups of GM tile rows, column by column, rows inside a
   // column; chunks of CH consecutive tiles dealt round-robin to the 8 XCDs.
-  // GM 4 / CH 32 (an XCD's chunk: 4 A panels x 8 B panels) 9.34-9.45 ms vs
-  // 9.47-9.50 for GM 8 / CH 64 (profiles/r5_gram_tile_order_ab.txt; bit-identical
-  // output).  A/B: DPSVM_GRAM_GM / DPSVM_GRAM_CH
+  // Three-product kernels: GM 4 / CH 32 (an XCD's chunk: 4 A panels x 8 B
+  // panels), 9.34-9.45 ms vs 9.47-9.50 for GM 8 / CH 64
+  // (profiles/r5_gram_tile_order_ab.txt; bit-identical output).  The one-product
+  // pass: 8 / 64, 6.73-6.93 vs 7.03-7.10 ms for 4 / 32
+  // (profiles/r6_gram_adapt/h1_tile_order_sweep.txt)
   std::vector<uint32_t> order;
-  static const int64_t GM_env = [] {
-    const char* e = std::getenv("DPSVM_GRAM_GM");
-    const int v = e ? atoi(e) : 4;
-    return (int64_t)(v >= 1 && v <= 64 ? v : 4);
-  }();
-  static const int64_t CH_env = [] {
-    const char* e = std::getenv("DPSVM_GRAM_CH");
-    const int v = e ? atoi(e) : 32;
-    return (int64_t)(v >= 8 && v <= 1024 ? v : 32);
-  }();
-  const int64_t GM = gm > 0 ? gm : GM_env, CH = ch > 0 ? ch : CH_env;
+  const int64_t GM = one_product ? 8 : 4, CH = one_product ? 64 : 32;
   for (int64_t g0 = 0; g0 < tm; g0 += GM) {
     const int64_t gm = std::min(GM, tm - g0);
     for (int64_t ty = 0; ty < tn; ++ty)
@@ -2689,7 +2320,7 @@ const TileTable& sym_tile_table(int64_t tm, int64_t tn, hipStream_t s, bool sym 
   HIP_CHECK(hipMalloc((void**)&t.dev, (size_t)total * sizeof(uint32_t)));
   HIP_CHECK(hipMemcpyAsync(t.dev, tab.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  return cache.emplace(std::make_tuple(device, tm, tn, sym, gm, ch), t).first->second;
+  return cache.emplace(std::make_tuple(device, tm, tn, sym, one_product), t).first->second;
 }
 }  // namespace
 
@@ -2713,12 +2344,14 @@ void gram_adapt_last(int64_t* tiles, int64_t* hot) {
   *hot = t_adapt_tiles >= 0 && t_adapt_hot ? (int64_t)*(volatile uint32_t*)t_adapt_hot : -1;
 }
 
-bool gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, hipStream_t s, GramAdaptPrep* prep) {
+void gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, int64_t ldo, hipStream_t s,
+                     GramAdaptPrep* prep) {
   *prep = GramAdaptPrep{};
+  DPSVM_CHECK(M > 0 && split_gram_path(GramShape{M, M, ldo, dp, true, true}, split_gemm_variant()) ==
+                           GramPath::Adaptive,
+              "gram_adapt_prep: this Gram's plan is not adaptive");
   const int nkb = (dp + 31) / 32;
   const int64_t tm2 = (M + 255) / 256, tn = (M + 127) / 128;
-  // (rbf_gemm_store_split's conditions on the shape for the adaptive pass)
-  if (M <= 0 || nkb < 5 || tm2 >= 65536 || tn >= 65536 || (M + 512) * (int64_t)nkb * 8 >= (1ll << 31)) return false;
   const int64_t ntiles = sym_tile_table(tm2, tn, s, true).count;
   const int64_t nq = (int64_t)((nkb + 1) / 2) * 8, ra = tm2 * 256;
   const size_t pb = (size_t)ra * nq * 16, rb = (size_t)M * 4, hb = (size_t)(2 * ntiles + 1) * 4;
@@ -2735,7 +2368,6 @@ bool gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, hipStre
   prep->M = M;
   prep->dp = dp;
   prep->ntiles = ntiles;
-  return true;
 }
 
 void gram_adapt_prep_free(GramAdaptPrep* prep) {
@@ -2745,6 +2377,155 @@ void gram_adapt_prep_free(GramAdaptPrep* prep) {
   *prep = GramAdaptPrep{};
 }
 
+namespace {
+// One launch function per GramPath (rbf_gemm_store_split switches over split_gram_path's answer).
+struct GramArgs {
+  const void* A;
+  const int32_t* Ash;
+  const float* Asq;
+  int64_t M;
+  const void* B;
+  const int32_t* Bsh;
+  const float* Bsq;
+  int64_t N;
+  int dp, nkb;
+  float gamma;
+  float* out;
+  int64_t ldo;
+  bool symmetric;
+  hipStream_t s;
+};
+
+int persistent_grid_limit() {  // one workgroup per CU
+  int n = 0;
+  HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()));
+  return std::max(8, n);
+}
+
+void launch_gram_tile(const GramArgs& g) {
+  const int64_t tm = (g.M + 127) / 128, tn = (g.N + 127) / 128;
+  dev::rbf_gemm_split_kernel<<<dim3((unsigned)tm, (unsigned)tn), dev::kSplitThreads, 0, g.s>>>(
+      (const dev::u4*)g.A, g.Ash, g.Asq, g.M, (const dev::u4*)g.B, g.Bsh, g.Bsq, g.N, g.nkb, g.gamma, g.out, g.ldo,
+      g.symmetric ? 1 : 0);
+  post_launch("rbf_gemm_store_split", g.s);
+}
+
+void launch_gram_glds(const GramArgs& g) {  // LDS-DMA, three k blocks in flight
+  const int64_t tm = (g.M + 127) / 128, tn = (g.N + 127) / 128;
+  dev::rbf_gemm_split_glds_kernel<<<dim3((unsigned)tm, (unsigned)tn), dev::kGldsThreads, 0, g.s>>>(
+      (const dev::u4*)g.A, g.Ash, g.Asq, g.M, (const dev::u4*)g.B, g.Bsh, g.Bsq, g.N, g.nkb, g.gamma, g.out, g.ldo,
+      g.symmetric ? 1 : 0);
+  post_launch("rbf_gemm_split_glds", g.s);
+}
+
+// wide-wave, a tile per workgroup: the symmetric Gram's upper tiles from the compact table where it can
+// index them (16-bit tile coordinates), else the whole grid
+void launch_gram_w64_grid(const GramArgs& g) {
+  const int64_t tm2 = (g.M + 255) / 256, tn = (g.N + 127) / 128;
+  auto kern = g_gram_stamps ? dev::rbf_gemm_split_w64_kernel<true> : dev::rbf_gemm_split_w64_kernel<false>;
+  if (g.symmetric && tm2 < 65536 && tn < 65536) {
+    const auto& tab = sym_tile_table(tm2, tn, g.s);
+    kern<<<dim3((unsigned)tab.count), dev::kW64Threads, 0, g.s>>>(
+        (const dev::u4*)g.A, g.Ash, g.Asq, g.M, (const dev::u4*)g.B, g.Bsh, g.Bsq, g.N, g.nkb, g.gamma, g.out, g.ldo,
+        1, tab.dev, g_gram_stamps);
+  } else {
+    kern<<<dim3((unsigned)tm2, (unsigned)tn), dev::kW64Threads, 0, g.s>>>(
+        (const dev::u4*)g.A, g.Ash, g.Asq, g.M, (const dev::u4*)g.B, g.Bsh, g.Bsq, g.N, g.nkb, g.gamma, g.out, g.ldo,
+        g.symmetric ? 1 : 0, nullptr, g_gram_stamps);
+  }
+  post_launch("rbf_gemm_split_w64", g.s);
+}
+
+// persistent over the tiles: one workgroup per CU, the LDS-DMA ring running on across tiles
+// (non-symmetric: every tile, same XCD order)
+void launch_gram_w64_persist(const GramArgs& g) {
+  const int64_t tm2 = (g.M + 255) / 256, tn = (g.N + 127) / 128;
+  const auto& t = sym_tile_table(tm2, tn, g.s, g.symmetric);
+  const int64_t grid = std::min<int64_t>(t.count, persistent_grid_limit());
+  auto pk = g_gram_stamps ? dev::rbf_gemm_split_w64p_kernel<true> : dev::rbf_gemm_split_w64p_kernel<false>;
+  pk<<<dim3((unsigned)grid), dev::kW64Threads, 0, g.s>>>(
+      (const dev::u4*)g.A, g.Ash, g.Asq, (int)g.M, (const dev::u4*)g.B, g.Bsh, g.Bsq, (int)g.N, g.nkb, g.gamma, g.out,
+      (int)g.ldo, g.symmetric ? 1 : 0, t.dev, (int)t.count, (int)tm2, (int)tn, g_gram_stamps, nullptr, nullptr, 0.f,
+      0.f, nullptr);
+  post_launch("rbf_gemm_split_w64p", g.s);
+}
+
+// adaptive: pass 1 one-product over every tile, pass 2 three products over the reported ones.  Its kernels
+// (h1s, w64p with AD) index a tile's stores from 64-bit tile bases with 32-bit offsets and the operand rows
+// in 32 bits: they also take Grams of more than 2^32 elements (200k rows: 160 GB)
+void launch_gram_adaptive(const GramArgs& g, float cold_tau, const GramAdaptPrep* prep) {
+  const void *A = g.A, *B = g.B;
+  const int32_t *Ash = g.Ash, *Bsh = g.Bsh;
+  const float *Asq = g.Asq, *Bsq = g.Bsq;
+  const int64_t M = g.M, N = g.N, ldo = g.ldo;
+  const int nkb = g.nkb;
+  const bool symmetric = g.symmetric;
+  const float gamma = g.gamma;
+  hipStream_t s = g.s;
+  const int64_t tm2 = (M + 255) / 256, tn = (N + 127) / 128;
+  const int64_t ntiles = sym_tile_table(tm2, tn, s, symmetric).count;
+  const int64_t grid = std::min<int64_t>(ntiles, persistent_grid_limit());
+  const auto& t1 = sym_tile_table(tm2, tn, s, symmetric, true);  // the one-product pass's own tile order
+  float c0 = 0.f, c1 = 0.f;
+  split_cold_consts(gamma, cold_tau, &c0, &c1);
+  // a solver's prep of these very rows: the h planes and R are there, the hot buffer is re-zeroed
+  const bool pre = prep && symmetric && prep->planes && prep->A == A && prep->M == M && prep->dp == g.dp &&
+                   prep->ntiles == ntiles;
+  const int64_t nr = symmetric ? M : M + N;
+  float* r = pre ? prep->r : nullptr;
+  uint32_t* hb = pre ? prep->hot : nullptr;  // [ntiles] per-tile reports, then the list's length and entries
+  if (!pre) {
+    HIP_CHECK(hipMallocAsync((void**)&r, (size_t)nr * 4, s));
+    HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * ntiles + 1) * 4, s));
+  }
+  HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(ntiles + 1) * 4, s));
+  float* br = r;
+  if (!pre) {
+    dev::split_log2norm_kernel<<<dim3((unsigned)((M + 255) / 256)), 256, 0, s>>>(Asq, (int)M, r);
+    if (!symmetric) {
+      br = r + M;
+      dev::split_log2norm_kernel<<<dim3((unsigned)((N + 255) / 256)), 256, 0, s>>>(Bsq, (int)N, br);
+    }
+    post_launch("split_log2norm", s);
+  }
+  const void *hA = A, *hB = B;
+  dev::u4* planes = nullptr;
+  if (pre) {
+    hA = hB = prep->planes;
+  } else {  // the h planes of the rows the tiles read (whole 256 / 128-row tiles)
+    const int64_t nq = (int64_t)((nkb + 1) / 2) * 8, ra = tm2 * 256, rb = symmetric ? 0 : tn * 128;
+    HIP_CHECK(hipMallocAsync((void**)&planes, (size_t)(ra + rb) * nq * 16, s));
+    dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)A, ra, nkb,
+                                                                                      planes);
+    hA = hB = planes;
+    if (!symmetric) {
+      dev::split_hplane_kernel<<<dim3((unsigned)((rb * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)B, rb, nkb,
+                                                                                        planes + ra * nq);
+      hB = planes + ra * nq;
+    }
+    post_launch("split_hplane", s);
+  }
+  // (stamps, set_gram_stamps: the one-product pass's 16 words a tile; pass 2 runs unstamped)
+  auto h1k = g_gram_stamps ? dev::rbf_gemm_split_h1s_kernel<true> : dev::rbf_gemm_split_h1s_kernel<false>;
+  h1k<<<dim3((unsigned)grid), dev::kH1sThreads, 0, s>>>(
+      (const dev::u4*)hA, Ash, Asq, r, (int)M, (const dev::u4*)hB, Bsh, Bsq, br, (int)N, nkb, gamma, c0, c1, g.out,
+      (int)ldo, symmetric ? 1 : 0, t1.dev, (int)ntiles, hb, hb + ntiles, g_gram_stamps);
+  if (planes) HIP_CHECK(hipFreeAsync(planes, s));
+  post_launch("rbf_gemm_split_h1", s);
+  dev::rbf_gemm_split_w64p_kernel<false, true><<<dim3((unsigned)grid), dev::kW64Threads, 0, s>>>(
+      (const dev::u4*)A, Ash, Asq, (int)M, (const dev::u4*)B, Bsh, Bsq, (int)N, nkb, gamma, g.out, (int)ldo,
+      symmetric ? 1 : 0, hb + ntiles + 1, 0, (int)tm2, (int)tn, nullptr, r, br, c0, c1, hb + ntiles);
+  post_launch("rbf_gemm_split_w64p_hot", s);
+  if (!t_adapt_hot) HIP_CHECK(hipHostMalloc((void**)&t_adapt_hot, 4, hipHostMallocDefault));
+  HIP_CHECK(hipMemcpyAsync(t_adapt_hot, hb + ntiles, 4, hipMemcpyDeviceToHost, s));
+  t_adapt_tiles = ntiles;
+  if (!pre) {
+    HIP_CHECK(hipFreeAsync(r, s));
+    HIP_CHECK(hipFreeAsync(hb, s));
+  }
+}
+}  // namespace
+
 void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, int64_t M, const void* B,
                           const int32_t* Bsh, const float* Bsq, int64_t N, int dp, float gamma, float* out,
                           int64_t ldo, hipStream_t s, bool symmetric, float cold_tau, const GramAdaptPrep* prep) {
@@ -2752,214 +2533,16 @@ void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, i
   if (M <= 0 || N <= 0) return;
   DPSVM_CHECK(!symmetric || (A == B && Asq == Bsq && Ash == Bsh && M == N && ldo % 4 == 0),
               "rbf_gemm_store_split: symmetric mode needs B == A, N == M");
-  const int64_t tm = (M + 127) / 128, tn = (N + 127) / 128;
-  DPSVM_CHECK(tn < 65536, "rbf_gemm_store_split: N too large for grid.y");
-  static const int ablate = [] {
-    const char* e = std::getenv("DPSVM_SPLIT_ABLATE");  // diagnostics (bench/gram_ab.py)
-    return e ? atoi(e) : 0;
-  }();
-  static const int kb = [] {
-    const char* e = std::getenv("DPSVM_SPLIT_KB");  // diagnostics: k blocks per stage (A/B)
-    return e && atoi(e) == 1 ? 1 : 2;
-  }();
-  const int variant = split_gemm_variant();
-  // default from 5 k blocks: the wide-wave LDS-DMA kernel (60000^2 x 784
-  // symmetric: 10.1-10.8 ms vs 10.9-11.1 for the persistent LDS-DMA kernel,
-  // bit-identical; profiles/r4_w64_gram_ab.txt)
-  // (32-bit store offsets inside a 256 x 128 tile: ldo < 2^24)
-  if ((variant == 5 || variant == 6 || variant == 7 || variant == 8 || variant == 11 || variant == 12 || (variant == 0 && (dp + 31) / 32 >= 5)) && ablate == 0 &&
-      ldo < (1ll << 24)) {
-    static const int nt = [] {
-      const char* e = std::getenv("DPSVM_GRAM_NT");  // A/B: 0 plain Gram stores, 1 non-temporal, 2 none (diagnostics)
-      return e ? atoi(e) : 0;
-    }();
-    const int64_t tm2 = (M + 255) / 256;
-    // Defaults, each bit-identical to the others (profiles/r6_gram_lds_readahead_ab.json):
-    //  - the LDS-DMA issue spread over the MFMA groups (9.41 -> 9.27 ms symmetric)
-    //    with the operand reads one MFMA group ahead (-> 8.81-8.93 ms);
-    //  - the packed-f32 / buffer-store epilogue (13.4k -> 10.0k cycles a tile);
-    //  - persistent over the tiles (below): 9.01 -> 8.86 ms symmetric, 2.47 -> 2.30 ms
-    //    for the P = 8 slab against the tile-per-workgroup kernel of the same tree.
-    // A/B: variants 5 (no spread), 6 (spread), 8 (spread + read-ahead), 11 (+ PE),
-    // 7 / 12 persistent without / with PE; DPSVM_GRAM_SPREAD=0, DPSVM_GRAM_PERSIST=0
-    static const int spread = [] {
-      const char* e = std::getenv("DPSVM_GRAM_SPREAD");
-      return e ? atoi(e) : 1;
-    }();
-    const int sp = variant == 5 ? 0 : variant == 6 ? 1 : variant == 8 || variant == 11 ? 2 : spread ? 2 : 0;
-    const bool pe = variant == 11 || variant == 12 || (variant == 0 && spread);
-    auto kern = g_gram_stamps ? (pe        ? dev::rbf_gemm_split_w64_kernel<3, 2, true>
-                                 : sp == 2 ? dev::rbf_gemm_split_w64_kernel<3, 2>
-                                           : dev::rbf_gemm_split_w64_kernel<3, 1>)
-                : nt == 2 ? dev::rbf_gemm_split_w64_kernel<2>
-                : nt      ? dev::rbf_gemm_split_w64_kernel<1>
-                : pe      ? dev::rbf_gemm_split_w64_kernel<0, 2, true>
-                : sp == 2 ? dev::rbf_gemm_split_w64_kernel<0, 2>
-                : sp == 1 ? dev::rbf_gemm_split_w64_kernel<0, 1>
-                          : dev::rbf_gemm_split_w64_kernel<0>;
-    static const bool compact = [] {  // A/B: DPSVM_GRAM_COMPACT=0 launches the full grid (half exit at once)
-      const char* e = std::getenv("DPSVM_GRAM_COMPACT");
-      return !(e && e[0] == '0');
-    }();
-    // persistent over the tiles (the default; variants 7 / 12; A/B:
-    // DPSVM_GRAM_PERSIST=0): one workgroup per CU, the LDS-DMA ring running on
-    // across tiles
-    static const int persist_env = [] {
-      const char* e = std::getenv("DPSVM_GRAM_PERSIST");
-      return e ? atoi(e) : 1;
-    }();
-    const int nkb = (dp + 31) / 32;
-    // (32-bit indices: the split operand buffers hold (rows + 512) x nkb x 8 u4, the output M x ldo floats)
-    const bool idx32 = (M + 512) * (int64_t)nkb * 8 < (1ll << 31) && (N + 512) * (int64_t)nkb * 8 < (1ll << 31) &&
-                       M * ldo < (1ll << 32) && N * ldo < (1ll << 32);
-    const bool persist = (variant == 7 || variant == 12 || (variant == 0 && persist_env == 1 && spread)) && nkb >= 3 && nt == 0 && idx32 &&
-                         tm2 < 65536 && tn < 65536 && (!symmetric || compact);
-    // the adaptive Gram's kernels (h1s, w64p with the packed epilogue) index a tile's stores from
-    // 64-bit tile bases with 32-bit offsets (256 rows x ldo x 4 B < 2^32) and the operand rows in
-    // 32 bits: they also take Grams of more than 2^32 elements (200k rows: 160 GB)
-    const bool idx_adapt = (M + 512) * (int64_t)nkb * 8 < (1ll << 31) && (N + 512) * (int64_t)nkb * 8 < (1ll << 31) &&
-                           ldo < (1ll << 22);
-    const bool adapt = pe && cold_tau > 0.f && gamma > 0.f && nkb >= 5 && nt == 0 && idx_adapt &&
-                       tm2 < 65536 && tn < 65536 && (!symmetric || compact) &&
-                       (variant == 0 || variant == 7 || variant == 12);
-    if (persist || adapt) {
-      const int cus = [] {
-        int n = 0;
-        HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()));
-        return std::max(8, n);
-      }();
-      const auto& t = sym_tile_table(tm2, tn, s, symmetric);  // non-symmetric: every tile, same XCD order
-      const uint32_t* tab = t.dev;
-      const int64_t ntiles = t.count;
-      const int64_t grid = std::min<int64_t>(ntiles, cus);
-      if (adapt) {
-        static const bool h1_order = [] {  // A/B: DPSVM_H1_ORDER=0 keeps the three-product kernel's grouping
-          const char* e = std::getenv("DPSVM_H1_ORDER");
-          return !(e && e[0] == '0') && !std::getenv("DPSVM_GRAM_GM") && !std::getenv("DPSVM_GRAM_CH");
-        }();
-        const auto& t1 = h1_order ? sym_tile_table(tm2, tn, s, symmetric, 8, 64) : t;
-        // adaptive: pass 1 one-product over every tile, pass 2 three products over the reported ones
-        float c0 = 0.f, c1 = 0.f;
-        split_cold_consts(gamma, cold_tau, &c0, &c1);
-        // a solver's prep of these very rows: the h planes and R are there, the hot buffer is re-zeroed
-        const bool pre = prep && symmetric && prep->planes && prep->A == A && prep->M == M && prep->dp == dp &&
-                         prep->ntiles == ntiles;
-        const int64_t nr = symmetric ? M : M + N;
-        float* r = pre ? prep->r : nullptr;
-        uint32_t* hb = pre ? prep->hot : nullptr;  // [ntiles] per-tile reports, then the list's length and entries
-        if (!pre) {
-          HIP_CHECK(hipMallocAsync((void**)&r, (size_t)nr * 4, s));
-          HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * ntiles + 1) * 4, s));
-        }
-        HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(ntiles + 1) * 4, s));
-        float* br = r;
-        if (!pre) {
-          dev::split_log2norm_kernel<<<dim3((unsigned)((M + 255) / 256)), 256, 0, s>>>(Asq, (int)M, r);
-          if (!symmetric) {
-            br = r + M;
-            dev::split_log2norm_kernel<<<dim3((unsigned)((N + 255) / 256)), 256, 0, s>>>(Bsq, (int)N, br);
-          }
-          post_launch("split_log2norm", s);
-        }
-        static const int h1_abl = [] {  // diagnostics (bench/gram_adapt_probe.py): h1 pass ablations
-          const char* e = std::getenv("DPSVM_H1_ABLATE");
-          return e ? atoi(e) : 0;
-        }();
-        const void *hA = A, *hB = B;
-        dev::u4* planes = nullptr;
-        if (pre) {
-          hA = hB = prep->planes;
-        } else {  // the h planes of the rows the tiles read (whole 256 / 128-row tiles)
-          const int64_t nq = (int64_t)((nkb + 1) / 2) * 8, ra = tm2 * 256, rb = symmetric ? 0 : tn * 128;
-          HIP_CHECK(hipMallocAsync((void**)&planes, (size_t)(ra + rb) * nq * 16, s));
-          dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)A, ra,
-                                                                                            nkb, planes);
-          hA = hB = planes;
-          if (!symmetric) {
-            dev::split_hplane_kernel<<<dim3((unsigned)((rb * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)B, rb,
-                                                                                              nkb, planes + ra * nq);
-            hB = planes + ra * nq;
-          }
-          post_launch("split_hplane", s);
-        }
-        // (stamps, set_gram_stamps: the one-product pass's 16 words a tile; pass 2 runs unstamped)
-        auto h1k = g_gram_stamps ? dev::rbf_gemm_split_h1s_kernel<0, true>
-                   : h1_abl == 1 ? dev::rbf_gemm_split_h1s_kernel<1>
-                   : h1_abl == 2 ? dev::rbf_gemm_split_h1s_kernel<2>
-                   : h1_abl == 3 ? dev::rbf_gemm_split_h1s_kernel<3>
-                   : h1_abl == 4 ? dev::rbf_gemm_split_h1s_kernel<4>
-                                 : dev::rbf_gemm_split_h1s_kernel<0>;
-        h1k<<<dim3((unsigned)grid), dev::kH1sThreads, 0, s>>>(
-            (const dev::u4*)hA, Ash, Asq, r, (int)M, (const dev::u4*)hB, Bsh, Bsq, br, (int)N, nkb, gamma, c0, c1, out,
-            (int)ldo, symmetric ? 1 : 0, t1.dev, (int)ntiles, hb, hb + ntiles, g_gram_stamps);
-        if (planes) HIP_CHECK(hipFreeAsync(planes, s));
-        post_launch("rbf_gemm_split_h1", s);
-        dev::rbf_gemm_split_w64p_kernel<0, true, true><<<dim3((unsigned)grid), dev::kW64Threads, 0, s>>>(
-            (const dev::u4*)A, Ash, Asq, (int)M, (const dev::u4*)B, Bsh, Bsq, (int)N, nkb, gamma, out, (int)ldo,
-            symmetric ? 1 : 0, hb + ntiles + 1, 0, (int)tm2, (int)tn, nullptr, r, br, c0, c1, hb + ntiles);
-        post_launch("rbf_gemm_split_w64p_hot", s);
-        if (!t_adapt_hot) HIP_CHECK(hipHostMalloc((void**)&t_adapt_hot, 4, hipHostMallocDefault));
-        HIP_CHECK(hipMemcpyAsync(t_adapt_hot, hb + ntiles, 4, hipMemcpyDeviceToHost, s));
-        t_adapt_tiles = ntiles;
-        if (!pre) {
-          HIP_CHECK(hipFreeAsync(r, s));
-          HIP_CHECK(hipFreeAsync(hb, s));
-        }
-        return;
-      }
-      auto pk = g_gram_stamps ? (pe ? dev::rbf_gemm_split_w64p_kernel<3, true> : dev::rbf_gemm_split_w64p_kernel<3>)
-                : pe ? dev::rbf_gemm_split_w64p_kernel<0, true> : dev::rbf_gemm_split_w64p_kernel<0>;
-      pk<<<dim3((unsigned)grid), dev::kW64Threads, 0, s>>>((const dev::u4*)A, Ash, Asq, (int)M, (const dev::u4*)B,
-                                                          Bsh, Bsq, (int)N, nkb, gamma, out, (int)ldo,
-                                                          symmetric ? 1 : 0, tab, (int)ntiles, (int)tm2, (int)tn,
-                                                          g_gram_stamps, nullptr, nullptr, 0.f, 0.f, nullptr);
-      post_launch("rbf_gemm_split_w64p", s);
-      return;
-    }
-    if (symmetric && compact && tm2 < 65536 && tn < 65536) {
-      const auto& tab = sym_tile_table(tm2, tn, s);
-      kern<<<dim3((unsigned)tab.count), dev::kW64Threads, 0, s>>>(
-          (const dev::u4*)A, Ash, Asq, M, (const dev::u4*)B, Bsh, Bsq, N, (dp + 31) / 32, gamma, out, ldo, 1, tab.dev,
-          g_gram_stamps);
-    } else {
-      kern<<<dim3((unsigned)tm2, (unsigned)tn), dev::kW64Threads, 0, s>>>(
-          (const dev::u4*)A, Ash, Asq, M, (const dev::u4*)B, Bsh, Bsq, N, (dp + 31) / 32, gamma, out, ldo,
-          symmetric ? 1 : 0, nullptr, g_gram_stamps);
-    }
-    post_launch("rbf_gemm_split_w64", s);
-    return;
+  DPSVM_CHECK((N + 127) / 128 < 65536, "rbf_gemm_store_split: N too large for grid.y");
+  const GramArgs g{A, Ash, Asq, M, B, Bsh, Bsq, N, dp, (dp + 31) / 32, gamma, out, ldo, symmetric, s};
+  const bool cold = cold_tau > 0.f && gamma > 0.f;
+  switch (split_gram_path(GramShape{M, N, ldo, dp, symmetric, cold}, split_gemm_variant())) {
+    case GramPath::Tile: return launch_gram_tile(g);
+    case GramPath::Glds: return launch_gram_glds(g);
+    case GramPath::W64Grid: return launch_gram_w64_grid(g);
+    case GramPath::W64Persist: return launch_gram_w64_persist(g);
+    case GramPath::Adaptive: return launch_gram_adaptive(g, cold_tau, prep);
   }
-  if ((variant == 0 || variant == 4) && ablate == 0 && (dp + 31) / 32 >= 5 && tm * tn < (1ll << 31)) {
-    // default: persistent LDS-DMA, one workgroup per CU (a multiple of 8)
-    static const int cus4 = [] {
-      int dev = 0, n = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-      return std::max(8, n / 8 * 8);
-    }();
-    const int64_t tiles = symmetric ? tm * (tm + 1) / 2 : tm * tn;
-    const int grid = (int)std::min<int64_t>(cus4, (tiles + 7) / 8 * 8);
-    dev::rbf_gemm_split_glds_persist_kernel<<<dim3((unsigned)grid), dev::kGldsThreads, 0, s>>>(
-        (const dev::u4*)A, Ash, Asq, M, (const dev::u4*)B, Bsh, Bsq, N, (dp + 31) / 32, gamma, out, ldo,
-        symmetric ? 1 : 0, (int)tm, (int)tn);
-    post_launch("rbf_gemm_split_glds_persist", s);
-    return;
-  }
-  if ((variant == 0 || variant == 3) && ablate == 0 && kb == 2) {  // LDS-DMA, three k blocks in flight (dp <= 128 by default)
-    dev::rbf_gemm_split_glds_kernel<<<dim3((unsigned)tm, (unsigned)tn), dev::kGldsThreads, 0, s>>>(
-        (const dev::u4*)A, Ash, Asq, M, (const dev::u4*)B, Bsh, Bsq, N, (dp + 31) / 32, gamma, out, ldo,
-        symmetric ? 1 : 0);
-    post_launch("rbf_gemm_split_glds", s);
-    return;
-  }
-  auto kern = kb == 1 ? dev::rbf_gemm_split_kernel<dev::SPLIT_STORE, 4, 1, 0>
-              : ablate == 1 ? dev::rbf_gemm_split_kernel<dev::SPLIT_STORE, 4, 2, 1>
-              : ablate == 2 ? dev::rbf_gemm_split_kernel<dev::SPLIT_STORE, 4, 2, 2>
-                            : dev::rbf_gemm_split_kernel<dev::SPLIT_STORE, 4, 2, 0>;
-  kern<<<dim3((unsigned)tm, (unsigned)tn), dev::kSplitThreads, 0, s>>>(
-      (const dev::u4*)A, Ash, Asq, M, (const dev::u4*)B, Bsh, Bsq, N, (dp + 31) / 32, gamma, out, ldo,
-      symmetric ? 1 : 0, nullptr, nullptr, nullptr);
-  post_launch("rbf_gemm_store_split", s);
 }
 
 void rbf_rows_indexed_split(const void* X, const int32_t* Xsh, const float* Xsq, const int32_t* a_rows,
@@ -2973,22 +2556,8 @@ void rbf_rows_indexed_split(const void* X, const int32_t* Xsh, const float* Xsq,
   // tiles read it once per 64 misses)
   const int64_t tm = (M_max + 191) / 192, tn = (N + 127) / 128;
   DPSVM_CHECK(tn < 65536, "rbf_rows_indexed_split: N too large for grid.y");
-  static const bool reg_staged = [] {  // A/B: DPSVM_ROWS_KERNEL=reg, the register-staged ROWS kernel
-    const char* e = std::getenv("DPSVM_ROWS_KERNEL");
-    return e && std::string(e) == "reg";
-  }();
   const int nkb = (dp + 31) / 32;
-  static const bool no_persist = [] {  // A/B: DPSVM_ROWS_KERNEL=glds, the tile-per-workgroup LDS-DMA kernel
-    const char* e = std::getenv("DPSVM_ROWS_KERNEL");
-    return e && std::string(e) == "glds";
-  }();
-  if (!reg_staged && !no_persist && nkb <= 2) {
-    static const int cus = [] {
-      int dev = 0, n = 0;
-      HIP_CHECK(hipGetDevice(&dev));
-      HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-      return std::max(1, n);
-    }();
+  if (nkb <= 2) {  // persistent small-K kernel
     // the scratch line of the fixed-count stores (64 floats, never read), one per device
     static std::mutex trash_mu;
     static float* trash_of[kMaxDevices] = {};
@@ -2999,59 +2568,26 @@ void rbf_rows_indexed_split(const void* X, const int32_t* Xsh, const float* Xsq,
       if (!trash_of[device]) HIP_CHECK(hipMalloc((void**)&trash_of[device], 64 * sizeof(float)));
       trash = trash_of[device];
     }
-    const int64_t grid = std::min<int64_t>(tm * tn, cus);
-    if (nkb == 1)
-      dev::rbf_rows_split_persist_kernel<1><<<dim3((unsigned)grid), dev::kRowsPersistThreads, 0, s>>>(
-          (const dev::u4*)X, Xsh, Xsq, a_rows, m_dev, (const dev::u4*)B, Bsh, Bsq, N, gamma, lines, ldl, out_rows,
-          trash);
-    else
-      dev::rbf_rows_split_persist_kernel<2><<<dim3((unsigned)grid), dev::kRowsPersistThreads, 0, s>>>(
-          (const dev::u4*)X, Xsh, Xsq, a_rows, m_dev, (const dev::u4*)B, Bsh, Bsq, N, gamma, lines, ldl, out_rows,
-          trash);
-  } else if (reg_staged) {
-    dev::rbf_gemm_split_kernel<dev::SPLIT_ROWS, 6, 1, 0, 2><<<dim3((unsigned)tm, (unsigned)tn), 768, 0, s>>>(
-        (const dev::u4*)X, Xsh, Xsq, M_max, (const dev::u4*)B, Bsh, Bsq, N, (dp + 31) / 32, gamma, lines, ldl, 0,
-        a_rows, out_rows, m_dev);
+    const int64_t grid = std::min<int64_t>(tm * tn, persistent_grid_limit());
+    auto k = nkb == 1 ? dev::rbf_rows_split_persist_kernel<1> : dev::rbf_rows_split_persist_kernel<2>;
+    k<<<dim3((unsigned)grid), dev::kRowsPersistThreads, 0, s>>>((const dev::u4*)X, Xsh, Xsq, a_rows, m_dev,
+                                                                (const dev::u4*)B, Bsh, Bsq, N, gamma, lines, ldl,
+                                                                out_rows, trash);
+  } else if (tm == 1 && !g_rows_stamps && (N + 512) * (int64_t)nkb * 8 < (1ll << 32)) {
+    // persistent over the column tiles (one tile row; 32-bit u4 offsets into B)
+    const int64_t grid = std::min<int64_t>(tn, persistent_grid_limit());
+    dev::rbf_rows_split_glds_persist_kernel<<<dim3((unsigned)grid), dev::kRowsGldsThreads, 0, s>>>(
+        (const dev::u4*)X, Xsh, Xsq, a_rows, m_dev, (const dev::u4*)B, Bsh, Bsq, N, nkb, gamma, lines, ldl, out_rows,
+        (int)tn);
   } else {
-    static const bool b_cached = [] {  // A/B: DPSVM_ROWS_BNT=0 streams B with the default cache policy
-      const char* e = std::getenv("DPSVM_ROWS_BNT");
-      return e && std::string(e) == "0";
-    }();
-    // B ring depth: 3 (A/B: DPSVM_ROWS_BRING=5 — 3.42 vs 3.26-3.28 ms at the
-    // synthetic-2m round shape: the kernel is not bound by the B stream's
-    // latency; profiles/r6_rows_kernel.txt)
-    static const int bring = [] {
-      const char* e = std::getenv("DPSVM_ROWS_BRING");
-      return e && atoi(e) == 5 ? 5 : 3;
-    }();
-    auto k = g_rows_stamps ? dev::rbf_rows_split_glds_kernel<2, 3, true>
-             : b_cached ? (bring == 5 ? dev::rbf_rows_split_glds_kernel<0, 5> : dev::rbf_rows_split_glds_kernel<0, 3>)
-                        : (bring == 5 ? dev::rbf_rows_split_glds_kernel<2, 5> : dev::rbf_rows_split_glds_kernel<2, 3>);
-    // persistent over the column tiles (one tile row, nkb >= 3; A/B:
-    // DPSVM_ROWS_PERSIST=0)
-    static const bool persist = [] {
-      const char* e = std::getenv("DPSVM_ROWS_PERSIST");
-      return !(e && e[0] == '0');
-    }();
-    if (persist && tm == 1 && nkb >= 3 && !g_rows_stamps && bring == 3 && (N + 512) * (int64_t)nkb * 8 < (1ll << 32)) {
-      static const int cus = [] {
-        int n = 0;
-        HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()));
-        return std::max(8, n);
-      }();
-      const int64_t grid = std::min<int64_t>(tn, cus);
-      auto kp = b_cached ? dev::rbf_rows_split_glds_persist_kernel<0> : dev::rbf_rows_split_glds_persist_kernel<2>;
-      kp<<<dim3((unsigned)grid), dev::kRowsGldsThreads, 0, s>>>((const dev::u4*)X, Xsh, Xsq, a_rows, m_dev,
-                                                                (const dev::u4*)B, Bsh, Bsq, N, nkb, gamma, lines, ldl,
-                                                                out_rows, (int)tn);
-    } else {
-      k<<<dim3((unsigned)tm, (unsigned)tn), dev::kRowsGldsThreads, 0, s>>>(
-          (const dev::u4*)X, Xsh, Xsq, a_rows, m_dev, (const dev::u4*)B, Bsh, Bsq, N, (dp + 31) / 32, gamma, lines,
-          ldl, out_rows, g_rows_stamps);
-    }
+    auto k = g_rows_stamps ? dev::rbf_rows_split_glds_kernel<true> : dev::rbf_rows_split_glds_kernel<false>;
+    k<<<dim3((unsigned)tm, (unsigned)tn), dev::kRowsGldsThreads, 0, s>>>((const dev::u4*)X, Xsh, Xsq, a_rows, m_dev,
+                                                                        (const dev::u4*)B, Bsh, Bsq, N, nkb, gamma,
+                                                                        lines, ldl, out_rows, g_rows_stamps);
   }
   post_launch("rbf_rows_indexed_split", s);
 }
+
 
 }  // namespace launch
 }  // namespace dpsvm

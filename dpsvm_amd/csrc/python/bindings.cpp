@@ -583,8 +583,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("k_set_gram_stamps", [](uintptr_t p) { launch::set_gram_stamps((uint64_t*)p); },
         "diagnostics: the wide-wave Gram kernel writes 8 u64 stamps per workgroup at p (0: off)");
   m.def("k_set_split_gemm_variant", [](int v) { launch::set_split_gemm_variant(v); },
-        "split STORE GEMM: 0 auto (4, or 3 when dp <= 128), 1 register-staged tile per workgroup, 3 LDS-DMA, 4 persistent LDS-DMA (tests / A/B)");
+        "split STORE GEMM test hook: 0 auto, 1 Tile, 3 Glds, 11 W64Grid, 12 W64Persist (launch::split_gram_path)");
   m.def("k_split_gemm_variant", []() { return launch::split_gemm_variant(); });
+  m.def("k_split_gram_path", [](int64_t M, int64_t N, int dp, int64_t ld, bool sym, bool cold) {
+    return std::string(launch::gram_path_name(
+        launch::split_gram_path(launch::GramShape{M, N, ld, dp, sym, cold}, launch::split_gemm_variant())));
+  }, py::arg("M"), py::arg("N"), py::arg("dp"), py::arg("ld"), py::arg("sym"), py::arg("cold"),
+     "the path rbf_gemm_store_split takes for an M x N Gram of dp columns into rows of ld floats, under the current "
+     "variant (cold: cold_tau > 0 and gamma > 0): Tile, Glds, W64Grid, W64Persist or Adaptive");
   m.def("k_split_rows", [](uintptr_t x, int64_t rows, int dp, int ldx, uintptr_t out, uintptr_t shift,
                            uintptr_t stream) {
     launch::split_rows_f16((const float*)x, rows, dp, ldx, (void*)out, (int32_t*)shift, (hipStream_t)stream);

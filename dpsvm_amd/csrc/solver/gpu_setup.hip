@@ -823,17 +823,22 @@ GpuSetupInfo GpuSolver::setup(const float* xh, int64_t n_x_rows, int64_t n, int 
     const int mode = adapt_env >= 0 ? adapt_env : m.p.gram_adapt;
     DPSVM_CHECK(mode >= 0 && mode <= 2, "gram_adapt must be 0 (auto), 1 (on) or 2 (off)");
     DPSVM_CHECK(m.p.gram_cold_tau > 0.f && m.p.gram_cold_tau <= 1e-3f, "gram_cold_tau must be in (0, 1e-3]");
-    // (the one-product pass needs >= 5 split blocks a row: dp > 128; shorter rows keep the three-product Gram)
-    // and the adaptive kernels' indexing (rbf_gemm_store_split's idx_adapt)
-    const bool cand = m.gram_split && m.kind == EngineKind::WsDense && mode != 2 && m.gamma > 0.f && m.dp > 128 &&
-                      (int64_t)(n + 512) * ((m.dp + 31) / 32) * 8 < (1ll << 31) && m.ldl < (1ll << 22);
+    // the Gram launches the solve will make, were they cold (launch::split_gram_path: the adaptive pass needs
+    // >= 5 split blocks a row and its kernels' index ranges; other shapes keep the three-product Gram).
+    // Replicated X: all n rows against the local ones; partitioned X: panel by panel, the largest shard first
+    const bool sym = m.replicated && m.off == 0 && m.nl == n;
+    const launch::GramShape shape{m.replicated ? n : shard_of(n, 0, m.world).size, m.nl, m.ldl, m.dp, sym,
+                                  m.gamma > 0.f};
+    const bool cand = m.gram_split && m.kind == EngineKind::WsDense && mode != 2 &&
+                      launch::split_gram_path(shape, launch::split_gemm_variant()) == launch::GramPath::Adaptive;
     const bool ok = cand && (mode == 1 || gram_cold_sample_ok(xh, n_x_rows, d, m.gamma, m.p.gram_cold_tau));
     m.gram_cold_tau = m.all_agree(ok, m.comm, m.world) ? m.p.gram_cold_tau : 0.f;
     if (m.gram_cold_tau > 0.f) m.info.gram = "split-f16-adaptive";
     // one rank's whole symmetric Gram: the split rows and the one-product pass's operands once, here
-    if (m.gram_cold_tau > 0.f && m.replicated && m.off == 0 && m.nl == n) {
+    if (m.gram_cold_tau > 0.f && sym) {
       launch::split_rows_f16(m.x, m.x_rows, m.dp, m.dp, m.xs, m.xsh, m.stream);
-      if (launch::gram_adapt_prep(m.xs, m.xsq, n, m.dp, m.stream, &m.gram_prep)) m.bytes += m.gram_prep.bytes;
+      launch::gram_adapt_prep(m.xs, m.xsq, n, m.dp, m.ldl, m.stream, &m.gram_prep);
+      m.bytes += m.gram_prep.bytes;
       HIP_CHECK(hipStreamSynchronize(m.stream));
     }
   }

@@ -72,6 +72,13 @@ def rbf_gram(a: torch.Tensor, b: torch.Tensor | None = None, gamma: float = 1.0,
     return out[:, :n]
 
 
+def split_gram_path(m: int, n: int, d: int, sym: bool = False, cold: bool = False) -> str:
+    """The launch path rbf_gram(split=True) takes for an m x n Gram of d
+    columns under the current variant (launch::split_gram_path: Tile, Glds,
+    W64Grid, W64Persist or Adaptive), with rbf_gram's own padding."""
+    return load().k_split_gram_path(m, n, (d + 15) // 16 * 16, (n + 127) // 128 * 128, sym, cold)
+
+
 def gram_adapt_last() -> tuple[int, int]:
     """(one-product tiles, hot tiles recomputed) of this thread's last adaptive
     split Gram, or (-1, -1) when it was not adaptive."""

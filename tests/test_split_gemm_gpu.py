@@ -88,8 +88,8 @@ def test_split_gram_extreme_row_scales(K):
 
 @pytest.mark.parametrize("n,m,d", [(1000, 777, 784), (4133, 2300, 300), (2600, 129, 1024)])
 def test_split_gram_persistent_bit_identical_to_tile_kernel(K, n, m, d):
-    """The LDS-DMA STORE GEMMs (tile per workgroup, persistent) run the
-    register-staged tile kernel's MFMA sequence per tile: the same bits,
+    """The LDS-DMA STORE GEMMs (tile per workgroup, wide-wave, persistent) run
+    the register-staged tile kernel's MFMA sequence per tile: the same bits,
     symmetric (upper tiles + mirrored stores) and plain, with partial edge tiles."""
     from dpsvm_amd._native import load
 
@@ -98,19 +98,57 @@ def test_split_gram_persistent_bit_identical_to_tile_kernel(K, n, m, d):
     x = torch.from_numpy(rng.random((n, d), dtype=np.float32)).cuda()
     y = torch.from_numpy(rng.standard_normal((m, d), dtype=np.float32)).cuda()
     g = 1.0 / d
+    # LDS-DMA (three k blocks in flight); wide-wave 256 x 128, a tile per workgroup; persistent; auto
+    paths = {1: "Tile", 3: "Glds", 11: "W64Grid", 12: "W64Persist", 0: "W64Persist"}
     try:
         C.k_set_split_gemm_variant(1)
         ref_sym, ref_xy = K.rbf_gram(x, None, g, split=True), K.rbf_gram(x, y, g, split=True)
         got = {}
-        for v in (3, 4, 5):  # LDS-DMA (three k blocks in flight); persistent LDS-DMA; wide-wave 256 x 128
+        for v in (1, 3, 11, 12, 0):
             C.k_set_split_gemm_variant(v)
-            got[v] = K.rbf_gram(x, None, g, split=True), K.rbf_gram(x, y, g, split=True)
+            assert K.split_gram_path(n, n, d, sym=True) == paths[v], v
+            assert K.split_gram_path(n, m, d) == paths[v], v
+            if v != 1:
+                got[v] = K.rbf_gram(x, None, g, split=True), K.rbf_gram(x, y, g, split=True)
     finally:
         C.k_set_split_gemm_variant(0)
     for v, (got_sym, got_xy) in got.items():
         assert torch.equal(got_sym, ref_sym), v
         assert torch.equal(got_xy, ref_xy), v
         assert torch.isfinite(got_sym).all() and torch.isfinite(got_xy).all()
+
+
+def test_split_gram_wide_output_beyond_packed_epilogue_range(K):
+    """Output rows of 2^21 floats or more: a 256-row tile no longer fits the
+    wide-wave kernels' 2^31-byte buffer descriptor (its late rows' stores were
+    dropped by the hardware range check, leaving the NaN fill), so the plan is
+    the LDS-DMA kernel with 64-bit indexing, adaptive or not: no NaN, and the
+    tile kernel's bits."""
+    from dpsvm_amd._native import load
+
+    free, _ = torch.cuda.mem_get_info()
+    if free < 24 << 30:
+        pytest.skip("needs ~12 GB of free device memory")
+    C = load()
+    m, n, d = 256, 2**21 + 2**19 + 77, 130  # 5 k blocks a row: the wide-wave kernels' range
+    gen = torch.Generator(device="cuda").manual_seed(21)
+    a = torch.rand((m, d), device="cuda", generator=gen)
+    b = torch.rand((n, d), device="cuda", generator=gen)
+    g = 1.0 / d
+    try:
+        C.k_set_split_gemm_variant(1)
+        ref = K.rbf_gram(a, b, g, split=True)
+    finally:
+        C.k_set_split_gemm_variant(0)
+    assert K.split_gram_path(m, n, d) == "Glds"
+    assert K.split_gram_path(m, n, d, cold=True) == "Glds"
+    got = K.rbf_gram(a, b, g, split=True)
+    assert not torch.isnan(got).any()
+    assert torch.equal(got, ref)
+    del got
+    cold = K.rbf_gram(a, b, g, split=True, cold_tau=2.0 ** -22)
+    assert K.gram_adapt_last() == (-1, -1)
+    assert torch.equal(cold, ref)
 
 
 def _split_model(X, dp):

@@ -21,7 +21,7 @@ rank count: tests/test_ws_gpu.py sharded-vs-replicated tests).
 
 With a pass-1 probe file (bench/pass1_probe.py: the multi-block f-update pass 1
 measured alone at a rank's shard shape, 60000 x 60000 / P, with the workgroup
-split the solver picks, ws_pass1_splits) pass 1 at P > 1 is that measurement
+split the solver picked in round 3) pass 1 at P > 1 is that measurement
 instead of the one-rank time / P — pass 1 does not divide by P (few selection
 groups per rank: profiles/r3_pass1_probe.txt).
 """
@@ -33,7 +33,7 @@ UNION = 6144      # rows per round (device_state.hpp kWsMaxAll); blocks of UNION
 
 
 def pass1_splits(G: int) -> int:
-    return max(1, min(16, 256 // max(1, G)))  # kernels ws_pass1_splits
+    return max(1, min(16, 256 // max(1, G)))  # the selection-geometry pass 1's slices (round 3)
 
 
 def pass1_v4_splits(p1G: int) -> int:

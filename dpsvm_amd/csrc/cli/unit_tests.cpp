@@ -11,6 +11,7 @@
 #include "dpsvm/common.hpp"
 #include "dpsvm/io.hpp"
 #include "dpsvm/solver.hpp"
+#include "dpsvm/ws_plan.hpp"
 #include "kernels/kernels.hpp"
 
 using namespace dpsvm;
@@ -241,6 +242,94 @@ static void test_gram_path() {
   EXPECT(path(1000, 777, 896, 100, false, false, 1) == GramPath::Tile);
 }
 
+// ws_round_plan / ws_round_shape (dpsvm/ws_plan.hpp): the working-set round's shape, case by case.
+// Unless stated: 60,000 rows, ws_size 192, ws_blocks auto, one rank, 256 CUs, the peer exchange's self test passes.
+static void test_ws_plan() {
+  struct Case {
+    const char* name;
+    WsPlanFacts f;
+    int blocks, q_max;
+  };
+  auto facts = [](auto&& edit) {
+    WsPlanFacts f;
+    f.n = 60000;
+    f.dp = 784;
+    f.uncoupled = true;
+    f.ws_dense = true;
+    f.cus = 256;
+    edit(f);
+    int32_t rpt = 0;
+    launch::ws_geometry((f.n + f.world - 1) / f.world, f.world, &f.ws_G, &rpt);
+    return f;
+  };
+  auto ranks = [](WsPlanFacts& f, int world, int share) {
+    f.world = world;
+    f.share = share;
+  };
+  auto cache = [](WsPlanFacts& f, int64_t L) {
+    f.ws_dense = false;
+    f.ws_cache = true;
+    f.L = L;
+  };
+  const Case cases[] = {
+      {"uncoupled dense", facts([](WsPlanFacts&) {}), 128, 48},
+      {"coupled dense", facts([](WsPlanFacts& f) { f.uncoupled = false; }), 32, 96},
+      {"uncoupled cache, L at the bound", facts([&](WsPlanFacts& f) { cache(f, 14336); }), 64, 48},
+      {"uncoupled cache, L below it", facts([&](WsPlanFacts& f) { cache(f, 14335); }), 1, 192},
+      {"below the auto row count", facts([](WsPlanFacts& f) { f.n = 49999; }), 1, 192},
+      {"at the auto row count", facts([](WsPlanFacts& f) { f.n = 50000; }), 128, 48},
+      {"ws_size 64, coupled", facts([](WsPlanFacts& f) { f.ws_size = 64, f.uncoupled = false; }), 32, 64},
+      {"ws_size 32, uncoupled", facts([](WsPlanFacts& f) { f.ws_size = 32; }), 128, 32},
+      {"ws_blocks 8", facts([](WsPlanFacts& f) { f.ws_blocks = 8; }), 8, 192},
+      {"ws_blocks 4, odd ws_size", facts([](WsPlanFacts& f) { f.ws_blocks = 4, f.ws_size = 95; }), 1, 95},
+      {"4 ranks on one device", facts([&](WsPlanFacts& f) { ranks(f, 4, 4); }), 64, 48},
+      {"8 ranks on one device", facts([&](WsPlanFacts& f) { ranks(f, 8, 8); }), 32, 48},
+      {"2 ranks, own devices", facts([&](WsPlanFacts& f) { ranks(f, 2, 1); }), 128, 48},
+      {"8 ranks, own devices", facts([&](WsPlanFacts& f) { ranks(f, 8, 1); }), 128, 48},
+      {"4 ranks on one device, forced collectives",
+       facts([&](WsPlanFacts& f) { ranks(f, 4, 4), f.force_collectives = true, f.device_comm = true; }), 128, 48},
+  };
+  for (const Case& c : cases) {
+    const WsRoundPlan p = ws_round_plan(c.f);
+    const WsRoundShape s = ws_round_resolve(c.f, p, true, true);
+    const bool ok = p.error.empty() && s.blocks == c.blocks && s.q_max == c.q_max;
+    if (!ok) fprintf(stderr, "  ws_plan %s: %d x %d (want %d x %d) %s\n", c.name, s.blocks, s.q_max, c.blocks, c.q_max, p.error.c_str());
+    EXPECT(ok);
+  }
+  {  // the headline's shape in full, and the coupled one
+    WsPlanFacts f = cases[0].f;
+    WsRoundShape s = ws_round_resolve(f, ws_round_plan(f), true, true);
+    EXPECT(s.ncand == kWsCand && s.direct_sub == 1 && s.n_new == 48 && s.inner_max == 192 && s.note.empty());
+    EXPECT(ws_round_plan(f).p1G == 59 && ws_round_plan(f).ks == 4);
+    f = cases[1].f;
+    s = ws_round_resolve(f, ws_round_plan(f), true, true);
+    EXPECT(s.ncand == kWsCandStd && s.direct_sub == 0 && s.n_new == 96 && s.inner_max == 384);
+    // exchange=peer at one rank (loopback): the solve gathers through the exchange
+    f = cases[0].f;
+    f.exchange = 2;
+    EXPECT(ws_round_resolve(f, ws_round_plan(f), true, true).direct_sub == 0);
+  }
+  {  // refused: ws_blocks x ws_size beyond the union capacity
+    const WsPlanFacts f = facts([](WsPlanFacts& f) { f.ws_blocks = 64; });
+    EXPECT(ws_round_plan(f).error.find("the round's union capacity") != std::string::npos);
+  }
+  {  // ws_blocks asked for, one block run: the note
+    const WsRoundShape s = ws_round_resolve(cases[9].f, ws_round_plan(cases[9].f), true, true);
+    EXPECT(s.note.find("one block per round") != std::string::npos && s.n_new == 95 && s.inner_max == 380);
+  }
+  {  // ranks sharing a device: the halved union fits the wave slots, the self test decides the carrier
+    const WsPlanFacts& f = cases[10].f;
+    const WsRoundPlan p = ws_round_plan(f);
+    EXPECT(p.xch_resident && p.xch_waves == 4 * (64 + 16 * 64) + 1024 && p.peer_multi && !p.collectives_multi);
+    EXPECT(ws_round_resolve(f, p, true, false).blocks == 1);   // self test failed, host communicator
+    EXPECT(ws_round_resolve(f, p, false, true).blocks == 1);   // a peer's cache is too small
+    // 8 ranks of one block each do not fit a 40-CU device: collectives, with the reason
+    WsPlanFacts g = facts([&](WsPlanFacts& f) { ranks(f, 8, 8), f.cus = 40, f.n = 3000; });
+    const WsRoundPlan q = ws_round_plan(g);
+    EXPECT(!q.xch_resident && !q.peer_one && q.note.find("8 ranks share a device") != std::string::npos);
+  }
+}
+
 static void test_gpu() {
   if (device_count() == 0) {
     printf("  (no GPU: device tests skipped)\n");
@@ -281,6 +370,7 @@ int main(int argc, char** argv) {
       {"cpu_solver_ranks", test_cpu_solver_ranks},
       {"cpu_checkpoint_resume", test_cpu_checkpoint_resume},
       {"gram_path", test_gram_path},
+      {"ws_plan", test_ws_plan},
   };
   if (gpu) tests.push_back({"gpu", test_gpu});
   for (auto& [name, fn] : tests) {

@@ -300,6 +300,10 @@ constexpr int kWsCacheWindow = 512;               // ws-cache: victim lines sear
 // ws-cache needs the round's rows (2 q_max: this round's and last round's
 // members are pinned) plus the victim window
 inline int64_t ws_cache_min_lines(int q_max) { return 2 * (int64_t)q_max + kWsCacheWindow; }
+// ... and its multi-block rounds the union's (P blocks of q rows), with the
+// multi-block merge's wider window
+constexpr int kWsWindowMulti = 8192;              // ws-cache: CLOCK victim window of the multi-block merge
+inline int64_t ws_cache_multi_min_lines(int blocks, int q) { return 2 * (int64_t)blocks * q + kWsWindowMulti; }
 
 // -s N (cache_lines > 0) on the engines a setup may choose: the reference takes
 // any count (svmTrainMain.cpp:71, default 10; cache.cu:49-60, 82-105).  The
@@ -313,6 +317,7 @@ inline int64_t production_line_cap(int64_t cache_lines, int ws_q, int engines) {
 }
 constexpr int kWsMergeThreads = 1024;             // multi-block merge: one workgroup
 constexpr int kWsMaxPass1Splits = 16;             // multi-block f-update pass 1: list slices over workgroups
+constexpr int kWsPass1Cols = 1024;                // ... its wide layout: columns per workgroup (ws_pass1_v4_kernel)
 constexpr int64_t kWsAutoBlocksRows = 50000;      // ws_blocks auto: multi-block rounds from this many rows on
 constexpr int64_t kWsSwitchRounds = 32;           // multi-block -> one-block graph switch granularity (rounds)
 

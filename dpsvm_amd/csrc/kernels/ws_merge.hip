@@ -1,6 +1,7 @@
 // Working-set engine, merge and gather: the stop test and the next working
 // set from every workgroup's candidate lists (one-block: ws_gather / ws_merge;
-// multi-block: ws_rank + ws_merge_multi, the union of P blocks), the cache
+// multi-block: ws_rank_merge, the rank sort and the union of P blocks in one
+// launch), the cache
 // mode's line assignment, and the sub-Gram rows of the set (ws_gather*).
 // Round structure and shared helpers: ws_common.hpp.
 #include <hip/hip_runtime.h>
@@ -297,7 +298,6 @@ __device__ __forceinline__ int multi_scan_merge(const int (&v)[X], int (&slot)[X
 // ((i / 2) mod P): each block gets up / low pairs, block 0 the global extremes
 // (so a round always holds the maximal violating pair and makes progress).
 constexpr int kMH = 8192;  // merge hash slots per side (load <= 0.19 at 3,072-row unions, <= 0.38 at 6,144)
-constexpr int kWsWindowMulti = 8192;  // cache mode: CLOCK victim window of the multi-block merge
 static_assert(kMH == 8192, "11-bit bucket hash");
 // keys: row indices (-1 empty) in buckets of four slots read as one 16-B LDS
 // word (a bucket fills left to right: no holes, so a free last slot ends a
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(kXCollectThreads) void ws_xcollect_cand_kernel(WsAr
 }
 
 // ws_rank: the multi-block merge's sort, spread over a grid of 2 sides x
-// kRankChunks workgroups instead of one workgroup's bitonic network (29 of the
+// kRankGroups (64) workgroups instead of one workgroup's bitonic network (29 of the
 // merge's 41 us at 3,072-row unions, profiles/r3_ws_stamps_32x96.json).  A
 // key's position in its side's ascending order is the number of keys below it:
 // real keys are unique (the global row index is in the low bits), so these
@@ -431,23 +431,18 @@ __global__ __launch_bounds__(kXCollectThreads) void ws_xcollect_cand_kernel(WsAr
 // SUB = 16 threads per key each counting over every SUB-th key pair (the SUB
 // lanes of one key read 16 consecutive 16-B pairs: no bank conflict, broadcast
 // over keys).
-constexpr int kRankThreads = 512;
-constexpr int kRankChunks = kWsMaxGroups * kWsCand / 32;  // 32 keys per workgroup, 16 threads per key
-template <int T>
 struct RankLds {
   uint64_t k[kWsMaxGroups * kWsCand];
-  int real[T / 64];
+  int real[kWsMergeThreads / 64];
 };
-// one rank workgroup's work (the caller checked c->done): T threads rank T /
-// 16 keys of one side, 16 threads per key; 2 x NK x 16 / T workgroups
-template <int T>
-constexpr int rank_chunks() { return kWsMaxGroups * kWsCand * 16 / T; }
-template <int T, bool kCoherent = false>
-__device__ __forceinline__ void ws_rank_body(const WsArgs& a, RankLds<T>& L) {
-  constexpr int NK = kWsMaxGroups * kWsCand, CH = rank_chunks<T>();
+// one rank workgroup's work (the caller checked c->done): kWsMergeThreads
+// threads rank 64 keys of one side, 16 threads per key; 2 x kRankGroups workgroups
+constexpr int kRankGroups = kWsMaxGroups * kWsCand * 16 / kWsMergeThreads;
+__device__ __forceinline__ void ws_rank_body(const WsArgs& a, RankLds& L) {
+  constexpr int T = kWsMergeThreads;
+  constexpr int NK = kWsMaxGroups * kWsCand, CH = kRankGroups;
   constexpr int KPW = NK / CH, SUB = T / KPW, PAIRS = NK / (2 * SUB);
   static_assert(NK % CH == 0 && T % KPW == 0 && SUB == 16 && NK % (2 * SUB) == 0, "rank geometry");
-  constexpr int kRankThreads = T;
   uint64_t* const s_k = L.k;
   int* const s_real = L.real;
   const WsCtrl* c = a.ctrl;
@@ -458,17 +453,17 @@ __device__ __forceinline__ void ws_rank_body(const WsArgs& a, RankLds<T>& L) {
   {
     // all NK / threads loads in flight before the LDS stores (a rolled loop
     // paid one L2 round trip per key: ~5 of the kernel's 8 us)
-    constexpr int PER = NK / kRankThreads;
-    static_assert(NK % kRankThreads == 0, "rank load geometry");
+    constexpr int PER = NK / T;
+    static_assert(NK % T == 0, "rank load geometry");
     uint64_t kk[PER];
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
-      const int e = tid + j * kRankThreads, l = e / kWsCand, r = e % kWsCand;
+      const int e = tid + j * T, l = e / kWsCand, r = e % kWsCand;
       kk[j] = l < G ? a.cand[(size_t)l * 2 * kWsCand + side * kWsCand + r] : kKeyNone;
     }
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
-      s_k[tid + j * kRankThreads] = kk[j];
+      s_k[tid + j * T] = kk[j];
       real += kk[j] != kKeyNone ? 1 : 0;
     }
   }
@@ -478,7 +473,7 @@ __device__ __forceinline__ void ws_rank_body(const WsArgs& a, RankLds<T>& L) {
   __syncthreads();
   int n_real = 0;
 #pragma unroll
-  for (int w = 0; w < kRankThreads / 64; ++w) n_real += s_real[w];
+  for (int w = 0; w < T / 64; ++w) n_real += s_real[w];
   const int e = chunk * KPW + tid / SUB, sub = tid % SUB;
   const uint64_t k = s_k[e];
   int cnt = 0;
@@ -490,21 +485,13 @@ __device__ __forceinline__ void ws_rank_body(const WsArgs& a, RankLds<T>& L) {
 #pragma unroll
   for (int o = 1; o < SUB; o <<= 1) cnt += __shfl_xor(cnt, o);
   uint64_t* out = a.sorted + (size_t)side * NK;
-  // coherent (the fused rank + merge): agent-scope (sc1) stores, read by
-  // another workgroup of the same launch with sc1 loads — no L2 write-back
+  // agent-scope (sc1) stores, read by another workgroup of the same launch
+  // (the merge) with sc1 loads — no L2 write-back
   auto put = [&](int i, uint64_t v) {
-    if constexpr (kCoherent) __hip_atomic_store(out + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else out[i] = v;
+    __hip_atomic_store(out + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   if (sub == 0 && k != kKeyNone) put(cnt, k);
   if (tid < KPW && chunk * KPW + tid >= n_real) put(chunk * KPW + tid, kKeyNone);
-}
-
-__global__ __launch_bounds__(kRankThreads) void ws_rank_kernel(WsArgs a) {
-  static_assert(rank_chunks<kRankThreads>() == kRankChunks, "rank grid");
-  __shared__ RankLds<kRankThreads> L;
-  if (a.ctrl->done != kRunning) return;
-  ws_rank_body<kRankThreads>(a, L);
 }
 
 struct MergeLds {
@@ -515,10 +502,9 @@ struct MergeLds {
   int wsum[kWsMergeThreads / 64];
   int msum[(kWsMaxGroups * kWsCand / kWsMergeThreads) * (kWsMergeThreads / 64)];
 };
-// the merge on one workgroup (the caller checked c->done).  coherent: the
-// ranked keys were written by other workgroups of the same launch (the fused
-// rank + merge): read them with agent-scope loads, not through this XCD's L2
-template <bool kCoherent>
+// the merge on one workgroup (the caller checked c->done).  The ranked keys
+// were written by other workgroups of the same launch (ws_rank_body): read
+// them with agent-scope loads, not through this XCD's L2
 __device__ __forceinline__ void ws_merge_multi_body(const WsArgs& a, MergeLds& L) {
   constexpr int T = kWsMergeThreads;
   constexpr int NK = kWsMaxGroups * kWsCand;  // keys per side
@@ -548,8 +534,7 @@ __device__ __forceinline__ void ws_merge_multi_body(const WsArgs& a, MergeLds& L
   // keys e = tid + x T of each side, in ascending order (ws_rank)
   uint64_t v[2][X];  // [side][element]
   auto ld_sorted = [&](int i) -> uint64_t {
-    if constexpr (kCoherent) return __hip_atomic_load(a.sorted + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return a.sorted[i];
+    return __hip_atomic_load(a.sorted + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
 #pragma unroll
   for (int x = 0; x < X; ++x) {
@@ -787,15 +772,6 @@ __device__ __forceinline__ void ws_merge_multi_body(const WsArgs& a, MergeLds& L
   }
 }
 
-__global__ __launch_bounds__(kWsMergeThreads) void ws_merge_multi_kernel(WsArgs a) {
-  __shared__ MergeLds L;
-  if (a.ctrl->done != kRunning) {
-    if (threadIdx.x == 0) a.ctrl->n_apply = 0;  // applied by the last ws_select already
-    return;
-  }
-  ws_merge_multi_body<false>(a, L);
-}
-
 // rank + merge in one launch: the rank workgroups publish their keys with
 // agent-scope (sc1) stores, every storing wave waits for them, then one lane a
 // workgroup takes a ticket (agent-scope add); the workgroup whose add comes
@@ -807,7 +783,7 @@ __global__ __launch_bounds__(kWsMergeThreads) void ws_merge_multi_kernel(WsArgs 
 // workgroup shape (1,024 threads: 2 x 64 rank workgroups of 64 keys).
 __global__ __launch_bounds__(kWsMergeThreads) void ws_rank_merge_kernel(WsArgs a) {
   __shared__ union {
-    RankLds<kWsMergeThreads> r;
+    RankLds r;
     MergeLds m;
   } L;
   __shared__ int s_last;
@@ -816,7 +792,7 @@ __global__ __launch_bounds__(kWsMergeThreads) void ws_rank_merge_kernel(WsArgs a
     if (blockIdx.x == 0 && threadIdx.x == 0) c->n_apply = 0;  // (the merge's early exit)
     return;
   }
-  ws_rank_body<kWsMergeThreads, true>(a, L.r);
+  ws_rank_body(a, L.r);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's sc1 stores done
   __syncthreads();
   if (threadIdx.x == 0)
@@ -825,7 +801,7 @@ __global__ __launch_bounds__(kWsMergeThreads) void ws_rank_merge_kernel(WsArgs a
   __syncthreads();
   if (!s_last) return;  // uniform
   if (threadIdx.x == 0) c->rank_cnt = 0;  // the next round's tickets (a later launch)
-  ws_merge_multi_body<true>(a, L.m);
+  ws_merge_multi_body(a, L.m);
 }
 
 
@@ -908,19 +884,8 @@ void ws_merge_multi(const WsArgs& a, hipStream_t s) {
               "(cache mode) <= 4096 union rows and L >= 2 P q_max + 4096 lines");
   DPSVM_CHECK(a.sorted != nullptr, "ws_merge_multi: no sort buffer");
   DPSVM_CHECK(!a.xpeer || a.xcw >= 4 * kWsCand, "ws_merge_multi: peer exchange slots too narrow");
-  static const bool split = [] {  // A/B: DPSVM_WS_RANK_MERGE=split, the two launches of round 5
-    const char* e = std::getenv("DPSVM_WS_RANK_MERGE");
-    return e && std::string(e) == "split";
-  }();
-  if (split) {
-    dev::ws_rank_kernel<<<2 * dev::kRankChunks, dev::kRankThreads, 0, s>>>(a);
-    post_launch("ws_rank", s);
-    dev::ws_merge_multi_kernel<<<1, kWsMergeThreads, 0, s>>>(a);
-    post_launch("ws_merge_multi", s);
-  } else {
-    dev::ws_rank_merge_kernel<<<2 * dev::rank_chunks<kWsMergeThreads>(), kWsMergeThreads, 0, s>>>(a);
-    post_launch("ws_rank_merge", s);
-  }
+  dev::ws_rank_merge_kernel<<<2 * dev::kRankGroups, kWsMergeThreads, 0, s>>>(a);
+  post_launch("ws_rank_merge", s);
 }
 
 void ws_gather(const WsArgs& a, hipStream_t s) {
@@ -956,7 +921,7 @@ void ws_pack_rows(const float* x, int64_t off, int64_t nl, int dp, const float* 
 bool ws_cache_supported(int64_t L, int q_max) { return L >= ws_cache_min_lines(q_max); }
 
 bool ws_cache_multi_supported(int64_t L, int blocks, int q_max) {
-  return L >= 2 * (int64_t)blocks * q_max + dev::kWsWindowMulti;
+  return L >= ws_cache_multi_min_lines(blocks, q_max);
 }
 
 }  // namespace launch

@@ -374,16 +374,16 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
 // thread 4 adjacent ones (16-B row loads): each wave reads 1 KiB of a changed
 // Gram row per load instead of 256 B (HBM row-buffer locality of the scattered
 // rows), and p1G = ceil(nl_max / 1024) groups x ks list slices fill the device.
-// TPP threads per partition x PARTS partitions = 1024 threads; a workgroup owns
-// 4 TPP columns (TPP 256: 1024 columns, four partitions — the default; TPP 512:
-// 2048 columns, two partitions — A/B, DPSVM_P1_COLS=2048).  NT: the Gram rows
+// Four partitions of 256 threads = 1024 threads; a workgroup owns kWsPass1Cols
+// (1024) columns.  NT: the Gram rows
 // by non-temporal loads (each changed row is read once a round: no L2 / MALL
 // reuse to keep; ws_pass1_nt picks it)
 constexpr int kP1Threads = 4 * kWsSelThreads;
-template <int TPP, bool NT, int CH = 12>  // CH rows x 16 B in flight per thread
+template <bool NT>
 __global__ __launch_bounds__(kP1Threads) void ws_pass1_v4_kernel(WsArgs a) {
+  constexpr int TPP = kWsPass1Cols / 4;  // threads per partition: 4 adjacent columns each
   constexpr int PARTS = kP1Threads / TPP;
-  constexpr int kP1Cols = 4 * TPP;                  // columns per workgroup
+  constexpr int CH = 12;  // rows x 16 B in flight per thread (8 / 16: profiles/r6_late/nt_stores_and_p1_depth_rejected.txt)
   __shared__ int32_t s_idx[kWsMaxAll];
   __shared__ float s_coef[kWsMaxAll];
   __shared__ f4 s_part[PARTS - 1][TPP];
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(kP1Threads) void ws_pass1_v4_kernel(WsArgs a) {
     }
   }
   __syncthreads();
-  const int64_t j0 = (int64_t)grp * kP1Cols + 4 * tid;
+  const int64_t j0 = (int64_t)grp * kWsPass1Cols + 4 * tid;
   const bool has = j0 < a.nl;  // j0 + 4 <= round_up(nl, 4) <= ldg: the 16-B load stays in the row
   f4 acc = {0.f, 0.f, 0.f, 0.f};
   const int per = (na + PARTS * KS - 1) / (PARTS * KS);
@@ -549,17 +549,6 @@ void ws_xcollect_part(const WsArgs& a, hipStream_t s) {
   post_launch("ws_xcollect_part", s);
 }
 
-int ws_pass1_splits(int G) {
-  // about one pass-1 workgroup per CU of the 256-CU device: the selection
-  // geometry gives a rank of P only G = ceil(60000 / P / 256) groups on the
-  // headline (30 at P = 8), and pass 1 is then bound by the few CUs issuing
-  // loads — 3,072 changed rows x 7,500 columns: 114 us with 30 workgroups, 38 us
-  // with 240; with 60,000 columns 235 workgroups beat 470 / 705 (158 vs 167 /
-  // 189 us; profiles/r3_pass1_probe.txt).  Every rank uses the same G, so the
-  // same slice count and the same summation order.
-  return std::max(1, std::min(kWsMaxPass1Splits, 256 / std::max(1, G)));
-}
-
 void ws_geometry(int64_t nl_max, int world, int32_t* G, int32_t* rpt) {
   // every rank the same geometry (sized for the largest shard); the merge reads
   // world * G <= 1024 candidate lists (kWsListsPerThread per merge thread), so
@@ -600,53 +589,21 @@ void ws_select(const WsArgs& a, hipStream_t s) {
   }
 }
 
-// columns per wide pass-1 workgroup (A/B: DPSVM_P1_COLS=2048)
-int ws_pass1_v4_cols() {
-  static const int cols = [] {
-    const char* e = std::getenv("DPSVM_P1_COLS");
-    return e && atoi(e) == 2048 ? 2048 : 1024;
-  }();
-  return cols;
-}
-
 // the wide pass 1's Gram row loads: non-temporal where the Gram is far larger
 // than the 256 MB MALL (> 1 GiB: the rows of a round are not read again before
 // they would be evicted) — headline 0.0170 -> 0.0160 s, same trajectory
 // (profiles/r6_p1_nt_ab.txt); default policy below, where a small Gram's rows
-// stay MALL-resident from round to round.  DPSVM_P1_NT=0 / 1 forces it.
+// stay MALL-resident from round to round.
 static bool ws_pass1_nt(const WsArgs& a) {
-  static const int env = [] {
-    const char* e = std::getenv("DPSVM_P1_NT");
-    return e ? atoi(e) : -1;
-  }();
-  if (env == 0 || env == 1) return env == 1;
   const int64_t lines = a.cache ? (int64_t)a.L : a.n;
   return lines * a.ldg * (int64_t)sizeof(float) > (int64_t(1) << 30);
-}
-
-// rows in flight per thread of the non-temporal wide pass 1 (A/B: DPSVM_P1_CH=8 / 16)
-static int ws_pass1_ch() {
-  static const int ch = [] {
-    const char* e = std::getenv("DPSVM_P1_CH");
-    const int v = e ? atoi(e) : 12;
-    return v == 8 || v == 16 ? v : 12;
-  }();
-  return ch;
 }
 
 void ws_select_pass(const WsArgs& a, int pass, hipStream_t s) {
   if (pass == 1 && a.p1v4) {
     const dim3 g(a.p1G * std::max(1, a.ks));
-    if (ws_pass1_v4_cols() == 2048)
-      dev::ws_pass1_v4_kernel<512, false><<<g, dev::kP1Threads, 0, s>>>(a);
-    else if (ws_pass1_nt(a) && ws_pass1_ch() == 16)
-      dev::ws_pass1_v4_kernel<256, true, 16><<<g, dev::kP1Threads, 0, s>>>(a);
-    else if (ws_pass1_nt(a) && ws_pass1_ch() == 8)
-      dev::ws_pass1_v4_kernel<256, true, 8><<<g, dev::kP1Threads, 0, s>>>(a);
-    else if (ws_pass1_nt(a))
-      dev::ws_pass1_v4_kernel<256, true><<<g, dev::kP1Threads, 0, s>>>(a);
-    else
-      dev::ws_pass1_v4_kernel<256, false><<<g, dev::kP1Threads, 0, s>>>(a);
+    if (ws_pass1_nt(a)) dev::ws_pass1_v4_kernel<true><<<g, dev::kP1Threads, 0, s>>>(a);
+    else dev::ws_pass1_v4_kernel<false><<<g, dev::kP1Threads, 0, s>>>(a);
     post_launch("ws_pass1_v4", s);
   } else if (pass == 1) {
     ws_select_mode<1>(a, s);
@@ -654,15 +611,6 @@ void ws_select_pass(const WsArgs& a, int pass, hipStream_t s) {
     ws_select_mode<2>(a, s);
   }
 }
-
-int ws_pass1_v4_groups(int64_t nl_max) {
-  const int64_t cols = ws_pass1_v4_cols();
-  return (int)std::max<int64_t>(1, (nl_max + cols - 1) / cols);
-}
-
-// the wide pass 1's list slices: about one workgroup per CU (the headline at one
-// rank: 59 groups x 4 slices; a rank of 8: 8 groups x 32 slices)
-int ws_pass1_v4_splits(int p1G) { return std::max(1, std::min(2 * kWsMaxPass1Splits, 256 / std::max(1, p1G))); }
 
 }  // namespace launch
 }  // namespace dpsvm

@@ -15,6 +15,7 @@
 #include "dpsvm/io.hpp"
 #include "dpsvm/solver.hpp"
 #include "dpsvm/params_io.hpp"
+#include "dpsvm/ws_plan.hpp"
 #include "../kernels/kernels.hpp"
 
 namespace py = pybind11;
@@ -286,6 +287,53 @@ PYBIND11_MODULE(_C, m) {
     return py::str(engine_name(k));
   }, py::arg("ws_dense") = false, py::arg("ws_cache") = false, py::arg("dense") = false,
         py::arg("cache_replicated") = false, py::arg("persistent") = false, py::arg("quarantine") = false);
+  // the working-set round's shape (dpsvm/ws_plan.hpp: ws_round_plan, then ws_round_shape for the given
+  // outcomes of the ranks' agreement and the peer exchange's self test), for tests
+  m.def("ws_round_plan", [](int64_t n, int world, int ws_size, int ws_blocks, int ws_new, int ws_inner, int dp,
+                            bool uncoupled, bool ws_dense, bool ws_cache, int64_t L, int share, int cus,
+                            int exchange, bool force_collectives, bool device_comm, int ws_G, bool replicated,
+                            bool peers_eligible, bool selftest_ok) {
+    WsPlanFacts f;
+    f.n = n, f.world = world, f.ws_size = ws_size, f.ws_blocks = ws_blocks, f.ws_new = ws_new, f.ws_inner = ws_inner;
+    f.dp = dp, f.uncoupled = uncoupled, f.ws_dense = ws_dense, f.ws_cache = ws_cache, f.L = L;
+    f.share = share, f.cus = cus, f.exchange = exchange, f.force_collectives = force_collectives;
+    f.device_comm = device_comm, f.ws_G = ws_G, f.replicated = replicated;
+    if (ws_G <= 0) {  // the selection geometry setup would use
+      int32_t rpt = 0;
+      launch::ws_geometry((n + world - 1) / world, world, &f.ws_G, &rpt);
+    }
+    const WsRoundPlan p = ws_round_plan(f);
+    py::dict d;
+    d["error"] = p.error;
+    if (!p.error.empty()) return d;
+    const WsRoundShape s = ws_round_resolve(f, p, peers_eligible, selftest_ok);
+    d["want_blocks"] = p.want_blocks;
+    d["mb_q"] = p.mb_q;
+    d["multi_elig"] = p.multi_elig;
+    d["xch_resident"] = p.xch_resident;
+    d["xch_waves"] = p.xch_waves;
+    d["p1G"] = p.p1G;
+    d["ks"] = p.ks;
+    d["peer_multi"] = p.peer_multi;
+    d["peer_one"] = p.peer_one;
+    d["xch_words_multi"] = p.xch_words_multi;
+    d["xch_words_one"] = p.xch_words_one;
+    d["blocks"] = s.blocks;
+    d["q_max"] = s.q_max;
+    d["n_new"] = s.n_new;
+    d["inner_max"] = s.inner_max;
+    d["ncand"] = s.ncand;
+    d["direct_sub"] = s.direct_sub;
+    d["note"] = p.note.empty() ? s.note : s.note.empty() ? p.note : p.note + "; " + s.note;
+    return d;
+  }, py::arg("n"), py::arg("world") = 1, py::arg("ws_size") = kWsMax, py::arg("ws_blocks") = 0, py::arg("ws_new") = 0,
+        py::arg("ws_inner") = 0, py::arg("dp") = 784, py::arg("uncoupled") = false, py::arg("ws_dense") = true,
+        py::arg("ws_cache") = false, py::arg("L") = 0, py::arg("share") = 1, py::arg("cus") = 256,
+        py::arg("exchange") = 0, py::arg("force_collectives") = false, py::arg("device_comm") = false,
+        py::arg("ws_G") = 0, py::arg("replicated") = true, py::arg("peers_eligible") = true,
+        py::arg("selftest_ok") = true);
+  m.attr("kWsCand") = kWsCand;
+  m.attr("kWsCandStd") = kWsCandStd;
   m.def("write_checkpoint", &write_checkpoint, py::arg("path"), py::arg("ck"));
   m.def("read_checkpoint", &read_checkpoint, py::arg("path"));
 

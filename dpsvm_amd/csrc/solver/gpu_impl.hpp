@@ -20,6 +20,7 @@
 
 #include "dpsvm/device_state.hpp"
 #include "dpsvm/solver.hpp"
+#include "dpsvm/ws_plan.hpp"
 #include "../kernels/kernels.hpp"
 #include "../runtime/hip_check.hpp"
 

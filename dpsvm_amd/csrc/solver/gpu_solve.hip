@@ -166,11 +166,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   // last completed launch times its per-launch decay predicts the stop test
   // to pass within the launch in flight, the following launches are single
   // rounds.  The status is identical on every rank, so is the decision.
-  static const bool tail_env = [] {  // A/B: DPSVM_SHORT_TAIL=0 keeps full launches to the end
-    const char* e = std::getenv("DPSVM_SHORT_TAIL");
-    return !(e && atoi(e) == 0);
-  }();
-  const bool can_short = tail_env && m.engine->shortens() && B > 1;
+  const bool can_short = m.engine->shortens() && B > 1;
   bool near = false;
   int near_left = 0;
   double prev_gap = -1.0;

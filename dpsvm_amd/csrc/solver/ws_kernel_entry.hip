@@ -246,7 +246,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   a.p1G = G;
   if (wide && blocks > 1) {  // the wide pass 1 (ws_pass1_v4_kernel)
     a.p1v4 = 1;
-    a.p1G = launch::ws_pass1_v4_groups(n);
+    a.p1G = ws_pass1_v4_groups(n);
   }
   a.dfs = st.up(std::vector<float>(), (size_t)n * a.ks);
   a.part = st.up(std::vector<double>(), (size_t)2 * a.p1G * a.ks);

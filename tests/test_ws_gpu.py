@@ -874,3 +874,29 @@ def test_shrinking_lends_the_whole_solvers_cache_bit_identically(monkeypatch):
         outs.append(json.loads(r.stdout.strip().splitlines()[-1]))
     assert outs[0]["phases"] >= 2 and outs[0]["conv"]
     assert outs[0] == outs[1]
+
+
+@pytest.mark.parametrize("n,gamma,kw", [
+    (50000, 2.0, {}),     # the smallest row count auto takes multi-block rounds at; K ~ I: the wide union
+    (50000, 0.01, {}),    # the same rows, strongly coupled
+    (3000, 0.01, dict(solver="ws", ws_blocks=4, ws_size=96)),
+])
+def test_setup_runs_the_round_plan(n, gamma, kw):
+    """The round shape a solver reports is ws_round_plan's for the same facts
+    (dpsvm/ws_plan.hpp; tests/test_ws_plan.py walks the plan itself on a CPU)."""
+    from dpsvm_amd._native import load
+
+    X, y = synthetic("blobs", n=n, d=16, seed=3)
+    s = SVC(C=1.0, gamma=gamma, max_iter=500, device="cuda", **kw).fit(X, y)
+    info = s.setup_info_
+    assert info["iteration"] == "ws-dense"
+    # the coupling sample: 96 rows at a fixed stride, mean off-diagonal K (gpu_setup.hip)
+    S = X[:: n // 96][:96].astype(np.float64)
+    d2 = ((S[:, None, :] - S[None, :, :]) ** 2).sum(-1)
+    coupling = np.exp(-gamma * d2)[np.triu_indices(96, 1)].mean()
+    assert coupling < 1e-6 or coupling > 1e-2, coupling  # far from the 1e-4 threshold either way
+    p = load().ws_round_plan(n, ws_size=kw.get("ws_size", 192), ws_blocks=kw.get("ws_blocks", 0), dp=info["dp"],
+                             uncoupled=bool(coupling < 1e-4), ws_dense=True)
+    print(n, gamma, coupling, info["ws_blocks"], info["ws_q_max"], p)
+    assert p["error"] == "" and (info["ws_blocks"], info["ws_q_max"]) == (p["blocks"], p["q_max"])
+    assert info["ws_blocks"] > 1

@@ -451,7 +451,7 @@ def test_ws_select_two_pass_line_search_matches_model(K, target, P, p_act):
 @pytest.mark.parametrize("ks", [2, 5])
 def test_ws_select_pass1_list_slices_match_model(K, ks):
     """Pass 1 split into ks slices of the changed-row list per selection group
-    (ws_pass1_splits: a rank's shard of a sharded run has few groups): the
+    (a rank's shard of a sharded run has few groups): the
     partials still sum to d'Qd and g'd, pass 2 sums the slices' changes, and f
     after the round matches the model and the one-slice kernel."""
     rng = np.random.default_rng(40 + ks)

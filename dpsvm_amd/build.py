@@ -53,6 +53,8 @@ LIB_SOURCES = [
     "kernels/setup_kernels.hip",
     "kernels/rbf_gemm.hip",
     "kernels/rbf_gemm_split.hip",
+    "kernels/rbf_rows_split.hip",
+    "kernels/rbf_predict_split.hip",
     "kernels/smo_fused.hip",
     "kernels/microbench.hip",
     "kernels/compact.hip",

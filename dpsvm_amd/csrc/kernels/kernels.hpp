@@ -116,13 +116,16 @@ void rbf_gemm_store(const float* A, const float* Asq, int64_t M, int lda, const 
 void rbf_rows_indexed(const float* X, const float* Xsq, const int32_t* a_rows, const int32_t* m_dev, int64_t M_max,
                       const float* B, const float* Bsq, int64_t N, int dp, float gamma, float* lines,
                       const int32_t* out_rows, int64_t ldl, hipStream_t s);
-// The same two GEMMs on fp16 MFMA over split operands (rbf_gemm_split.hip):
+// The same two GEMMs on fp16 MFMA over split operands (rbf_gemm_split.hip,
+// rbf_rows_split.hip; the decision GEMM in rbf_predict_split.hip):
 // every X row scaled by 2^shift and stored as fp16 hi / lo planes ("split
 // rows", split_row_u4(dp) 16-B units per row; buffers hold split_pad_rows(rows)
 // rows, pad zeroed); fp32 accuracy, bit-identical under operand swap
 int64_t split_row_u4(int dp);
 int64_t split_pad_rows(int64_t rows);
 void split_rows_f16(const float* x, int64_t rows, int dp, int ldx, void* out, int32_t* shift, hipStream_t s);
+// the persistent split kernels' grid limit: one workgroup per CU of the current device
+int persistent_grid_limit();
 // The split STORE GEMM's launch plan (host only: no HIP call, no environment, no state).
 //   Adaptive    one-product pass + three-product hot tiles: cold, >= 5 k blocks, ldo < 2^21, rows / tiles in 32 bits
 //   W64Persist  persistent wide-wave kernel: the same without cold, and M ldo, N ldo < 2^32 (the headline Gram)

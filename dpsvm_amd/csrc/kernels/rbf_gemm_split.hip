@@ -43,10 +43,14 @@
 //               product Grams of more than 2^32 elements)
 //   Glds        128 x 128 LDS-DMA tiles, 64-bit indexing: everything else
 //   Tile        forced only
-// The working-set row GEMM (rbf_rows_indexed_split): the persistent small-K
-// kernel up to 2 k blocks, else the LDS-DMA rows kernel, persistent over the
-// column tiles for one tile row.  Variants that lost their A/B are not
-// compiled; their measurements are in profiles/.
+// Variants that lost their A/B are not compiled; their measurements are in
+// profiles/.
+//
+// This file: the operand prep (split rows, h planes, log2 norms), the STORE
+// GEMMs (tile, glds, w64, w64p, h1s) and their launch plan.  The working-set
+// row GEMM is in rbf_rows_split.hip, the decision GEMM in
+// rbf_predict_split.hip; the k blocks and epilogues all of them share are in
+// split_mma.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,7 +65,7 @@
 #include "dpsvm/common.hpp"
 #include "device_util.hpp"
 #include "kernels.hpp"
-#include "split_util.hpp"
+#include "split_mma.hpp"
 #include "../runtime/hip_check.hpp"
 
 namespace dpsvm {
@@ -147,29 +151,6 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
   }
 }
 
-// XCD-aware tile order (as rbf_gemm.hip): linear workgroup id L runs on XCD
-// L % 8; chunks of 64 tiles (8 x 8 tile blocks) are dealt so that an XCD's
-// consecutive tiles share panels in its L2.  A bijection on the tm x tn grid.
-__device__ __forceinline__ void xcd_tile_of(int64_t L, int64_t tm, int64_t tn, int64_t& tx, int64_t& ty) {
-  const int64_t total = tm * tn;
-  constexpr int64_t CH = 64, GM = 8;
-  const int64_t full = total / (8 * CH) * (8 * CH);
-  int64_t T = L;
-  if (L < full) {
-    const int64_t xcd = L % 8, local = L / 8;
-    T = ((local / CH) * 8 + xcd) * CH + local % CH;
-  }
-  const int64_t first_m = (T / (GM * tn)) * GM;
-  const int64_t gm = min(GM, tm - first_m);
-  const int64_t in = T - first_m * tn;
-  tx = first_m + in % gm;
-  ty = in / gm;
-}
-
-__device__ __forceinline__ void xcd_tile(int64_t& tx, int64_t& ty) {
-  xcd_tile_of(blockIdx.x + (int64_t)blockIdx.y * gridDim.x, gridDim.x, gridDim.y, tx, ty);
-}
-
 // The register-staged tile kernel: the first split STORE GEMM, kept as the
 // tests' bit-identity reference for the LDS-DMA kernels below (GramPath::Tile,
 // forced only).  WM x WN = 4 x 2 waves, a 128 x 128 workgroup tile; KB = 2
@@ -242,10 +223,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void rbf_gemm_split_kernel(
   __syncthreads();
 
   f16v H[2], P[2], Q[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) H[j][r] = P[j][r] = Q[j][r] = 0.f;
+  zero_acc(H, P, Q);
 
   // operand rows of this lane: A row wm*32 + (lane&31), B rows TM + wn*64 + 32 j + (lane&31)
   const int sw = lane & 15, hl = lane >> 5;
@@ -258,22 +236,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void rbf_gemm_split_kernel(
 #pragma unroll
     for (int blk = 0; blk < KB; ++blk) {
       if (kt * KB + blk >= nkb) break;  // uniform
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int ch = (8 * blk + 2 * ks + hl) ^ sw, cl = (8 * blk + 4 + 2 * ks + hl) ^ sw;
-        const h8 ah = __builtin_bit_cast(h8, lds[cur][ra + ch]);
-        const h8 al = __builtin_bit_cast(h8, lds[cur][ra + cl]);
-        const h8 bh0 = __builtin_bit_cast(h8, lds[cur][rb0 + ch]);
-        const h8 bl0 = __builtin_bit_cast(h8, lds[cur][rb0 + cl]);
-        const h8 bh1 = __builtin_bit_cast(h8, lds[cur][rb1 + ch]);
-        const h8 bl1 = __builtin_bit_cast(h8, lds[cur][rb1 + cl]);
-        H[0] = mfma32_f16(ah, bh0, H[0]);
-        H[1] = mfma32_f16(ah, bh1, H[1]);
-        P[0] = mfma32_f16(ah, bl0, P[0]);
-        P[1] = mfma32_f16(ah, bl1, P[1]);
-        Q[0] = mfma32_f16(al, bh0, Q[0]);
-        Q[1] = mfma32_f16(al, bh1, Q[1]);
-      }
+      w32_kblock(H, P, Q, lds[cur], lds[cur], ra, rb0, rb1, hl, sw, 8 * blk);
     }
     if (more) {
 #pragma unroll
@@ -284,12 +247,13 @@ __global__ __launch_bounds__(kSplitThreads, 1) void rbf_gemm_split_kernel(
   }
 
   // ---- epilogue: K = exp(-g max(|a|^2 + |b|^2 - 2 dot, 0)), dot = 2^-(sa+sb) (H + (P + Q)) ----
-  // (all values first, into H; then the stores: unpredicated for interior tiles)
+  // (all values first, into H; then the stores: unpredicated for interior tiles.  The A rows' data goes
+  // through registers ahead of the B columns' global loads, so this loop is w32_values written out)
   float asq_r[16];
   int ash_r[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+    const int lr = wm * 32 + mfma32_row(r) + 4 * hl;
     asq_r[r] = s_asq[lr];
     ash_r[r] = s_ash[lr];
   }
@@ -300,49 +264,10 @@ __global__ __launch_bounds__(kSplitThreads, 1) void rbf_gemm_split_kernel(
     const float bsq = Bsq[cc];
     const int bsh = Bsh[cc];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float dot = ldexpf(H[j][r] + (P[j][r] + Q[j][r]), -(ash_r[r] + bsh));
-      H[j][r] = rbf_split_value(asq_r[r], bsq, dot, gamma);
-    }
+    for (int r = 0; r < 16; ++r) H[j][r] = w32_value(H[j][r], P[j][r], Q[j][r], ash_r[r], bsh, asq_r[r], bsq, gamma);
   }
-  const bool interior = m0 + TM <= M && n0 + TN <= N;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-      if (interior || (row < M && col < N)) out[row * ldo + col] = H[j][r];
-    }
-  }
-  if (sym && ty != tx) {
-    // transposed tile: a lane holds 4 consecutive rows per group -> 16-B stores out[col][row .. row+3]
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t row = m0 + wm * 32 + 8 * q + 4 * hl;
-        float* dst = out + col * ldo + row;
-        f4 v;
-        v.x = H[j][4 * q + 0];
-        v.y = H[j][4 * q + 1];
-        v.z = H[j][4 * q + 2];
-        v.w = H[j][4 * q + 3];
-        if (interior) {
-          *(f4*)dst = v;
-        } else if (col < M) {
-          if (row + 3 < N) {
-            *(f4*)dst = v;
-          } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-              if (row + c < N) dst[c] = v[c];
-          }
-        }
-      }
-    }
-  }
+  w32_store_tile(H, out, ldo, m0 + wm * 32, n0 + wn * 64, hl, lane, M, N, m0 + TM <= M && n0 + TN <= N,
+                 sym && ty != tx);
 }
 
 // ---------------------------------------------------------------------------
@@ -397,8 +322,7 @@ __global__ __launch_bounds__(kGldsThreads, 1) void rbf_gemm_split_glds_kernel(
     u4* dst = lds + (kb & (NB - 1)) * BUF + 32 * wave * CPR;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const void*)(src[i] + (int64_t)kb * 8),
-                                       (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, 0);
+      lds_dma16(src[i] + (int64_t)kb * 8, dst + 8 * i * CPR);
   };
   __syncthreads();  // row data written (no DMA in flight yet)
   dma(0);
@@ -406,10 +330,7 @@ __global__ __launch_bounds__(kGldsThreads, 1) void rbf_gemm_split_glds_kernel(
   if (nkb > 2) dma(2);
 
   f16v H[2], P[2], Q[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) H[j][r] = P[j][r] = Q[j][r] = 0.f;
+  zero_acc(H, P, Q);
   const int sw = ((lane & 31) >> 1) & 7;
   const int ra = (wm * 32 + (lane & 31)) * CPR;
   const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR, rb1 = rb0 + 32 * CPR;
@@ -419,621 +340,20 @@ __global__ __launch_bounds__(kGldsThreads, 1) void rbf_gemm_split_glds_kernel(
     if (ahead == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    ring_barrier();
     if (kb + 3 < nkb) dma(kb + 3);  // into the buffer of block kb - 1 (every wave is past it)
     const u4* buf = lds + (kb & (NB - 1)) * BUF;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int ch = (2 * ks + hl) ^ sw, cl = (4 + 2 * ks + hl) ^ sw;
-      const h8 ah = __builtin_bit_cast(h8, buf[ra + ch]);
-      const h8 al = __builtin_bit_cast(h8, buf[ra + cl]);
-      const h8 bh0 = __builtin_bit_cast(h8, buf[rb0 + ch]);
-      const h8 bl0 = __builtin_bit_cast(h8, buf[rb0 + cl]);
-      const h8 bh1 = __builtin_bit_cast(h8, buf[rb1 + ch]);
-      const h8 bl1 = __builtin_bit_cast(h8, buf[rb1 + cl]);
-      H[0] = mfma32_f16(ah, bh0, H[0]);
-      H[1] = mfma32_f16(ah, bh1, H[1]);
-      P[0] = mfma32_f16(ah, bl0, P[0]);
-      P[1] = mfma32_f16(ah, bl1, P[1]);
-      Q[0] = mfma32_f16(al, bh0, Q[0]);
-      Q[1] = mfma32_f16(al, bh1, Q[1]);
-    }
+    w32_kblock(H, P, Q, buf, buf, ra, rb0, rb1, hl, sw);
   }
 
   // ---- epilogue (as the tile kernel) ----
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int cb = TM + wn * 64 + 32 * j + (lane & 31);
-    const float bsq = s_sq[cb];
-    const int bsh = s_sh[cb];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-      const float dot = ldexpf(H[j][r] + (P[j][r] + Q[j][r]), -(s_sh[lr] + bsh));
-      H[j][r] = rbf_split_value(s_sq[lr], bsq, dot, gamma);
-    }
+    w32_values(H[j], P[j], Q[j], s_sq + wm * 32 + 4 * hl, s_sh + wm * 32 + 4 * hl, s_sq[cb], s_sh[cb], gamma);
   }
-  const bool interior = m0 + TM <= M && n0 + TN <= N;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-      if (interior || (row < M && col < N)) out[row * ldo + col] = H[j][r];
-    }
-  }
-  if (sym && ty != tx) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t row = m0 + wm * 32 + 8 * q + 4 * hl;
-        float* dst = out + col * ldo + row;
-        f4 v;
-        v.x = H[j][4 * q + 0];
-        v.y = H[j][4 * q + 1];
-        v.z = H[j][4 * q + 2];
-        v.w = H[j][4 * q + 3];
-        if (interior) {
-          *(f4*)dst = v;
-        } else if (col < M) {
-          if (row + 3 < N) {
-            *(f4*)dst = v;
-          } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-              if (row + c < N) dst[c] = v[c];
-          }
-        }
-      }
-    }
-  }
-}
-
-// the 32-bit LDS byte address of a __shared__ pointer (asm ds_read operands)
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-
-// ---------------------------------------------------------------------------
-// LDS-DMA ROWS GEMM: a working-set round's cache misses (up to 192 indexed A
-// rows, a_rows[0 .. *m_dev)) against all of this rank's B rows, K written to
-// the misses' cache lines.  The register-staged form of it (the tile kernel
-// above with indexed rows, since removed) waited for each 32-k stage's loads
-// before the next could start, so on synthetic-2m (K = 1024, 2M B rows: the
-// 8 GB split X panel per round) it ran at 2.3 TB/s of B bytes and 3.5 ms per
-// round (profiles/r4_big_inputs).  Here the operands of
-// a 192 x 128 tile go through three 32-k LDS buffers by global_load_lds_dwordx4
-// (40 KiB each; the row data after them in the same array), the next block's
-// DMA in flight while a block is multiplied; the waves (6 x 2, 32 x 64 each)
-// run the tile kernel's MFMA sequence and epilogue per element, so the rows are
-// bit-identical to the Gram kernels'.  Ten waves issue the DMA: 40
-// wave instructions of 8 rows x 128 B per block, 4 per wave.
-// ---------------------------------------------------------------------------
-constexpr int kRowsGldsThreads = 768;
-// kRowsBAux: cache policy of the B operand's DMA (2 = nt: streamed once per
-// round, kept from evicting the A rows every tile re-reads from L2)
-// NBR: B ring depth.  A and B have separate rings: A three deep (block kb + 2
-// issued at block kb), B NBR deep (block kb + NBR - 1 issued at kb); the waves
-// that stage A (0-5) and B (6-9) wait on their own DMA counts.  Measured at the
-// synthetic-2m round shape (bench/rows_probe.py, profiles/r6_rows_kernel.txt):
-// a B ring 5 deep does not beat 3, B read from L2 instead of HBM saves only
-// ~10%, and the operand reads one MFMA group ahead (the Gram's read-ahead)
-// change nothing — the k loop runs at ~46% MFMA with the chip at ~1.57 GHz.
-// ST: diagnostics build with per-workgroup stamps (entry, first block landed,
-// k loop done, stores issued, stores done; s_memrealtime at entry / end) at
-// stamps[8 (blockIdx.y gridDim.x + blockIdx.x) ..] (bench/rows_probe.py --stamps)
-constexpr int kRowsBAux = 2;
-template <bool ST>
-__global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_kernel(
-    const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
-    const int32_t* __restrict__ a_rows, const int32_t* __restrict__ m_dev, const u4* __restrict__ B,
-    const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq, int64_t N, int nkb, float gamma,
-    float* __restrict__ out, int64_t ldo, const int32_t* __restrict__ out_rows, uint64_t* __restrict__ stamps) {
-  uint64_t st[5] = {0, 0, 0, 0, 0}, rt0 = 0;
-  if constexpr (ST) {
-    st[0] = __builtin_amdgcn_s_memtime();
-    rt0 = __builtin_amdgcn_s_memrealtime();
-  }
-  constexpr int WN = 2, TM = 192, TN = 128, CPR = 8, NA = 3, NBR = 3;
-  constexpr int BUFA = TM * CPR, BUFB = TN * CPR;
-  constexpr int DMA_WAVES = (TM + TN) / 32;  // 10: each fills 32 rows (4 instructions of 8 rows)
-  static_assert(NA * BUFA * 16 + NBR * BUFB * 16 + (3 * TM + 2 * TN) * 4 <= 160 * 1024, "LDS");
-  int64_t tx, ty;
-  xcd_tile(tx, ty);
-  const int M = *m_dev;
-  if (tx * TM >= M) return;  // uniform: no barrier reached
-  __shared__ u4 lds[NA * BUFA + NBR * BUFB + (3 * TM + 2 * TN) / 4];
-  u4* const ldsA = lds;
-  u4* const ldsB = lds + NA * BUFA;
-  float* s_asq = (float*)(lds + NA * BUFA + NBR * BUFB);
-  int32_t* s_ash = (int32_t*)(s_asq + TM);
-  int32_t* s_orow = s_ash + TM;
-  float* s_bsq = (float*)(s_orow + TM);
-  int32_t* s_bsh = (int32_t*)(s_bsq + TN);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
-  const int64_t m0 = tx * TM, n0 = ty * TN;
-  const int64_t rstride = (int64_t)nkb * 8;  // u4 per split row
-  if (tid < TM) {
-    const int64_t row = m0 + tid;
-    const int64_t ar = a_rows[min(row, (int64_t)M - 1)];
-    s_asq[tid] = Asq[ar];
-    s_ash[tid] = Ash[ar];
-    s_orow[tid] = row < M ? out_rows[row] : -1;
-  } else if (tid < TM + TN) {
-    const int64_t cc = min(n0 + (tid - TM), N - 1);
-    s_bsq[tid - TM] = Bsq[cc];
-    s_bsh[tid - TM] = Bsh[cc];
-  }
-  // DMA sources: wave w < 10 fills stage rows 32 w + 8 i + (lane >> 3) (rows
-  // >= TM: B row r - TM of its own ring); lane position p = lane & 7 takes
-  // global chunk p ^ ((row >> 1) & 7) (the read swizzle; TM is a multiple of
-  // 16, so B rows keep it re-based at 0); A rows past M re-read a valid row
-  // (never stored)
-  const u4* src[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = min(32 * wave + 8 * i + (lane >> 3), TM + TN - 1);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    const int64_t grow = r < TM ? (int64_t)a_rows[min(m0 + r, (int64_t)M - 1)] : n0 + (r - TM);
-    src[i] = (r < TM ? A : B) + grow * rstride + c;
-  }
-  const bool dma_wave = wave < DMA_WAVES;
-  const bool b_wave = 32 * wave >= TM;  // waves 6 .. 9 stage B rows only (TM = 192 = 6 x 32)
-  auto dma = [&](int kb) {
-    if (b_wave) {
-      u4* dst = ldsB + (kb % NBR) * BUFB + (32 * wave - TM) * CPR;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((const void*)(src[i] + (int64_t)kb * 8),
-                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, kRowsBAux);
-    } else {
-      u4* dst = ldsA + (kb % NA) * BUFA + 32 * wave * CPR;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((const void*)(src[i] + (int64_t)kb * 8),
-                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, 0);
-    }
-  };
-  const int ahead = b_wave ? NBR - 1 : NA - 1;  // blocks a staging wave keeps issued past the current one
-  __syncthreads();  // row data written (no DMA in flight yet)
-  if (dma_wave) {
-    for (int b = 0; b < ahead && b < nkb; ++b) dma(b);
-  }
-
-  f16v H[2], P[2], Q[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) H[j][r] = P[j][r] = Q[j][r] = 0.f;
-  const int sw = ((lane & 31) >> 1) & 7;
-  const int ra = (wm * 32 + (lane & 31)) * CPR;
-  const int rb0 = (wn * 64 + (lane & 31)) * CPR, rb1 = rb0 + 32 * CPR;
-  const bool live = m0 + wm * 32 < M;  // a wave whose rows all lie past M only stages
-  for (int kb = 0; kb < nkb; ++kb) {
-    // retire block kb's DMA: a staging wave's younger blocks kb + 1 .. (4
-    // pieces each) may stay in flight (uniform per wave)
-    const int younger = min(ahead - 1, nkb - 1 - kb);
-    if (younger >= 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (younger == 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if constexpr (ST) {
-      if (kb == 0) st[1] = __builtin_amdgcn_s_memtime();
-    }
-    // block kb + ahead into its ring's buffer of block kb - 1 (every wave is past it)
-    if (dma_wave && kb + ahead < nkb) dma(kb + ahead);
-    if (live) {
-      const u4* bufa = ldsA + (kb % NA) * BUFA;
-      const u4* bufb = ldsB + (kb % NBR) * BUFB;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int ch = (2 * ks + hl) ^ sw, cl = (4 + 2 * ks + hl) ^ sw;
-        const h8 ah = __builtin_bit_cast(h8, bufa[ra + ch]);
-        const h8 al = __builtin_bit_cast(h8, bufa[ra + cl]);
-        const h8 bh0 = __builtin_bit_cast(h8, bufb[rb0 + ch]);
-        const h8 bl0 = __builtin_bit_cast(h8, bufb[rb0 + cl]);
-        const h8 bh1 = __builtin_bit_cast(h8, bufb[rb1 + ch]);
-        const h8 bl1 = __builtin_bit_cast(h8, bufb[rb1 + cl]);
-        H[0] = mfma32_f16(ah, bh0, H[0]);
-        H[1] = mfma32_f16(ah, bh1, H[1]);
-        P[0] = mfma32_f16(ah, bl0, P[0]);
-        P[1] = mfma32_f16(ah, bl1, P[1]);
-        Q[0] = mfma32_f16(al, bh0, Q[0]);
-        Q[1] = mfma32_f16(al, bh1, Q[1]);
-      }
-    }
-  }
-  if (!live) return;
-  if constexpr (ST) st[2] = __builtin_amdgcn_s_memtime();
-
-  // ---- epilogue: K = exp(-g max(|a|^2 + |b|^2 - 2 dot, 0)) ----
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int cb = wn * 64 + 32 * j + (lane & 31);
-    const float bsq = s_bsq[cb];
-    const int bsh = s_bsh[cb];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-      const float dot = ldexpf(H[j][r] + (P[j][r] + Q[j][r]), -(s_ash[lr] + bsh));
-      H[j][r] = rbf_split_value(s_asq[lr], bsq, dot, gamma);
-    }
-  }
-  const bool interior = n0 + TN <= N;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int32_t orow = s_orow[wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-      if (orow >= 0 && (interior || col < N)) out[(int64_t)orow * ldo + col] = H[j][r];
-    }
-  }
-  if constexpr (ST) {
-    st[3] = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    st[4] = __builtin_amdgcn_s_memtime();
-    const uint64_t rt1 = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0) {
-      uint64_t* o = stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
-#pragma unroll
-      for (int i = 0; i < 5; ++i) o[i] = st[i];
-      o[5] = rt0;
-      o[6] = rt1;
-      o[7] = 0;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Persistent LDS-DMA ROWS GEMM (the default for one tile row, M <= 192, and
-// nkb >= 3: a one-block ws-cache round's misses against all of this rank's B
-// rows — synthetic-2m's round).  The tile-per-workgroup kernel above spends
-// ~8% of a tile in its prologue (the miss rows' data and DMA sources, the
-// first blocks' latency) and the device runs ~239 of 256 workgroups at a time
-// (stamps, profiles/r6_rows_kernel.txt).  Here one workgroup per CU walks
-// column tiles ty = b, b + G, ...: the A side (the misses' |x|^2, shifts,
-// output lines and DMA sources) is set up once, and the DMA rings run on
-// across tiles — during a tile's last two k blocks the prefetch slots load
-// blocks 0 and 1 of the next (A's are the same blocks, B's the next tile's
-// rows), the next tile's B row data is loaded into registers during the k
-// loop and stored into the other parity of a row-data area after it.  Every
-// DMA wave issues 4 pieces every k block (the last tile re-loads its own
-// blocks 0 / 1 into dead buffers), so one uniform vmcnt(4) retires a block;
-// each epilogue ends with vmcnt(0).  Same MFMA sequence and epilogue per tile:
-// bit-identical to the kernel above.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kRowsGldsThreads, 1) void rbf_rows_split_glds_persist_kernel(
-    const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
-    const int32_t* __restrict__ a_rows, const int32_t* __restrict__ m_dev, const u4* __restrict__ B,
-    const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq, int64_t N, int nkb, float gamma,
-    float* __restrict__ out, int64_t ldo, const int32_t* __restrict__ out_rows, int ntiles) {
-  constexpr int WN = 2, TM = 192, TN = 128, CPR = 8, NBUF = 3;
-  constexpr int BUFA = TM * CPR, BUFB = TN * CPR;
-  constexpr int DMA_WAVES = (TM + TN) / 32;  // 10: waves 0-5 stage A rows, 6-9 B rows (4 pieces of 8 rows each)
-  __shared__ u4 lds[NBUF * BUFA + NBUF * BUFB + (3 * TM + 4 * TN) / 4];
-  u4* const ldsA = lds;
-  u4* const ldsB = lds + NBUF * BUFA;
-  float* const s_asq = (float*)(lds + NBUF * (BUFA + BUFB));
-  int32_t* const s_ash = (int32_t*)(s_asq + TM);
-  int32_t* const s_orow = s_ash + TM;
-  float* const s_bsq = (float*)(s_orow + TM);    // [2][TN] by parity
-  int32_t* const s_bsh = (int32_t*)(s_bsq + 2 * TN);  // [2][TN]
-  const int M = *m_dev;
-  const int G = gridDim.x;
-  int ty = blockIdx.x;
-  if (ty >= ntiles || M <= 0) return;  // uniform
-  // (the wave index in an SGPR: the epilogue's row addresses stay scalar
-  // instead of 16 VGPRs hoisted across the tile loop)
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
-  const int64_t rstride = (int64_t)nkb * 8;  // u4 per split row
-  if (tid < TM) {
-    const int64_t ar = a_rows[min(tid, M - 1)];
-    s_asq[tid] = Asq[ar];
-    s_ash[tid] = Ash[ar];
-    s_orow[tid] = tid < M ? out_rows[tid] : -1;
-  } else if (tid < TM + TN) {
-    const int64_t cc = min((int64_t)ty * TN + (tid - TM), N - 1);
-    s_bsq[tid - TM] = Bsq[cc];
-    s_bsh[tid - TM] = Bsh[cc];
-  }
-  // DMA sources: the kernel above's geometry; A's fixed for the launch, B's as
-  // a per-lane offset from the tile's first row (a uniform base per tile)
-  const bool dma_wave = wave < DMA_WAVES;
-  const bool b_wave = 32 * wave >= TM;
-  // (32-bit u4 offsets: launcher, (N + 512) x nkb x 8 < 2^32; registers are
-  // what the 96 accumulators leave at three waves per SIMD)
-  uint32_t off[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = min(32 * wave + 8 * i + (lane >> 3), TM + TN - 1);
-    const uint32_t c = (uint32_t)((lane & 7) ^ ((r >> 1) & 7));
-    off[i] = r < TM ? (uint32_t)a_rows[min(r, M - 1)] * (uint32_t)rstride + c : (uint32_t)(r - TM) * (uint32_t)rstride + c;
-  }
-  // piece set of global block g (kb of tile tt): into ring buffer g % 3
-  auto dma = [&](uint32_t g, int kb, int tt) {
-    const u4* base = b_wave ? B + (int64_t)tt * TN * rstride + (int64_t)kb * 8 : A + (int64_t)kb * 8;  // uniform
-    u4* dst = b_wave ? ldsB + (g % NBUF) * BUFB + (32 * wave - TM) * CPR : ldsA + (g % NBUF) * BUFA + 32 * wave * CPR;
-    if (b_wave) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((const void*)(base + off[i]),
-                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, kRowsBAux);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((const void*)(base + off[i]),
-                                         (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, 0);
-    }
-  };
-  __syncthreads();  // row data written (no DMA in flight yet)
-  uint32_t g = 0;   // k blocks started over all of this workgroup's tiles
-  if (dma_wave) {
-    dma(0, 0, ty);
-    dma(1, 1, ty);  // (launcher: nkb >= 3)
-  }
-  const int sw = ((lane & 31) >> 1) & 7;
-  const int ra = (wm * 32 + (lane & 31)) * CPR;
-  const int rb0 = (wn * 64 + (lane & 31)) * CPR, rb1 = rb0 + 32 * CPR;
-  const bool live = wm * 32 < M;  // a wave whose rows all lie past M only stages
-  int par = 0;
-  while (true) {
-    const int tn_next = ty + G;
-    const bool has_next = tn_next < ntiles;  // uniform
-    const int tp = has_next ? tn_next : ty;  // the last tile prefetches itself into dead buffers
-    // the next tile's B row data, in flight across the k loop
-    float nbsq = 0.f;
-    int32_t nbsh = 0;
-    if (has_next && tid >= TM && tid < TM + TN) {
-      const int64_t cc = min((int64_t)tn_next * TN + (tid - TM), N - 1);
-      nbsq = Bsq[cc];
-      nbsh = Bsh[cc];
-    }
-    f16v H[2], P[2], Q[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) H[j][r] = P[j][r] = Q[j][r] = 0.f;
-    for (int kb = 0; kb < nkb; ++kb) {
-      // block kb landed: only block kb + 1's 4 pieces may stay in flight
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      // block kb + 2 of this tile, or block kb + 2 - nkb of the next, into the
-      // buffer of block g - 1 (every wave is past it)
-      if (dma_wave) {
-        const bool own = kb + 2 < nkb;
-        dma(g + 2, own ? kb + 2 : kb + 2 - nkb, own ? ty : tp);
-      }
-      if (live) {
-        const u4* bufa = ldsA + (g % NBUF) * BUFA;
-        const u4* bufb = ldsB + (g % NBUF) * BUFB;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const int ch = (2 * ks + hl) ^ sw, cl = (4 + 2 * ks + hl) ^ sw;
-          const h8 ah = __builtin_bit_cast(h8, bufa[ra + ch]);
-          const h8 al = __builtin_bit_cast(h8, bufa[ra + cl]);
-          const h8 bh0 = __builtin_bit_cast(h8, bufb[rb0 + ch]);
-          const h8 bl0 = __builtin_bit_cast(h8, bufb[rb0 + cl]);
-          const h8 bh1 = __builtin_bit_cast(h8, bufb[rb1 + ch]);
-          const h8 bl1 = __builtin_bit_cast(h8, bufb[rb1 + cl]);
-          H[0] = mfma32_f16(ah, bh0, H[0]);
-          H[1] = mfma32_f16(ah, bh1, H[1]);
-          P[0] = mfma32_f16(ah, bl0, P[0]);
-          P[1] = mfma32_f16(ah, bl1, P[1]);
-          Q[0] = mfma32_f16(al, bh0, Q[0]);
-          Q[1] = mfma32_f16(al, bh1, Q[1]);
-        }
-      }
-      ++g;
-    }
-    // the next tile's B row data into the other parity (last read by the
-    // previous tile's epilogue, before this tile's first barrier)
-    if (has_next && tid >= TM && tid < TM + TN) {
-      s_bsq[(par ^ 1) * TN + (tid - TM)] = nbsq;
-      s_bsh[(par ^ 1) * TN + (tid - TM)] = nbsh;
-    }
-    if (live) {
-      // ---- epilogue (the kernel above's) ----
-      // (per-lane addresses from a laundered lane id: hoisted out of the tile
-      // loop they would hold registers across the k loop and spill)
-      int el = lane;
-      asm volatile("" : "+v"(el));
-      const int ehl = el >> 5;
-      const int64_t n0 = (int64_t)ty * TN;
-      const float* bq = s_bsq + par * TN;
-      const int32_t* bs = s_bsh + par * TN;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int cb = wn * 64 + 32 * j + (el & 31);
-        const float bsq = bq[cb];
-        const int bsh = bs[cb];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * ehl;
-          const float dot = ldexpf(H[j][r] + (P[j][r] + Q[j][r]), -(s_ash[lr] + bsh));
-          H[j][r] = rbf_split_value(s_asq[lr], bsq, dot, gamma);
-        }
-      }
-      const bool interior = n0 + TN <= N;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int32_t orow = s_orow[wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * ehl];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int64_t col = n0 + wn * 64 + 32 * j + (el & 31);
-          if (orow >= 0 && (interior || col < N)) out[(int64_t)orow * ldo + col] = H[j][r];
-        }
-      }
-    }
-    // the stores and the next tile's blocks 0 / 1 retired: the loop's uniform
-    // vmcnt(4) holds at the next tile's first block (and no DMA is in flight
-    // when the kernel ends)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!has_next) break;
-    ty = tn_next;
-    par ^= 1;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Persistent small-K ROWS GEMM (nkb <= 2 k blocks: d <= 64, covtype's 54
-// features).  There a tile is two k blocks of MFMA work against 24-98 KiB of
-// operand and store traffic, so a tile-per-workgroup grid is a chain of
-// latencies (load, multiply, store) per tile.  Here one 768-thread workgroup
-// per CU walks the tiles of its grid stride (64 x 192 up to 192 x 64 by the
-// miss count): the A rows of its tile row (<= 48 KiB) are staged into LDS
-// once, the B column tiles (and their |x|^2 / shifts) stream through two LDS buffers by LDS-DMA, the next
-// tile's DMA issued before this tile's multiply, so its latency hides under
-// the multiply, the epilogue and the stores; a wave then waits with vmcnt(16)
-// (its 16 stores of the tile before are younger than that DMA), so the stores
-// drain under the next tile instead of being waited for (every live lane
-// stores exactly 16 values: rows past M and columns past N go to a scratch
-// line).  MFMA sequence and epilogue as the rows kernels above: bit-identical rows.
-// ---------------------------------------------------------------------------
-constexpr int kRowsPersistThreads = 768;
-template <int NKB>
-__global__ __launch_bounds__(kRowsPersistThreads, 1) void rbf_rows_split_persist_kernel(
-    const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
-    const int32_t* __restrict__ a_rows, const int32_t* __restrict__ m_dev, const u4* __restrict__ B,
-    const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq, int64_t N, float gamma,
-    float* __restrict__ out, int64_t ldo, const int32_t* __restrict__ out_rows, float* __restrict__ trash) {
-  // 12 waves of 32 x 32 (one MFMA tile, three accumulators each), laid out by
-  // the round's miss count M: WM x WN = 2 x 6 (64 x 192 tiles) up to 64
-  // misses, 4 x 3 (128 x 96) up to 128, else 6 x 2 (192 x 64) — the fewest,
-  // widest tiles that cover the live rows (a tile's cost is mostly latency)
-  constexpr int CPR = 8, TMX = 192, TNX = 192;
-  constexpr int ABUF = TMX * NKB * CPR, BBUF = TNX * NKB * CPR;  // u4
-  const int M = *m_dev;
-  const int WM = M <= 64 ? 2 : M <= 128 ? 4 : 6, WN = 12 / WM, TM = 32 * WM, TN = 32 * WN;
-  const int tn = (int)((N + TN - 1) / TN), tm = (M + TM - 1) / TM, total = tm * tn;
-  int L = blockIdx.x;
-  if (L >= total) return;  // uniform
-  __shared__ u4 lds[ABUF + 2 * BBUF + (2 * 2 * TNX) / 4 + (3 * TMX) / 4];
-  u4* s_a = lds;                                          // [NKB][TM rows][CPR]
-  u4* s_b = lds + ABUF;                                   // [2][NKB][TN rows][CPR]
-  float* s_bsq = (float*)(lds + ABUF + 2 * BBUF);         // [2][TNX], then s_bsh [2][TNX]
-  int32_t* s_bsh = (int32_t*)(s_bsq + 2 * TNX);
-  float* s_asq = (float*)(s_bsh + 2 * TNX);
-  int32_t* s_ash = (int32_t*)(s_asq + TMX);
-  int32_t* s_orow = s_ash + TMX;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
-  constexpr int64_t rstride = (int64_t)NKB * 8;
-  const int nb = TN * NKB / 8, nv = (TN + 63) / 64;  // B-row DMA instructions; |x|^2 (and shift) ones per tile
-  // B DMA of column tile ty into buffer b: instruction i (8 k-rows x 128 B) by
-  // wave i % 12, then the |x|^2 / shift dwords by the waves after
-  auto dma = [&](int ty, int b) {
-    const int64_t n0 = (int64_t)ty * TN;
-    for (int i = wave; i < nb + 2 * nv; i += 12) {
-      if (i < nb) {
-        const int q = 8 * i + (lane >> 3), kb = q / TN, r = q % TN;
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        __builtin_amdgcn_global_load_lds((const void*)(B + (n0 + r) * rstride + kb * 8 + c),
-                                         (__attribute__((address_space(3))) void*)(s_b + b * BBUF + 8 * i * CPR),
-                                         16, 0, 0);
-      } else {
-        const int v = i - nb, part = v % nv;
-        const int64_t cc = min(n0 + 64 * part + lane, N - 1);
-        if (v < nv)
-          __builtin_amdgcn_global_load_lds((const void*)(Bsq + cc),
-                                           (__attribute__((address_space(3))) void*)(s_bsq + b * TNX + 64 * part), 4,
-                                           0, 0);
-        else
-          __builtin_amdgcn_global_load_lds((const void*)(Bsh + cc),
-                                           (__attribute__((address_space(3))) void*)(s_bsh + b * TNX + 64 * part), 4,
-                                           0, 0);
-      }
-    }
-  };
-  dma(L % tn, 0);
-  int ltx = -1, buf = 0;
-  bool stored = false;  // this wave's 16 stores of the previous tile are younger than the pending DMA
-  const int sw = ((lane & 31) >> 1) & 7;
-  for (; L < total; L += gridDim.x) {
-    const int tx = L / tn, ty = L % tn;
-    const int64_t m0 = (int64_t)tx * TM, n0 = (int64_t)ty * TN;
-    if (tx != ltx) {
-      // the A rows of this tile row (plain loads: the first tile, or a new tile
-      // row of a multi-block round's misses); every wave is past the old rows
-      __syncthreads();
-      for (int id = tid; id < TM * NKB * CPR; id += kRowsPersistThreads) {
-        const int kb = id / (TM * CPR), r = (id / CPR) % TM, c = id % CPR;
-        const int64_t ar = a_rows[min(m0 + r, (int64_t)M - 1)];
-        s_a[(kb * TM + r) * CPR + (c ^ ((r >> 1) & 7))] = A[ar * rstride + kb * 8 + c];
-      }
-      if (tid < TM) {
-        const int64_t row = m0 + tid;
-        const int64_t ar = a_rows[min(row, (int64_t)M - 1)];
-        s_asq[tid] = Asq[ar];
-        s_ash[tid] = Ash[ar];
-        s_orow[tid] = row < M ? out_rows[row] : -1;
-      }
-      ltx = tx;
-      stored = false;  // those loads were waited for: nothing older is outstanding
-    }
-    const bool live = m0 + wm * 32 < M;
-    // this tile's DMA has landed; the previous tile's stores may still drain
-    if (stored) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (L + (int)gridDim.x < total) dma((L + gridDim.x) % tn, buf ^ 1);  // every wave is past buffer buf ^ 1
-    if (live) {
-      f16v H, P, Q;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) H[r] = P[r] = Q[r] = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        const int ra = ((kb * TM) + wm * 32 + (lane & 31)) * CPR;
-        const int rb = (buf * BBUF) + (kb * TN + wn * 32 + (lane & 31)) * CPR;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const int ch = (2 * ks + hl) ^ sw, cl = (4 + 2 * ks + hl) ^ sw;
-          const h8 ah = __builtin_bit_cast(h8, s_a[ra + ch]);
-          const h8 al = __builtin_bit_cast(h8, s_a[ra + cl]);
-          const h8 bh = __builtin_bit_cast(h8, s_b[rb + ch]);
-          const h8 bl = __builtin_bit_cast(h8, s_b[rb + cl]);
-          H = mfma32_f16(ah, bh, H);
-          P = mfma32_f16(ah, bl, P);
-          Q = mfma32_f16(al, bh, Q);
-        }
-      }
-      const int cb = wn * 32 + (lane & 31);
-      const float bsq = s_bsq[buf * TNX + cb];
-      const int bsh = s_bsh[buf * TNX + cb];
-      const int64_t col = n0 + cb;
-      const bool ok = col < N;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-        const float dot = ldexpf(H[r] + (P[r] + Q[r]), -(s_ash[lr] + bsh));
-        const float v = rbf_split_value(s_asq[lr], bsq, dot, gamma);
-        const int32_t orow = s_orow[lr];
-        // exactly 16 stores per lane (the vmcnt(16) above): rows past M and
-        // columns past N go to the scratch line
-        float* dst = (orow >= 0 && ok) ? out + (int64_t)orow * ldo + col : trash + lane;
-        *dst = v;
-      }
-    }
-    stored = live;
-    buf ^= 1;
-  }
+  w32_store_tile(H, out, ldo, m0 + wm * 32, n0 + wn * 64, hl, lane, M, N, m0 + TM <= M && n0 + TN <= N,
+                 sym && ty != tx);
 }
 
 // The w64 kernels' epilogue: the values two at a time in
@@ -1048,7 +368,11 @@ __global__ __launch_bounds__(kRowsPersistThreads, 1) void rbf_rows_split_persist
 // AD: the adaptive Gram's hot-tile pass — every element takes the one-product
 // value where split_cold allows it (R = log2 |x| from Ar / Br, global loads:
 // this pass runs only the few tiles the one-product pass reported).
-typedef int i4v_t __attribute__((ext_vector_type(4)));
+// The stores are h1_store_block's (below), written here per group of four
+// rows between the groups' values: built as values plus h1_store_block calls
+// the five w64 / w64p kernels come out 57-88 instructions longer with other
+// waits and six more branches (no spill), so the two stay separate — a change
+// to the packed stores is made in both.
 template <bool AD = false>
 __device__ __forceinline__ void w64_epilogue_pe(f16v (&H)[2][2], const f16v (&P)[2][2], const f16v (&Q)[2][2],
                                                 const float* s_sq, const int32_t* s_sh, int lane, int wm, int wn,
@@ -1056,14 +380,12 @@ __device__ __forceinline__ void w64_epilogue_pe(f16v (&H)[2][2], const f16v (&P)
                                                 int64_t ldo, float gamma, const float* Ar = nullptr,
                                                 const float* Br = nullptr, float c0 = 0.f, float c1 = 0.f) {
   constexpr int TM = 256, TN = 128;
-  typedef i4v_t i4v;
   const int hl = lane >> 5;
   float* const ob = out + m0 * ldo + n0;  // direct block
   float* const mb = out + n0 * ldo + m0;  // mirrored block (symmetric: M == N)
   const uint32_t ld = (uint32_t)ldo;
   const int rlim = (int)min<int64_t>(M - m0, TM);  // tile rows inside [0, M)
   const int clim = (int)min<int64_t>(N - n0, TN);  // tile columns inside [0, N)
-  typedef float f2 __attribute__((ext_vector_type(2)));
   constexpr uint32_t OOB = 0x80000000u;
   const int64_t ob_bytes = min<int64_t>((M - m0) * ldo * 4 - n0 * 4, (int64_t)OOB);
   const int64_t mb_bytes = min<int64_t>((N - n0) * ldo * 4 - m0 * 4, (int64_t)OOB);
@@ -1243,8 +565,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
   }
   auto dma_piece = [&](int kb, int i) {
     u4* dst = lds + (kb % NB) * BUF + 48 * wave * CPR;
-    __builtin_amdgcn_global_load_lds((const void*)(base[i] + (int64_t)kb * 8 + off[i]),
-                                     (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, 0);
+    lds_dma16(base[i] + (int64_t)kb * 8 + off[i], dst + 8 * i * CPR);
   };
   auto dma = [&](int kb) {
 #pragma unroll
@@ -1255,12 +576,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
   if (nkb > 1) dma(1);
 
   f16v H[2][2], P[2][2], Q[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) H[i][j][r] = P[i][j][r] = Q[i][j][r] = 0.f;
+  zero_acc(H, P, Q);
   const int sw = ((lane & 31) >> 1) & 7;
   const int ra0 = (wm * 64 + (lane & 31)) * CPR;
   const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR;
@@ -1268,9 +584,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
     // retire block kb's DMA (block kb + 1 may stay in flight)
     if (kb + 1 < nkb) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    ring_barrier();
     if constexpr (ST) {
       if (kb == 0) st[1] = __builtin_amdgcn_s_memtime();
     }
@@ -1283,64 +597,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    const u4* buf = lds + (kb % NB) * BUF;
-    // LDS reads issued one MFMA group ahead, in asm with counted waits (the
-    // compiler drains lgkmcnt to 0 around the LDS-DMA): a group's fragments
-    // land while the previous group's MFMAs run, except the block's first.
-    // Eight fragments live at most.  A wait names the fragments it retires
-    // ("+v"), so no MFMA can move above it
-    const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
-    auto rd2 = [&](uint32_t base, int c, h8& x0, h8& x1) {
-      const uint32_t a0 = base + 16u * (uint32_t)c;
-      asm volatile("ds_read_b128 %0, %1" : "=v"(x0) : "v"(a0) : "memory");
-      asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(x1) : "v"(a0) : "memory");  // + 32 rows
-    };
-    const int ch0 = hl ^ sw, cl0 = (4 + hl) ^ sw, ch1 = (2 + hl) ^ sw, cl1 = (6 + hl) ^ sw;
-    h8 ah0, ah1, bh0, bh1, bl0, bl1, al0, al1, bh0n, bh1n;
-    rd2(abase, ch0, ah0, ah1);
-    rd2(bbase, ch0, bh0, bh1);
-    rd2(bbase, cl0, bl0, bl1);
-    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0), "+v"(bh1));
-    H[0][0] = mfma32_f16(ah0, bh0, H[0][0]);
-    H[0][1] = mfma32_f16(ah0, bh1, H[0][1]);
-    H[1][0] = mfma32_f16(ah1, bh0, H[1][0]);
-    H[1][1] = mfma32_f16(ah1, bh1, H[1][1]);
-    piece(0);
-    rd2(abase, cl0, al0, al1);
-    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
-    P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
-    P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
-    P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
-    P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
-    piece(1);
-    rd2(abase, ch1, ah0, ah1);  // k step 1 (A hi of step 0 is dead)
-    rd2(bbase, ch1, bh0n, bh1n);
-    asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(al0), "+v"(al1));
-    Q[0][0] = mfma32_f16(al0, bh0, Q[0][0]);
-    Q[0][1] = mfma32_f16(al0, bh1, Q[0][1]);
-    Q[1][0] = mfma32_f16(al1, bh0, Q[1][0]);
-    Q[1][1] = mfma32_f16(al1, bh1, Q[1][1]);
-    piece(2);
-    rd2(bbase, cl1, bl0, bl1);
-    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0n), "+v"(bh1n));
-    H[0][0] = mfma32_f16(ah0, bh0n, H[0][0]);
-    H[0][1] = mfma32_f16(ah0, bh1n, H[0][1]);
-    H[1][0] = mfma32_f16(ah1, bh0n, H[1][0]);
-    H[1][1] = mfma32_f16(ah1, bh1n, H[1][1]);
-    piece(3);
-    rd2(abase, cl1, al0, al1);
-    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
-    P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
-    P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
-    P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
-    P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
-    piece(4);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al0), "+v"(al1));
-    Q[0][0] = mfma32_f16(al0, bh0n, Q[0][0]);
-    Q[0][1] = mfma32_f16(al0, bh1n, Q[0][1]);
-    Q[1][0] = mfma32_f16(al1, bh0n, Q[1][0]);
-    Q[1][1] = mfma32_f16(al1, bh1n, Q[1][1]);
-    piece(5);
+    w64_kblock(H, P, Q, lds + (kb % NB) * BUF, ra0, rb0, hl, sw, piece);
   }
 
   if constexpr (ST) st[2] = __builtin_amdgcn_s_memtime();
@@ -1355,14 +612,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64_kernel(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     st[4] = __builtin_amdgcn_s_memtime();
     const uint64_t rt1 = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0) {
-      uint64_t* o = stamps + (size_t)blockIdx.x * 8;
-#pragma unroll
-      for (int i = 0; i < 5; ++i) o[i] = st[i];
-      o[5] = rt0;
-      o[6] = rt1;
-      o[7] = ((uint64_t)tx << 32) | (uint64_t)ty;
-    }
+    if (tid == 0) write_stamps(stamps + (size_t)blockIdx.x * 8, st, rt0, rt1, tx, ty);
   }
 }
 
@@ -1400,8 +650,7 @@ __device__ __forceinline__ void w64p_piece(const u4* __restrict__ src, u4* lds, 
   constexpr int BUF = 384 * 8;
   u4* dst = lds + buf * BUF + dst_row8 + i * 64;
   const char* base = (const char*)(src + (u + (uint32_t)i * step));  // uniform
-  __builtin_amdgcn_global_load_lds((const void*)(base + ((i & 1) ? off_o : off_e)),
-                                   (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+  lds_dma16(base + ((i & 1) ? off_o : off_e), dst);
 }
 
 // a tile's |x|^2 and shifts into row-data parity par: dwords d = 64 (2 wave +
@@ -1423,8 +672,7 @@ __device__ __forceinline__ void w64p_row_dma(const float* __restrict__ Asq, cons
     const int r = r0 + lane;
     const int ri = a_rows ? min(m0 + r, M - 1) : min(n0 + (r - TM), N - 1);
     const uint32_t* src = d0 >= 2 * ROWS ? arr : arr + ri;  // padding: any valid address
-    __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(s_rows + par * RD + d0),
-                                     4, 0, 0);
+    lds_dma4(src, s_rows + par * RD + d0);
   }
 }
 
@@ -1499,6 +747,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
     const uint32_t tp = has_next ? tn_next : t;
     const int nm0 = (int)(tp >> 16) * TM, nn0 = (int)(tp & 0xffffu) * TN;
     f16v H[2][2], P[2][2], Q[2][2];
+    // (written out, not zero_acc: that form costs the k loop's entry a wait state)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1512,9 +761,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
       // of itself into dead buffers) and every epilogue ends with vmcnt(0): one
       // wait, no branch (a taken branch a piece cost ~10% of the loop)
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      ring_barrier();
       if constexpr (ST) {
         if (kb == 0) st[1] = __builtin_amdgcn_s_memtime();
       }
@@ -1532,60 +779,7 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
         else PIECE_A(uA, pbuf, j < 2 ? j : j - 1);
         __builtin_amdgcn_sched_barrier(0);
       };
-      // operand fragments read one MFMA group ahead (as in the w64 kernel)
-      const u4* buf = lds + (g % NB) * BUF;
-      const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
-      auto rd2 = [&](uint32_t base, int c, h8& x0, h8& x1) {
-        const uint32_t a0 = base + 16u * (uint32_t)c;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(x0) : "v"(a0) : "memory");
-        asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(x1) : "v"(a0) : "memory");  // + 32 rows
-      };
-      const int ch0 = hl ^ sw, cl0 = (4 + hl) ^ sw, ch1 = (2 + hl) ^ sw, cl1 = (6 + hl) ^ sw;
-      h8 ah0, ah1, bh0, bh1, bl0, bl1, al0, al1, bh0n, bh1n;
-      rd2(abase, ch0, ah0, ah1);
-      rd2(bbase, ch0, bh0, bh1);
-      rd2(bbase, cl0, bl0, bl1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0), "+v"(bh1));
-      H[0][0] = mfma32_f16(ah0, bh0, H[0][0]);
-      H[0][1] = mfma32_f16(ah0, bh1, H[0][1]);
-      H[1][0] = mfma32_f16(ah1, bh0, H[1][0]);
-      H[1][1] = mfma32_f16(ah1, bh1, H[1][1]);
-      piece(0);
-      rd2(abase, cl0, al0, al1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
-      P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
-      P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
-      P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
-      P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
-      piece(1);
-      rd2(abase, ch1, ah0, ah1);
-      rd2(bbase, ch1, bh0n, bh1n);
-      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(al0), "+v"(al1));
-      Q[0][0] = mfma32_f16(al0, bh0, Q[0][0]);
-      Q[0][1] = mfma32_f16(al0, bh1, Q[0][1]);
-      Q[1][0] = mfma32_f16(al1, bh0, Q[1][0]);
-      Q[1][1] = mfma32_f16(al1, bh1, Q[1][1]);
-      piece(2);
-      rd2(bbase, cl1, bl0, bl1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah0), "+v"(ah1), "+v"(bh0n), "+v"(bh1n));
-      H[0][0] = mfma32_f16(ah0, bh0n, H[0][0]);
-      H[0][1] = mfma32_f16(ah0, bh1n, H[0][1]);
-      H[1][0] = mfma32_f16(ah1, bh0n, H[1][0]);
-      H[1][1] = mfma32_f16(ah1, bh1n, H[1][1]);
-      piece(3);
-      rd2(abase, cl1, al0, al1);
-      asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bl0), "+v"(bl1));
-      P[0][0] = mfma32_f16(ah0, bl0, P[0][0]);
-      P[0][1] = mfma32_f16(ah0, bl1, P[0][1]);
-      P[1][0] = mfma32_f16(ah1, bl0, P[1][0]);
-      P[1][1] = mfma32_f16(ah1, bl1, P[1][1]);
-      piece(4);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al0), "+v"(al1));
-      Q[0][0] = mfma32_f16(al0, bh0n, Q[0][0]);
-      Q[0][1] = mfma32_f16(al0, bh1n, Q[0][1]);
-      Q[1][0] = mfma32_f16(al1, bh0n, Q[1][0]);
-      Q[1][1] = mfma32_f16(al1, bh1n, Q[1][1]);
-      piece(5);
+      w64_kblock(H, P, Q, lds + (g % NB) * BUF, ra0, rb0, hl, sw, piece);
       ++g;
     }
     if constexpr (ST) st[2] = __builtin_amdgcn_s_memtime();
@@ -1661,8 +855,6 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
 __device__ __forceinline__ bool h1_values(f16v (&H)[2][2], const float* s_sq, const int32_t* s_sh, const float* s_r,
                                           int lane, int wm, int wn, float gamma, float c0, float c1) {
   constexpr int TM = 256;
-  typedef i4v_t i4v;
-  typedef float f2 __attribute__((ext_vector_type(2)));
   const int hl = lane >> 5;
   const float ng = -gamma, l2e = 1.4426950408889634f;
   bool hot = false;
@@ -1714,11 +906,11 @@ __device__ __forceinline__ bool h1_values(f16v (&H)[2][2], const float* s_sq, co
 // the stores of one 32 x 32 MFMA block (i, j) of a wave's values v: 16 direct
 // 4-B stores per lane, and for a mirroring wave 4 transposed 16-B ones (plus,
 // on the last row tile, a partial quad's values one at a time); out-of-range
-// offsets where a value has no place (the hardware drops those).
+// offsets where a value has no place (the hardware drops those).  The same
+// stores as w64_epilogue_pe's (above), which keeps its own copy: see there.
 __device__ __forceinline__ void h1_store_block(const f16v& v, int i, int j, int lane, int wm, int wn, bool mirror,
                                                bool valid, float* out, int m0, int n0, int M, int N, int ldo) {
   constexpr int TM = 256, TN = 128;
-  typedef i4v_t i4v;
   constexpr uint32_t OOB = 0x80000000u;
   const int hl = lane >> 5;
   float* const ob = out + ((int64_t)m0 * ldo + n0);
@@ -1815,9 +1007,7 @@ __device__ __noinline__ void h1s_dma(const u4* __restrict__ A, const int32_t* __
         const int r = 64 * i + lane;
         const int ri = i < 4 ? min(m0_ + r, M - 1) : min(n0_ + (r - TM), N - 1);
         const uint32_t* src = dw == 3 ? (const uint32_t*)Asq : (i < 4 ? rd_a : rd_b) + ri;
-        __builtin_amdgcn_global_load_lds(
-            (const void*)src, (__attribute__((address_space(3))) void*)(s_rows + par_ * RD + 64 * (6 * dw + i)),
-            4, 0, 0);
+        lds_dma4(src, s_rows + par_ * RD + 64 * (6 * dw + i));
       }
     };
     {
@@ -1930,9 +1120,7 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
         for (int r = 0; r < 16; ++r) H[i][j][r] = 0.f;
     // FS: the tile's first stage (stamps)
     auto stage = [&]<bool FS = false>() {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      ring_barrier();
       if constexpr (ST && FS) stamp(1, (uint32_t)__builtin_amdgcn_s_memtime());
       const u4* buf = lds + (g % NB) * BUF;
       const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
@@ -2023,146 +1211,6 @@ __global__ __launch_bounds__(256) void split_log2norm_kernel(const float* __rest
   if (i < n) r[i] = split_log2norm(sq[i]);
 }
 
-// ---------------------------------------------------------------------------
-// Decision GEMM on split operands (predict: training accuracy, GpuPredictor,
-// svmTest, the shrinking phases' gradient update): dec_i = sum_j coef_j K(A_i,
-// B_j) with A = query rows, B = support vectors.  A workgroup owns 128 query
-// rows and a range of SV tiles; the (SV tile, k block) sequence is ONE LDS-DMA
-// pipeline (the LDS-DMA STORE kernel's staging: four 32-k buffers, three blocks
-// in flight across tile boundaries — the query panel is the same for every SV
-// tile), and each SV tile's 128 x 128 kernel block is folded into per-row sums
-// in registers (no store).  Partial sums per SV split: partial[split][row].
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kGldsThreads, 1) void rbf_predict_split_kernel(
-    const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq, int64_t M,
-    const u4* __restrict__ B, const int32_t* __restrict__ Bsh, const float* __restrict__ Bsq,
-    const float* __restrict__ coef, int64_t N, int nkb, float gamma, float* __restrict__ partial, int64_t ldp,
-    int per) {
-  constexpr int WN = 2, TM = 128, TN = 128, ROWS = TM + TN, CPR = 8, BUF = ROWS * CPR, NB = 4;
-  __shared__ u4 lds[NB * BUF + 2 * TM / 4];
-  float* s_asq = (float*)(lds + NB * BUF);
-  int32_t* s_ash = (int32_t*)(lds + NB * BUF) + TM;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
-  const int64_t m0 = (int64_t)blockIdx.x * TM;
-  const int64_t tn_all = (N + TN - 1) / TN;
-  const int64_t t0 = (int64_t)blockIdx.y * per, t1 = min(t0 + per, tn_all);
-  float* out = partial + (int64_t)blockIdx.y * ldp + m0;
-  if (t0 >= t1) {  // uniform: an empty split contributes zeros
-    if (tid < TM) out[tid] = 0.f;
-    return;
-  }
-  const int64_t rstride = (int64_t)nkb * 8;
-  if (tid < TM) {
-    const int64_t ri = min(m0 + tid, M - 1);
-    s_asq[tid] = Asq[ri];
-    s_ash[tid] = Ash[ri];
-  }
-  const u4* src[4];
-  bool isb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = 32 * wave + 8 * i + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    isb[i] = r >= TM;
-    src[i] = r < TM ? A + (m0 + r) * rstride + c : B + (t0 * TN + (r - TM)) * rstride + c;
-  }
-  const int64_t nblk = (t1 - t0) * nkb;
-  auto dma = [&](int64_t g) {
-    const int64_t t = g / nkb, kb = g - t * nkb;
-    u4* dst = lds + (g & (NB - 1)) * BUF + 32 * wave * CPR;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds(
-          (const void*)(src[i] + (isb[i] ? t * TN * rstride : 0) + kb * 8),
-          (__attribute__((address_space(3))) void*)(dst + 8 * i * CPR), 16, 0, 0);
-  };
-  __syncthreads();
-  dma(0);
-  if (nblk > 1) dma(1);
-  if (nblk > 2) dma(2);
-
-  f16v H[2], P[2], Q[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) H[j][r] = P[j][r] = Q[j][r] = 0.f;
-  float acc[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const int sw = ((lane & 31) >> 1) & 7;
-  const int ra = (wm * 32 + (lane & 31)) * CPR;
-  const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR, rb1 = rb0 + 32 * CPR;
-  int kb = 0;
-  int64_t t = t0;
-  for (int64_t g = 0; g < nblk; ++g) {
-    const int64_t ahead = min((int64_t)2, nblk - 1 - g);
-    if (ahead == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (g + 3 < nblk) dma(g + 3);
-    const u4* buf = lds + (g & (NB - 1)) * BUF;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int ch = (2 * ks + hl) ^ sw, cl = (4 + 2 * ks + hl) ^ sw;
-      const h8 ah = __builtin_bit_cast(h8, buf[ra + ch]);
-      const h8 al = __builtin_bit_cast(h8, buf[ra + cl]);
-      const h8 bh0 = __builtin_bit_cast(h8, buf[rb0 + ch]);
-      const h8 bl0 = __builtin_bit_cast(h8, buf[rb0 + cl]);
-      const h8 bh1 = __builtin_bit_cast(h8, buf[rb1 + ch]);
-      const h8 bl1 = __builtin_bit_cast(h8, buf[rb1 + cl]);
-      H[0] = mfma32_f16(ah, bh0, H[0]);
-      H[1] = mfma32_f16(ah, bh1, H[1]);
-      P[0] = mfma32_f16(ah, bl0, P[0]);
-      P[1] = mfma32_f16(ah, bl1, P[1]);
-      Q[0] = mfma32_f16(al, bh0, Q[0]);
-      Q[1] = mfma32_f16(al, bh1, Q[1]);
-    }
-    if (++kb == nkb) {  // the SV tile is complete: fold its kernel block into the row sums
-      const int64_t n0 = t * TN;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int64_t col = n0 + wn * 64 + 32 * j + (lane & 31);
-        const int64_t cc = col < N ? col : N - 1;
-        const float cf = col < N ? coef[cc] : 0.f;
-        const float bsq = Bsq[cc];
-        const int bsh = Bsh[cc];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int lr = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-          const float dot = ldexpf(H[j][r] + (P[j][r] + Q[j][r]), -(s_ash[lr] + bsh));
-          acc[r] += cf * rbf_split_value(s_asq[lr], bsq, dot, gamma);
-          H[j][r] = P[j][r] = Q[j][r] = 0.f;
-        }
-      }
-      kb = 0;
-      ++t;
-    }
-  }
-  // the 32 columns of a lane group, then the two column waves through LDS
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float v = acc[r];
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    v += __shfl_xor(v, 16, 64);
-    acc[r] = v;
-  }
-  __syncthreads();  // every wave is past its last operand read (no DMA in flight)
-  float* red = (float*)lds;  // [WN][TM]
-  if ((lane & 31) == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wn * TM + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl] = acc[r];
-  }
-  __syncthreads();
-  if (tid < TM) out[tid] = red[tid] + red[TM + tid];
-}
-
 }  // namespace dev
 
 namespace launch {
@@ -2217,50 +1265,18 @@ const char* gram_path_name(GramPath p) {
 
 // diagnostics: non-null = the wide-wave Gram kernel writes per-workgroup stamps here
 uint64_t* g_gram_stamps = nullptr;
-// diagnostics: non-null = the LDS-DMA rows kernel writes per-workgroup stamps here
-uint64_t* g_rows_stamps = nullptr;
-void set_rows_stamps(uint64_t* p) { g_rows_stamps = p; }
 
 void set_gram_stamps(uint64_t* p) { g_gram_stamps = p; }
 
 int64_t split_row_u4(int dp) { return (int64_t)((dp + 31) / 32) * 8; }
 
-void rbf_predict_split(const float* A, const float* Asq, int64_t M, int lda, const float* B, const float* Bsq,
-                       const float* coef, int64_t N, int ldb, int dp, float gamma, float* partial, int64_t ldp,
-                       int max_splits, hipStream_t s) {
-  // both operands split into stream-ordered scratch (rows padded: the kernel reads whole 128-row tiles)
-  const int nkb = (dp + 31) / 32;
-  const int64_t pa = split_pad_rows(M), pb = split_pad_rows(N), ru = split_row_u4(dp) * 16;
-  void *a_pl = nullptr, *b_pl = nullptr;
-  int32_t *a_sh = nullptr, *b_sh = nullptr;
-  HIP_CHECK(hipMallocAsync(&a_pl, (size_t)(pa * ru), s));
-  HIP_CHECK(hipMallocAsync(&b_pl, (size_t)(pb * ru), s));
-  HIP_CHECK(hipMallocAsync((void**)&a_sh, (size_t)pa * 4, s));
-  HIP_CHECK(hipMallocAsync((void**)&b_sh, (size_t)pb * 4, s));
-  HIP_CHECK(hipMemsetAsync(a_pl, 0, (size_t)(pa * ru), s));
-  HIP_CHECK(hipMemsetAsync(b_pl, 0, (size_t)(pb * ru), s));
-  HIP_CHECK(hipMemsetAsync(a_sh, 0, (size_t)pa * 4, s));
-  HIP_CHECK(hipMemsetAsync(b_sh, 0, (size_t)pb * 4, s));
-  split_rows_f16(A, M, dp, lda, a_pl, a_sh, s);
-  split_rows_f16(B, N, dp, ldb, b_pl, b_sh, s);
-  const int64_t tm = (M + 127) / 128, tn = (N + 127) / 128;
-  // ~2 workgroups per CU of a 256-CU device, at most the scratch's splits
-  int64_t splits = std::max<int64_t>(1, std::min<int64_t>({(int64_t)max_splits, tn, (512 + tm - 1) / tm}));
-  const int per = (int)((tn + splits - 1) / splits);
-  splits = (tn + per - 1) / per;
-  dev::rbf_predict_split_kernel<<<dim3((unsigned)tm, (unsigned)splits), dev::kGldsThreads, 0, s>>>(
-      (const dev::u4*)a_pl, a_sh, Asq, M, (const dev::u4*)b_pl, b_sh, Bsq, coef, N, nkb, gamma, partial, ldp, per);
-  post_launch("rbf_predict_split", s);
-  // zero the splits the reduce reads beyond the launched ones
-  if (splits < max_splits)
-    HIP_CHECK(hipMemsetAsync(partial + splits * ldp, 0, (size_t)(max_splits - splits) * ldp * 4, s));
-  HIP_CHECK(hipFreeAsync(a_pl, s));
-  HIP_CHECK(hipFreeAsync(b_pl, s));
-  HIP_CHECK(hipFreeAsync(a_sh, s));
-  HIP_CHECK(hipFreeAsync(b_sh, s));
-}
-
 int64_t split_pad_rows(int64_t rows) { return (rows + 255) / 256 * 256 + 256; }
+
+int persistent_grid_limit() {
+  int n = 0;
+  HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()));
+  return std::max(8, n);
+}
 
 void split_rows_f16(const float* x, int64_t rows, int dp, int ldx, void* out, int32_t* shift, hipStream_t s) {
   if (rows <= 0) return;
@@ -2396,12 +1412,6 @@ struct GramArgs {
   hipStream_t s;
 };
 
-int persistent_grid_limit() {  // one workgroup per CU
-  int n = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()));
-  return std::max(8, n);
-}
-
 void launch_gram_tile(const GramArgs& g) {
   const int64_t tm = (g.M + 127) / 128, tn = (g.N + 127) / 128;
   dev::rbf_gemm_split_kernel<<<dim3((unsigned)tm, (unsigned)tn), dev::kSplitThreads, 0, g.s>>>(
@@ -2454,74 +1464,66 @@ void launch_gram_w64_persist(const GramArgs& g) {
 // (h1s, w64p with AD) index a tile's stores from 64-bit tile bases with 32-bit offsets and the operand rows
 // in 32 bits: they also take Grams of more than 2^32 elements (200k rows: 160 GB)
 void launch_gram_adaptive(const GramArgs& g, float cold_tau, const GramAdaptPrep* prep) {
-  const void *A = g.A, *B = g.B;
-  const int32_t *Ash = g.Ash, *Bsh = g.Bsh;
-  const float *Asq = g.Asq, *Bsq = g.Bsq;
-  const int64_t M = g.M, N = g.N, ldo = g.ldo;
-  const int nkb = g.nkb;
-  const bool symmetric = g.symmetric;
-  const float gamma = g.gamma;
-  hipStream_t s = g.s;
-  const int64_t tm2 = (M + 255) / 256, tn = (N + 127) / 128;
-  const int64_t ntiles = sym_tile_table(tm2, tn, s, symmetric).count;
+  const int64_t tm2 = (g.M + 255) / 256, tn = (g.N + 127) / 128;
+  const int64_t ntiles = sym_tile_table(tm2, tn, g.s, g.symmetric).count;
   const int64_t grid = std::min<int64_t>(ntiles, persistent_grid_limit());
-  const auto& t1 = sym_tile_table(tm2, tn, s, symmetric, true);  // the one-product pass's own tile order
+  const auto& t1 = sym_tile_table(tm2, tn, g.s, g.symmetric, true);  // the one-product pass's own tile order
   float c0 = 0.f, c1 = 0.f;
-  split_cold_consts(gamma, cold_tau, &c0, &c1);
+  split_cold_consts(g.gamma, cold_tau, &c0, &c1);
   // a solver's prep of these very rows: the h planes and R are there, the hot buffer is re-zeroed
-  const bool pre = prep && symmetric && prep->planes && prep->A == A && prep->M == M && prep->dp == g.dp &&
+  const bool pre = prep && g.symmetric && prep->planes && prep->A == g.A && prep->M == g.M && prep->dp == g.dp &&
                    prep->ntiles == ntiles;
-  const int64_t nr = symmetric ? M : M + N;
+  const int64_t nr = g.symmetric ? g.M : g.M + g.N;
   float* r = pre ? prep->r : nullptr;
   uint32_t* hb = pre ? prep->hot : nullptr;  // [ntiles] per-tile reports, then the list's length and entries
   if (!pre) {
-    HIP_CHECK(hipMallocAsync((void**)&r, (size_t)nr * 4, s));
-    HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * ntiles + 1) * 4, s));
+    HIP_CHECK(hipMallocAsync((void**)&r, (size_t)nr * 4, g.s));
+    HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * ntiles + 1) * 4, g.s));
   }
-  HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(ntiles + 1) * 4, s));
+  HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(ntiles + 1) * 4, g.s));
   float* br = r;
   if (!pre) {
-    dev::split_log2norm_kernel<<<dim3((unsigned)((M + 255) / 256)), 256, 0, s>>>(Asq, (int)M, r);
-    if (!symmetric) {
-      br = r + M;
-      dev::split_log2norm_kernel<<<dim3((unsigned)((N + 255) / 256)), 256, 0, s>>>(Bsq, (int)N, br);
+    dev::split_log2norm_kernel<<<dim3((unsigned)((g.M + 255) / 256)), 256, 0, g.s>>>(g.Asq, (int)g.M, r);
+    if (!g.symmetric) {
+      br = r + g.M;
+      dev::split_log2norm_kernel<<<dim3((unsigned)((g.N + 255) / 256)), 256, 0, g.s>>>(g.Bsq, (int)g.N, br);
     }
-    post_launch("split_log2norm", s);
+    post_launch("split_log2norm", g.s);
   }
-  const void *hA = A, *hB = B;
+  const void *hA = g.A, *hB = g.B;
   dev::u4* planes = nullptr;
   if (pre) {
     hA = hB = prep->planes;
   } else {  // the h planes of the rows the tiles read (whole 256 / 128-row tiles)
-    const int64_t nq = (int64_t)((nkb + 1) / 2) * 8, ra = tm2 * 256, rb = symmetric ? 0 : tn * 128;
-    HIP_CHECK(hipMallocAsync((void**)&planes, (size_t)(ra + rb) * nq * 16, s));
-    dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)A, ra, nkb,
+    const int64_t nq = (int64_t)((g.nkb + 1) / 2) * 8, ra = tm2 * 256, rb = g.symmetric ? 0 : tn * 128;
+    HIP_CHECK(hipMallocAsync((void**)&planes, (size_t)(ra + rb) * nq * 16, g.s));
+    dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, g.s>>>((const dev::u4*)g.A, ra, g.nkb,
                                                                                       planes);
     hA = hB = planes;
-    if (!symmetric) {
-      dev::split_hplane_kernel<<<dim3((unsigned)((rb * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)B, rb, nkb,
+    if (!g.symmetric) {
+      dev::split_hplane_kernel<<<dim3((unsigned)((rb * nq + 255) / 256)), 256, 0, g.s>>>((const dev::u4*)g.B, rb, g.nkb,
                                                                                         planes + ra * nq);
       hB = planes + ra * nq;
     }
-    post_launch("split_hplane", s);
+    post_launch("split_hplane", g.s);
   }
   // (stamps, set_gram_stamps: the one-product pass's 16 words a tile; pass 2 runs unstamped)
   auto h1k = g_gram_stamps ? dev::rbf_gemm_split_h1s_kernel<true> : dev::rbf_gemm_split_h1s_kernel<false>;
-  h1k<<<dim3((unsigned)grid), dev::kH1sThreads, 0, s>>>(
-      (const dev::u4*)hA, Ash, Asq, r, (int)M, (const dev::u4*)hB, Bsh, Bsq, br, (int)N, nkb, gamma, c0, c1, g.out,
-      (int)ldo, symmetric ? 1 : 0, t1.dev, (int)ntiles, hb, hb + ntiles, g_gram_stamps);
-  if (planes) HIP_CHECK(hipFreeAsync(planes, s));
-  post_launch("rbf_gemm_split_h1", s);
-  dev::rbf_gemm_split_w64p_kernel<false, true><<<dim3((unsigned)grid), dev::kW64Threads, 0, s>>>(
-      (const dev::u4*)A, Ash, Asq, (int)M, (const dev::u4*)B, Bsh, Bsq, (int)N, nkb, gamma, g.out, (int)ldo,
-      symmetric ? 1 : 0, hb + ntiles + 1, 0, (int)tm2, (int)tn, nullptr, r, br, c0, c1, hb + ntiles);
-  post_launch("rbf_gemm_split_w64p_hot", s);
+  h1k<<<dim3((unsigned)grid), dev::kH1sThreads, 0, g.s>>>(
+      (const dev::u4*)hA, g.Ash, g.Asq, r, (int)g.M, (const dev::u4*)hB, g.Bsh, g.Bsq, br, (int)g.N, g.nkb, g.gamma, c0,
+      c1, g.out, (int)g.ldo, g.symmetric ? 1 : 0, t1.dev, (int)ntiles, hb, hb + ntiles, g_gram_stamps);
+  if (planes) HIP_CHECK(hipFreeAsync(planes, g.s));
+  post_launch("rbf_gemm_split_h1", g.s);
+  dev::rbf_gemm_split_w64p_kernel<false, true><<<dim3((unsigned)grid), dev::kW64Threads, 0, g.s>>>(
+      (const dev::u4*)g.A, g.Ash, g.Asq, (int)g.M, (const dev::u4*)g.B, g.Bsh, g.Bsq, (int)g.N, g.nkb, g.gamma, g.out,
+      (int)g.ldo, g.symmetric ? 1 : 0, hb + ntiles + 1, 0, (int)tm2, (int)tn, nullptr, r, br, c0, c1, hb + ntiles);
+  post_launch("rbf_gemm_split_w64p_hot", g.s);
   if (!t_adapt_hot) HIP_CHECK(hipHostMalloc((void**)&t_adapt_hot, 4, hipHostMallocDefault));
-  HIP_CHECK(hipMemcpyAsync(t_adapt_hot, hb + ntiles, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(t_adapt_hot, hb + ntiles, 4, hipMemcpyDeviceToHost, g.s));
   t_adapt_tiles = ntiles;
   if (!pre) {
-    HIP_CHECK(hipFreeAsync(r, s));
-    HIP_CHECK(hipFreeAsync(hb, s));
+    HIP_CHECK(hipFreeAsync(r, g.s));
+    HIP_CHECK(hipFreeAsync(hb, g.s));
   }
 }
 }  // namespace
@@ -2543,49 +1545,6 @@ void rbf_gemm_store_split(const void* A, const int32_t* Ash, const float* Asq, i
     case GramPath::W64Persist: return launch_gram_w64_persist(g);
     case GramPath::Adaptive: return launch_gram_adaptive(g, cold_tau, prep);
   }
-}
-
-void rbf_rows_indexed_split(const void* X, const int32_t* Xsh, const float* Xsq, const int32_t* a_rows,
-                            const int32_t* m_dev, int64_t M_max, const void* B, const int32_t* Bsh, const float* Bsq,
-                            int64_t N, int dp, float gamma, float* lines, const int32_t* out_rows, int64_t ldl,
-                            hipStream_t s) {
-  if (M_max <= 0 || N <= 0) return;
-  // 192 x 128 tiles (12 waves): a one-block round's misses (<= 192 rows) are
-  // one tile row, so every column panel of B — all of this rank's rows, the
-  // bytes that bound this GEMM — is read from HBM once per round (64-row
-  // tiles read it once per 64 misses)
-  const int64_t tm = (M_max + 191) / 192, tn = (N + 127) / 128;
-  DPSVM_CHECK(tn < 65536, "rbf_rows_indexed_split: N too large for grid.y");
-  const int nkb = (dp + 31) / 32;
-  if (nkb <= 2) {  // persistent small-K kernel
-    // the scratch line of the fixed-count stores (64 floats, never read), one per device
-    static std::mutex trash_mu;
-    static float* trash_of[kMaxDevices] = {};
-    float* trash = nullptr;
-    {
-      const int device = current_device();
-      std::lock_guard<std::mutex> lk(trash_mu);
-      if (!trash_of[device]) HIP_CHECK(hipMalloc((void**)&trash_of[device], 64 * sizeof(float)));
-      trash = trash_of[device];
-    }
-    const int64_t grid = std::min<int64_t>(tm * tn, persistent_grid_limit());
-    auto k = nkb == 1 ? dev::rbf_rows_split_persist_kernel<1> : dev::rbf_rows_split_persist_kernel<2>;
-    k<<<dim3((unsigned)grid), dev::kRowsPersistThreads, 0, s>>>((const dev::u4*)X, Xsh, Xsq, a_rows, m_dev,
-                                                                (const dev::u4*)B, Bsh, Bsq, N, gamma, lines, ldl,
-                                                                out_rows, trash);
-  } else if (tm == 1 && !g_rows_stamps && (N + 512) * (int64_t)nkb * 8 < (1ll << 32)) {
-    // persistent over the column tiles (one tile row; 32-bit u4 offsets into B)
-    const int64_t grid = std::min<int64_t>(tn, persistent_grid_limit());
-    dev::rbf_rows_split_glds_persist_kernel<<<dim3((unsigned)grid), dev::kRowsGldsThreads, 0, s>>>(
-        (const dev::u4*)X, Xsh, Xsq, a_rows, m_dev, (const dev::u4*)B, Bsh, Bsq, N, nkb, gamma, lines, ldl, out_rows,
-        (int)tn);
-  } else {
-    auto k = g_rows_stamps ? dev::rbf_rows_split_glds_kernel<true> : dev::rbf_rows_split_glds_kernel<false>;
-    k<<<dim3((unsigned)tm, (unsigned)tn), dev::kRowsGldsThreads, 0, s>>>((const dev::u4*)X, Xsh, Xsq, a_rows, m_dev,
-                                                                        (const dev::u4*)B, Bsh, Bsq, N, nkb, gamma,
-                                                                        lines, ldl, out_rows, g_rows_stamps);
-  }
-  post_launch("rbf_rows_indexed_split", s);
 }
 
 

@@ -1,6 +1,8 @@
-// Device helpers shared by the split-operand fp16 MFMA GEMMs
-// (rbf_gemm_split.hip): operand vector types, the
-// 32x32x16 f16 MFMA and the XCD-aware persistent tile order.
+// Device helpers shared by the split-operand fp16 MFMA kernels (the GEMMs of
+// rbf_gemm_split.hip, rbf_rows_split.hip and rbf_predict_split.hip, and
+// ws_recompute.hip): operand vector types, the value epilogue, the 32x32x16
+// f16 MFMA and the XCD-aware tile orders.  The GEMMs' k blocks and tile
+// epilogues built on these are in split_mma.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +16,8 @@ namespace dev {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+typedef int i4v __attribute__((ext_vector_type(4)));
+typedef float f2 __attribute__((ext_vector_type(2)));
 
 // K from a split GEMM's dot product — the epilogue of EVERY split kernel (the
 // Gram, its indexed rows, the predictions, the recompute rounds), so they all
@@ -49,6 +53,34 @@ __device__ __forceinline__ bool split_cold(float t1, float s, float c0, float c1
 
 __device__ __forceinline__ f16v mfma32_f16(h8 a, h8 b, f16v c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+// the 32-bit LDS byte address of a __shared__ pointer (asm ds_read operands)
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+
+// XCD-aware tile order (as rbf_gemm.hip): linear workgroup id L runs on XCD
+// L % 8; chunks of 64 tiles (8 x 8 tile blocks) are dealt so that an XCD's
+// consecutive tiles share panels in its L2.  A bijection on the tm x tn grid.
+__device__ __forceinline__ void xcd_tile_of(int64_t L, int64_t tm, int64_t tn, int64_t& tx, int64_t& ty) {
+  const int64_t total = tm * tn;
+  constexpr int64_t CH = 64, GM = 8;
+  const int64_t full = total / (8 * CH) * (8 * CH);
+  int64_t T = L;
+  if (L < full) {
+    const int64_t xcd = L % 8, local = L / 8;
+    T = ((local / CH) * 8 + xcd) * CH + local % CH;
+  }
+  const int64_t first_m = (T / (GM * tn)) * GM;
+  const int64_t gm = min(GM, tm - first_m);
+  const int64_t in = T - first_m * tn;
+  tx = first_m + in % gm;
+  ty = in / gm;
+}
+
+__device__ __forceinline__ void xcd_tile(int64_t& tx, int64_t& ty) {
+  xcd_tile_of(blockIdx.x + (int64_t)blockIdx.y * gridDim.x, gridDim.x, gridDim.y, tx, ty);
 }
 
 // XCD-aware tile order in 32-bit arithmetic (persistent kernels: tm * tn <

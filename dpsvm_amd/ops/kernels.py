@@ -183,7 +183,7 @@ def rbf_rows_indexed(x: torch.Tensor, rows, gamma: float, out_lines=None, n_line
     """The working-set cache engine's row GEMM (rbf_gemm EPI_ROWS: A rows by
     index, output rows to their lines, M read on the device): lines
     [n_lines][n] with line out_lines[i] = K(x_rows[i], x_j).  split=True: the
-    fp16 split-operand kernel (rbf_gemm_split.hip)."""
+    fp16 split-operand kernels (rbf_rows_split.hip)."""
     C = load()
     rows = [int(r) for r in rows]
     m = len(rows)

@@ -22,6 +22,8 @@ HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
 # GEMMs, the working-set rounds, the pair-at-a-time dense engines)
 SPILL_FREE = [
     "kernels/rbf_gemm_split.hip",
+    "kernels/rbf_rows_split.hip",
+    "kernels/rbf_predict_split.hip",
     "kernels/ws_select.hip",
     "kernels/ws_merge.hip",
     "kernels/ws_solve.hip",

@@ -1,4 +1,5 @@
-"""The fp16 split-operand RBF GEMM (kernels/rbf_gemm_split.hip) vs a float64
+"""The fp16 split-operand RBF GEMMs (kernels/rbf_gemm_split.hip; the indexed
+rows: kernels/rbf_rows_split.hip) vs a float64
 reference and vs the f32-MFMA GEMM (rbf_gemm.hip): same accuracy class, and
 bit-identical values under operand swap (symmetric Gram == full Gram ==
 indexed rows), which the sharded and cache-mode working-set engines rely on."""

@@ -167,6 +167,8 @@ struct SolveResult {
   int status = 0;             // 1 converged, 2 max_iter, 3 no violating pair, 4 non-finite
   double t_setup = 0.0, t_solve = 0.0;
   double t_gram = 0.0;  // device time of the resident Gram GEMM inside t_solve (dense mode)
+  // the solve ran on the resident Gram an earlier solve of the same GpuSolver built (set_labels: t_gram = 0)
+  bool gram_reused = false;
   // adaptive split Gram (gram_adapt, docs/DESIGN.md §13): tiles of the one-product pass and how many of them
   // held an element the error bound rejected (recomputed with all three products); -1: not adaptive
   int64_t gram_tiles = -1, gram_hot_tiles = -1;

@@ -50,6 +50,30 @@ void write_model(const std::string& path, const Model& m, int precision = 9, boo
 // Auto-detects the dpsvm format vs the legacy seq format (2nd line has commas).
 Model read_model(const std::string& path, bool force_legacy = false);
 
+// One-vs-rest multi-class model: k machines (machine c: classes[c] against the
+// rest) with one gamma on the union of their support vectors.
+//   decision[i][c] = sum_s coef[s][c] K(x_s, x_i) - b[c]
+struct MultiModel {
+  float gamma = 0.f;
+  int d = 0;
+  std::vector<float> classes;  // k class labels
+  std::vector<float> b;        // k
+  std::vector<float> coef;     // nsv*k row-major: alpha_c * y_c of the union's rows
+  std::vector<float> x;        // nsv*d
+  int k() const { return (int)classes.size(); }
+  int64_t nsv() const { return classes.empty() ? 0 : (int64_t)(coef.size() / classes.size()); }
+};
+// alphas, ys: k rows of n (machine c's dual variables and its +1 / -1 labels).
+// Union SVs = the rows with any alpha_c > 0, in global index order.
+MultiModel make_multi_model(const Dataset& ds, const std::vector<float>& classes, const std::vector<float>& alphas,
+                            const std::vector<float>& ys, const std::vector<float>& b, float gamma);
+// Text: "dpsvm-ovr <k> <nsv> <d>" \n classes \n gamma \n b_0 .. b_{k-1} \n then per SV its k
+// coefficients and d features; numbers comma-separated, `precision` as write_model.
+void write_multi_model(const std::string& path, const MultiModel& m, int precision = 9);
+MultiModel read_multi_model(const std::string& path);
+// true when the file starts with the multi-class header
+bool is_multi_model(const std::string& path);
+
 // Deterministic synthetic generators (identical on every rank; row-seeded so a
 // rank can generate only its own rows).
 enum class Synth : int {

@@ -51,6 +51,8 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
 
 // Decision values d(x) = sum_sv alpha y K(sv,x) - b  (svmTrain.cu:646-658)
 std::vector<float> decision_cpu(const Model& m, const float* x, int64_t n, int d, int threads = 0);
+// One-vs-rest decision values [n][k]: column c = sum_sv coef[sv][c] K(sv, x) - b[c] (k passes of decision_cpu)
+std::vector<float> decision_multi_cpu(const MultiModel& m, const float* x, int64_t n, int d, int threads = 0);
 // fraction of rows with sign(decision) == y  (>= 0 -> +1)
 double accuracy_from_decision(const std::vector<float>& dec, const float* y, int64_t n);
 
@@ -114,6 +116,14 @@ class GpuSolver {
   // after solve(): the whole gradient on every rank (the shards all-gathered;
   // a collective at world > 1)
   std::vector<float> gradient_all();
+  // After setup(): other labels on the same rows (host, global n; mapped to +1 / -1 as setup does).  X, |x|^2,
+  // the split operands, the engine, the round plan and the captured graphs stay (they hold the label buffer's
+  // address, which does not move).  The next solve() on a dense engine then keeps the resident Gram — it
+  // depends on X and gamma alone — when a Gram completed by an earlier solve() of this object is still in place
+  // (not after release_cache() or a failed solve): that solve reports gram_reused, t_gram = 0.  A solve() not
+  // preceded by set_labels() rebuilds the Gram in its timed region as ever.  One-vs-rest training: k solves, one
+  // setup, one Gram.
+  void set_labels(const float* y);
   // the stop tolerance of the next solve() (kernel arguments updated, captured graphs rebuilt)
   void set_eps(float eps);
   // free the kernel-row cache / resident Gram until the next solve() (which
@@ -167,8 +177,13 @@ class GpuPredictor {
  public:
   // precision: 0 auto (split-operand GEMM from 128 padded features), 1 f32-input MFMA, 2 split-operand
   GpuPredictor(const Model& m, int device, int precision = 0);
+  // one-vs-rest machines on the union of their SVs: decision_multi() only
+  GpuPredictor(const MultiModel& m, int device, int precision = 0);
   ~GpuPredictor();
   std::vector<float> decision(const float* x_host, int64_t n, int d);
+  // [n][k] decision values of a multi-class model (launch::rbf_predict_multi), chunked like decision()
+  std::vector<float> decision_multi(const float* x_host, int64_t n, int d);
+  int k() const;  // columns of decision_multi (0: a binary model)
   // device pointers, stream = hipStream_t as void*
   void decision_device(const float* x_dev, int64_t n, int d, int ld, float* out_dev, void* stream);
   struct Impl;
@@ -191,6 +206,17 @@ void select_partials(const float* f, const float* alpha, const float* y, int64_t
 void predict(const float* x, const float* xsq, int64_t n, int ld, const float* sv,
              const float* svsq, const float* coef, int64_t nsv, int sv_ld, float gamma, float b,
              float* dec, void* stream);
+// dec[i * k + c] = sum_j coef[j * k + c] K(x_i, sv_j) - b[c] (launch::rbf_predict_multi; b: device, k floats)
+void predict_multi(const float* x, const float* xsq, int64_t n, int ld, const float* sv, const float* svsq,
+                   const float* coef, int k, int64_t nsv, int sv_ld, float gamma, const float* b, float* dec,
+                   void* stream);
+// diagnostics (bench/predict_multi_probe.py): ms per repetition, event-timed, of the multi-output launch
+// (multi) or of k single-output rbf_predict launches, one per row of coef_cols [k][ldcc] (column c's
+// coefficients, zero-padded as predict's coef), into dec
+std::vector<float> predict_multi_bench(const float* x, const float* xsq, int64_t n, int ld, const float* sv,
+                                       const float* svsq, const float* coef, const float* coef_cols, int64_t ldcc,
+                                       int k, int64_t nsv, float gamma, const float* b, float* dec, bool multi,
+                                       int reps, void* stream);
 int64_t compact_nonzero(const float* alpha, int64_t n, int* idx_out, void* stream);
 // Gram block K[i][j] = K(a_i, b_j) (dense-mode GEMM; symmetric: b == a)
 void rbf_gram(const float* a, const float* asq, int64_t m, const float* b, const float* bsq, int64_t n, int ld,

@@ -65,6 +65,8 @@ void write_model(const std::string& path, const Model& m, int precision, bool le
 }
 
 namespace {
+const char* const kMultiMagic = "dpsvm-ovr";
+
 std::vector<float> split_floats(const std::string& line) {
   std::vector<float> v;
   const char* p = line.data();
@@ -90,6 +92,8 @@ Model read_model(const std::string& path, bool force_legacy) {
   std::string line;
   Model m;
   if (!std::getline(in, line)) fail("model file " + path + " is empty");
+  if (line.rfind(kMultiMagic, 0) == 0)
+    fail("model file " + path + " is a multi-class (one-vs-rest) model: read it with read_multi_model");
   m.gamma = split_floats(line).at(0);
   std::string second;
   bool have_second = (bool)std::getline(in, second);
@@ -118,6 +122,103 @@ Model read_model(const std::string& path, bool force_legacy) {
     m.x.insert(m.x.end(), v.begin() + 2, v.end());
   }
   if (m.d < 0) m.d = 0;
+  return m;
+}
+
+// ---------------------------------------------------------------------------
+// one-vs-rest multi-class model
+// ---------------------------------------------------------------------------
+MultiModel make_multi_model(const Dataset& ds, const std::vector<float>& classes, const std::vector<float>& alphas,
+                            const std::vector<float>& ys, const std::vector<float>& b, float gamma) {
+  const int64_t k = (int64_t)classes.size(), n = ds.n;
+  DPSVM_CHECK(k >= 1, "multi-class model: no classes");
+  DPSVM_CHECK((int64_t)alphas.size() == k * n && (int64_t)ys.size() == k * n, "alphas / ys must be k rows of n");
+  DPSVM_CHECK((int64_t)b.size() == k, "b must have k entries");
+  MultiModel m;
+  m.gamma = gamma;
+  m.d = ds.d;
+  m.classes = classes;
+  m.b = b;
+  for (int64_t i = 0; i < n; ++i) {
+    bool sv = false;
+    for (int64_t c = 0; c < k && !sv; ++c) sv = alphas[(size_t)(c * n + i)] > 0.f;
+    if (!sv) continue;
+    for (int64_t c = 0; c < k; ++c)
+      m.coef.push_back(alphas[(size_t)(c * n + i)] * (ys[(size_t)(c * n + i)] > 0.f ? 1.f : -1.f));
+    m.x.insert(m.x.end(), ds.x.begin() + (size_t)i * ds.d, ds.x.begin() + (size_t)(i + 1) * ds.d);
+  }
+  return m;
+}
+
+void write_multi_model(const std::string& path, const MultiModel& m, int precision) {
+  const int k = m.k();
+  const int64_t nsv = m.nsv();
+  DPSVM_CHECK(k >= 1 && (int)m.b.size() == k, "multi-class model: classes and b must have k >= 1 entries");
+  DPSVM_CHECK((int64_t)m.coef.size() == nsv * k && (int64_t)m.x.size() == nsv * m.d,
+              "multi-class model: coef must be nsv x k and x nsv x d");
+  FILE* fp = fopen(path.c_str(), "w");
+  if (!fp) fail("Model output file " + path + " could not be opened for writing.");
+  std::vector<char> buf(1 << 20);
+  setvbuf(fp, buf.data(), _IOFBF, buf.size());
+  char fmt[16];
+  snprintf(fmt, sizeof(fmt), "%%.%dg", precision);
+  auto row = [&](const float* v, int64_t count, bool first) {
+    for (int64_t i = 0; i < count; ++i) {
+      if (!first || i) fputc(',', fp);
+      if (v[i] == 0.f) fputc('0', fp);
+      else fprintf(fp, fmt, (double)v[i]);
+    }
+  };
+  fprintf(fp, "%s %d %lld %d\n", kMultiMagic, k, (long long)nsv, m.d);
+  row(m.classes.data(), k, true);
+  fputc('\n', fp);
+  fprintf(fp, fmt, (double)m.gamma);
+  fputc('\n', fp);
+  row(m.b.data(), k, true);
+  fputc('\n', fp);
+  for (int64_t i = 0; i < nsv; ++i) {
+    row(&m.coef[(size_t)i * k], k, true);
+    row(m.x.data() + (size_t)i * m.d, m.d, false);
+    fputc('\n', fp);
+  }
+  if (fclose(fp) != 0) fail("error writing model " + path);
+}
+
+bool is_multi_model(const std::string& path) {
+  std::ifstream in(path);
+  if (!in.is_open()) fail("Couldn't open model file " + path);
+  std::string line;
+  return std::getline(in, line) && line.rfind(kMultiMagic, 0) == 0;
+}
+
+MultiModel read_multi_model(const std::string& path) {
+  std::ifstream in(path);
+  if (!in.is_open()) fail("Couldn't open model file " + path);
+  std::string line;
+  if (!std::getline(in, line)) fail("model file " + path + " is empty");
+  if (line.rfind(kMultiMagic, 0) != 0)
+    fail("read_multi_model: " + path + " is not a multi-class (one-vs-rest) model: read it with read_model");
+  long long k = 0, nsv = 0, d = 0;
+  {
+    std::istringstream hs(line.substr(std::string(kMultiMagic).size()));
+    if (!(hs >> k >> nsv >> d) || k < 1 || nsv < 0 || d < 0) fail("read_multi_model: bad header: " + line.substr(0, 80));
+  }
+  auto next = [&](const char* what, size_t count) {
+    if (!std::getline(in, line)) fail(std::string("read_multi_model: missing ") + what);
+    auto v = split_floats(line);
+    if (v.size() != count) fail(std::string("read_multi_model: wrong number of values in ") + what);
+    return v;
+  };
+  MultiModel m;
+  m.d = (int)d;
+  m.classes = next("the class line", (size_t)k);
+  m.gamma = next("the gamma line", 1)[0];
+  m.b = next("the b line", (size_t)k);
+  for (long long i = 0; i < nsv; ++i) {
+    const auto v = next("a support vector line", (size_t)(k + d));
+    m.coef.insert(m.coef.end(), v.begin(), v.begin() + k);
+    m.x.insert(m.x.end(), v.begin() + k, v.end());
+  }
   return m;
 }
 

@@ -200,6 +200,16 @@ void rbf_predict(const float* A, const float* Asq, int64_t M, int lda, const flo
                  const float* Bsq, const float* coef, int64_t N, int ldb, int dp, float gamma,
                  float b, float* partial, float* dec, const float* y, int32_t* correct,
                  hipStream_t s, int precision = 0);
+// k decision values a row on one SV set (one-vs-rest machines: one gamma, the union of their SVs):
+//   dec[i * ldd + c] = sum_j coef[j * ldc + c] K(A_i, B_j) - b[c], c < k   (b: device, k floats)
+// Where rbf_predict runs the split-operand GEMM (predict_uses_split; precision as there) and k > 1, the
+// multi-output kernel (rbf_predict_split.hip): the kernel block computed once per 32 columns.  Else (dp < 128:
+// there is no f32 twin; k == 1) k rbf_predict launches into the columns, so k == 1 holds rbf_predict's values.
+//   scratch: predict_multi_scratch_floats(M, N, k) floats
+int64_t predict_multi_scratch_floats(int64_t M, int64_t N, int k);
+void rbf_predict_multi(const float* A, const float* Asq, int64_t M, int lda, const float* B, const float* Bsq,
+                       const float* coef, int ldc, int k, int64_t N, int ldb, int dp, float gamma, const float* b,
+                       float* scratch, float* dec, int64_t ldd, hipStream_t s, int precision = 0);
 
 // SV compaction: idx_out[k] = i for the k-th alpha[i] > 0 (index order)
 // scratch: >= compact_scratch_ints(n) ints; count written to *count_dev

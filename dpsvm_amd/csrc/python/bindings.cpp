@@ -111,6 +111,7 @@ py::dict result_dict(const SolveResult& r) {
   d["t_setup"] = r.t_setup;
   d["t_solve"] = r.t_solve;
   d["t_gram"] = r.t_gram;
+  d["gram_reused"] = r.gram_reused;
   d["gram_tiles"] = r.gram_tiles;
   d["gram_hot_tiles"] = r.gram_hot_tiles;
   d["verify_f_err"] = r.verify_f_err;
@@ -427,6 +428,43 @@ PYBIND11_MODULE(_C, m) {
   m.def("write_model", &write_model, py::arg("path"), py::arg("model"), py::arg("precision") = 9,
         py::arg("legacy") = false);
   m.def("read_model", &read_model, py::arg("path"), py::arg("force_legacy") = false);
+  py::class_<MultiModel>(m, "MultiModel")
+      .def(py::init<>())
+      .def_readwrite("gamma", &MultiModel::gamma)
+      .def_readwrite("d", &MultiModel::d)
+      .def_property_readonly("k", &MultiModel::k)
+      .def_property_readonly("nsv", &MultiModel::nsv)
+      .def_property("classes", [](const MultiModel& md) { return to_np(md.classes); },
+                    [](MultiModel& md, F32 a) { md.classes = from_np(a); })
+      .def_property("b", [](const MultiModel& md) { return to_np(md.b); },
+                    [](MultiModel& md, F32 a) { md.b = from_np(a); })
+      .def_property("coef", [](const MultiModel& md) { return to_np2(md.coef, md.nsv(), md.k()); },
+                    [](MultiModel& md, F32 a) { md.coef = from_np(a); })
+      .def_property("x", [](const MultiModel& md) { return to_np2(md.x, md.nsv(), md.d); },
+                    [](MultiModel& md, F32 a) { md.x = from_np(a); });
+  m.def("make_multi_model", [](F32 x, F32 classes, F32 alphas, F32 ys, F32 b, float gamma) {
+    if (x.ndim() != 2) throw py::value_error("x must be 2-D (n, d)");
+    if (alphas.ndim() != 2 || ys.ndim() != 2 || alphas.shape(1) != x.shape(0) || ys.shape(1) != x.shape(0) ||
+        alphas.shape(0) != classes.size() || ys.shape(0) != classes.size())
+      throw py::value_error("alphas and ys must be (k, n)");
+    Dataset ds;
+    ds.n = x.shape(0);
+    ds.d = (int)x.shape(1);
+    ds.x = from_np(x);
+    return make_multi_model(ds, from_np(classes), from_np(alphas), from_np(ys), from_np(b), gamma);
+  }, py::arg("x"), py::arg("classes"), py::arg("alphas"), py::arg("ys"), py::arg("b"), py::arg("gamma"));
+  m.def("write_multi_model", &write_multi_model, py::arg("path"), py::arg("model"), py::arg("precision") = 9);
+  m.def("read_multi_model", &read_multi_model, py::arg("path"));
+  m.def("is_multi_model", &is_multi_model, py::arg("path"));
+  m.def("decision_multi_cpu", [](const MultiModel& md, F32 x, int threads) {
+    if (x.ndim() != 2) throw py::value_error("x must be 2-D");
+    std::vector<float> dec;
+    {
+      py::gil_scoped_release r;
+      dec = decision_multi_cpu(md, x.data(), x.shape(0), (int)x.shape(1), threads);
+    }
+    return to_np2(dec, x.shape(0), md.k());
+  }, py::arg("model"), py::arg("x"), py::arg("threads") = 0);
   m.def("decision_cpu", [](const Model& md, F32 x, int threads) {
     if (x.ndim() != 2) throw py::value_error("x must be 2-D");
     std::vector<float> dec;
@@ -502,6 +540,15 @@ PYBIND11_MODULE(_C, m) {
         }
         return py::make_tuple(to_np(r.alpha), result_dict(r));
       }, py::arg("resume") = nullptr, py::arg("progress") = py::none())
+      .def("set_labels", [](GpuSolver& s, F32 y) {
+        if (y.ndim() != 1 || y.shape(0) != s.info().n) throw py::value_error("y must have n entries");
+        py::gil_scoped_release rel;
+        s.set_labels(y.data());
+      }, py::arg("y"), "other labels on the rows of setup(): the next solve() keeps the resident Gram")
+      .def("release_cache", [](GpuSolver& s) {
+        py::gil_scoped_release rel;
+        s.release_cache();
+      })
       .def("train_accuracy", [](GpuSolver& s, F32 alpha, float b) {
         SolveResult r;
         r.alpha = from_np(alpha);
@@ -564,6 +611,17 @@ PYBIND11_MODULE(_C, m) {
 
   py::class_<GpuPredictor, std::shared_ptr<GpuPredictor>>(m, "GpuPredictor")
       .def(py::init<const Model&, int, int>(), py::arg("model"), py::arg("device") = 0, py::arg("precision") = 0)
+      .def(py::init<const MultiModel&, int, int>(), py::arg("model"), py::arg("device") = 0,
+           py::arg("precision") = 0)
+      .def("decision_multi", [](GpuPredictor& p, F32 x) {
+        if (x.ndim() != 2) throw py::value_error("x must be 2-D");
+        std::vector<float> out;
+        {
+          py::gil_scoped_release rel;
+          out = p.decision_multi(x.data(), x.shape(0), (int)x.shape(1));
+        }
+        return to_np2(out, x.shape(0), p.k());
+      }, py::arg("x"))
       .def("decision", [](GpuPredictor& p, F32 x) {
         if (x.ndim() != 2) throw py::value_error("x must be 2-D");
         std::vector<float> out;
@@ -600,6 +658,21 @@ PYBIND11_MODULE(_C, m) {
     kernels::predict((const float*)x, (const float*)xsq, n, ld, (const float*)sv, (const float*)svsq,
                      (const float*)coef, nsv, ld, gamma, b, (float*)dec, (void*)stream);
   });
+  m.def("k_predict_multi", [](uintptr_t x, uintptr_t xsq, int64_t n, int ld, uintptr_t sv, uintptr_t svsq,
+                              uintptr_t coef, int k, int64_t nsv, float gamma, uintptr_t b, uintptr_t dec,
+                              uintptr_t stream) {
+    kernels::predict_multi((const float*)x, (const float*)xsq, n, ld, (const float*)sv, (const float*)svsq,
+                           (const float*)coef, k, nsv, ld, gamma, (const float*)b, (float*)dec, (void*)stream);
+  });
+  m.def("k_predict_multi_bench", [](uintptr_t x, uintptr_t xsq, int64_t n, int ld, uintptr_t sv, uintptr_t svsq,
+                                    uintptr_t coef, uintptr_t coef_cols, int64_t ldcc, int k, int64_t nsv,
+                                    float gamma, uintptr_t b, uintptr_t dec, bool multi, int reps,
+                                    uintptr_t stream) {
+    return kernels::predict_multi_bench((const float*)x, (const float*)xsq, n, ld, (const float*)sv,
+                                        (const float*)svsq, (const float*)coef, (const float*)coef_cols, ldcc, k,
+                                        nsv, gamma, (const float*)b, (float*)dec, multi, reps, (void*)stream);
+  }, "diagnostics (bench/predict_multi_probe.py): event-timed ms per repetition of the multi-output launch "
+     "(multi) or of k single-output rbf_predict launches on coef_cols' rows");
   m.def("k_rbf_gram", [](uintptr_t a, uintptr_t asq, int64_t m_, uintptr_t b, uintptr_t bsq, int64_t n, int ld,
                          float gamma, uintptr_t out, int64_t out_ld, bool symmetric, uintptr_t stream) {
     kernels::rbf_gram((const float*)a, (const float*)asq, m_, (const float*)b, (const float*)bsq, n, ld, gamma,

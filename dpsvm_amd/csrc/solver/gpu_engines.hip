@@ -71,7 +71,13 @@ void split_x(GpuSolver::Impl& m) {
 // local rows) by one MFMA GEMM inside the timed region.
 struct DenseBase : Engine {
   EventTimer gram_timer;
+  bool gram_ran = false;  // by this solve (else gram_seconds() is 0, not the previous solve's time)
   void gram(GpuSolver::Impl& m, SolveResult& res) {
+    gram_ran = !m.reuse_gram;
+    if (m.reuse_gram) {  // set_labels: the Gram an earlier solve built is still in the lines
+      res.gram_reused = true;
+      return;
+    }
     trace::Range gram_range("dpsvm/gram_gemm");
     gram_timer.start(m.stream);
     split_x(m);
@@ -151,7 +157,7 @@ struct DenseBase : Engine {
     gram(m, res);
     seed_keys(m, iter0, b_hi, b_lo);
   }
-  double gram_seconds() override { return gram_timer.seconds(); }
+  double gram_seconds() override { return gram_ran ? gram_timer.seconds() : 0.0; }
   Pending pending(GpuSolver::Impl& m) override {
     // blocks have even length: the last kernel wrote record 1 (the persistent
     // engine leaves "no pending pair" there)

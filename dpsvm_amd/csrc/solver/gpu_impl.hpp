@@ -134,6 +134,10 @@ struct GpuSolver::Impl {
   EngineKind kind = EngineKind::Chain;
   std::unique_ptr<gpu::Engine> engine;
   std::vector<float> h_y;
+  // the resident Gram across solves (GpuSolver::set_labels): gram_valid = the lines hold a Gram a completed
+  // solve built; labels_swapped = set_labels was called since the last solve; reuse_gram = this solve's decision
+  // (labels_swapped && gram_valid), read by DenseBase::gram
+  bool gram_valid = false, labels_swapped = false, reuse_gram = false;
 
   hipGraphExec_t gexec = nullptr;
   hipGraph_t graph = nullptr;

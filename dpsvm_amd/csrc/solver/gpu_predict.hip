@@ -212,11 +212,12 @@ struct GpuPredictor::Impl {
   int precision = 0;  // launch::rbf_predict's: 0 auto, 1 f32, 2 split
   float gamma = 0.f, b = 0.f;
   int64_t nsv = 0;
-  float *sv = nullptr, *svsq = nullptr, *coef = nullptr;
+  int k = 0;  // > 0: a multi-class model (coef [nsv][k], bk its k thresholds)
+  float *sv = nullptr, *svsq = nullptr, *coef = nullptr, *bk = nullptr;
   hipStream_t stream = nullptr;
   ~Impl() {
     (void)hipSetDevice(device);
-    for (void* p : {(void*)sv, (void*)svsq, (void*)coef}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)sv, (void*)svsq, (void*)coef, (void*)bk}) if (p) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -252,10 +253,76 @@ GpuPredictor::GpuPredictor(const Model& mdl, int device, int precision) : impl_(
   HIP_CHECK(hipStreamSynchronize(m.stream));
 }
 
+GpuPredictor::GpuPredictor(const MultiModel& mdl, int device, int precision) : impl_(new Impl) {
+  auto& m = *impl_;
+  DPSVM_CHECK(precision >= 0 && precision <= 2, "GpuPredictor: precision must be 0 (auto), 1 (f32) or 2 (split)");
+  DPSVM_CHECK(mdl.k() >= 1 && (int)mdl.b.size() == mdl.k(), "GpuPredictor: a multi-class model needs k >= 1 classes");
+  m.device = device;
+  m.precision = precision;
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
+  m.d = std::max(1, mdl.d);
+  m.dp = pad_features(m.d);
+  m.gamma = mdl.gamma;
+  m.k = mdl.k();
+  m.nsv = mdl.nsv();
+  const int64_t pad = round_up(std::max<int64_t>(m.nsv, 1), 128) + 128;
+  size_t tb = 0;
+  m.sv = dmalloc<float>((size_t)pad * m.dp, &tb);
+  m.svsq = dmalloc<float>((size_t)pad, &tb);
+  m.coef = dmalloc<float>((size_t)pad * m.k, &tb);
+  m.bk = dmalloc<float>((size_t)m.k, &tb);
+  HIP_CHECK(hipMemsetAsync(m.sv, 0, (size_t)pad * m.dp * 4, m.stream));
+  HIP_CHECK(hipMemsetAsync(m.svsq, 0, pad * 4, m.stream));
+  HIP_CHECK(hipMemsetAsync(m.coef, 0, (size_t)pad * m.k * 4, m.stream));
+  HIP_CHECK(hipMemcpyAsync(m.bk, mdl.b.data(), (size_t)m.k * 4, hipMemcpyHostToDevice, m.stream));
+  if (m.nsv) {
+    HIP_CHECK(hipMemcpy2DAsync(m.sv, (size_t)m.dp * 4, mdl.x.data(), (size_t)mdl.d * 4, (size_t)mdl.d * 4,
+                               (size_t)m.nsv, hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipMemcpyAsync(m.coef, mdl.coef.data(), (size_t)m.nsv * m.k * 4, hipMemcpyHostToDevice, m.stream));
+    launch::row_sqnorm(m.sv, m.nsv, m.dp, m.dp, m.svsq, m.stream);
+  }
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
 GpuPredictor::~GpuPredictor() = default;
+
+int GpuPredictor::k() const { return impl_->k; }
+
+std::vector<float> GpuPredictor::decision_multi(const float* xh, int64_t nt, int d) {
+  auto& m = *impl_;
+  DPSVM_CHECK(m.k > 0, "decision_multi: this predictor holds a binary model");
+  DPSVM_CHECK(d == m.d || m.nsv == 0, "feature count mismatch between model and data");
+  HIP_CHECK(hipSetDevice(m.device));
+  std::vector<float> out((size_t)nt * m.k);
+  if (nt == 0) return out;
+  const int64_t chunk = 1 << 20;
+  size_t tb = 0;
+  const int64_t crows = std::min<int64_t>(nt, chunk), cpad = round_up(crows, 128) + 128;
+  float* dx = dmalloc<float>((size_t)cpad * m.dp, &tb);
+  float* dsq = dmalloc<float>((size_t)cpad, &tb);
+  float* ddec = dmalloc<float>((size_t)cpad * m.k, &tb);
+  float* scratch = dmalloc<float>((size_t)launch::predict_multi_scratch_floats(crows, m.nsv, m.k), &tb);
+  for (int64_t r0 = 0; r0 < nt; r0 += chunk) {
+    const int64_t rows = std::min(chunk, nt - r0);
+    HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)cpad * m.dp * 4, m.stream));
+    HIP_CHECK(hipMemcpy2DAsync(dx, (size_t)m.dp * 4, xh + (size_t)r0 * d, (size_t)d * 4, (size_t)d * 4,
+                               (size_t)rows, hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipMemsetAsync(dsq, 0, cpad * 4, m.stream));
+    launch::row_sqnorm(dx, rows, m.dp, m.dp, dsq, m.stream);
+    launch::rbf_predict_multi(dx, dsq, rows, m.dp, m.sv, m.svsq, m.coef, m.k, m.k, m.nsv, m.dp, m.dp, m.gamma, m.bk,
+                              scratch, ddec, m.k, m.stream, m.precision);
+    HIP_CHECK(hipMemcpyAsync(out.data() + (size_t)r0 * m.k, ddec, (size_t)rows * m.k * 4, hipMemcpyDeviceToHost,
+                             m.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  for (void* p : {(void*)dx, (void*)dsq, (void*)ddec, (void*)scratch}) (void)hipFree(p);
+  return out;
+}
 
 std::vector<float> GpuPredictor::decision(const float* xh, int64_t nt, int d) {
   auto& m = *impl_;
+  DPSVM_CHECK(m.k == 0, "decision: this predictor holds a multi-class model (decision_multi)");
   DPSVM_CHECK(d == m.d || m.nsv == 0, "feature count mismatch between model and data");
   HIP_CHECK(hipSetDevice(m.device));
   std::vector<float> out((size_t)nt);
@@ -285,6 +352,7 @@ std::vector<float> GpuPredictor::decision(const float* xh, int64_t nt, int d) {
 
 void GpuPredictor::decision_device(const float* x_dev, int64_t nt, int d, int ld, float* out_dev, void* stream) {
   auto& m = *impl_;
+  DPSVM_CHECK(m.k == 0, "decision_device: this predictor holds a multi-class model");
   DPSVM_CHECK(d == m.d, "feature count mismatch");
   DPSVM_CHECK(ld % 16 == 0 && ld >= m.dp, "decision_device: ld must be a multiple of 16 >= padded d");
   hipStream_t s = (hipStream_t)stream;
@@ -388,6 +456,51 @@ void predict(const float* x, const float* xsq, int64_t n, int ld, const float* s
   launch::rbf_predict(x, xsq, n, ld, sv, svsq, coef, nsv, sv_ld, ld, gamma, b, part, dec, nullptr, nullptr, s);
   HIP_CHECK(hipStreamSynchronize(s));
   (void)hipFree(part);
+}
+
+void predict_multi(const float* x, const float* xsq, int64_t n, int ld, const float* sv, const float* svsq,
+                   const float* coef, int k, int64_t nsv, int sv_ld, float gamma, const float* b, float* dec,
+                   void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  DPSVM_CHECK(ld == sv_ld && ld % 16 == 0 && k >= 1, "predict_multi: ld == sv_ld, multiple of 16; k >= 1");
+  size_t tb = 0;
+  float* scratch = dmalloc<float>((size_t)launch::predict_multi_scratch_floats(n, nsv, k), &tb);
+  launch::rbf_predict_multi(x, xsq, n, ld, sv, svsq, coef, k, k, nsv, sv_ld, ld, gamma, b, scratch, dec, k, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  (void)hipFree(scratch);
+}
+
+std::vector<float> predict_multi_bench(const float* x, const float* xsq, int64_t n, int ld, const float* sv,
+                                       const float* svsq, const float* coef, const float* coef_cols, int64_t ldcc,
+                                       int k, int64_t nsv, float gamma, const float* b, float* dec, bool multi,
+                                       int reps, void* stream) {
+  DPSVM_CHECK(ld % 16 == 0 && k >= 1 && reps > 0, "predict_multi_bench: arguments");
+  hipStream_t s = (hipStream_t)stream;
+  size_t tb = 0;
+  float* scratch = dmalloc<float>((size_t)launch::predict_multi_scratch_floats(n, nsv, k), &tb);
+  hipEvent_t e0, e1;
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
+  std::vector<float> ms;
+  for (int r = 0; r < reps; ++r) {
+    HIP_CHECK(hipEventRecord(e0, s));
+    if (multi) {
+      launch::rbf_predict_multi(x, xsq, n, ld, sv, svsq, coef, k, k, nsv, ld, ld, gamma, b, scratch, dec, k, s);
+    } else {
+      for (int c = 0; c < k; ++c)
+        launch::rbf_predict(x, xsq, n, ld, sv, svsq, coef_cols + (size_t)c * ldcc, nsv, ld, ld, gamma, 0.f, scratch,
+                            dec, nullptr, nullptr, s);
+    }
+    HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float t = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+    ms.push_back(t);
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipFree(scratch);
+  return ms;
 }
 
 void rbf_gram(const float* a, const float* asq, int64_t m, const float* b, const float* bsq, int64_t n, int ld,

@@ -139,6 +139,19 @@ void GpuSolver::set_eps(float eps) {
 }
 const GpuSetupInfo& GpuSolver::info() const { return impl_->info; }
 
+void GpuSolver::set_labels(const float* y) {
+  auto& m = *impl_;
+  DPSVM_CHECK(m.engine && m.y, "set_labels: call setup() first");
+  DPSVM_CHECK(y != nullptr, "set_labels: y is null");
+  HIP_CHECK(hipSetDevice(m.device));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  m.h_y.assign(y, y + m.n);
+  for (auto& v : m.h_y) v = v > 0 ? 1.f : -1.f;  // as place_vectors
+  HIP_CHECK(hipMemcpyAsync(m.y, m.h_y.data(), m.n * 4, hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  m.labels_swapped = true;
+}
+
 void GpuSolver::release_cache() {
   auto& m = *impl_;
   if (!m.lines) return;
@@ -152,6 +165,7 @@ void GpuSolver::release_cache() {
   m.gexec = m.gexec1 = nullptr;
   m.graph = m.graph1 = nullptr;
   HIP_CHECK(hipFree(m.lines));
+  m.gram_valid = false;
   m.lines = nullptr;
   m.args.lines = nullptr;
   m.wsa.gram = nullptr;

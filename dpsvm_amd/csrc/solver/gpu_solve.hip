@@ -94,6 +94,10 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
     m.args.lines = m.lines;
     m.wsa.gram = m.lines;
   }
+  // the resident Gram is kept only on request (set_labels) and only a completed one; it is not valid again
+  // before this solve has ended well
+  m.reuse_gram = m.labels_swapped && m.gram_valid && m.dense;
+  m.labels_swapped = m.gram_valid = false;
   // ---- state init (alpha = 0, f = -y, empty cache) or resume ----
   int64_t iter0 = 0;
   float b_hi0 = 0.f, b_lo0 = 0.f;
@@ -250,7 +254,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   HIP_CHECK(hipStreamSynchronize(m.stream));
   res.t_solve = secs_since(t0);
   res.t_gram = m.engine->gram_seconds();
-  if (m.gram_cold_tau > 0.f) launch::gram_adapt_last(&res.gram_tiles, &res.gram_hot_tiles);
+  if (m.gram_cold_tau > 0.f && !res.gram_reused) launch::gram_adapt_last(&res.gram_tiles, &res.gram_hot_tiles);
   if (m.p.checkpoint_every > 0 && !m.p.checkpoint_path.empty()) {
     st = m.read_status();
     if (st.done == kMaxIter) m.snapshot(st);  // resumable continuation point
@@ -339,6 +343,8 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   }
   res.alpha.resize((size_t)m.n);
   HIP_CHECK(hipMemcpy(res.alpha.data(), m.alpha, m.n * 4, hipMemcpyDeviceToHost));
+  // the solve ended by its own stop rules: the lines hold a whole Gram (no engine writes them after the GEMM)
+  m.gram_valid = m.dense && (st.done == kConverged || st.done == kMaxIter || st.done == kNoPair);
   return res;
 }
 

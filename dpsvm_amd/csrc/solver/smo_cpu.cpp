@@ -362,6 +362,25 @@ std::vector<float> decision_cpu(const Model& m, const float* x, int64_t n, int d
   return dec;
 }
 
+std::vector<float> decision_multi_cpu(const MultiModel& m, const float* x, int64_t n, int d, int threads) {
+  const int k = m.k();
+  const int64_t nsv = m.nsv();
+  std::vector<float> out((size_t)n * k);
+  Model one;
+  one.gamma = m.gamma;
+  one.d = m.d;
+  one.x = m.x;
+  one.y.assign((size_t)nsv, 1.f);
+  one.alpha.resize((size_t)nsv);
+  for (int c = 0; c < k; ++c) {
+    for (int64_t s = 0; s < nsv; ++s) one.alpha[s] = m.coef[(size_t)s * k + c];  // alpha * y, y = 1
+    one.b = m.b[c];
+    const std::vector<float> dec = decision_cpu(one, x, n, d, threads);
+    for (int64_t i = 0; i < n; ++i) out[(size_t)i * k + c] = dec[i];
+  }
+  return out;
+}
+
 double accuracy_from_decision(const std::vector<float>& dec, const float* y, int64_t n) {
   if (n <= 0) return 0.0;
   int64_t ok = 0;

@@ -6,6 +6,9 @@ Reference capability map (farshid83/dpsvm):
   save() / load_model()-> svmTrainMain.cpp:386-416 model writer, seq_test.cpp:212-249 reader
 Labels: the reference requires +1/-1 (svmTrain.cu:58,73); any two distinct
 labels are accepted here and mapped (classes_[1] -> +1), like scikit-learn.
+More than two labels train one-vs-rest machines (no reference counterpart):
+one device solver, one resident Gram, a label swap per machine, and one
+multi-output decision GEMM over the union of the machines' support vectors.
 """
 from __future__ import annotations
 
@@ -234,13 +237,21 @@ class SVCConfig:
 
 
 class SVC:
-    """Binary RBF C-SVM trained by modified SMO on MI355X (or the CPU).
+    """RBF C-SVM trained by modified SMO on MI355X (or the CPU).
 
     Attributes after fit: ``alpha_`` (dual variables, len n), ``b_`` (threshold:
     decision = sum alpha_i y_i K(x_i, x) - b), ``intercept_`` (= -b_),
     ``support_`` (indices with alpha > 0), ``support_vectors_``, ``dual_coef_``
     (alpha*y of the SVs), ``n_iter_``, ``status_``, ``fit_time_`` (SMO loop
     seconds, the reference's timed region), ``stats_`` (cache / pass counters).
+
+    More than two distinct labels: k one-vs-rest machines (machine c separates
+    ``classes_[c]`` from the rest).  Then ``alpha_`` is (k, n), ``b_`` /
+    ``intercept_`` / ``n_iter_`` (k,), ``support_`` / ``support_vectors_`` the
+    union of the machines' SVs, ``dual_coef_`` (k, nsv), ``stats_`` a list of
+    the k solves' dicts, ``fit_time_`` their sum, ``status_`` their maximum;
+    ``decision_function`` returns (n, k) and ``predict`` the class of the
+    largest value (ties: the lowest class index).
     """
 
     def __init__(self, C: float = 1.0, gamma: Optional[float] = None, eps: float = 1e-3,
@@ -248,6 +259,7 @@ class SVC:
         self.config = SVCConfig(C=C, gamma=gamma, eps=eps, max_iter=max_iter, device=device, **kwargs)
         self._model = None
         self._gpu_pred = None
+        self._multi = False
         self.classes_ = np.array([-1.0, 1.0], dtype=np.float32)
 
     # ------------------------------------------------------------------ labels
@@ -284,6 +296,10 @@ class SVC:
         if self.config.engines == "all" or self.config.host_cache_lines or self.config.cache_engine == "chain":
             load_quarantine()  # the quarantined pair-at-a-time cache engines (plugin)
         X = _as_f32_2d(X)
+        y1 = _as_1d(y)
+        if len(np.unique(y1)) > 2:
+            return self._fit_multi(X, y1, comm, resume, progress, rank_rows)
+        self._multi = False
         ys = self._encode(y)
         n, d = X.shape[0], X.shape[1]
         if rank_rows is None and ys.shape[0] != n:
@@ -346,9 +362,94 @@ class SVC:
         self._gpu_pred = None
         return self
 
+    def _fit_multi(self, X: np.ndarray, y: np.ndarray, comm, resume, progress, rank_rows) -> "SVC":
+        """One-vs-rest: k machines on one X.  On the GPU one solver — setup()
+        (X upload, norms, operand prep, engine choice) once, the resident Gram
+        built by machine 0's solve and kept by the label swaps after it."""
+        for name, val in (("comm", comm), ("resume", resume), ("rank_rows", rank_rows)):
+            if val is not None:
+                raise NotImplementedError(f"multi-class (one-vs-rest) training runs on one rank from a cold start: "
+                                          f"{name} is only supported with two classes")
+        C = load()
+        n, d = X.shape
+        if y.shape[0] != n:
+            raise ValueError("len(y) != X.shape[0]")
+        cfg = self.config
+        p = cfg.to_native(d)
+        classes = np.unique(y)
+        k = len(classes)
+        Ys = np.stack([np.where(y == c, 1.0, -1.0).astype(np.float32) for c in classes])
+        kind, dev = cfg.device_kind()
+        self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
+        t0 = time.perf_counter()
+        alphas, infos = [], []
+        self._solver = None
+        if kind == "cuda" and self._use_shrink(p, n, d, dev, None):
+            for c in range(k):  # ShrinkingSolver has no label swap: one per machine
+                shr = C.ShrinkingSolver(p, None, dev)
+                setup = shr.setup(X, Ys[c])
+                if c == 0:
+                    self.setup_info_ = setup
+                a, info = shr.solve(None, progress)
+                alphas.append(a)
+                infos.append(dict(info))
+                del shr
+        elif kind == "cuda":
+            solver = C.GpuSolver(p, None, dev)
+            self.setup_info_ = solver.setup(X, n, Ys[0])
+            for c in range(k):
+                if c:
+                    solver.set_labels(Ys[c])
+                a, info = solver.solve(None, progress)
+                alphas.append(a)
+                infos.append(dict(info))
+            del solver  # the resident Gram is not held past fit
+        else:
+            for c in range(k):
+                a, info = C.solve_cpu(X, Ys[c], p, None, None, progress)
+                alphas.append(a)
+                infos.append(dict(info))
+        self.wall_time_ = time.perf_counter() - t0
+        self._multi = True
+        self.classes_ = classes
+        self.alpha_ = np.stack(alphas).astype(np.float32)
+        self.b_ = np.array([i["b"] for i in infos], dtype=np.float32)
+        self.intercept_ = -self.b_
+        self.n_iter_ = np.array([i["iters"] for i in infos], dtype=np.int64)
+        self.n_rounds_ = np.array([i.get("outer", 0) for i in infos], dtype=np.int64)
+        self.status_ = int(max(i["status"] for i in infos))
+        self.converged_ = bool(all(i["converged"] for i in infos))
+        self.fit_time_ = float(sum(i["t_solve"] for i in infos))
+        self.setup_time_ = float(infos[0]["t_setup"])
+        self.stats_ = infos
+        if any(i["status"] == 2 and i.get("outer", 0) > 0 for i in infos):
+            import warnings
+
+            warnings.warn("a one-vs-rest machine stopped at max_iter before its gap closed: raise max_iter to "
+                          "converge", RuntimeWarning, stacklevel=3)
+        self.gamma_ = p.gamma
+        self.n_features_in_ = d
+        self._X_train, self._y_train, self._Ys = X, y, Ys
+        self.support_ = np.nonzero((self.alpha_ > 0).any(axis=0))[0]
+        self.support_vectors_ = X[self.support_]
+        self.dual_coef_ = (self.alpha_[:, self.support_] * Ys[:, self.support_]).astype(np.float32)
+        self.n_support_ = int(len(self.support_))
+        self._model = None
+        self._gpu_pred = None
+        return self
+
     # ------------------------------------------------------------------ model
     def to_model(self):
         C = load()
+        if self._model is None and self._multi:
+            try:
+                cls = np.asarray(self.classes_, dtype=np.float32)
+                self._file_classes = bool(np.array_equal(cls.astype(self.classes_.dtype), self.classes_))
+            except (TypeError, ValueError):
+                self._file_classes = False
+            if not self._file_classes:  # the predictors need only the columns' order
+                cls = np.arange(len(self.classes_), dtype=np.float32)
+            self._model = C.make_multi_model(self._X_train, cls, self.alpha_, self._Ys, self.b_, self.gamma_)
         if self._model is None:
             if self._X_train is None:
                 raise RuntimeError("to_model() needs the full training set on this rank")
@@ -356,7 +457,18 @@ class SVC:
         return self._model
 
     def save(self, path: str, precision: int = 9, legacy: bool = False) -> None:
-        """Write the reference text model (gamma, b, then alpha,y,x... per SV)."""
+        """Write the reference text model (gamma, b, then alpha,y,x... per SV);
+        after a multi-class fit the one-vs-rest format ("dpsvm-ovr k nsv d",
+        classes, gamma, b_0..b_k-1, then the k coefficients and x per SV)."""
+        if self._multi:
+            if legacy:
+                raise ValueError("the legacy format holds one binary machine")
+            model = self.to_model()
+            if not self._file_classes:
+                raise ValueError("the multi-class model file holds numeric class labels exactly representable in "
+                                 "float32")
+            load().write_multi_model(path, model, precision)
+            return
         load().write_model(path, self.to_model(), precision, legacy)
 
     # ------------------------------------------------------------------ predict
@@ -373,12 +485,16 @@ class SVC:
         if X.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X.shape[1]} features, model has {self.n_features_in_}")
         gp = self._predictor()
+        if self._multi:
+            return gp.decision_multi(X) if gp is not None else load().decision_multi_cpu(self.to_model(), X, 0)
         if gp is not None:
             return gp.decision(X)
         return load().decision_cpu(self.to_model(), X, 0)
 
     def predict(self, X) -> np.ndarray:
         dec = self.decision_function(X)
+        if self._multi:
+            return self.classes_[np.argmax(dec, axis=1)]  # ties: the lowest class index
         return self._decode(np.where(dec < 0, -1.0, 1.0))  # d >= 0 -> +1 (svmTrain.cu:654-657)
 
     def score(self, X, y) -> float:
@@ -387,6 +503,8 @@ class SVC:
 
     def train_accuracy(self) -> float:
         """Training accuracy computed on device (distributed across ranks)."""
+        if self._multi:
+            return self.score(self._X_train, self._y_train)  # the multi-output predictor
         if getattr(self, "_solver", None) is not None:
             return float(self._solver.train_accuracy(self.alpha_, self.b_))
         return self.score(self._X_train, self._y_train)
@@ -432,5 +550,47 @@ class LoadedModel:
         return float(np.mean(self.predict(X) == np.where(_as_1d(y) > 0, 1.0, -1.0)))
 
 
-def load_model(path: str, device: str = "auto", legacy: bool = False) -> LoadedModel:
-    return LoadedModel(load().read_model(path, legacy), device)
+class LoadedMultiModel:
+    """A one-vs-rest model read from a multi-class model file."""
+
+    def __init__(self, model, device: str = "auto"):
+        self.model = model
+        self.device = device
+        self.classes_ = np.asarray(model.classes)
+        self._gpu = None
+
+    @property
+    def gamma(self) -> float:
+        return self.model.gamma
+
+    @property
+    def b(self) -> np.ndarray:
+        return self.model.b
+
+    @property
+    def n_support(self) -> int:
+        return self.model.nsv
+
+    def decision_function(self, X) -> np.ndarray:
+        X = _as_f32_2d(X)
+        use_gpu = self.device.startswith("cuda") or (self.device == "auto" and gpu_available())
+        if use_gpu:
+            if self._gpu is None:
+                dev = int(self.device.split(":")[1]) if ":" in self.device else 0
+                self._gpu = load().GpuPredictor(self.model, dev)
+            return self._gpu.decision_multi(X)
+        return load().decision_multi_cpu(self.model, X, 0)
+
+    def predict(self, X) -> np.ndarray:
+        return self.classes_[np.argmax(self.decision_function(X), axis=1)]
+
+    def score(self, X, y) -> float:
+        return float(np.mean(self.predict(X) == _as_1d(y)))
+
+
+def load_model(path: str, device: str = "auto", legacy: bool = False):
+    """A LoadedModel, or a LoadedMultiModel for a multi-class (one-vs-rest) file."""
+    C = load()
+    if not legacy and C.is_multi_model(path):
+        return LoadedMultiModel(C.read_multi_model(path), device)
+    return LoadedModel(C.read_model(path, legacy), device)

@@ -147,6 +147,31 @@ def rbf_decision(x: torch.Tensor, sv: torch.Tensor, coef: torch.Tensor, gamma: f
     return dec[: x.shape[0]]
 
 
+def rbf_decision_multi(x: torch.Tensor, sv: torch.Tensor, coef: torch.Tensor, gamma: float,
+                       b: torch.Tensor) -> torch.Tensor:
+    """dec[i, c] = sum_s coef[s, c] exp(-gamma |x_i - sv_s|^2) - b[c]: k
+    one-vs-rest machines on one SV set.  From 128 padded features and k > 1 the
+    multi-output split-operand kernel (the kernel block computed once per 32
+    columns, folded by f32 MFMA); else k single-output launches, so k == 1
+    returns rbf_decision's values."""
+    C = load()
+    if coef.ndim != 2 or coef.shape[0] != sv.shape[0] or b.numel() != coef.shape[1]:
+        raise ValueError("coef must be [nsv, k] and b [k]")
+    k = coef.shape[1]
+    xp, dp = _pad_rows_cols(x)
+    svp, _ = _pad_rows_cols(sv)
+    xsq = torch.zeros(xp.shape[0], device=x.device)
+    svsq = torch.zeros(svp.shape[0], device=x.device)
+    cf = coef.to(device=x.device, dtype=torch.float32).contiguous()
+    bd = b.to(device=x.device, dtype=torch.float32).contiguous()
+    C.k_row_sqnorm(xp.data_ptr(), xp.shape[0], dp, dp, xsq.data_ptr(), _stream(x))
+    C.k_row_sqnorm(svp.data_ptr(), svp.shape[0], dp, dp, svsq.data_ptr(), _stream(x))
+    dec = torch.zeros(x.shape[0], k, device=x.device)
+    C.k_predict_multi(xp.data_ptr(), xsq.data_ptr(), x.shape[0], dp, svp.data_ptr(), svsq.data_ptr(), cf.data_ptr(),
+                      k, sv.shape[0], float(gamma), bd.data_ptr(), dec.data_ptr(), _stream(x))
+    return dec
+
+
 def compact_positive(alpha: torch.Tensor) -> torch.Tensor:
     """Indices i with alpha_i > 0, in index order (ballot + scan kernels)."""
     C = load()

@@ -6,6 +6,7 @@
 #include <getopt.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -42,6 +43,9 @@ struct Options {
   bool quiet = false;
   bool skip_accuracy = false;
   int shrink = 0;             // one GPU, shrinking phases (solve_shrinking): 0 auto (shrink_auto), 1 off, 2 on
+  // --class-weight P,N: C_i = C * P for the +1 rows, C * N for the -1 rows (per-row C; one rank, ws engines)
+  bool class_weight = false;
+  float cw_pos = 1.f, cw_neg = 1.f;
 };
 
 inline void usage_train(const char* prog, bool seq) {
@@ -94,6 +98,8 @@ inline void usage_train(const char* prog, bool seq) {
                "                          32 blocks of 96 rows from 50k rows, halved after every damped round)\n"
                "   --shrink[=auto|on|off] :  one GPU: LIBSVM-style shrinking (phases on the rows that can still\n"
                "                         violate; auto, the default: on when the whole Gram is not resident)\n"
+               "   --class-weight P,N  :  multipliers of C for the +1 / -1 rows (LIBSVM -wi; one rank, working-set\n"
+               "                          engines, --cpu or svmSeq; not with --solver smo, --shrink=on, checkpoints, --resume)\n"
                "   --eta x|gram        :  pair engines' K(hi, lo): from the X rows (default) | the resident Gram\n"
                "   --gram auto|f32|split :  Gram / kernel-row GEMMs: f32-input MFMA, or fp16 MFMA over hi/lo split\n"
                "                          operands (fp32 accuracy); auto = split for the ws engines\n"
@@ -118,7 +124,8 @@ inline Options parse_train(int argc, char** argv, bool seq) {
     OPT_LEGG, OPT_QUIET, OPT_SKIPACC, OPT_VERBOSE, OPT_HOSTC, OPT_PERSIST, OPT_PBLOCK, OPT_XCH,
     OPT_DP, OPT_FCACHE, OPT_CENG, OPT_CGROUPS, OPT_ROWS, OPT_XKB, OPT_XSLEEP, OPT_XSTRIDE, OPT_XMEM,
     OPT_XTMO, OPT_WDOG, OPT_CENSUS, OPT_NOVR, OPT_PJSON, OPT_SOLVER, OPT_WSSIZE, OPT_WSNEW, OPT_WSREL, OPT_WSBLOCKS,
-    OPT_WSINNER, OPT_WSBLOCK, OPT_ETA, OPT_WSWSS, OPT_GRAM, OPT_SHRINK, OPT_ENGINES, OPT_GRAM_ADAPT
+    OPT_WSINNER, OPT_WSBLOCK, OPT_ETA, OPT_WSWSS, OPT_GRAM, OPT_SHRINK, OPT_ENGINES, OPT_GRAM_ADAPT,
+    OPT_CLASSW
   };
   static struct option longopts[] = {
       {"num-att", required_argument, 0, 'a'},     {"num-ex", required_argument, 0, 'x'},
@@ -154,6 +161,7 @@ inline Options parse_train(int argc, char** argv, bool seq) {
       {"ws-wss", required_argument, 0, OPT_WSWSS}, {"gram", required_argument, 0, OPT_GRAM},
       {"gram-adapt", required_argument, 0, OPT_GRAM_ADAPT},
       {"shrink", optional_argument, 0, OPT_SHRINK}, {"engines", required_argument, 0, OPT_ENGINES},
+      {"class-weight", required_argument, 0, OPT_CLASSW},
       {0, 0, 0, 0}};
   while (true) {
     int idx = 0;
@@ -204,6 +212,18 @@ inline Options parse_train(int argc, char** argv, bool seq) {
         const std::string v = optarg ? optarg : "on";
         if (v != "auto" && v != "off" && v != "on") usage_train(argv[0], seq);
         o.shrink = v == "on" ? 2 : v == "off" ? 1 : 0;
+        break;
+      }
+      case OPT_CLASSW: {
+        char* end = nullptr;
+        o.cw_pos = strtof(optarg, &end);
+        if (end == optarg || *end != ',') usage_train(argv[0], seq);
+        const char* second = end + 1;
+        o.cw_neg = strtof(second, &end);
+        if (end == second || *end != '\0' || !(o.cw_pos > 0.f) || !(o.cw_neg > 0.f) || !std::isfinite(o.cw_pos) ||
+            !std::isfinite(o.cw_neg))
+          usage_train(argv[0], seq);
+        o.class_weight = true;
         break;
       }
       case OPT_VERBOSE: o.p.verbose = true; break;
@@ -344,6 +364,22 @@ struct RunExtras {
   GpuSetupInfo setup;  // engine, geometry, exchange, residency (GPU runs)
 };
 
+// --class-weight: the per-row bounds C_i, and the settings a weighted solve resolves or refuses (as SVC.fit does)
+inline std::vector<float> class_weight_rows(Options& o, const Dataset& ds, int world) {
+  std::vector<float> rc((size_t)ds.n);
+  for (int64_t i = 0; i < ds.n; ++i) rc[i] = o.p.C * (ds.y[i] > 0 ? o.cw_pos : o.cw_neg);
+  if (world > 1) fail("--class-weight runs on one rank");
+  if (!o.resume.empty() || !o.p.checkpoint_path.empty()) fail("--class-weight: checkpoints and --resume are not supported");
+  if (o.cpu) return rc;
+  if (o.p.solver == 1) fail("--class-weight needs the working-set engines (not --solver smo)");
+  o.p.solver = 2;
+  if (o.shrink == 2) fail("--class-weight: --shrink=on is not supported");
+  o.shrink = 1;
+  if (o.p.ws_recompute == 1) fail("--class-weight: ws_recompute on is not supported");
+  o.p.ws_recompute = 2;
+  return rc;
+}
+
 inline void write_metrics(const std::string& path, const Options& o, const SolveResult& r, int64_t n, int d,
                           int64_t nsv, double acc, const std::string& backend, const std::string& device,
                           const RunExtras& x) {
@@ -352,8 +388,14 @@ inline void write_metrics(const std::string& path, const Options& o, const Solve
     std::cerr << "cannot write metrics " << path << "\n";
     return;
   }
+  std::string cw;
+  if (o.class_weight) {
+    char b[96];
+    snprintf(b, sizeof(b), "\"class_weight\": [%.9g, %.9g], ", o.cw_pos, o.cw_neg);
+    cw = b;
+  }
   fprintf(fp,
-          "{\"backend\": \"%s\", \"device\": \"%s\", \"world\": %d, \"n\": %lld, \"d\": %d, \"C\": %g, "
+          "{%s\"backend\": \"%s\", \"device\": \"%s\", \"world\": %d, \"n\": %lld, \"d\": %d, \"C\": %g, "
           "\"gamma\": %g, \"eps\": %g, \"clip\": \"%s\", \"iterations\": %lld, \"status\": %d, "
           "\"converged\": %s, \"b\": %.9g, \"b_hi\": %.9g, \"b_lo\": %.9g, \"n_sv\": %lld, "
           "\"train_accuracy\": %.9g, \"t_load_s\": %.6f, \"t_setup_s\": %.6f, \"t_solve_s\": %.6f, "
@@ -365,7 +407,7 @@ inline void write_metrics(const std::string& path, const Options& o, const Solve
           "\"poll_batch\": %d, \"cus\": %d, \"blocks_per_cu\": %d, \"census\": \"%s\", \"engine_note\": \"%s\", \"cache_note\": \"%s\", "
           "\"rounds\": %lld, \"ws_blocks\": %d, \"ws_blocks_end\": %d, \"ws_one_block_from_round\": %lld, "
           "\"ws_damped_rounds\": %lld, \"gram\": \"%s\", \"params\": %s}\n",
-          backend.c_str(), json_escape(device).c_str(), r.world, (long long)n, d, o.p.C, o.p.gamma, o.p.eps,
+          cw.c_str(), backend.c_str(), json_escape(device).c_str(), r.world, (long long)n, d, o.p.C, o.p.gamma, o.p.eps,
           o.p.clip == ClipMode::Box ? "box" : "independent", (long long)r.iters, r.status,
           r.converged() ? "true" : "false", r.b, r.b_hi, r.b_lo, (long long)nsv, acc, x.t_load, r.t_setup,
           r.t_solve, r.t_gram, x.t_accuracy, x.t_model_write, x.engine.c_str(), x.exchange.c_str(),

@@ -19,7 +19,12 @@ int main(int argc, char** argv) {
     ProgressFn prog = [](const Progress& p) {
       std::cout << "Current iteration number: " << p.iter << "  b_hi " << p.b_hi << "  b_lo " << p.b_lo << "\n";
     };
-    SolveResult r = solve_cpu(ds, o.p, nullptr, resume.get(), prog);
+    std::vector<float> row_c;
+    if (o.class_weight) {  // --class-weight P,N: the per-row bounds of the CPU solver (refused with checkpoints / --resume)
+      o.cpu = true;
+      row_c = cli::class_weight_rows(o, ds, 1);
+    }
+    SolveResult r = solve_cpu(ds, o.p, nullptr, resume.get(), prog, row_c.empty() ? nullptr : row_c.data());
     cli::print_outcome(r, o.p.eps);
     Model mdl = make_model(ds, r.alpha, r.b, o.p.gamma);
     cli::RunExtras extras;

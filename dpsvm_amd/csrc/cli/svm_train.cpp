@@ -37,6 +37,8 @@ int main(int argc, char** argv) {
       std::cout << "Resuming from " << o.resume << " at iteration " << resume->iter << "\n";
     }
 
+    std::vector<float> row_c;
+    if (o.class_weight) row_c = cli::class_weight_rows(o, ds, world);
     std::vector<SolveResult> results((size_t)world);
     std::vector<double> accs((size_t)world, -1.0);
     std::string backend = o.cpu ? "cpu" : "hip";
@@ -75,7 +77,8 @@ int main(int argc, char** argv) {
         Communicator* comm = comms[r].get();
         ProgressFn prog = r == 0 ? ProgressFn(progress) : ProgressFn();
         if (o.cpu) {
-          results[r] = solve_cpu(ds, o.p, world > 1 ? comm : nullptr, resume.get(), prog);
+          results[r] = solve_cpu(ds, o.p, world > 1 ? comm : nullptr, resume.get(), prog,
+                                 row_c.empty() ? nullptr : row_c.data());
           if (r == 0) std::cout << "SETUP DONE\n";
           return;
         }
@@ -113,6 +116,7 @@ int main(int argc, char** argv) {
           extras.exchange = info.exchange;
           extras.setup = info;
         }
+        if (!row_c.empty()) solver.set_row_C(row_c.data());
         results[r] = solver.solve(resume.get(), prog);
         const double ta0 = cli::now_s();
         if (!o.skip_accuracy) accs[r] = solver.train_accuracy(results[r]);

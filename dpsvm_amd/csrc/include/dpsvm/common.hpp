@@ -301,6 +301,66 @@ DPSVM_HD PairUpdate pair_update(float a_hi_old, float a_lo_old, float y_hi, floa
   return u;
 }
 
+// Per-row C (C_i = C w_i, sample / class weights): set membership in the
+// compare form.  For C_i > 0 and a in [0, C_i] these equal in_up / in_low; a
+// row with C_i = 0 (a is 0) is in neither set — in_up would put it in I_up
+// and the solver would stall on zero-length steps.
+DPSVM_HD bool in_up_w(float a, float y, float Ci) { return y > 0.f ? a < Ci : a > 0.f; }
+DPSVM_HD bool in_low_w(float a, float y, float Ci) { return y > 0.f ? a > 0.f : a < Ci; }
+
+// pair_update with a bound per row: a_hi in [0, C_hi], a_lo in [0, C_lo].  The
+// box is LIBSVM's two-bound geometry; with C_hi == C_lo every expression is
+// pair_update's, in the same order (bit-equal results).
+DPSVM_HD PairUpdate pair_update_w(float a_hi_old, float a_lo_old, float y_hi, float y_lo, float b_hi,
+                                  float b_lo, float k_hl, float C_hi, float C_lo, float tau, int clip_mode,
+                                  bool same) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float eta = (1.0f + 1.0f) - 2.0f * k_hl;
+  if (!(eta >= tau)) eta = tau;
+  float s = y_lo * y_hi;
+  float a_lo_new = a_lo_old + (y_lo * (b_hi - b_lo) / eta);
+  float a_hi_new;
+  if (clip_mode == (int)ClipMode::Box && !same) {
+    float L, H;
+    float hi_at_L, hi_at_H;  // a_hi value implied when a_lo lands on L / H (-1: none)
+    if (y_hi != y_lo) {
+      const float dl = a_lo_old - a_hi_old;
+      L = dl > 0.f ? dl : 0.f;
+      hi_at_L = dl > 0.f ? 0.f : -1.f;
+      H = C_hi + dl < C_lo ? C_hi + dl : C_lo;
+      hi_at_H = C_hi + dl < C_lo ? C_hi : -1.f;
+    } else {
+      const float sm = a_lo_old + a_hi_old;
+      L = sm - C_hi > 0.f ? sm - C_hi : 0.f;
+      hi_at_L = sm - C_hi > 0.f ? C_hi : -1.f;
+      H = sm < C_lo ? sm : C_lo;
+      hi_at_H = sm < C_lo ? 0.f : -1.f;
+    }
+    if (a_lo_new <= L) {
+      a_lo_new = L;
+      a_hi_new = hi_at_L >= 0.f ? hi_at_L : a_hi_old + (s * (a_lo_old - a_lo_new));
+    } else if (a_lo_new >= H) {
+      a_lo_new = H;
+      a_hi_new = hi_at_H >= 0.f ? hi_at_H : a_hi_old + (s * (a_lo_old - a_lo_new));
+    } else {
+      a_hi_new = a_hi_old + (s * (a_lo_old - a_lo_new));
+    }
+    a_hi_new = clip01(a_hi_new, 0.0f, C_hi);  // guards fp round-off only
+  } else {
+    a_hi_new = a_hi_old + (s * (a_lo_old - a_lo_new));
+    a_lo_new = clip01(a_lo_new, 0.0f, C_lo);
+    a_hi_new = clip01(a_hi_new, 0.0f, C_hi);
+  }
+  PairUpdate u;
+  u.a_hi_new = a_hi_new;
+  u.a_lo_new = a_lo_new;
+  u.c_hi = (a_hi_new - a_hi_old) * y_hi;
+  u.c_lo = (a_lo_new - a_lo_old) * y_lo;
+  return u;
+}
+
 // Stop test of the reference do/while tail (svmTrainMain.cpp:310).
 DPSVM_HD bool gap_open(float b_hi, float b_lo, float eps) { return b_lo > (b_hi + (2.0f * eps)); }
 

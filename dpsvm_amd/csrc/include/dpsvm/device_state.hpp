@@ -425,6 +425,8 @@ struct WsArgs {
                        // (world 1, dense, blocks of <= 64 rows: no ws_gather launch)
   int32_t ncand;       // multi-block selection: keys per side a list holds (kWsCandStd for unions of <=
                        // kWsAutoUnion rows, kWsCand beyond; 0 = kWsCand); the tail of a list is kKeyNone
+  const float* c_row;  // [n] global per-row bounds C_i = C w_i (GpuSolver::set_row_C); nullptr: the scalar C.
+                       // Read by the kRowC instantiations of ws_select / ws_solve only (one rank)
 };
 // keys per side and list of the multi-block selection (ws_select pass 2, the peer exchange)
 constexpr int ws_ncand(int ncand) { return ncand > 0 && ncand < kWsCand ? ncand : kWsCand; }

@@ -46,8 +46,11 @@ void check_resume(const Checkpoint& ck, int64_t n, int d, const SolverParams& p,
 // CPU solver (C10 seq / the no-GPU path and the test oracle).  X is replicated,
 // f and the kernel-row cache are sharded by `comm` (nullptr = one rank).
 // ---------------------------------------------------------------------------
+// row_C: optional per-row bounds C_i (global n, finite and >= 0, a positive one per label; not with resume):
+// the box 0 <= alpha_i <= C_i in selection, pair update and the final checks.  nullptr: the scalar p.C.
 SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* comm = nullptr,
-                      const Checkpoint* resume = nullptr, const ProgressFn& progress = {});
+                      const Checkpoint* resume = nullptr, const ProgressFn& progress = {},
+                      const float* row_C = nullptr);
 
 // Decision values d(x) = sum_sv alpha y K(sv,x) - b  (svmTrain.cu:646-658)
 std::vector<float> decision_cpu(const Model& m, const float* x, int64_t n, int d, int threads = 0);
@@ -124,6 +127,17 @@ class GpuSolver {
   // preceded by set_labels() rebuilds the Gram in its timed region as ever.  One-vs-rest training: k solves, one
   // setup, one Gram.
   void set_labels(const float* y);
+  // After setup(): per-row bounds C_i of the next solves (host, global n; finite and >= 0, at least one row of
+  // each label with C_i > 0), the sample / class weights' C w_i; nullptr returns to the scalar C.  Working-set
+  // engines on one rank, ws_recompute rounds excluded.  The weighted instantiations of ws_select / ws_solve read
+  // a device copy whose address does not move once allocated: the captured graphs are rebuilt only when the
+  // kernels' pointer changes (the first call, or back to nullptr).  Like set_labels it asks the next solve() to
+  // keep a completed resident Gram — a row with C_i = 0 stays at alpha_i = 0 while its gradient entry is kept up
+  // to date, so k-fold cross-validation is k solves on one Gram with the held-out decisions read from gradient().
+  // Call order with set_labels: the labels first, then the bounds; solve() checks the bounds against the labels
+  // then current again (a set_labels after set_row_C may leave a label without a row of positive C_i: refused),
+  // and refuses a resume, before it touches any state.
+  void set_row_C(const float* c);
   // the stop tolerance of the next solve() (kernel arguments updated, captured graphs rebuilt)
   void set_eps(float eps);
   // free the kernel-row cache / resident Gram until the next solve() (which
@@ -274,7 +288,8 @@ struct WsSolveProbe {
 WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float>& f, const std::vector<float>& alpha,
                             const std::vector<float>& y, const std::vector<int32_t>& qb, int q_max, int blocks,
                             int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
-                            float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss = 1);
+                            float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss = 1,
+                            const std::vector<float>& row_C = {});  // [P * q_max] per-row bounds (empty: scalar C)
 // ws_select: the f update of a round's alpha changes (apply rows: lines into
 // gram [L][ldg], coefficients) and the per-workgroup candidates.  blocks == 1:
 // the one-pass kernel; blocks > 1: pass 1 (d_f, line-search partials) and pass 2
@@ -294,7 +309,8 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               const std::vector<float>& dalpha, const std::vector<int32_t>& apply_line,
                               const std::vector<float>& apply_coef, const std::vector<int32_t>& nab, int blocks,
                               int p_round, int p_act, int q_max, float C, int64_t outer, int ks = 0,
-                              int reps = 0, bool wide = false);
+                              int reps = 0, bool wide = false,
+                              const std::vector<float>& row_C = {});  // [n] per-row bounds (empty: scalar C)
 }  // namespace kernels
 
 int device_count();

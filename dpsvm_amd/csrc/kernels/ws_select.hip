@@ -42,7 +42,11 @@ constexpr int ws_sel_parts() {
   return MODE == 2 ? 1 : ws_parts<RPT>();
 }
 
-template <int RPT, int MODE>
+// kRowC: per-row bounds C_i (WsArgs::c_row, global [n]) — the classification reads c_row[gj] beside alpha / y
+// (one more coalesced 4-byte stream of n per round) in the compare form (in_up_w / in_low_w: a C_i = 0 row is
+// in neither set), and the line-search fix-ups clip a row to its own bound.  Separate instantiations: the
+// scalar ones keep their code.
+template <int RPT, int MODE, bool kRowC = false>
 __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void ws_select_kernel(WsArgs a) {
   constexpr int PARTS = ws_sel_parts<RPT, MODE>();
   constexpr int CH = RPT >= 32 ? 1 : RPT >= 8 ? 4 : 48 / RPT;  // Gram loads in flight per thread (vmcnt <= 63)
@@ -213,7 +217,9 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
           if (k >= c->nab[p]) continue;
           const int64_t gi = c->apply_idx[i];
           if (gi >= a.off && gi < a.off + a.nl) continue;
-          if (t < 1.f) a.alpha[gi] = clip01(a.alpha[gi] - (1.f - t) * a.dalpha[gi], 0.f, a.C);
+          float cb = a.C;
+          if constexpr (kRowC) cb = a.c_row[gi];
+          if (t < 1.f) a.alpha[gi] = clip01(a.alpha[gi] - (1.f - t) * a.dalpha[gi], 0.f, cb);
           a.dalpha[gi] = 0.f;
         }
       }
@@ -229,7 +235,9 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
           acc[r] = t == 1.f ? d : t * d;
           const float dj = a.dalpha[a.off + j];
           if (dj != 0.f) {
-            if (t < 1.f) a.alpha[a.off + j] = clip01(a.alpha[a.off + j] - (1.f - t) * dj, 0.f, a.C);
+            float cb = a.C;
+            if constexpr (kRowC) cb = a.c_row[a.off + j];
+            if (t < 1.f) a.alpha[a.off + j] = clip01(a.alpha[a.off + j] - (1.f - t) * dj, 0.f, cb);
             a.dalpha[a.off + j] = 0.f;
           }
         }
@@ -260,8 +268,14 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
     if (has[r] && part == 0) {
       const int64_t gj = a.off + base + r * kWsSelThreads;
       const float av = a.alpha[gj], yv = a.y[gj];
-      if (in_up(av, yv, a.C)) ku[r] = make_key(f[r], (uint32_t)gj);
-      if (in_low(av, yv, a.C)) kl[r] = make_key(-f[r], (uint32_t)gj);
+      if constexpr (kRowC) {
+        const float cv = a.c_row[gj];
+        if (in_up_w(av, yv, cv)) ku[r] = make_key(f[r], (uint32_t)gj);
+        if (in_low_w(av, yv, cv)) kl[r] = make_key(-f[r], (uint32_t)gj);
+      } else {
+        if (in_up(av, yv, a.C)) ku[r] = make_key(f[r], (uint32_t)gj);
+        if (in_low(av, yv, a.C)) kl[r] = make_key(-f[r], (uint32_t)gj);
+      }
     }
   }
   // each wave's nc smallest keys per side, then wave 0 merges the four lists.
@@ -567,17 +581,25 @@ bool ws_supported(int64_t nl_max, int world, int q_max) {
   return q_max >= 2 && q_max <= kWsMax && rpt <= kWsMaxRPT && nl_max < (int64_t)1 << 31 && world <= kWsMaxGroups;
 }
 
-template <int MODE>
-static void ws_select_mode(const WsArgs& a, hipStream_t s) {
+template <int MODE, bool kRowC>
+static void ws_select_rpt(const WsArgs& a, hipStream_t s) {
   const dim3 grid(a.G * (MODE == 1 ? std::max(1, a.ks) : 1));
   auto threads = [](int rpt) { return dim3(MODE == 2 ? kWsSelThreads : kWsSelThreads * (rpt <= 4 ? 4 : rpt <= 16 ? 2 : 1)); };
-  if (a.rpt <= 1) dev::ws_select_kernel<1, MODE><<<grid, threads(1), 0, s>>>(a);
-  else if (a.rpt <= 2) dev::ws_select_kernel<2, MODE><<<grid, threads(2), 0, s>>>(a);
-  else if (a.rpt <= 4) dev::ws_select_kernel<4, MODE><<<grid, threads(4), 0, s>>>(a);
-  else if (a.rpt <= 8) dev::ws_select_kernel<8, MODE><<<grid, threads(8), 0, s>>>(a);
-  else if (a.rpt <= 16) dev::ws_select_kernel<16, MODE><<<grid, threads(16), 0, s>>>(a);
-  else dev::ws_select_kernel<32, MODE><<<grid, threads(32), 0, s>>>(a);
+  if (a.rpt <= 1) dev::ws_select_kernel<1, MODE, kRowC><<<grid, threads(1), 0, s>>>(a);
+  else if (a.rpt <= 2) dev::ws_select_kernel<2, MODE, kRowC><<<grid, threads(2), 0, s>>>(a);
+  else if (a.rpt <= 4) dev::ws_select_kernel<4, MODE, kRowC><<<grid, threads(4), 0, s>>>(a);
+  else if (a.rpt <= 8) dev::ws_select_kernel<8, MODE, kRowC><<<grid, threads(8), 0, s>>>(a);
+  else if (a.rpt <= 16) dev::ws_select_kernel<16, MODE, kRowC><<<grid, threads(16), 0, s>>>(a);
+  else dev::ws_select_kernel<32, MODE, kRowC><<<grid, threads(32), 0, s>>>(a);
   post_launch("ws_select", s);
+}
+
+template <int MODE>
+static void ws_select_mode(const WsArgs& a, hipStream_t s) {
+  if constexpr (MODE != 1) {  // pass 1 neither classifies nor clips: one instantiation
+    if (a.c_row != nullptr) return ws_select_rpt<MODE, true>(a, s);  // per-row C
+  }
+  ws_select_rpt<MODE, false>(a, s);
 }
 
 void ws_select(const WsArgs& a, hipStream_t s) {

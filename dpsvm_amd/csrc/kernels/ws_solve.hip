@@ -21,11 +21,14 @@ namespace dev {
 constexpr int kWsSolvePollBatch = 10;
 
 // the sub-Gram load of one launch per round; the loop: ws_solve.hpp
-template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS = 3>
+// kRowC: per-row bounds (WsArgs::c_row): the rows' C_i into LDS beside s_a / s_y, straight from c_row[idx] on every
+// load path; separate instantiations, the scalar ones keep their code
+template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS = 3, bool kRowC = false>
 __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float K[];  // q rows of the sub-Gram, stride q_max
   __shared__ float s_a[kWsMax + 128], s_y[kWsMax], s_f[kWsMax];  // s_a: + 2 x 64 scratch words
   __shared__ int32_t s_idx[kWsMax], s_line[kWsMax];
+  __shared__ float s_c[kRowC ? kWsMax : 1];
   WsCtrl* c = a.ctrl;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) WS_STAMP(0);
@@ -93,6 +96,7 @@ __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
       s_y[tid] = aux[2 * a.aux_stride + tid];
       s_idx[tid] = c->idx[par][ib + tid];
       s_line[tid] = c->line[par][ib + tid];
+      if constexpr (kRowC) s_c[tid] = a.c_row[c->idx[par][ib + tid]];
     }
   } else if (a.direct_sub) {
     // blocks of <= 64 rows at world 1 (dense): the entries straight from the
@@ -110,11 +114,12 @@ __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
     __syncthreads();
     // the rows' f / alpha / y in flight with the entries (one memory round trip
     // for both, stored after)
-    float fv = 0.f, av = 0.f, yv = 0.f;
+    float fv = 0.f, av = 0.f, yv = 0.f, cv = 0.f;
     if (tid < q) {
       fv = a.f[gi];  // one rank: local row = global row
       av = a.alpha[gi];
       yv = a.y[gi];
+      if constexpr (kRowC) cv = a.c_row[gi];
     }
     const int n = q * ldk;
     constexpr int U = 4;  // n <= 64 x 64 = U x threads: one pass
@@ -140,6 +145,7 @@ __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
       s_f[tid] = fv;
       s_a[tid] = av;
       s_y[tid] = yv;
+      if constexpr (kRowC) s_c[tid] = cv;
     }
   } else {
     // q rows of the q_max-stride sub-Gram into LDS (147 KiB at q = 192): 16-B
@@ -169,6 +175,7 @@ __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
       s_y[tid] = aux[2 * a.aux_stride + tid];
       s_idx[tid] = c->idx[par][ib + tid];
       s_line[tid] = c->line[par][ib + tid];
+      if constexpr (kRowC) s_c[tid] = a.c_row[c->idx[par][ib + tid]];
     }
   }
   bool xfail = false;
@@ -180,8 +187,12 @@ __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
   if (tid == 0) WS_STAMP(3);
   if (wave != 0) return;
 
-  ws_solve_run<kBox, kFull, kMulti, kW2, NS>(a, c, K, s_a, s_y, s_f, s_idx, s_line, q, blk, ib, it0, b_hi, b_lo,
-                                             xfail);
+  if constexpr (kRowC)
+    ws_solve_run<kBox, kFull, kMulti, kW2, NS, true>(a, c, K, s_a, s_y, s_f, s_idx, s_line, q, blk, ib, it0, b_hi,
+                                                     b_lo, xfail, s_c);
+  else
+    ws_solve_run<kBox, kFull, kMulti, kW2, NS>(a, c, K, s_a, s_y, s_f, s_idx, s_line, q, blk, ib, it0, b_hi, b_lo,
+                                               xfail);
 }
 
 }  // namespace dev
@@ -191,35 +202,39 @@ namespace launch {
 void ws_solve(const WsArgs& a, hipStream_t s) {
   const size_t lds = (size_t)a.q_max * a.q_max * sizeof(float);
   const bool box = a.clip == (int)ClipMode::Box, full = a.q_max == kWsMax, multi = a.blocks > 1, w2 = a.wss == 2;
+  const bool rowc = a.c_row != nullptr;  // per-row C: the kRowC instantiations (second half of each table)
   using Fn = void (*)(WsArgs);
-#define WS_SOLVE_FNS(W2)                                                                                         \
-  dev::ws_solve_kernel<false, false, false, W2>, dev::ws_solve_kernel<false, true, false, W2>,                  \
-      dev::ws_solve_kernel<true, false, false, W2>, dev::ws_solve_kernel<true, true, false, W2>,                \
-      dev::ws_solve_kernel<false, false, true, W2>, dev::ws_solve_kernel<false, true, true, W2>,                \
-      dev::ws_solve_kernel<true, false, true, W2>, dev::ws_solve_kernel<true, true, true, W2>
-  static const Fn fns[16] = {WS_SOLVE_FNS(false), WS_SOLVE_FNS(true)};
+#define WS_SOLVE_FNS(W2, RC)                                                                                     \
+  dev::ws_solve_kernel<false, false, false, W2, 3, RC>, dev::ws_solve_kernel<false, true, false, W2, 3, RC>,    \
+      dev::ws_solve_kernel<true, false, false, W2, 3, RC>, dev::ws_solve_kernel<true, true, false, W2, 3, RC>,  \
+      dev::ws_solve_kernel<false, false, true, W2, 3, RC>, dev::ws_solve_kernel<false, true, true, W2, 3, RC>,  \
+      dev::ws_solve_kernel<true, false, true, W2, 3, RC>, dev::ws_solve_kernel<true, true, true, W2, 3, RC>
+  static const Fn fns[32] = {WS_SOLVE_FNS(false, false), WS_SOLVE_FNS(true, false), WS_SOLVE_FNS(false, true),
+                             WS_SOLVE_FNS(true, true)};
 #undef WS_SOLVE_FNS
   // two slots per lane when q_max <= 128 (never kFull)
-#define WS_SOLVE_FNS2(W2)                                                                                        \
-  dev::ws_solve_kernel<false, false, false, W2, 2>, dev::ws_solve_kernel<true, false, false, W2, 2>,            \
-      dev::ws_solve_kernel<false, false, true, W2, 2>, dev::ws_solve_kernel<true, false, true, W2, 2>
-  static const Fn fns2[8] = {WS_SOLVE_FNS2(false), WS_SOLVE_FNS2(true)};
+#define WS_SOLVE_FNS2(W2, RC)                                                                                    \
+  dev::ws_solve_kernel<false, false, false, W2, 2, RC>, dev::ws_solve_kernel<true, false, false, W2, 2, RC>,    \
+      dev::ws_solve_kernel<false, false, true, W2, 2, RC>, dev::ws_solve_kernel<true, false, true, W2, 2, RC>
+  static const Fn fns2[16] = {WS_SOLVE_FNS2(false, false), WS_SOLVE_FNS2(true, false), WS_SOLVE_FNS2(false, true),
+                              WS_SOLVE_FNS2(true, true)};
 #undef WS_SOLVE_FNS2
   // one slot per lane when q_max <= 64 (blocks of the 64-block rounds)
-#define WS_SOLVE_FNS1(W2)                                                                                        \
-  dev::ws_solve_kernel<false, false, false, W2, 1>, dev::ws_solve_kernel<true, false, false, W2, 1>,            \
-      dev::ws_solve_kernel<false, false, true, W2, 1>, dev::ws_solve_kernel<true, false, true, W2, 1>
-  static const Fn fns1[8] = {WS_SOLVE_FNS1(false), WS_SOLVE_FNS1(true)};
+#define WS_SOLVE_FNS1(W2, RC)                                                                                    \
+  dev::ws_solve_kernel<false, false, false, W2, 1, RC>, dev::ws_solve_kernel<true, false, false, W2, 1, RC>,    \
+      dev::ws_solve_kernel<false, false, true, W2, 1, RC>, dev::ws_solve_kernel<true, false, true, W2, 1, RC>
+  static const Fn fns1[16] = {WS_SOLVE_FNS1(false, false), WS_SOLVE_FNS1(true, false), WS_SOLVE_FNS1(false, true),
+                              WS_SOLVE_FNS1(true, true)};
 #undef WS_SOLVE_FNS1
-  const int v = (w2 ? 8 : 0) + (multi ? 4 : 0) + (box ? 2 : 0) + (full ? 1 : 0);
-  const int v2 = (w2 ? 4 : 0) + (multi ? 2 : 0) + (box ? 1 : 0);
+  const int v = (rowc ? 16 : 0) + (w2 ? 8 : 0) + (multi ? 4 : 0) + (box ? 2 : 0) + (full ? 1 : 0);
+  const int v2 = (rowc ? 8 : 0) + (w2 ? 4 : 0) + (multi ? 2 : 0) + (box ? 1 : 0);
   const bool one = a.q_max <= 64, two = !one && a.q_max <= 128;
   const Fn fn = one ? fns1[v2] : two ? fns2[v2] : fns[v];
   // dynamic LDS above 64 KiB needs the attribute (160 KiB on gfx950); the
   // largest size set so far per device and kernel (rank threads of one process
   // launch on different devices concurrently)
-  static std::atomic<size_t> attr[kMaxDevices][32];
-  std::atomic<size_t>& at = attr[current_device()][one ? 24 + v2 : two ? 16 + v2 : v];
+  static std::atomic<size_t> attr[kMaxDevices][64];
+  std::atomic<size_t>& at = attr[current_device()][one ? 48 + v2 : two ? 32 + v2 : v];
   size_t cur = at.load(std::memory_order_relaxed);
   if (lds > 64 * 1024 && lds > cur) {
     HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -24,6 +24,7 @@ __device__ __forceinline__ float sel_lanes(float a, float b, uint64_t m) {
   return r;
 }
 
+// C: the placed row's own bound (per-row C: C_i; a row with C_i = 0 lands in neither set)
 template <int NS>
 __device__ __forceinline__ void ws_place(int pos, float an, float yv, float fp, int lane, float C, float (&fu)[NS],
                                          float (&fl)[NS]) {
@@ -54,10 +55,13 @@ __device__ __forceinline__ void ws_place(int pos, float an, float yv, float fp, 
 // y_lo (b_hi - b_lo) / eta from a refined hardware reciprocal: the sub-problem
 // step needs no bit parity with the pair-at-a-time engines (f is updated from
 // the alphas actually taken, so it stays consistent), and the IEEE division
-// sequence is the longest dependent chain of a step.
+// sequence is the longest dependent chain of a step.  C_hi / C_lo: the two
+// rows' bounds (pair_update_w's geometry; the scalar path passes C twice and
+// compiles to pair_update's expressions).
 template <bool kBox>
 __device__ __forceinline__ PairUpdate ws_pair_step(float a_hi, float a_lo, float y_hi, float y_lo, float bh, float bl,
-                                                   float khl, float C, float tau, bool same, bool* clipped) {
+                                                   float khl, float C_hi, float C_lo, float tau, bool same,
+                                                   bool* clipped) {
 #pragma clang fp contract(off)
   float eta = (1.0f + 1.0f) - 2.0f * khl;
   eta = eta >= tau ? eta : tau;
@@ -72,23 +76,23 @@ __device__ __forceinline__ PairUpdate ws_pair_step(float a_hi, float a_lo, float
     // labels / positions select — the same values the branches produced
     const float dl = a_lo - a_hi, sm = a_lo + a_hi;
     const bool diff = y_hi != y_lo;
-    const float L = diff ? (dl > 0.f ? dl : 0.f) : (sm - C > 0.f ? sm - C : 0.f);
-    const float hL = diff ? (dl > 0.f ? 0.f : -1.f) : (sm - C > 0.f ? C : -1.f);
-    const float H = diff ? (C + dl < C ? C + dl : C) : (sm < C ? sm : C);
-    const float hH = diff ? (C + dl < C ? C : -1.f) : (sm < C ? 0.f : -1.f);
+    const float L = diff ? (dl > 0.f ? dl : 0.f) : (sm - C_hi > 0.f ? sm - C_hi : 0.f);
+    const float hL = diff ? (dl > 0.f ? 0.f : -1.f) : (sm - C_hi > 0.f ? C_hi : -1.f);
+    const float H = diff ? (C_hi + dl < C_lo ? C_hi + dl : C_lo) : (sm < C_lo ? sm : C_lo);
+    const float hH = diff ? (C_hi + dl < C_lo ? C_hi : -1.f) : (sm < C_lo ? 0.f : -1.f);
     const bool atL = a_lo_new <= L, atH = !atL && a_lo_new >= H;
     const float lo_box = atL ? L : (atH ? H : a_lo_new);
     const float snap = atL ? hL : (atH ? hH : -1.f);
-    const float hi_box = clip01(snap >= 0.f ? snap : a_hi + (s * (a_lo - lo_box)), 0.0f, C);
-    const float hi_same = clip01(a_hi + (s * (a_lo - a_lo_new)), 0.0f, C);
-    const float lo_same = clip01(a_lo_new, 0.0f, C);
+    const float hi_box = clip01(snap >= 0.f ? snap : a_hi + (s * (a_lo - lo_box)), 0.0f, C_hi);
+    const float hi_same = clip01(a_hi + (s * (a_lo - a_lo_new)), 0.0f, C_hi);
+    const float lo_same = clip01(a_lo_new, 0.0f, C_lo);
     a_lo_new = same ? lo_same : lo_box;
     a_hi_new = same ? hi_same : hi_box;
   } else {
     a_hi_new = a_hi + (s * (a_lo - a_lo_new));
     const float lo_raw = a_lo_new, hi_raw = a_hi_new;
-    a_lo_new = clip01(a_lo_new, 0.0f, C);
-    a_hi_new = clip01(a_hi_new, 0.0f, C);
+    a_lo_new = clip01(a_lo_new, 0.0f, C_lo);
+    a_hi_new = clip01(a_hi_new, 0.0f, C_hi);
     *clipped = (lo_raw != a_lo_new) | (hi_raw != a_hi_new);  // sum(alpha y) no longer kept
   }
   PairUpdate u;
@@ -144,13 +148,14 @@ __device__ __forceinline__ int ws_argpos(const float (&x)[2], float v) {
 // for blocks of <= 64 rows)
 // The sub-problem loop and the round's commit, on wave 0 once the q rows are in
 // LDS: K (q rows, stride a.q_max), s_a (+ 128 scratch words), s_y, s_f, s_idx,
-// s_line.  blk / ib: the block and its first row (multi-block rounds); it0,
+// s_line, and with kRowC (per-row C, WsArgs::c_row) the rows' bounds s_c.  blk / ib: the block and its first row (multi-block rounds); it0,
 // b_hi, b_lo: the round's pair count and global selection at entry; xfail: the
 // peer exchange gave up (no step, kCommFail kept).
-template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS>
+template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS, bool kRowC = false>
 __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const float* K, float* s_a, const float* s_y,
                                              const float* s_f, const int32_t* s_idx, const int32_t* s_line, int q,
-                                             int blk, int ib, int64_t it0, float b_hi, float b_lo, bool xfail) {
+                                             int blk, int ib, int64_t it0, float b_hi, float b_lo, bool xfail,
+                                             const float* s_c = nullptr) {
   static_assert(NS == 3 || ((NS == 2 || NS == 1) && !kFull), "slots");
   const int lane = threadIdx.x & 63;
   const int ldk = a.q_max;
@@ -165,8 +170,14 @@ __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const f
     const float fv = v ? s_f[p] : 0.f;
     a0[s] = v ? s_a[p] : 0.f;
     yr[s] = v ? s_y[p] : 1.f;
-    fu[s] = v && in_up(a0[s], yr[s], C) ? fv : INF;
-    fl[s] = v && in_low(a0[s], yr[s], C) ? -fv : INF;
+    if constexpr (kRowC) {
+      const float cr = v ? s_c[p] : 0.f;  // the compare-form sets: a C_i = 0 row is in neither
+      fu[s] = v && in_up_w(a0[s], yr[s], cr) ? fv : INF;
+      fl[s] = v && in_low_w(a0[s], yr[s], cr) ? -fv : INF;
+    } else {
+      fu[s] = v && in_up(a0[s], yr[s], C) ? fv : INF;
+      fl[s] = v && in_low(a0[s], yr[s], C) ? -fv : INF;
+    }
   }
   int64_t room = a.max_iter - it0;
   if (kMulti) {  // the active blocks share max_iter
@@ -240,8 +251,14 @@ __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const f
       if constexpr (!kW2) kh[s] = K[ph * ldk + p];
       kl[s] = K[pl * ldk + p];
     }
+    float C_hi = C, C_lo = C;
+    if constexpr (kRowC) {
+      C_hi = s_c[ph];
+      C_lo = s_c[pl];
+    }
     bool clipped = false;
-    const PairUpdate up = ws_pair_step<kBox>(a_hi, a_lo, y_hi, y_lo, bh, bl, khl, C, a.tau, ph == pl, &clipped);
+    const PairUpdate up =
+        ws_pair_step<kBox>(a_hi, a_lo, y_hi, y_lo, bh, bl, khl, C_hi, C_lo, a.tau, ph == pl, &clipped);
     if (kMulti && !kBox) clipped_any |= clipped;
     float f_lo_new, f_hi_new;
 #pragma unroll
@@ -261,8 +278,8 @@ __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const f
       f_lo_new = bl + (up.c_hi * khl + up.c_lo * kll);
       f_hi_new = bh + (up.c_hi * khh + up.c_lo * klh);
     }
-    ws_place(pl, up.a_lo_new, y_lo, f_lo_new, lane, C, fu, fl);
-    ws_place(ph, up.a_hi_new, y_hi, f_hi_new, lane, C, fu, fl);  // hi written last (svmTrainMain.cpp:298-299)
+    ws_place(pl, up.a_lo_new, y_lo, f_lo_new, lane, C_lo, fu, fl);
+    ws_place(ph, up.a_hi_new, y_hi, f_hi_new, lane, C_hi, fu, fl);  // hi written last (svmTrainMain.cpp:298-299)
     // lane 0 writes the pair's alphas, the other lanes a private scratch word
     // each (no exec-mask branch in the loop, no bank conflict)
     s_a[lane == 0 ? pl : kWsMax + lane] = up.a_lo_new;

@@ -477,9 +477,15 @@ PYBIND11_MODULE(_C, m) {
 
   // ---------------- solvers ----------------
   m.def("solve_cpu", [](F32 x, F32 y, const SolverParams& p, std::shared_ptr<Communicator> comm,
-                        const Checkpoint* resume, py::object progress) {
+                        const Checkpoint* resume, py::object progress, py::object row_C) {
     Dataset ds;
     check_xy(x, y, ds.n, ds.d);
+    std::vector<float> rc;
+    if (!row_C.is_none()) {
+      const F32 c = row_C.cast<F32>();
+      if (c.ndim() != 1 || c.shape(0) != ds.n) throw py::value_error("row_C must have n entries");
+      rc = from_np(c);
+    }
     ds.x = from_np(x);
     ds.y = from_np(y);
     for (auto& v : ds.y) v = v > 0 ? 1.f : -1.f;
@@ -487,11 +493,11 @@ PYBIND11_MODULE(_C, m) {
     SolveResult r;
     {
       py::gil_scoped_release rel;
-      r = solve_cpu(ds, p, comm.get(), resume, prog);
+      r = solve_cpu(ds, p, comm.get(), resume, prog, rc.empty() ? nullptr : rc.data());
     }
     return py::make_tuple(to_np(r.alpha), result_dict(r));
   }, py::arg("x"), py::arg("y"), py::arg("params"), py::arg("comm") = nullptr, py::arg("resume") = nullptr,
-     py::arg("progress") = py::none());
+     py::arg("progress") = py::none(), py::arg("row_C") = py::none());
 
   m.def("solve_shrinking", [](F32 x, F32 y, const SolverParams& p, int device, const Checkpoint* resume,
                               py::object progress, std::shared_ptr<Communicator> comm) {
@@ -545,6 +551,26 @@ PYBIND11_MODULE(_C, m) {
         py::gil_scoped_release rel;
         s.set_labels(y.data());
       }, py::arg("y"), "other labels on the rows of setup(): the next solve() keeps the resident Gram")
+      .def("set_row_C", [](GpuSolver& s, py::object c) {
+        if (c.is_none()) {
+          py::gil_scoped_release rel;
+          s.set_row_C(nullptr);
+          return;
+        }
+        const F32 a = c.cast<F32>();
+        if (a.ndim() != 1 || a.shape(0) != s.info().n) throw py::value_error("row_C must have n entries");
+        py::gil_scoped_release rel;
+        s.set_row_C(a.data());
+      }, py::arg("row_C"), "per-row bounds C_i of the next solves (None: the scalar C); the next solve() keeps the "
+                           "resident Gram")
+      .def("gradient", [](GpuSolver& s) {
+        std::vector<float> g;
+        {
+          py::gil_scoped_release rel;
+          g = s.gradient();
+        }
+        return to_np(g);
+      }, "after solve(): this rank's gradient f_j = sum_i alpha_i y_i K(i, j) - y_j as the solver maintained it")
       .def("release_cache", [](GpuSolver& s) {
         py::gil_scoped_release rel;
         s.release_cache();
@@ -755,10 +781,12 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("k_ws_solve", [vi](const F32& K, const F32& f, const F32& alpha, const F32& y, const I32& qb, int q_max,
                            int blocks, int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
-                           float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss) {
+                           float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss,
+                           py::object row_C) {
     const auto r = kernels::ws_solve_probe(from_np(K), from_np(f), from_np(alpha), from_np(y), vi(qb), q_max, blocks,
                                            p_round, C, clip, eps, rel, eps_floor, tau, b_hi, b_lo, inner_max, iter0,
-                                           max_iter, wss);
+                                           max_iter, wss,
+                                           row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()));
     py::dict d;
     d["alpha"] = to_np(r.alpha);
     d["steps"] = r.steps;
@@ -771,13 +799,18 @@ PYBIND11_MODULE(_C, m) {
     d["p_act"] = r.p_act;
     d["p1_round"] = r.p1_round;
     return d;
-  });
+  }, py::arg("K"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("qb"), py::arg("q_max"), py::arg("blocks"),
+        py::arg("p_round"), py::arg("C"), py::arg("clip"), py::arg("eps"), py::arg("rel"), py::arg("eps_floor"),
+        py::arg("tau"), py::arg("b_hi"), py::arg("b_lo"), py::arg("inner_max"), py::arg("iter0"), py::arg("max_iter"),
+        py::arg("wss"), py::arg("row_C") = py::none());
   m.def("k_ws_select", [vi](const F32& gram, int64_t L, int64_t ldg, const F32& f, const F32& alpha, const F32& y,
                             const F32& dalpha, const I32& lines, const F32& coef, const I32& nab, int blocks,
-                            int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps, bool wide) {
+                            int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps, bool wide,
+                            py::object row_C) {
     const auto r = kernels::ws_select_probe(from_np(gram), L, ldg, from_np(f), from_np(alpha), from_np(y),
                                             from_np(dalpha), vi(lines), from_np(coef), vi(nab), blocks, p_round, p_act,
-                                            q_max, C, outer, ks, reps, wide);
+                                            q_max, C, outer, ks, reps, wide,
+                                            row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()));
     py::dict d;
     d["f"] = to_np(r.f);
     d["alpha"] = to_np(r.alpha);
@@ -798,10 +831,21 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("gram"), py::arg("L"), py::arg("ldg"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("dalpha"),
         py::arg("lines"), py::arg("coef"), py::arg("nab"), py::arg("blocks"), py::arg("p_round"), py::arg("p_act"),
         py::arg("q_max"), py::arg("C"), py::arg("outer"), py::arg("ks") = 0, py::arg("reps") = 0,
-        py::arg("wide") = false);
+        py::arg("wide") = false, py::arg("row_C") = py::none());
   m.def("production_line_cap", &production_line_cap, py::arg("cache_lines"), py::arg("ws_size"),
         py::arg("engines") = 0, "-s N on the engines a setup may choose (device_state.hpp)");
   m.def("ws_cache_min_lines", &ws_cache_min_lines, py::arg("ws_size"));
+  // the pair step of every engine and its two-bound form (common.hpp): (a_hi_new, a_lo_new, c_hi, c_lo)
+  m.def("pair_update", [](float a_hi, float a_lo, float y_hi, float y_lo, float b_hi, float b_lo, float k_hl, float C,
+                          float tau, int clip, bool same) {
+    const PairUpdate u = pair_update(a_hi, a_lo, y_hi, y_lo, b_hi, b_lo, k_hl, C, tau, clip, same);
+    return py::make_tuple(u.a_hi_new, u.a_lo_new, u.c_hi, u.c_lo);
+  });
+  m.def("pair_update_w", [](float a_hi, float a_lo, float y_hi, float y_lo, float b_hi, float b_lo, float k_hl,
+                            float C_hi, float C_lo, float tau, int clip, bool same) {
+    const PairUpdate u = pair_update_w(a_hi, a_lo, y_hi, y_lo, b_hi, b_lo, k_hl, C_hi, C_lo, tau, clip, same);
+    return py::make_tuple(u.a_hi_new, u.a_lo_new, u.c_hi, u.c_lo);
+  });
   m.def("make_key", [](float f, uint32_t idx) { return make_key(f, idx); });
   m.def("key_value", [](uint64_t k) { return key_value(k); });
   m.def("key_index", [](uint64_t k) { return key_index(k); });

@@ -134,10 +134,14 @@ struct GpuSolver::Impl {
   EngineKind kind = EngineKind::Chain;
   std::unique_ptr<gpu::Engine> engine;
   std::vector<float> h_y;
-  // the resident Gram across solves (GpuSolver::set_labels): gram_valid = the lines hold a Gram a completed
-  // solve built; labels_swapped = set_labels was called since the last solve; reuse_gram = this solve's decision
-  // (labels_swapped && gram_valid), read by DenseBase::gram
-  bool gram_valid = false, labels_swapped = false, reuse_gram = false;
+  // the resident Gram across solves (GpuSolver::set_labels / set_row_C): gram_valid = the lines hold a Gram a
+  // completed solve built; problem_swapped = another problem on the same X was set (labels or per-row C) since
+  // the last solve; reuse_gram = this solve's decision (problem_swapped && gram_valid), read by DenseBase::gram
+  bool gram_valid = false, problem_swapped = false, reuse_gram = false;
+  // per-row bounds (GpuSolver::set_row_C): the device copy (allocated once: its address stays in the kernel
+  // arguments and the captured graphs) and the host values (the post-solve box check); wsa.c_row = row_c or null
+  float* row_c = nullptr;
+  std::vector<float> h_row_c;
 
   hipGraphExec_t gexec = nullptr;
   hipGraph_t graph = nullptr;

@@ -46,7 +46,7 @@ GpuSolver::Impl::~Impl() {
                     (void*)key_of, (void*)ref, (void*)hslot_of, (void*)hkey_of, (void*)partials, (void*)ctrl,
                     (void*)records, (void*)my_record, (void*)pf, (void*)rf, (void*)rcf, (void*)stamps,
                     (void*)plru_meta, (void*)plru_stats, (void*)wsctrl, (void*)wscand, (void*)wssub, (void*)wsdfs, (void*)wsdalpha, (void*)wspart, (void*)wssorted,
-                    (void*)wsxq, (void*)wsxqsq, (void*)wsiota, xs, (void*)xsh, wsxs, (void*)wsxsh})
+                    (void*)wsxq, (void*)wsxqsq, (void*)wsiota, xs, (void*)xsh, wsxs, (void*)wsxsh, (void*)row_c})
     if (ptr) (void)hipFree(ptr);
   if (status_h) (void)hipHostFree(status_h);
   if (hlines_h) (void)hipHostFree(hlines_h);
@@ -149,7 +149,44 @@ void GpuSolver::set_labels(const float* y) {
   for (auto& v : m.h_y) v = v > 0 ? 1.f : -1.f;  // as place_vectors
   HIP_CHECK(hipMemcpyAsync(m.y, m.h_y.data(), m.n * 4, hipMemcpyHostToDevice, m.stream));
   HIP_CHECK(hipStreamSynchronize(m.stream));
-  m.labels_swapped = true;
+  m.problem_swapped = true;
+}
+
+void GpuSolver::set_row_C(const float* c) {
+  auto& m = *impl_;
+  DPSVM_CHECK(m.engine && m.y, "set_row_C: call setup() first");
+  DPSVM_CHECK(m.working_set() && m.world == 1 && !m.ws_recompute,
+              "set_row_C: per-row C runs on the working-set engines (ws-dense, ws-cache with the row cache) on one "
+              "rank");
+  if (c) {
+    bool pos = false, neg = false;
+    for (int64_t i = 0; i < m.n; ++i) {
+      DPSVM_CHECK(std::isfinite(c[i]) && c[i] >= 0.f, "set_row_C: every C_i must be finite and >= 0");
+      if (c[i] > 0.f) (m.h_y[i] > 0.f ? pos : neg) = true;
+    }
+    DPSVM_CHECK(pos && neg, "set_row_C: each label needs at least one row with C_i > 0");
+  }
+  HIP_CHECK(hipSetDevice(m.device));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  if (c) {
+    if (!m.row_c) m.row_c = gpu::dmalloc<float>((size_t)m.n, &m.bytes);
+    m.info.bytes_device = m.bytes;
+    m.h_row_c.assign(c, c + m.n);
+    HIP_CHECK(hipMemcpyAsync(m.row_c, m.h_row_c.data(), m.n * 4, hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+  }
+  const float* arg = c ? m.row_c : nullptr;
+  if (arg != m.wsa.c_row) {
+    // the captured graphs hold the old kernels and arguments: recaptured by the next solve
+    m.wsa.c_row = arg;
+    if (m.gexec) (void)hipGraphExecDestroy(m.gexec);
+    if (m.graph) (void)hipGraphDestroy(m.graph);
+    if (m.gexec1) (void)hipGraphExecDestroy(m.gexec1);
+    if (m.graph1) (void)hipGraphDestroy(m.graph1);
+    m.gexec = m.gexec1 = nullptr;
+    m.graph = m.graph1 = nullptr;
+  }
+  m.problem_swapped = true;
 }
 
 void GpuSolver::release_cache() {

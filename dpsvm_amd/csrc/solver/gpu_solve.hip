@@ -88,16 +88,26 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   res.cache_lines = m.L;
   auto ts0 = Clock::now();
 
+  // per-row C: refused combinations before any state changes (a refused call keeps a requested Gram reuse)
+  DPSVM_CHECK(!(m.wsa.c_row && resume), "per-row C (set_row_C): resume is not supported");
+  if (m.wsa.c_row) {
+    // the bounds were validated against the labels current at set_row_C; set_labels may have come after
+    bool pos = false, neg = false;
+    for (int64_t i = 0; i < m.n; ++i)
+      if (m.h_row_c[i] > 0.f) (m.h_y[i] > 0.f ? pos : neg) = true;
+    DPSVM_CHECK(pos && neg, "per-row C (set_row_C): each label needs at least one row with C_i > 0");
+  }
+
   if (!m.lines) {  // released (release_cache): the same L lines again, empty
     m.lines = gpu::dmalloc<float>((size_t)m.L * m.ldl, &m.bytes);
     m.info.bytes_device = m.bytes;
     m.args.lines = m.lines;
     m.wsa.gram = m.lines;
   }
-  // the resident Gram is kept only on request (set_labels) and only a completed one; it is not valid again
-  // before this solve has ended well
-  m.reuse_gram = m.labels_swapped && m.gram_valid && m.dense;
-  m.labels_swapped = m.gram_valid = false;
+  // the resident Gram is kept only on request (set_labels / set_row_C) and only a completed one; it is not
+  // valid again before this solve has ended well
+  m.reuse_gram = m.problem_swapped && m.gram_valid && m.dense;
+  m.problem_swapped = m.gram_valid = false;
   // ---- state init (alpha = 0, f = -y, empty cache) or resume ----
   int64_t iter0 = 0;
   float b_hi0 = 0.f, b_lo0 = 0.f;
@@ -268,7 +278,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
     std::vector<float> ah((size_t)m.n);
     HIP_CHECK(hipMemcpy(ah.data(), m.alpha, m.n * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < m.n; ++i)
-      if (!(ah[i] >= 0.f && ah[i] <= m.p.C))
+      if (!(ah[i] >= 0.f && ah[i] <= (m.wsa.c_row ? m.h_row_c[i] : m.p.C)))
         fail("DPSVM_VERIFY: alpha[" + std::to_string(i) + "] = " + std::to_string(ah[i]) + " outside [0, C]");
     std::vector<float> fd((size_t)m.nl), fr((size_t)m.nl);
     HIP_CHECK(hipMemcpy(fd.data(), m.f, m.nl * 4, hipMemcpyDeviceToHost));

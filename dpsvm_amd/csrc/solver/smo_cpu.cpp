@@ -83,7 +83,7 @@ class RowCache {
 }  // namespace
 
 SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* comm,
-                      const Checkpoint* resume, const ProgressFn& progress) {
+                      const Checkpoint* resume, const ProgressFn& progress, const float* row_C) {
   auto t_setup0 = Clock::now();
   const int64_t n = ds.n;
   const int d = ds.d;
@@ -98,6 +98,17 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   const float C = p.C;
   const float* X = ds.x.data();
   const float* Y = ds.y.data();
+  // per-row bounds C_i (global n; nullptr: the scalar C): the compare-form sets and the two-bound pair step
+  const float* Cr = row_C;
+  if (Cr) {
+    bool pos = false, neg = false;
+    for (int64_t i = 0; i < n; ++i) {
+      DPSVM_CHECK(std::isfinite(Cr[i]) && Cr[i] >= 0.f, "row_C: every C_i must be finite and >= 0");
+      if (Cr[i] > 0.f) (Y[i] > 0.f ? pos : neg) = true;
+    }
+    DPSVM_CHECK(pos && neg, "row_C: each label needs at least one row with C_i > 0");
+    DPSVM_CHECK(!resume, "row_C: resume is not supported with per-row C");
+  }
 
   // flush-to-zero on every solver thread (restored for the caller on return):
   // adult-shape 48.5k iterations 199 s -> see profiles/r1_cpu_ftz.txt
@@ -194,8 +205,10 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
     for (int64_t j = b; j < e; ++j) {
       const int64_t g = off + j;
       const float a = alpha[g], yj = Y[g], fj = f[j];
-      if (in_up(a, yj, C)) kh = std::min(kh, make_key(fj, (uint32_t)g));
-      if (in_low(a, yj, C)) kl = std::min(kl, make_key(-fj, (uint32_t)g));
+      const bool up = Cr ? in_up_w(a, yj, Cr[g]) : in_up(a, yj, C);
+      const bool low = Cr ? in_low_w(a, yj, Cr[g]) : in_low(a, yj, C);
+      if (up) kh = std::min(kh, make_key(fj, (uint32_t)g));
+      if (low) kl = std::min(kl, make_key(-fj, (uint32_t)g));
     }
     th_hi[t] = kh;
     th_lo[t] = kl;
@@ -233,8 +246,10 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
     }
     const float k_hl = std::exp(-gamma * dist2);
     const float a_hi_old = alpha[i_hi], a_lo_old = alpha[i_lo];
-    PairUpdate u = pair_update(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, C, p.tau,
-                               (int)p.clip, i_hi == i_lo);
+    PairUpdate u = Cr ? pair_update_w(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, Cr[i_hi], Cr[i_lo],
+                                      p.tau, (int)p.clip, i_hi == i_lo)
+                      : pair_update(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, C, p.tau,
+                                    (int)p.clip, i_hi == i_lo);
     alpha[i_lo] = u.a_lo_new;
     alpha[i_hi] = u.a_hi_new;  // hi written last: wins if i_hi == i_lo
     // ---- f update over local rows ----
@@ -306,7 +321,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   if (trace::verify_enabled()) {
     // invariants: alpha in [0, C]; incremental f == f recomputed from alpha
     for (int64_t i = 0; i < n; ++i)
-      if (!(alpha[i] >= 0.f && alpha[i] <= C))
+      if (!(alpha[i] >= 0.f && alpha[i] <= (Cr ? Cr[i] : C)))
         fail("DPSVM_VERIFY: alpha[" + std::to_string(i) + "] outside [0, C]");
     std::vector<float> fr((size_t)nl);
     recompute_f(fr);

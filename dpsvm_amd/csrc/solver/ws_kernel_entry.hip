@@ -112,7 +112,8 @@ WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int 
 WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float>& f, const std::vector<float>& alpha,
                             const std::vector<float>& y, const std::vector<int32_t>& qb, int q_max, int blocks,
                             int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
-                            float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss) {
+                            float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss,
+                            const std::vector<float>& row_C) {
   DPSVM_CHECK(blocks >= 1 && blocks <= kWsMaxBlocks && (int)qb.size() == blocks && q_max >= 2 && q_max <= kWsMax,
               "ws_solve_probe: 1 <= blocks <= 128, qb per block, q_max <= 192");
   const size_t nq = (size_t)blocks * q_max;
@@ -120,6 +121,7 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
               "ws_solve_probe: K [P][q_max][q_max], f / alpha / y [P][q_max]");
   for (int p = 0; p < blocks; ++p) DPSVM_CHECK(qb[p] >= 0 && qb[p] <= q_max, "ws_solve_probe: qb[p] <= q_max");
   DPSVM_CHECK(blocks > 1 || p_round == 1, "ws_solve_probe: one block means p_round 1");
+  DPSVM_CHECK(row_C.empty() || row_C.size() == nq, "ws_solve_probe: row_C [P][q_max] or empty");
   Stream st;
   const int stride = blocks * kWsMax;
   std::vector<float> sub(nq * q_max + 3 * (size_t)stride, 0.f);
@@ -164,6 +166,7 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
   a.clip = clip;
   a.max_iter = max_iter;
   a.wss = wss;
+  if (!row_C.empty()) a.c_row = st.up(row_C, nq);  // row a of block p is global row p q_max + a
   a.clip_fallback = 1;
   a.t_halve = 0.9f;
   a.world = 1;
@@ -198,7 +201,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               const std::vector<float>& dalpha, const std::vector<int32_t>& apply_line,
                               const std::vector<float>& apply_coef, const std::vector<int32_t>& nab, int blocks,
                               int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps,
-                              bool wide) {
+                              bool wide, const std::vector<float>& row_C) {
   const int64_t n = (int64_t)f.size();
   DPSVM_CHECK(n >= 1 && (int64_t)alpha.size() == n && (int64_t)y.size() == n && (int64_t)dalpha.size() == n,
               "ws_select_probe: f / alpha / y / dalpha of n rows");
@@ -206,6 +209,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   DPSVM_CHECK(blocks >= 1 && blocks <= kWsMaxBlocks && (int)nab.size() == blocks && q_max >= 2 && q_max <= kWsMax,
               "ws_select_probe: nab per block, q_max <= 192");
   DPSVM_CHECK(apply_line.size() == apply_coef.size(), "ws_select_probe: apply lines / coefficients");
+  DPSVM_CHECK(row_C.empty() || (int64_t)row_C.size() == n, "ws_select_probe: row_C of n rows or empty");
   int64_t tot = 0;
   for (int p = 0; p < blocks; ++p) {
     DPSVM_CHECK(nab[p] >= 0 && nab[p] <= q_max, "ws_select_probe: nab[p] <= q_max");
@@ -259,6 +263,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   a.rank = 0;
   a.q_max = q_max;
   a.C = C;
+  if (!row_C.empty()) a.c_row = st.up(row_C, (size_t)n);
   a.blocks = blocks;
   a.t_halve = 0.9f;
   a.clip_fallback = 1;

@@ -144,6 +144,10 @@ class SVCConfig:
     # sample passes the bound) | on | off
     gram_adapt: str = "auto"
     gram_cold_tau: float = 2.0 ** -22
+    # per-row C (C_i = C * w_i): None | "balanced" (n / (2 n_c) per class, scikit-learn's formula; one-vs-rest:
+    # each machine's two sides) | {label: weight} (missing labels 1).  Multiplied by fit(sample_weight=).  Any
+    # weights run the working-set engines on one rank (solver auto -> ws, shrink / ws_recompute auto -> off)
+    class_weight: Any = None
 
     def shrink_mode(self) -> str:
         s = self.shrink
@@ -224,6 +228,29 @@ class SVCConfig:
         p.gram_cold_tau = float(self.gram_cold_tau)
         return p
 
+    def weighted_params(self, p, comm=None, resume=None, rank_rows=None) -> str:
+        """Resolve / refuse the settings of a solve with per-row C; returns the note for ``engine_note``."""
+        for name, val in (("comm", comm), ("resume", resume), ("rank_rows", rank_rows),
+                          ("checkpoint_path", self.checkpoint_path)):
+            if val:
+                raise NotImplementedError(f"sample / class weights (per-row C) run on one rank from a cold start "
+                                          f"without checkpoints: {name} is not supported")
+        if self.solver == "smo":
+            raise NotImplementedError("sample / class weights need the working-set engines: the pair-at-a-time "
+                                      "engines (solver='smo') keep bit parity with the reference and take one C")
+        if self.shrink_mode() == "on":
+            raise NotImplementedError("sample / class weights: shrink='on' is not supported (the shrinking phases "
+                                      "subset the rows, not the weights)")
+        if self.ws_recompute == "on":
+            raise NotImplementedError("sample / class weights: ws_recompute='on' is not supported (its selection "
+                                      "takes one C)")
+        note = "per-row C"
+        if self.solver == "auto":
+            note += ": solver auto -> ws"
+        p.solver = 2
+        p.ws_recompute = 2
+        return note
+
     def device_kind(self) -> tuple[str, int]:
         dev = self.device
         if dev == "auto":
@@ -252,6 +279,11 @@ class SVC:
     the k solves' dicts, ``fit_time_`` their sum, ``status_`` their maximum;
     ``decision_function`` returns (n, k) and ``predict`` the class of the
     largest value (ties: the lowest class index).
+
+    Sample / class weights (``fit(sample_weight=)``, ``class_weight``): row i's
+    box is ``0 <= alpha_i <= C * w_i``; ``row_C_`` holds the bounds ((n,), or
+    (k, n)), ``n_bounded_`` counts ``alpha_i == C_i > 0``.  ``cross_val_decision``
+    / ``cross_val_score``: k folds as k solves on one resident Gram.
     """
 
     def __init__(self, C: float = 1.0, gamma: Optional[float] = None, eps: float = 1e-3,
@@ -287,18 +319,72 @@ class SVC:
         mode = self.config.shrink_mode()
         return mode == "on" or (mode == "auto" and bool(load().shrink_auto(p, n, d, dev, comm)))
 
+    # ------------------------------------------------------------------ weights
+    @staticmethod
+    def _sample_weight(sample_weight, n: int) -> np.ndarray:
+        """float64 (n,), validated: finite and >= 0 (ones when None)"""
+        if sample_weight is None:
+            return np.ones(n, dtype=np.float64)
+        w = np.asarray(_as_1d(sample_weight), dtype=np.float64)
+        if w.shape[0] != n:
+            raise ValueError(f"sample_weight has {w.shape[0]} entries, X has {n} rows")
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("sample_weight must be finite and >= 0")
+        return w
+
+    @staticmethod
+    def _class_dict(cw, y: np.ndarray) -> np.ndarray:
+        """a {label: weight} dict as per-row weights (missing labels 1)"""
+        out = np.ones(len(y), dtype=np.float64)
+        for lab, wv in cw.items():
+            wv = float(wv)
+            if not math.isfinite(wv) or wv < 0:
+                raise ValueError("class_weight values must be finite and >= 0")
+            out[y == lab] = wv
+        return out
+
+    def _row_C(self, w64: np.ndarray, ys: np.ndarray) -> np.ndarray:
+        """C_i = C * w_i in float32; each side of ys needs a positive bound"""
+        rc = (np.float32(self.config.C) * w64.astype(np.float32)).astype(np.float32)
+        if not np.all(np.isfinite(rc)):
+            raise ValueError("C * weight overflows float32")
+        if not (np.any(rc[ys > 0] > 0) and np.any(rc[ys <= 0] > 0)):
+            raise ValueError("weights leave one class without a row of positive C_i")
+        return rc
+
+    def _binary_weights(self, y1: np.ndarray, ys: np.ndarray, sample_weight) -> Optional[np.ndarray]:
+        """row weights of a binary fit (class weight x sample weight), None without any"""
+        cw = self.config.class_weight
+        if cw is None and sample_weight is None:
+            return None
+        n = len(ys)
+        w = self._sample_weight(sample_weight, n)
+        if cw is None:
+            return w
+        if isinstance(cw, str):
+            if cw != "balanced":
+                raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
+            n_pos = int(np.sum(ys > 0))
+            if n_pos == 0 or n_pos == n:
+                raise ValueError("class_weight='balanced' needs both classes")
+            return w * np.where(ys > 0, n / (2.0 * n_pos), n / (2.0 * (n - n_pos)))
+        if isinstance(cw, dict):
+            return w * self._class_dict(cw, y1)
+        raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
+
     # ------------------------------------------------------------------ fit
     def fit(self, X, y, comm=None, resume=None, progress: Optional[Callable] = None,
-            rank_rows: Optional[int] = None) -> "SVC":
+            rank_rows: Optional[int] = None, sample_weight=None) -> "SVC":
         """Train.  ``comm``: a native communicator (see dpsvm_amd.parallel) for
-        multi-rank training; ``resume``: checkpoint path or native Checkpoint."""
+        multi-rank training; ``resume``: checkpoint path or native Checkpoint;
+        ``sample_weight``: per-row multipliers of C (with ``class_weight``)."""
         C = load()
         if self.config.engines == "all" or self.config.host_cache_lines or self.config.cache_engine == "chain":
             load_quarantine()  # the quarantined pair-at-a-time cache engines (plugin)
         X = _as_f32_2d(X)
         y1 = _as_1d(y)
         if len(np.unique(y1)) > 2:
-            return self._fit_multi(X, y1, comm, resume, progress, rank_rows)
+            return self._fit_multi(X, y1, comm, resume, progress, rank_rows, sample_weight)
         self._multi = False
         ys = self._encode(y)
         n, d = X.shape[0], X.shape[1]
@@ -306,6 +392,11 @@ class SVC:
             raise ValueError("len(y) != X.shape[0]")
         cfg = self.config
         p = cfg.to_native(d)
+        w = self._binary_weights(y1, ys, sample_weight)
+        row_C = note = None
+        if w is not None:  # any weights: the weighted path (no shortcut for all ones)
+            row_C = self._row_C(w, ys)
+            note = cfg.weighted_params(p, comm, resume, rank_rows)
         if cfg.log_every and progress is None:
             def progress(it, bh, bl, el, hits, misses):  # noqa: E306
                 print(f"iter {it}  b_hi {bh:.6g}  b_lo {bl:.6g}  gap {bl - bh:.3g}  "
@@ -316,7 +407,7 @@ class SVC:
         kind, dev = cfg.device_kind()
         self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
         t0 = time.perf_counter()
-        if kind == "cuda" and rank_rows is None and self._use_shrink(p, n, d, dev, comm):
+        if kind == "cuda" and rank_rows is None and row_C is None and self._use_shrink(p, n, d, dev, comm):
             shr = C.ShrinkingSolver(p, comm, dev)
             self.setup_info_ = shr.setup(X, ys)  # the whole-problem phases' solver; iteration "ws+shrinking"
             alpha, info = shr.solve(ck, progress)
@@ -325,12 +416,16 @@ class SVC:
         elif kind == "cuda":
             solver = C.GpuSolver(p, comm, dev)
             self.setup_info_ = solver.setup(X, ys.shape[0], ys)
+            if row_C is not None:
+                solver.set_row_C(row_C)
+                en = self.setup_info_.get("engine_note", "")
+                self.setup_info_["engine_note"] = (en + "; " if en else "") + note
             alpha, info = solver.solve(ck, progress)
             self._solver = solver
         else:
             if rank_rows is not None:
                 raise ValueError("partitioned X needs the GPU solver")
-            alpha, info = C.solve_cpu(X, ys, p, comm, ck, progress)
+            alpha, info = C.solve_cpu(X, ys, p, comm, ck, progress, row_C)
             self._solver = None
         self.wall_time_ = time.perf_counter() - t0
         self.alpha_ = alpha
@@ -343,6 +438,9 @@ class SVC:
         self.fit_time_ = float(info["t_solve"])
         self.setup_time_ = float(info["t_setup"])
         self.stats_ = dict(info)
+        self.row_C_ = row_C
+        bound = row_C if row_C is not None else np.float32(cfg.C)
+        self.n_bounded_ = int(np.sum((alpha == bound) & (alpha > 0))) if rank_rows is None else None
         if self.status_ == 2 and self.n_rounds_ > 0:
             import warnings
 
@@ -362,7 +460,29 @@ class SVC:
         self._gpu_pred = None
         return self
 
-    def _fit_multi(self, X: np.ndarray, y: np.ndarray, comm, resume, progress, rank_rows) -> "SVC":
+    def _multi_weights(self, y: np.ndarray, classes: np.ndarray, sample_weight) -> Optional[np.ndarray]:
+        """(k, n) row weights of the one-vs-rest machines, None without any"""
+        cw = self.config.class_weight
+        if cw is None and sample_weight is None:
+            return None
+        n, k = len(y), len(classes)
+        w = self._sample_weight(sample_weight, n)
+        W = np.tile(w, (k, 1))
+        if cw is None:
+            return W
+        if isinstance(cw, str):
+            if cw != "balanced":
+                raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
+            for c in range(k):  # each machine's two sides
+                n_c = int(np.sum(y == classes[c]))
+                W[c] *= np.where(y == classes[c], n / (2.0 * n_c), n / (2.0 * (n - n_c)))
+            return W
+        if isinstance(cw, dict):
+            return W * self._class_dict(cw, y)[None, :]  # a row's own label, in every machine
+        raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
+
+    def _fit_multi(self, X: np.ndarray, y: np.ndarray, comm, resume, progress, rank_rows,
+                   sample_weight=None) -> "SVC":
         """One-vs-rest: k machines on one X.  On the GPU one solver — setup()
         (X upload, norms, operand prep, engine choice) once, the resident Gram
         built by machine 0's solve and kept by the label swaps after it."""
@@ -379,12 +499,17 @@ class SVC:
         classes = np.unique(y)
         k = len(classes)
         Ys = np.stack([np.where(y == c, 1.0, -1.0).astype(np.float32) for c in classes])
+        W = self._multi_weights(y, classes, sample_weight)
+        RC = note = None
+        if W is not None:
+            RC = np.stack([self._row_C(W[c], Ys[c]) for c in range(k)])
+            note = cfg.weighted_params(p)
         kind, dev = cfg.device_kind()
         self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
         t0 = time.perf_counter()
         alphas, infos = [], []
         self._solver = None
-        if kind == "cuda" and self._use_shrink(p, n, d, dev, None):
+        if kind == "cuda" and RC is None and self._use_shrink(p, n, d, dev, None):
             for c in range(k):  # ShrinkingSolver has no label swap: one per machine
                 shr = C.ShrinkingSolver(p, None, dev)
                 setup = shr.setup(X, Ys[c])
@@ -397,16 +522,21 @@ class SVC:
         elif kind == "cuda":
             solver = C.GpuSolver(p, None, dev)
             self.setup_info_ = solver.setup(X, n, Ys[0])
+            if RC is not None:
+                en = self.setup_info_.get("engine_note", "")
+                self.setup_info_["engine_note"] = (en + "; " if en else "") + note
             for c in range(k):
                 if c:
                     solver.set_labels(Ys[c])
+                if RC is not None:
+                    solver.set_row_C(RC[c])
                 a, info = solver.solve(None, progress)
                 alphas.append(a)
                 infos.append(dict(info))
             del solver  # the resident Gram is not held past fit
         else:
             for c in range(k):
-                a, info = C.solve_cpu(X, Ys[c], p, None, None, progress)
+                a, info = C.solve_cpu(X, Ys[c], p, None, None, progress, None if RC is None else RC[c])
                 alphas.append(a)
                 infos.append(dict(info))
         self.wall_time_ = time.perf_counter() - t0
@@ -422,6 +552,9 @@ class SVC:
         self.fit_time_ = float(sum(i["t_solve"] for i in infos))
         self.setup_time_ = float(infos[0]["t_setup"])
         self.stats_ = infos
+        self.row_C_ = RC
+        bound = RC if RC is not None else np.float32(cfg.C)
+        self.n_bounded_ = int(np.sum((self.alpha_ == bound) & (self.alpha_ > 0)))
         if any(i["status"] == 2 and i.get("outer", 0) > 0 for i in infos):
             import warnings
 
@@ -437,6 +570,75 @@ class SVC:
         self._model = None
         self._gpu_pred = None
         return self
+
+    # ------------------------------------------------------------------ cross-validation
+    @staticmethod
+    def cv_folds(n: int, cv: int = 5, seed: int = 0) -> list:
+        """The folds of cross_val_decision: ``np.random.default_rng(seed).permutation(n)`` split by
+        ``np.array_split`` into ``cv`` near-equal parts (fold k = the k-th part's row indices)."""
+        if not 2 <= cv <= n:
+            raise ValueError("cv must be in [2, n]")
+        return np.array_split(np.random.default_rng(seed).permutation(n), cv)
+
+    def cross_val_decision(self, X, y, cv: int = 5, seed: int = 0, sample_weight=None) -> np.ndarray:
+        """Out-of-fold decision values (n,) of a binary problem: fold k's rows get the decision of the model
+        trained with their weights zeroed (C_i = 0: alpha_i stays 0, the row is out of the problem).  On the
+        GPU one solver, one setup() and one resident Gram serve the ``cv`` solves: a held-out row's gradient
+        entry f_i = sum_j alpha_j y_j K_ij - y_i is kept by every round's f update, so its decision value is
+        f_i + y_i - b, read from the solver's gradient — no sub-Gram, no second upload, no predict pass.
+        Folds: ``cv_folds(n, cv, seed)``.  ``class_weight='balanced'`` is computed on all n rows.  Settings
+        resolve as for a weighted fit.  ``cv_stats_``: the per-fold solve dicts."""
+        C = load()
+        X = _as_f32_2d(X)
+        y1 = _as_1d(y)
+        if len(np.unique(y1)) != 2:
+            raise ValueError("cross_val_decision is binary: y needs two classes")
+        ys = self._encode(y)
+        n, d = X.shape
+        if ys.shape[0] != n:
+            raise ValueError("len(y) != X.shape[0]")
+        cfg = self.config
+        p = cfg.to_native(d)
+        w = self._binary_weights(y1, ys, sample_weight)
+        if w is None:
+            w = np.ones(n, dtype=np.float64)
+        cfg.weighted_params(p)
+        folds = self.cv_folds(n, cv, seed)
+        rcs = []
+        for fold in folds:
+            wf = w.copy()
+            wf[fold] = 0.0
+            rcs.append(self._row_C(wf, ys))
+        kind, dev = cfg.device_kind()
+        dec = np.zeros(n, dtype=np.float32)
+        stats = []
+        t0 = time.perf_counter()
+        if kind == "cuda":
+            solver = C.GpuSolver(p, None, dev)
+            self.cv_setup_info_ = solver.setup(X, n, ys)
+            for fold, rc in zip(folds, rcs):
+                solver.set_row_C(rc)
+                _, info = solver.solve(None, None)  # cold: alpha = 0, f = -y
+                g = solver.gradient()
+                dec[fold] = (g[fold].astype(np.float64) + ys[fold] - float(info["b"])).astype(np.float32)
+                stats.append(dict(info))
+            del solver
+        else:
+            for fold, rc in zip(folds, rcs):
+                alpha, info = C.solve_cpu(X, ys, p, None, None, None, rc)
+                model = C.make_model(X, ys, alpha, float(info["b"]), p.gamma)
+                dec[fold] = C.decision_cpu(model, np.ascontiguousarray(X[fold]), 0)
+                stats.append(dict(info))
+        self.cv_wall_time_ = time.perf_counter() - t0
+        self.cv_stats_ = stats
+        self.cv_folds_ = folds
+        return dec
+
+    def cross_val_score(self, X, y, cv: int = 5, seed: int = 0, sample_weight=None) -> float:
+        """accuracy of the signs of cross_val_decision (>= 0 -> the positive class)"""
+        dec = self.cross_val_decision(X, y, cv, seed, sample_weight)
+        ys = self._encode(y)
+        return float(np.mean(np.where(dec < 0, -1.0, 1.0) == ys))
 
     # ------------------------------------------------------------------ model
     def to_model(self):

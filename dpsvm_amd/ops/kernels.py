@@ -249,13 +249,14 @@ def ws_merge_multi(cand, blocks: int, q_max: int, n_new: int, eps: float, prev_u
 def ws_solve(K, f, alpha, y, qb, q_max: int, C_: float, clip: str = "independent", eps: float = 1e-3,
              rel: float = 0.3, eps_floor: float = 3e-4, tau: float = 1e-12, b_hi: float = 0.0, b_lo: float = 0.0,
              inner_max: int = 768, p_round: int | None = None, iteration: int = 0, max_iter: int = 1 << 40,
-             wss: int = 1) -> dict:
+             wss: int = 1, row_C=None) -> dict:
     """One launch of the sub-problem solver (ws_solve_kernel): P = len(qb)
     blocks, block p with qb[p] rows, sub-Gram K[p] ([q_max][q_max]) and f /
     alpha / y [p][q_max]; b_hi / b_lo = the round's global selection (the local
     tolerance is max(eps_floor, rel (b_lo - b_hi) / 2)).  P > 1 runs the
     multi-block kernel (p_round active blocks share max_iter).  wss: 1 the
-    reference's first-order pair choice, 2 second order (WSS2)."""
+    reference's first-order pair choice, 2 second order (WSS2).  row_C: per-row
+    bounds C_i [p][q_max] (None: the scalar C_; the kRowC instantiations)."""
     import numpy as np
 
     P = len(qb)
@@ -263,19 +264,21 @@ def ws_solve(K, f, alpha, y, qb, q_max: int, C_: float, clip: str = "independent
     return load().k_ws_solve(f32(K), f32(f), f32(alpha), f32(y), np.asarray(qb, dtype=np.int32), q_max, P,
                              P if p_round is None else p_round, float(C_), 1 if clip == "box" else 0, float(eps),
                              float(rel), float(eps_floor), float(tau), float(b_hi), float(b_lo), int(inner_max),
-                             int(iteration), int(max_iter), int(wss))
+                             int(iteration), int(max_iter), int(wss),
+                             row_C=None if row_C is None else f32(row_C))
 
 
 def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float, q_max: int = 192,
               p_round: int | None = None, p_act: int | None = None, outer: int = 1, ks: int = 0,
-              wide: bool = False) -> dict:
+              wide: bool = False, row_C=None) -> dict:
     """The working-set f update + candidate selection (ws_select_kernel) on a
     dense gram [L][ldg >= n] (rows = lines).  len(nab) == 1: the one-pass
     kernel; more blocks: pass 1 (d_f, d'Qd / g'd partials) and pass 2 (line
     search t, f += t d_f, alpha = alpha_new - (1 - t) d_alpha, candidates).
     ks > 1: pass 1 split into ks list slices per selection group (dfs then
     holds slice 0, part [G][ks][2]).  wide: the wide pass 1 (1024-column
-    groups, 16-B row loads; part [p1G][ks][2])."""
+    groups, 16-B row loads; part [p1G][ks][2]).  row_C: per-row bounds C_i
+    [n] (None: the scalar C_)."""
     import numpy as np
 
     g = np.ascontiguousarray(np.asarray(gram, dtype=np.float32))
@@ -284,7 +287,8 @@ def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float
     return load().k_ws_select(g.reshape(-1), g.shape[0], g.shape[1], f32(f), f32(alpha), f32(y), f32(dalpha),
                               np.asarray(apply_lines, dtype=np.int32), f32(apply_coef), np.asarray(nab, dtype=np.int32),
                               P, P if p_round is None else p_round, P if p_act is None else p_act, q_max, float(C_),
-                              int(outer), ks=int(ks), wide=bool(wide))
+                              int(outer), ks=int(ks), wide=bool(wide),
+                              row_C=None if row_C is None else f32(row_C))
 
 
 def fused_select(f: torch.Tensor, alpha: torch.Tensor, y: torch.Tensor, C_: float, rows_per_group: int = 256):

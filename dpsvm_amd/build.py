@@ -48,6 +48,7 @@ LIB_SOURCES = [
     "solver/gpu_engines.hip",
     "solver/gpu_solve.hip",
     "solver/gpu_predict.hip",
+    "solver/kernel_entry.hip",
     "solver/ws_kernel_entry.hip",
     "solver/gpu_shrink.cpp",
     "kernels/setup_kernels.hip",

@@ -206,7 +206,7 @@ class GpuPredictor {
   std::unique_ptr<Impl> impl_;
 };
 
-// Low-level kernel entry points exposed for unit tests (device pointers).
+// Low-level kernel entry points exposed for unit tests (device pointers; kernel_entry.hip).
 namespace kernels {
 void row_sqnorm(const float* x, int64_t n, int d, int ld, float* out, void* stream);
 // known-bytes 16-B streaming read (FETCH_SIZE probe, bench/fetch_probe.py)

@@ -35,6 +35,17 @@ py::array_t<float> to_np2(const std::vector<float>& v, int64_t rows, int cols) {
   if (!v.empty()) memcpy(a.mutable_data(), v.data(), v.size() * 4);
   return a;
 }
+// decision values of a 2-D matrix, the GIL released around fn(x, n, d): (n, cols), or (n,) for cols == 0
+template <class Fn>
+py::array_t<float> decide(const F32& x, int cols, Fn&& fn) {
+  if (x.ndim() != 2) throw py::value_error("x must be 2-D");
+  std::vector<float> out;
+  {
+    py::gil_scoped_release rel;
+    out = fn(x.data(), (int64_t)x.shape(0), (int)x.shape(1));
+  }
+  return cols ? to_np2(out, x.shape(0), cols) : to_np(out);
+}
 std::vector<float> from_np(const F32& a) { return std::vector<float>(a.data(), a.data() + a.size()); }
 
 void check_xy(const F32& x, const F32& y, int64_t& n, int& d) {
@@ -457,22 +468,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("read_multi_model", &read_multi_model, py::arg("path"));
   m.def("is_multi_model", &is_multi_model, py::arg("path"));
   m.def("decision_multi_cpu", [](const MultiModel& md, F32 x, int threads) {
-    if (x.ndim() != 2) throw py::value_error("x must be 2-D");
-    std::vector<float> dec;
-    {
-      py::gil_scoped_release r;
-      dec = decision_multi_cpu(md, x.data(), x.shape(0), (int)x.shape(1), threads);
-    }
-    return to_np2(dec, x.shape(0), md.k());
+    return decide(x, md.k(),
+                  [&](const float* xd, int64_t n, int d) { return decision_multi_cpu(md, xd, n, d, threads); });
   }, py::arg("model"), py::arg("x"), py::arg("threads") = 0);
   m.def("decision_cpu", [](const Model& md, F32 x, int threads) {
-    if (x.ndim() != 2) throw py::value_error("x must be 2-D");
-    std::vector<float> dec;
-    {
-      py::gil_scoped_release r;
-      dec = decision_cpu(md, x.data(), x.shape(0), (int)x.shape(1), threads);
-    }
-    return to_np(dec);
+    return decide(x, 0, [&](const float* xd, int64_t n, int d) { return decision_cpu(md, xd, n, d, threads); });
   }, py::arg("model"), py::arg("x"), py::arg("threads") = 0);
 
   // ---------------- solvers ----------------
@@ -640,22 +640,10 @@ PYBIND11_MODULE(_C, m) {
       .def(py::init<const MultiModel&, int, int>(), py::arg("model"), py::arg("device") = 0,
            py::arg("precision") = 0)
       .def("decision_multi", [](GpuPredictor& p, F32 x) {
-        if (x.ndim() != 2) throw py::value_error("x must be 2-D");
-        std::vector<float> out;
-        {
-          py::gil_scoped_release rel;
-          out = p.decision_multi(x.data(), x.shape(0), (int)x.shape(1));
-        }
-        return to_np2(out, x.shape(0), p.k());
+        return decide(x, p.k(), [&](const float* xd, int64_t n, int d) { return p.decision_multi(xd, n, d); });
       }, py::arg("x"))
       .def("decision", [](GpuPredictor& p, F32 x) {
-        if (x.ndim() != 2) throw py::value_error("x must be 2-D");
-        std::vector<float> out;
-        {
-          py::gil_scoped_release rel;
-          out = p.decision(x.data(), x.shape(0), (int)x.shape(1));
-        }
-        return to_np(out);
+        return decide(x, 0, [&](const float* xd, int64_t n, int d) { return p.decision(xd, n, d); });
       })
       .def("decision_device", [](GpuPredictor& p, uintptr_t x, int64_t n, int d, int ld, uintptr_t out,
                                  uintptr_t stream) {

@@ -62,6 +62,21 @@ bool GpuSolver::Impl::all_agree(bool mine, Communicator* c, int w) {
   return v == 1ull;
 }
 
+void GpuSolver::Impl::allreduce_sum_host(double* v, int64_t count, const char* what) {
+  if (world == 1) return;
+  if (comm->device_memory()) {
+    size_t tb = 0;
+    double* d = dmalloc<double>((size_t)count, &tb);
+    HIP_CHECK(hipMemcpy(d, v, count * 8, hipMemcpyHostToDevice));
+    comm->allreduce_sum_f64(d, count, stream);
+    HIP_CHECK(hipMemcpyAsync(v, d, count * 8, hipMemcpyDeviceToHost, stream));
+    sync_collective(comm, stream, what);
+    (void)hipFree(d);
+  } else {
+    comm->allreduce_sum_f64(v, count, nullptr);
+  }
+}
+
 // Peer exchange setup (collective over the communicator): receive buffers,
 // pointer / IPC-handle all-gather, mapping, and an in-kernel ping that every
 // rank must pass.  Returns false (everywhere) if any rank failed.

@@ -8,8 +8,8 @@
 //                     small collectives that work on device and host communicators
 //   gpu_engines.hip   the iteration engines (seed + block of iterations / rounds)
 //   gpu_solve.hip     the timed SMO loop, checkpoints, invariant checks
-//   gpu_predict.hip   SV compaction, accuracy, decision values, GpuPredictor,
-//                     kernel-level test entry points
+//   gpu_predict.hip   SV compaction, accuracy, decision values, GpuPredictor
+//   kernel_entry.hip, ws_kernel_entry.hip   kernel-level test entry points
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -184,6 +184,8 @@ struct GpuSolver::Impl {
   void allgather_bytes(const void* send, void* recv, size_t bytes);  // host buffers
   // every rank of `c` agrees: true only if `mine` is true everywhere
   bool all_agree(bool mine, Communicator* c, int w);
+  // element-wise SUM over ranks of a host double buffer; `what` names the collective in a watchdog message
+  void allreduce_sum_host(double* v, int64_t count, const char* what);
   // region_words: u64 words of the exchange region (0: the SMO engines' key parities)
   bool setup_exchange(int64_t region_words = 0);
   // residency census of the chosen persistent engine (collective: agreed)

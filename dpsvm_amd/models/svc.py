@@ -49,13 +49,42 @@ def _as_1d(y) -> np.ndarray:
 
 
 _CLIP = {"independent": 0, "box": 1}
-_XMODE = {"auto": 0, "replicated": 1, "partitioned": 2}
-_EXCHANGE = {"auto": 0, "allreduce": 1, "peer": 2}
-_PERSIST = {"auto": 0, "off": 1, "on": 2}
-_CACHE_ENGINE = {"fused": 0, "chain": 1}
-_XCH_MEM = {"auto": 0, "uncached": 1, "coarse": 2}
-_DP = {"auto": 0, "shard": 1, "replicate": 2}
-_SOLVER = {"auto": 0, "smo": 1, "ws": 2}
+_DP = {"auto": 0, "shard": 1, "replicate": 2}           # SolverParams.dp_policy
+_GRAM = {"auto": 0, "f32": 1, "split": 2}               # SolverParams.gram_precision
+_AUTO_ON_OFF = {"auto": 0, "on": 1, "off": 2}
+# SVCConfig fields whose SolverParams attribute has the same name: the enums by their table ...
+_ENUMS = {
+    "x_mode": {"auto": 0, "replicated": 1, "partitioned": 2},
+    "exchange": {"auto": 0, "allreduce": 1, "peer": 2},
+    "persist": {"auto": 0, "off": 1, "on": 2},
+    "cache_engine": {"fused": 0, "chain": 1},
+    "engines": {"production": 0, "all": 1},
+    "xch_mem": {"auto": 0, "uncached": 1, "coarse": 2},
+    "solver": {"auto": 0, "smo": 1, "ws": 2},
+    "ws_recompute": _AUTO_ON_OFF,
+    "eta": {"x": 0, "gram": 1},
+    "gram_adapt": _AUTO_ON_OFF,
+}
+# ... and the plain ones by their type
+_PLAIN = {
+    float: ("C", "eps", "tau", "cache_mb", "cache_frac", "xch_timeout_s", "watchdog_s", "ws_rel", "ws_t_halve",
+            "gram_cold_tau"),
+    int: ("max_iter", "cache_lines", "host_cache_lines", "spec_rows", "graph_block", "log_every", "checkpoint_every",
+          "persist_block", "cache_groups", "rows_per_group", "xch_poll_batch", "xch_sleep", "xch_stride",
+          "census_groups", "ws_size", "ws_new", "ws_blocks", "ws_inner", "ws_wss", "ws_block"),
+    bool: ("use_graph", "verbose", "force_collectives", "force_cache", "verify_ranks"),
+}
+
+
+def _parse_device(dev: str) -> tuple[str, int]:
+    """auto | cpu | cuda | cuda:N -> ("cuda", N) or ("cpu", 0); anything else is a ValueError"""
+    if dev == "auto":
+        return ("cuda", 0) if gpu_available() else ("cpu", 0)
+    if dev == "cpu":
+        return ("cpu", 0)
+    if dev.startswith("cuda"):
+        return ("cuda", int(dev.split(":")[1]) if ":" in dev else 0)
+    raise ValueError(f"unknown device {dev!r}")
 
 
 def _pick(table: dict, value: str, name: str) -> int:
@@ -162,70 +191,22 @@ class SVCConfig:
 
     def to_native(self, d: int):
         C = load()
-        if self.clip not in _CLIP:
-            raise ValueError(f"clip must be one of {list(_CLIP)}")
-        if self.x_mode not in _XMODE:
-            raise ValueError(f"x_mode must be one of {list(_XMODE)}")
         if not self.C > 0:
             raise ValueError("C must be > 0")
-        p = C.SolverParams()
-        p.C = float(self.C)
-        p.gamma = self.resolved_gamma(d)
-        p.eps = float(self.eps)
-        p.max_iter = int(self.max_iter)
-        p.clip = C.ClipMode.box if self.clip == "box" else C.ClipMode.independent
-        p.tau = float(self.tau)
-        p.cache_lines = int(self.cache_lines)
-        p.cache_mb = float(self.cache_mb)
-        p.cache_frac = float(self.cache_frac)
-        p.host_cache_lines = int(self.host_cache_lines)
-        p.spec_rows = int(self.spec_rows)
-        p.graph_block = int(self.graph_block)
-        p.use_graph = bool(self.use_graph)
-        p.x_mode = _XMODE[self.x_mode]
-        p.log_every = int(self.log_every)
-        p.verbose = bool(self.verbose)
-        p.checkpoint_every = int(self.checkpoint_every)
-        p.checkpoint_path = self.checkpoint_path or ""
-        p.force_collectives = bool(self.force_collectives)
-        if self.exchange not in _EXCHANGE:
-            raise ValueError(f"exchange must be one of {list(_EXCHANGE)}")
-        p.exchange = _EXCHANGE[self.exchange]
-        if self.persist not in _PERSIST:
-            raise ValueError(f"persist must be one of {list(_PERSIST)}")
-        p.persist = _PERSIST[self.persist]
-        p.persist_block = int(self.persist_block)
-        p.dp_policy = _pick(_DP, self.dp, "dp")
-        p.force_cache = bool(self.force_cache)
-        p.cache_engine = _pick(_CACHE_ENGINE, self.cache_engine, "cache_engine")
-        p.engines = _pick({"production": 0, "all": 1}, self.engines, "engines")
-        p.cache_groups = int(self.cache_groups)
         if self.rows_per_group % 256:
             raise ValueError("rows_per_group must be a multiple of 256")
-        p.rows_per_group = int(self.rows_per_group)
-        p.xch_poll_batch = int(self.xch_poll_batch)
-        p.xch_sleep = int(self.xch_sleep)
-        p.xch_stride = int(self.xch_stride)
-        p.xch_mem = _pick(_XCH_MEM, self.xch_mem, "xch_mem")
-        p.xch_timeout_s = float(self.xch_timeout_s)
-        p.watchdog_s = float(self.watchdog_s)
-        p.census_groups = int(self.census_groups)
-        p.verify_ranks = bool(self.verify_ranks)
-        p.solver = _pick(_SOLVER, self.solver, "solver")
-        p.ws_size = int(self.ws_size)
-        p.ws_new = int(self.ws_new)
-        p.ws_rel = float(self.ws_rel)
-        p.ws_blocks = int(self.ws_blocks)
-        p.ws_inner = int(self.ws_inner)
-        p.ws_wss = int(self.ws_wss)
-        p.ws_t_halve = float(self.ws_t_halve)
+        p = C.SolverParams()
+        for cast, names in _PLAIN.items():
+            for name in names:
+                setattr(p, name, cast(getattr(self, name)))
+        for name, table in _ENUMS.items():
+            setattr(p, name, _pick(table, getattr(self, name), name))
+        p.gamma = self.resolved_gamma(d)
+        p.clip = C.ClipMode.box if _pick(_CLIP, self.clip, "clip") else C.ClipMode.independent
+        p.checkpoint_path = self.checkpoint_path or ""
+        p.dp_policy = _pick(_DP, self.dp, "dp")
+        p.gram_precision = _pick(_GRAM, self.gram, "gram")
         p.ws_clip_fallback = int(bool(self.ws_clip_fallback))
-        p.ws_block = int(self.ws_block)
-        p.ws_recompute = _pick({"auto": 0, "on": 1, "off": 2}, self.ws_recompute, "ws_recompute")
-        p.eta = _pick({"x": 0, "gram": 1}, self.eta, "eta")
-        p.gram_precision = _pick({"auto": 0, "f32": 1, "split": 2}, self.gram, "gram")
-        p.gram_adapt = _pick({"auto": 0, "on": 1, "off": 2}, self.gram_adapt, "gram_adapt")
-        p.gram_cold_tau = float(self.gram_cold_tau)
         return p
 
     def weighted_params(self, p, comm=None, resume=None, rank_rows=None) -> str:
@@ -252,15 +233,7 @@ class SVCConfig:
         return note
 
     def device_kind(self) -> tuple[str, int]:
-        dev = self.device
-        if dev == "auto":
-            return ("cuda", 0) if gpu_available() else ("cpu", 0)
-        if dev == "cpu":
-            return ("cpu", 0)
-        if dev.startswith("cuda"):
-            idx = int(dev.split(":")[1]) if ":" in dev else 0
-            return ("cuda", idx)
-        raise ValueError(f"unknown device {dev!r}")
+        return _parse_device(self.device)
 
 
 class SVC:
@@ -352,33 +325,94 @@ class SVC:
             raise ValueError("weights leave one class without a row of positive C_i")
         return rc
 
-    def _binary_weights(self, y1: np.ndarray, ys: np.ndarray, sample_weight) -> Optional[np.ndarray]:
-        """row weights of a binary fit (class weight x sample weight), None without any"""
+    def _weights(self, y: np.ndarray, Ys: np.ndarray, sample_weight) -> Optional[np.ndarray]:
+        """(k, n) float64 row weights of the machines Ys (class weight x sample weight), None without any.
+        ``balanced``: each machine's two sides; a dict: a row's own label y, in every machine."""
         cw = self.config.class_weight
         if cw is None and sample_weight is None:
             return None
-        n = len(ys)
-        w = self._sample_weight(sample_weight, n)
+        k, n = Ys.shape
+        W = np.tile(self._sample_weight(sample_weight, n), (k, 1))
         if cw is None:
-            return w
-        if isinstance(cw, str):
-            if cw != "balanced":
-                raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
-            n_pos = int(np.sum(ys > 0))
+            return W
+        if isinstance(cw, dict):
+            return W * self._class_dict(cw, y)[None, :]
+        if not isinstance(cw, str) or cw != "balanced":
+            raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
+        for c in range(k):
+            n_pos = int(np.sum(Ys[c] > 0))
             if n_pos == 0 or n_pos == n:
                 raise ValueError("class_weight='balanced' needs both classes")
-            return w * np.where(ys > 0, n / (2.0 * n_pos), n / (2.0 * (n - n_pos)))
-        if isinstance(cw, dict):
-            return w * self._class_dict(cw, y1)
-        raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
+            W[c] *= np.where(Ys[c] > 0, n / (2.0 * n_pos), n / (2.0 * (n - n_pos)))
+        return W
+
+    def _problem(self, d: int, y: np.ndarray, Ys: np.ndarray, sample_weight, comm=None, resume=None, rank_rows=None):
+        """the native params, the machines' row bounds (k, n) or None, and a weighted solve's engine note"""
+        p = self.config.to_native(d)
+        W = self._weights(y, Ys, sample_weight)
+        if W is None:
+            return p, None, None
+        RC = np.stack([self._row_C(W[c], Ys[c]) for c in range(len(Ys))])  # any weights: no shortcut for all ones
+        return p, RC, self.config.weighted_params(p, comm, resume, rank_rows)
 
     # ------------------------------------------------------------------ fit
+    def _solve_machines(self, X: np.ndarray, Ys: np.ndarray, RC: Optional[np.ndarray], p, note=None, comm=None,
+                        resume=None, progress=None, rank_rows=None, hook=None, keep=False):
+        """The solves of one fit on one X: machine c has the labels ``Ys[c]`` and the row bounds ``RC[c]`` (RC None:
+        the scalar C); ``Ys`` (1, n) under more rows of RC is one set of labels for all of them (the folds of a
+        cross-validation).  On the GPU one solver: setup() (X upload, norms, operand prep, engine choice) once, then
+        per machine set_labels (after the first), set_row_C (with RC) and solve; the resident Gram built by the
+        first solve is kept by the swaps after it.  ``hook(c, solver)`` runs after machine c's solve on the live
+        GpuSolver.  Returns the alphas, the info dicts, the setup info (None on the CPU) and, with ``keep``, the
+        GpuSolver (else it is dropped here, with its Gram)."""
+        C = load()
+        k, n = Ys.shape
+        m = k if RC is None else len(RC)
+        ck = C.read_checkpoint(resume) if isinstance(resume, str) else resume
+        kind, dev = self.config.device_kind()
+        alphas, infos, setup, solver = [], [], None, None
+        if kind == "cuda" and rank_rows is None and RC is None and self._use_shrink(p, n, X.shape[1], dev, comm):
+            for c in range(m):  # ShrinkingSolver has no label swap: one per machine
+                shr = C.ShrinkingSolver(p, comm, dev)
+                s = shr.setup(X, Ys[c])  # the whole-problem phases' solver; iteration "ws+shrinking"
+                a, info = shr.solve(ck, progress)
+                if c == 0:
+                    setup = s
+                    if m == 1:
+                        setup["engine_note"] = f"{info['shrink_phases']} shrinking phases: {info['phase_log']}"
+                alphas.append(a)
+                infos.append(dict(info))
+                del shr
+        elif kind == "cuda":
+            solver = C.GpuSolver(p, comm, dev)
+            setup = solver.setup(X, n, Ys[0])
+            if note:
+                en = setup.get("engine_note", "")
+                setup["engine_note"] = (en + "; " if en else "") + note
+            for c in range(m):
+                if c and k > 1:
+                    solver.set_labels(Ys[c])
+                if RC is not None:
+                    solver.set_row_C(RC[c])
+                a, info = solver.solve(ck, progress)
+                if hook is not None:
+                    hook(c, solver)
+                alphas.append(a)
+                infos.append(dict(info))
+        else:
+            if rank_rows is not None:
+                raise ValueError("partitioned X needs the GPU solver")
+            for c in range(m):
+                a, info = C.solve_cpu(X, Ys[c if k > 1 else 0], p, comm, ck, progress, None if RC is None else RC[c])
+                alphas.append(a)
+                infos.append(dict(info))
+        return alphas, infos, setup, solver if keep else None
+
     def fit(self, X, y, comm=None, resume=None, progress: Optional[Callable] = None,
             rank_rows: Optional[int] = None, sample_weight=None) -> "SVC":
         """Train.  ``comm``: a native communicator (see dpsvm_amd.parallel) for
         multi-rank training; ``resume``: checkpoint path or native Checkpoint;
         ``sample_weight``: per-row multipliers of C (with ``class_weight``)."""
-        C = load()
         if self.config.engines == "all" or self.config.host_cache_lines or self.config.cache_engine == "chain":
             load_quarantine()  # the quarantined pair-at-a-time cache engines (plugin)
         X = _as_f32_2d(X)
@@ -391,43 +425,15 @@ class SVC:
         if rank_rows is None and ys.shape[0] != n:
             raise ValueError("len(y) != X.shape[0]")
         cfg = self.config
-        p = cfg.to_native(d)
-        w = self._binary_weights(y1, ys, sample_weight)
-        row_C = note = None
-        if w is not None:  # any weights: the weighted path (no shortcut for all ones)
-            row_C = self._row_C(w, ys)
-            note = cfg.weighted_params(p, comm, resume, rank_rows)
+        p, RC, note = self._problem(d, y1, ys[None, :], sample_weight, comm, resume, rank_rows)
         if cfg.log_every and progress is None:
             def progress(it, bh, bl, el, hits, misses):  # noqa: E306
                 print(f"iter {it}  b_hi {bh:.6g}  b_lo {bl:.6g}  gap {bl - bh:.3g}  "
                       f"{it / max(el, 1e-9):.0f} it/s  hits {hits} misses {misses}", flush=True)
-        ck = None
-        if resume is not None:
-            ck = C.read_checkpoint(resume) if isinstance(resume, str) else resume
-        kind, dev = cfg.device_kind()
-        self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
         t0 = time.perf_counter()
-        if kind == "cuda" and rank_rows is None and row_C is None and self._use_shrink(p, n, d, dev, comm):
-            shr = C.ShrinkingSolver(p, comm, dev)
-            self.setup_info_ = shr.setup(X, ys)  # the whole-problem phases' solver; iteration "ws+shrinking"
-            alpha, info = shr.solve(ck, progress)
-            self.setup_info_["engine_note"] = f"{info['shrink_phases']} shrinking phases: {info['phase_log']}"
-            self._solver = None
-        elif kind == "cuda":
-            solver = C.GpuSolver(p, comm, dev)
-            self.setup_info_ = solver.setup(X, ys.shape[0], ys)
-            if row_C is not None:
-                solver.set_row_C(row_C)
-                en = self.setup_info_.get("engine_note", "")
-                self.setup_info_["engine_note"] = (en + "; " if en else "") + note
-            alpha, info = solver.solve(ck, progress)
-            self._solver = solver
-        else:
-            if rank_rows is not None:
-                raise ValueError("partitioned X needs the GPU solver")
-            alpha, info = C.solve_cpu(X, ys, p, comm, ck, progress, row_C)
-            self._solver = None
-        self.wall_time_ = time.perf_counter() - t0
+        (alpha,), (info,), setup, self._solver = self._solve_machines(X, ys[None, :], RC, p, note, comm, resume,
+                                                                      progress, rank_rows, keep=True)
+        self._publish(p, d, time.perf_counter() - t0, setup)
         self.alpha_ = alpha
         self.b_ = float(info["b"])
         self.intercept_ = -self.b_
@@ -437,8 +443,8 @@ class SVC:
         self.converged_ = bool(info["converged"])
         self.fit_time_ = float(info["t_solve"])
         self.setup_time_ = float(info["t_setup"])
-        self.stats_ = dict(info)
-        self.row_C_ = row_C
+        self.stats_ = info
+        self.row_C_ = row_C = None if RC is None else RC[0]
         bound = row_C if row_C is not None else np.float32(cfg.C)
         self.n_bounded_ = int(np.sum((alpha == bound) & (alpha > 0))) if rank_rows is None else None
         if self.status_ == 2 and self.n_rounds_ > 0:
@@ -448,98 +454,42 @@ class SVC:
                           "working-set model differs from the reference's pair-at-a-time iterate at the same cap; "
                           "raise max_iter to converge, or solver='smo' for the reference's trajectory (engines='all' "
                           "when the Gram is not resident)", RuntimeWarning, stacklevel=2)
-        self.gamma_ = p.gamma
-        self.n_features_in_ = d
         self._X_train, self._y_train = (X, ys) if rank_rows is None else (None, None)
         if rank_rows is None:
             self.support_ = np.nonzero(alpha > 0)[0]
             self.support_vectors_ = X[self.support_]
             self.dual_coef_ = (alpha[self.support_] * ys[self.support_]).astype(np.float32)
             self.n_support_ = int(len(self.support_))
-        self._model = None
-        self._gpu_pred = None
         return self
 
-    def _multi_weights(self, y: np.ndarray, classes: np.ndarray, sample_weight) -> Optional[np.ndarray]:
-        """(k, n) row weights of the one-vs-rest machines, None without any"""
-        cw = self.config.class_weight
-        if cw is None and sample_weight is None:
-            return None
-        n, k = len(y), len(classes)
-        w = self._sample_weight(sample_weight, n)
-        W = np.tile(w, (k, 1))
-        if cw is None:
-            return W
-        if isinstance(cw, str):
-            if cw != "balanced":
-                raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
-            for c in range(k):  # each machine's two sides
-                n_c = int(np.sum(y == classes[c]))
-                W[c] *= np.where(y == classes[c], n / (2.0 * n_c), n / (2.0 * (n - n_c)))
-            return W
-        if isinstance(cw, dict):
-            return W * self._class_dict(cw, y)[None, :]  # a row's own label, in every machine
-        raise ValueError(f"class_weight must be None, 'balanced' or a dict (got {cw!r})")
+    def _publish(self, p, d: int, wall: float, setup) -> None:
+        """the fitted attributes that do not depend on the number of machines"""
+        kind, dev = self.config.device_kind()
+        self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
+        self.wall_time_ = wall
+        if setup is not None:
+            self.setup_info_ = setup
+        self.gamma_ = p.gamma
+        self.n_features_in_ = d
+        self._model = None
+        self._gpu_pred = None
 
     def _fit_multi(self, X: np.ndarray, y: np.ndarray, comm, resume, progress, rank_rows,
                    sample_weight=None) -> "SVC":
-        """One-vs-rest: k machines on one X.  On the GPU one solver — setup()
-        (X upload, norms, operand prep, engine choice) once, the resident Gram
-        built by machine 0's solve and kept by the label swaps after it."""
+        """One-vs-rest: k machines on one X, the GpuSolver dropped (with its resident Gram) after the last."""
         for name, val in (("comm", comm), ("resume", resume), ("rank_rows", rank_rows)):
             if val is not None:
                 raise NotImplementedError(f"multi-class (one-vs-rest) training runs on one rank from a cold start: "
                                           f"{name} is only supported with two classes")
-        C = load()
         n, d = X.shape
         if y.shape[0] != n:
             raise ValueError("len(y) != X.shape[0]")
-        cfg = self.config
-        p = cfg.to_native(d)
         classes = np.unique(y)
-        k = len(classes)
         Ys = np.stack([np.where(y == c, 1.0, -1.0).astype(np.float32) for c in classes])
-        W = self._multi_weights(y, classes, sample_weight)
-        RC = note = None
-        if W is not None:
-            RC = np.stack([self._row_C(W[c], Ys[c]) for c in range(k)])
-            note = cfg.weighted_params(p)
-        kind, dev = cfg.device_kind()
-        self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
+        p, RC, note = self._problem(d, y, Ys, sample_weight)
         t0 = time.perf_counter()
-        alphas, infos = [], []
-        self._solver = None
-        if kind == "cuda" and RC is None and self._use_shrink(p, n, d, dev, None):
-            for c in range(k):  # ShrinkingSolver has no label swap: one per machine
-                shr = C.ShrinkingSolver(p, None, dev)
-                setup = shr.setup(X, Ys[c])
-                if c == 0:
-                    self.setup_info_ = setup
-                a, info = shr.solve(None, progress)
-                alphas.append(a)
-                infos.append(dict(info))
-                del shr
-        elif kind == "cuda":
-            solver = C.GpuSolver(p, None, dev)
-            self.setup_info_ = solver.setup(X, n, Ys[0])
-            if RC is not None:
-                en = self.setup_info_.get("engine_note", "")
-                self.setup_info_["engine_note"] = (en + "; " if en else "") + note
-            for c in range(k):
-                if c:
-                    solver.set_labels(Ys[c])
-                if RC is not None:
-                    solver.set_row_C(RC[c])
-                a, info = solver.solve(None, progress)
-                alphas.append(a)
-                infos.append(dict(info))
-            del solver  # the resident Gram is not held past fit
-        else:
-            for c in range(k):
-                a, info = C.solve_cpu(X, Ys[c], p, None, None, progress, None if RC is None else RC[c])
-                alphas.append(a)
-                infos.append(dict(info))
-        self.wall_time_ = time.perf_counter() - t0
+        alphas, infos, setup, self._solver = self._solve_machines(X, Ys, RC, p, note, progress=progress)
+        self._publish(p, d, time.perf_counter() - t0, setup)
         self._multi = True
         self.classes_ = classes
         self.alpha_ = np.stack(alphas).astype(np.float32)
@@ -553,22 +503,18 @@ class SVC:
         self.setup_time_ = float(infos[0]["t_setup"])
         self.stats_ = infos
         self.row_C_ = RC
-        bound = RC if RC is not None else np.float32(cfg.C)
+        bound = RC if RC is not None else np.float32(self.config.C)
         self.n_bounded_ = int(np.sum((self.alpha_ == bound) & (self.alpha_ > 0)))
         if any(i["status"] == 2 and i.get("outer", 0) > 0 for i in infos):
             import warnings
 
             warnings.warn("a one-vs-rest machine stopped at max_iter before its gap closed: raise max_iter to "
                           "converge", RuntimeWarning, stacklevel=3)
-        self.gamma_ = p.gamma
-        self.n_features_in_ = d
         self._X_train, self._y_train, self._Ys = X, y, Ys
         self.support_ = np.nonzero((self.alpha_ > 0).any(axis=0))[0]
         self.support_vectors_ = X[self.support_]
         self.dual_coef_ = (self.alpha_[:, self.support_] * Ys[:, self.support_]).astype(np.float32)
         self.n_support_ = int(len(self.support_))
-        self._model = None
-        self._gpu_pred = None
         return self
 
     # ------------------------------------------------------------------ cross-validation
@@ -597,38 +543,30 @@ class SVC:
         n, d = X.shape
         if ys.shape[0] != n:
             raise ValueError("len(y) != X.shape[0]")
-        cfg = self.config
-        p = cfg.to_native(d)
-        w = self._binary_weights(y1, ys, sample_weight)
-        if w is None:
-            w = np.ones(n, dtype=np.float64)
-        cfg.weighted_params(p)
+        p = self.config.to_native(d)
+        W = self._weights(y1, ys[None, :], sample_weight)
+        w = np.ones(n, dtype=np.float64) if W is None else W[0]
+        self.config.weighted_params(p)
         folds = self.cv_folds(n, cv, seed)
         rcs = []
         for fold in folds:
             wf = w.copy()
             wf[fold] = 0.0
             rcs.append(self._row_C(wf, ys))
-        kind, dev = cfg.device_kind()
-        dec = np.zeros(n, dtype=np.float32)
-        stats = []
+        grads = []  # the GPU solves' gradients: cold solves (alpha = 0, f = -y)
         t0 = time.perf_counter()
-        if kind == "cuda":
-            solver = C.GpuSolver(p, None, dev)
-            self.cv_setup_info_ = solver.setup(X, n, ys)
-            for fold, rc in zip(folds, rcs):
-                solver.set_row_C(rc)
-                _, info = solver.solve(None, None)  # cold: alpha = 0, f = -y
-                g = solver.gradient()
-                dec[fold] = (g[fold].astype(np.float64) + ys[fold] - float(info["b"])).astype(np.float32)
-                stats.append(dict(info))
-            del solver
-        else:
-            for fold, rc in zip(folds, rcs):
-                alpha, info = C.solve_cpu(X, ys, p, None, None, None, rc)
-                model = C.make_model(X, ys, alpha, float(info["b"]), p.gamma)
+        alphas, stats, setup, _ = self._solve_machines(X, ys[None, :], np.stack(rcs), p,
+                                                       hook=lambda c, solver: grads.append(solver.gradient()))
+        dec = np.zeros(n, dtype=np.float32)
+        for c, fold in enumerate(folds):
+            b = float(stats[c]["b"])
+            if grads:
+                dec[fold] = (grads[c][fold].astype(np.float64) + ys[fold] - b).astype(np.float32)
+            else:
+                model = C.make_model(X, ys, alphas[c], b, p.gamma)
                 dec[fold] = C.decision_cpu(model, np.ascontiguousarray(X[fold]), 0)
-                stats.append(dict(info))
+        if setup is not None:
+            self.cv_setup_info_ = setup
         self.cv_wall_time_ = time.perf_counter() - t0
         self.cv_stats_ = stats
         self.cv_folds_ = folds
@@ -715,12 +653,14 @@ class SVC:
         return dataclasses.asdict(self.config)
 
 
-class LoadedModel:
-    """A model read from a reference-format file (svmTest path)."""
+class _Loaded:
+    """What the loaded models share: the device, the GpuPredictor built on first use, the model's scalars."""
 
     def __init__(self, model, device: str = "auto"):
         self.model = model
         self.device = device
+        if device != "auto":
+            _parse_device(device)  # an unknown string fails here, not at the first prediction
         self._gpu = None
 
     @property
@@ -728,22 +668,28 @@ class LoadedModel:
         return self.model.gamma
 
     @property
-    def b(self) -> float:
+    def b(self):
         return self.model.b
 
     @property
     def n_support(self) -> int:
         return self.model.nsv
 
+    def _predictor(self):
+        """the device predictor, None on the CPU"""
+        kind, dev = _parse_device(self.device)
+        if kind == "cuda" and self._gpu is None:
+            self._gpu = load().GpuPredictor(self.model, dev)
+        return self._gpu
+
+
+class LoadedModel(_Loaded):
+    """A model read from a reference-format file (svmTest path)."""
+
     def decision_function(self, X) -> np.ndarray:
         X = _as_f32_2d(X)
-        use_gpu = self.device.startswith("cuda") or (self.device == "auto" and gpu_available())
-        if use_gpu:
-            if self._gpu is None:
-                dev = int(self.device.split(":")[1]) if ":" in self.device else 0
-                self._gpu = load().GpuPredictor(self.model, dev)
-            return self._gpu.decision(X)
-        return load().decision_cpu(self.model, X, 0)
+        gp = self._predictor()
+        return gp.decision(X) if gp is not None else load().decision_cpu(self.model, X, 0)
 
     def predict(self, X) -> np.ndarray:
         return np.where(self.decision_function(X) < 0, -1.0, 1.0).astype(np.float32)
@@ -752,36 +698,17 @@ class LoadedModel:
         return float(np.mean(self.predict(X) == np.where(_as_1d(y) > 0, 1.0, -1.0)))
 
 
-class LoadedMultiModel:
+class LoadedMultiModel(_Loaded):
     """A one-vs-rest model read from a multi-class model file."""
 
     def __init__(self, model, device: str = "auto"):
-        self.model = model
-        self.device = device
+        super().__init__(model, device)
         self.classes_ = np.asarray(model.classes)
-        self._gpu = None
-
-    @property
-    def gamma(self) -> float:
-        return self.model.gamma
-
-    @property
-    def b(self) -> np.ndarray:
-        return self.model.b
-
-    @property
-    def n_support(self) -> int:
-        return self.model.nsv
 
     def decision_function(self, X) -> np.ndarray:
         X = _as_f32_2d(X)
-        use_gpu = self.device.startswith("cuda") or (self.device == "auto" and gpu_available())
-        if use_gpu:
-            if self._gpu is None:
-                dev = int(self.device.split(":")[1]) if ":" in self.device else 0
-                self._gpu = load().GpuPredictor(self.model, dev)
-            return self._gpu.decision_multi(X)
-        return load().decision_multi_cpu(self.model, X, 0)
+        gp = self._predictor()
+        return gp.decision_multi(X) if gp is not None else load().decision_multi_cpu(self.model, X, 0)
 
     def predict(self, X) -> np.ndarray:
         return self.classes_[np.argmax(self.decision_function(X), axis=1)]

@@ -311,6 +311,48 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               int p_round, int p_act, int q_max, float C, int64_t outer, int ks = 0,
                               int reps = 0, bool wide = false,
                               const std::vector<float>& row_C = {});  // [n] per-row bounds (empty: scalar C)
+// The one-block merge (ws_merge.hpp) through the two round kernels that run it
+// in every workgroup, one launch each: round `outer` builds parity outer & 1
+// from cand = [G][2][kWsCand] lists (the merge reads the first kWsCand1 keys a
+// side) and the previous set (newest first, parity (outer & 1) ^ 1).  subg /
+// aux / idx are filled with a sentinel (NaN / -1) before the launch; n_apply
+// starts at kWsProbeApply, so a stop shows as 0.
+//   ws_gather_probe         dense: the sub-Gram rows from gram [n][ldg]
+//   ws_subgram_split_probe  recompute rounds: the sub-Gram tiles from x [n][d]
+//                           (padded to pad_features(d) <= 64 columns, |x|^2 by
+//                           row_sqnorm, operands by split_rows_f16: the solver's)
+constexpr int kWsProbeApply = 7;
+struct WsGatherProbe {
+  int done = 0, q = 0, n_apply = 0;
+  float b_hi = 0.f, b_lo = 0.f;
+  std::vector<int32_t> idx;  // [q] the set, newest first
+  std::vector<float> subg;   // [q_max][q_max]
+  std::vector<float> aux;    // [3][kWsMax] f / alpha / y of the set
+};
+WsGatherProbe ws_gather_probe(const std::vector<float>& gram, int64_t n, int64_t ldg, const std::vector<uint64_t>& cand,
+                              const std::vector<int32_t>& prev_set, const std::vector<float>& f,
+                              const std::vector<float>& alpha, const std::vector<float>& y, int q_max, int n_new,
+                              float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer);
+WsGatherProbe ws_subgram_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<uint64_t>& cand,
+                                     const std::vector<int32_t>& prev_set, const std::vector<float>& f,
+                                     const std::vector<float>& alpha, const std::vector<float>& y, float gamma,
+                                     int q_max, int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite,
+                                     int64_t outer);
+// ws_fupdate_split: the recompute rounds' selection pass, one launch on x [n][d]
+// (operands as above) with the apply list of a round (rows, coefficients) and
+// the run's state `done`; cand is prefilled with kWsProbeKey (neither a key of
+// a row < 2^31 nor kKeyNone)
+constexpr uint64_t kWsProbeKey = 0xABCDABCDFFFFFFFFull;
+struct WsFupdateProbe {
+  std::vector<float> f;
+  std::vector<uint64_t> cand;  // [G][2][kWsCand]
+  int nonfinite = 0, G = 0, rpt = 0;
+  int64_t rows_computed = 0;
+};
+WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<float>& f,
+                                      const std::vector<float>& alpha, const std::vector<float>& y,
+                                      const std::vector<int32_t>& apply_idx, const std::vector<float>& apply_coef,
+                                      float gamma, float C, int done);
 }  // namespace kernels
 
 int device_count();

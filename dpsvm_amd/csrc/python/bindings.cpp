@@ -820,6 +820,53 @@ PYBIND11_MODULE(_C, m) {
         py::arg("lines"), py::arg("coef"), py::arg("nab"), py::arg("blocks"), py::arg("p_round"), py::arg("p_act"),
         py::arg("q_max"), py::arg("C"), py::arg("outer"), py::arg("ks") = 0, py::arg("reps") = 0,
         py::arg("wide") = false, py::arg("row_C") = py::none());
+  auto vu = [](const U64& a) { return std::vector<uint64_t>(a.data(), a.data() + a.size()); };
+  auto gather_dict = [](const kernels::WsGatherProbe& r) {
+    py::dict d;
+    d["done"] = r.done;
+    d["q"] = r.q;
+    d["idx"] = r.idx;
+    d["b_hi"] = r.b_hi;
+    d["b_lo"] = r.b_lo;
+    d["n_apply"] = r.n_apply;
+    d["subg"] = to_np(r.subg);
+    d["aux"] = to_np(r.aux);
+    return d;
+  };
+  m.def("k_ws_gather", [vi, vu, gather_dict](const F32& gram, int64_t n, int64_t ldg, const U64& cand, const I32& prev,
+                                             const F32& f, const F32& alpha, const F32& y, int q_max, int n_new,
+                                             float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer) {
+    return gather_dict(kernels::ws_gather_probe(from_np(gram), n, ldg, vu(cand), vi(prev), from_np(f), from_np(alpha),
+                                                from_np(y), q_max, n_new, eps, iter, max_iter, nonfinite, outer));
+  }, py::arg("gram"), py::arg("n"), py::arg("ldg"), py::arg("cand"), py::arg("prev"), py::arg("f"), py::arg("alpha"),
+        py::arg("y"), py::arg("q_max"), py::arg("n_new"), py::arg("eps"), py::arg("iter"), py::arg("max_iter"),
+        py::arg("nonfinite"), py::arg("outer"));
+  m.def("k_ws_subgram_split", [vi, vu, gather_dict](const F32& x, int64_t n, int d, const U64& cand, const I32& prev,
+                                                    const F32& f, const F32& alpha, const F32& y, float gamma,
+                                                    int q_max, int n_new, float eps, int64_t iter, int64_t max_iter,
+                                                    int nonfinite, int64_t outer) {
+    return gather_dict(kernels::ws_subgram_split_probe(from_np(x), n, d, vu(cand), vi(prev), from_np(f),
+                                                       from_np(alpha), from_np(y), gamma, q_max, n_new, eps, iter,
+                                                       max_iter, nonfinite, outer));
+  }, py::arg("x"), py::arg("n"), py::arg("d"), py::arg("cand"), py::arg("prev"), py::arg("f"), py::arg("alpha"),
+        py::arg("y"), py::arg("gamma"), py::arg("q_max"), py::arg("n_new"), py::arg("eps"), py::arg("iter"),
+        py::arg("max_iter"), py::arg("nonfinite"), py::arg("outer"));
+  m.def("k_ws_fupdate_split", [vi](const F32& x, int64_t n, int d, const F32& f, const F32& alpha, const F32& y,
+                                   const I32& apply_idx, const F32& apply_coef, float gamma, float C, int done) {
+    const auto r = kernels::ws_fupdate_split_probe(from_np(x), n, d, from_np(f), from_np(alpha), from_np(y),
+                                                   vi(apply_idx), from_np(apply_coef), gamma, C, done);
+    py::dict d_;
+    d_["f"] = to_np(r.f);
+    d_["cand"] = r.cand;
+    d_["nonfinite"] = r.nonfinite;
+    d_["rows_computed"] = r.rows_computed;
+    d_["G"] = r.G;
+    d_["rpt"] = r.rpt;
+    return d_;
+  }, py::arg("x"), py::arg("n"), py::arg("d"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("apply_idx"),
+        py::arg("apply_coef"), py::arg("gamma"), py::arg("C"), py::arg("done"));
+  m.attr("kWsProbeKey") = kernels::kWsProbeKey;
+  m.attr("kWsProbeApply") = kernels::kWsProbeApply;
   m.def("production_line_cap", &production_line_cap, py::arg("cache_lines"), py::arg("ws_size"),
         py::arg("engines") = 0, "-s N on the engines a setup may choose (device_state.hpp)");
   m.def("ws_cache_min_lines", &ws_cache_min_lines, py::arg("ws_size"));

@@ -1,10 +1,24 @@
 // Kernel-level test entry points of the working-set engine (ws_*.hip): each
 // runs ONE kernel (or the two f-update passes) on crafted device state and
-// returns the state it leaves, so tests/test_kernels_gpu.py can check the
+// returns the state it leaves, so tests/test_ws_kernels_gpu.py can check the
 // merge (sort, stop test, union, block assignment), the LDS pair loop and the
 // line-search f update against float64 numpy models of the same rules —
 // independently of the end-to-end solves (tests/test_ws_gpu.py), where one
 // kernel's bug could hide behind another's.
+//
+//   ws_merge_multi_probe    ws_rank_merge: the multi-block merge (sort, stop test, union, block layout)
+//   ws_solve_probe          ws_solve: the LDS pair loop, one or P blocks
+//   ws_select_probe         ws_select: the f update and candidate lists (one pass; two passes with the line
+//                           search; list slices; the wide pass 1)
+//   ws_gather_probe         ws_gather, dense, one block: the one-block merge of ws_merge.hpp (lists folded
+//                           four to a thread, stop codes, radix threshold, class order, dedup, previous-set
+//                           retention) and the sub-Gram rows / aux gathered from a resident Gram
+//   ws_subgram_split_probe  ws_subgram_split: the same merge, and the sub-Gram tiles computed from the split X
+//                           rows — the resident split Gram's bits, zeros in the columns past q
+//   ws_fupdate_split_probe  ws_fupdate_split: the recompute rounds' selection pass — f in the documented
+//                           summation order over the split Gram's bits, the candidate lists, the stop states
+// (tests/test_ws_kernels_gpu.py the first three, tests/test_ws_recompute_kernels_gpu.py the last three.)  A
+// probe checks its arguments before it launches: a malformed call raises.
 //
 // Reference rules: the I-set classification and selection functors
 // (svmTrain.cu:41-95, 400-467), the pair update and clipping
@@ -12,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <limits>
 
 #include "gpu_impl.hpp"
 
@@ -301,6 +316,203 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   r.n_damped = o.n_damped;
   r.p1_round = o.p1_round;
   r.nonfinite = o.nonfinite;
+  return r;
+}
+
+namespace {
+
+// x [n][d] as the solver holds it: rows of pad_features(d) floats (zero
+// padded), |x|^2 by row_sqnorm, the split GEMMs' operands by split_rows_f16
+struct SplitX {
+  int dp = 0;
+  float* xsq = nullptr;
+  void* xs = nullptr;
+  int32_t* xsh = nullptr;
+  SplitX(Stream& st, const std::vector<float>& x, int64_t n, int d) {
+    dp = pad_features(d);
+    const int64_t pr = launch::split_pad_rows(n);
+    std::vector<float> xp((size_t)n * dp, 0.f);
+    for (int64_t i = 0; i < n; ++i) std::copy(x.begin() + i * d, x.begin() + (i + 1) * d, xp.begin() + i * dp);
+    const float* xd = st.up(xp, (size_t)pr * dp);
+    HIP_CHECK(hipStreamSynchronize(st.s));  // xp leaves scope
+    xsq = st.up(std::vector<float>(), (size_t)pr);
+    xs = st.up(std::vector<uint8_t>(), (size_t)pr * launch::split_row_u4(dp) * 16);
+    xsh = st.up(std::vector<int32_t>(), (size_t)pr);
+    launch::row_sqnorm(xd, n, dp, dp, xsq, st.s);
+    launch::split_rows_f16(xd, n, dp, dp, xs, xsh, st.s);
+  }
+};
+
+void check_split_x(const std::vector<float>& x, int64_t n, int d) {
+  DPSVM_CHECK(n >= 1 && n < ((int64_t)1 << 31) && d >= 1 && (int64_t)x.size() == n * d, "ws probe: x must be [n][d]");
+  DPSVM_CHECK(pad_features(d) <= 64, "ws probe: the recompute kernels take dp <= 64");
+}
+
+// the crafted state of one one-block merge: every row the merge can pick must
+// be a row of the problem (the kernels read f / alpha / y / Gram / X at it)
+void check_merge_state(int64_t n, const std::vector<uint64_t>& cand, const std::vector<int32_t>& prev_set,
+                       const std::vector<float>& f, const std::vector<float>& alpha, const std::vector<float>& y,
+                       int q_max, int n_new, int nonfinite) {
+  DPSVM_CHECK(n >= 1 && n < ((int64_t)1 << 31) && (int64_t)f.size() == n && (int64_t)alpha.size() == n &&
+                  (int64_t)y.size() == n,
+              "ws merge probe: f / alpha / y of n rows");
+  DPSVM_CHECK(q_max >= 2 && q_max <= kWsMax && n_new >= 1 && (nonfinite == 0 || nonfinite == 1),
+              "ws merge probe: 2 <= q_max <= 192, n_new >= 1, nonfinite 0 / 1");
+  const int64_t G = (int64_t)cand.size() / (2 * kWsCand);
+  DPSVM_CHECK(G >= 1 && G <= (int64_t)kWsMaxGroups * kWsListsPerThread && (int64_t)cand.size() == G * 2 * kWsCand,
+              "ws merge probe: cand must be [G][2][kWsCand = 16] with G <= 1024");
+  DPSVM_CHECK((int64_t)prev_set.size() <= q_max, "ws merge probe: previous set longer than q_max");
+  for (int32_t r : prev_set) DPSVM_CHECK(r >= 0 && r < n, "ws merge probe: previous-set row out of range");
+  for (int64_t l = 0; l < 2 * G; ++l)
+    for (int r = 0; r < kWsCand1; ++r) {
+      const uint64_t k = cand[(size_t)l * kWsCand + r];
+      DPSVM_CHECK(k == kKeyNone || (int64_t)key_index(k) < n, "ws merge probe: candidate row out of range");
+    }
+}
+
+// control record and arguments of round `outer` of a one-block engine
+struct MergeRound {
+  WsCtrl* dc = nullptr;
+  WsArgs a{};
+  MergeRound(Stream& st, int64_t n, const std::vector<uint64_t>& cand, const std::vector<int32_t>& prev_set,
+             const std::vector<float>& f, const std::vector<float>& alpha, const std::vector<float>& y, int q_max,
+             int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer) {
+    auto c = blank_ctrl();
+    const int par = (int)(outer & 1);
+    c->outer = outer;
+    c->iter = iter;
+    c->nonfinite = nonfinite;
+    c->n_apply = kWsProbeApply;
+    c->q[par ^ 1] = (int32_t)prev_set.size();
+    for (size_t i = 0; i < prev_set.size(); ++i) c->idx[par ^ 1][i] = prev_set[i];
+    for (int i = 0; i < kWsMaxAll; ++i) c->idx[par][i] = -1;
+    std::vector<WsCtrl> hc(1);
+    memcpy(&hc[0], c.get(), sizeof(WsCtrl));
+    dc = st.up(hc, 1);
+    HIP_CHECK(hipStreamSynchronize(st.s));  // hc leaves scope
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    float* sub = st.up(std::vector<float>((size_t)q_max * q_max + 3 * kWsMax, nan), (size_t)q_max * q_max + 3 * kWsMax);
+    a.ctrl = dc;
+    a.cand = a.cand_out = st.up(cand, cand.size());
+    a.G = a.G_all = (int32_t)(cand.size() / (2 * kWsCand));
+    a.rpt = 1;
+    a.f = st.up(f, (size_t)n);
+    a.alpha = st.up(alpha, (size_t)n);
+    a.y = st.up(y, (size_t)n);
+    a.n = a.nl = n;
+    a.off = 0;
+    a.world = 1;
+    a.blocks = 1;
+    a.q_max = q_max;
+    a.n_new = n_new;
+    a.eps = eps;
+    a.max_iter = max_iter;
+    a.subg = sub;
+    a.aux = sub + (size_t)q_max * q_max;
+    a.aux_stride = kWsMax;
+  }
+  WsGatherProbe result(Stream& st, int64_t outer) const {
+    const WsCtrl o = download(dc, 1, st.s)[0];
+    const int par = (int)(outer & 1);
+    WsGatherProbe r;
+    r.done = o.done;
+    r.n_apply = o.n_apply;
+    r.b_hi = o.b_hi;
+    r.b_lo = o.b_lo;
+    r.q = o.q[par];
+    r.idx.assign(o.idx[par], o.idx[par] + std::max(0, std::min(r.q, (int)kWsMax)));
+    r.subg = download(a.subg, (size_t)a.q_max * a.q_max, st.s);
+    r.aux = download(a.aux, (size_t)3 * kWsMax, st.s);
+    return r;
+  }
+};
+
+}  // namespace
+
+WsGatherProbe ws_gather_probe(const std::vector<float>& gram, int64_t n, int64_t ldg, const std::vector<uint64_t>& cand,
+                              const std::vector<int32_t>& prev_set, const std::vector<float>& f,
+                              const std::vector<float>& alpha, const std::vector<float>& y, int q_max, int n_new,
+                              float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer) {
+  check_merge_state(n, cand, prev_set, f, alpha, y, q_max, n_new, nonfinite);
+  DPSVM_CHECK(ldg >= n && (int64_t)gram.size() == n * ldg && outer >= 0, "ws_gather_probe: gram [n][ldg >= n]");
+  Stream st;
+  MergeRound m(st, n, cand, prev_set, f, alpha, y, q_max, n_new, eps, iter, max_iter, nonfinite, outer);
+  m.a.gram = st.up(gram, gram.size());
+  m.a.ldg = ldg;
+  launch::ws_gather(m.a, st.s);  // dense, one block: ws_gather_kernel
+  return m.result(st, outer);
+}
+
+WsGatherProbe ws_subgram_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<uint64_t>& cand,
+                                     const std::vector<int32_t>& prev_set, const std::vector<float>& f,
+                                     const std::vector<float>& alpha, const std::vector<float>& y, float gamma,
+                                     int q_max, int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite,
+                                     int64_t outer) {
+  check_split_x(x, n, d);
+  check_merge_state(n, cand, prev_set, f, alpha, y, q_max, n_new, nonfinite);
+  DPSVM_CHECK(outer >= 0, "ws_subgram_split_probe: outer >= 0");
+  Stream st;
+  SplitX sx(st, x, n, d);
+  MergeRound m(st, n, cand, prev_set, f, alpha, y, q_max, n_new, eps, iter, max_iter, nonfinite, outer);
+  DPSVM_CHECK(launch::ws_recompute_supported(m.a, sx.dp), "ws_subgram_split_probe: shape not supported");
+  launch::ws_subgram_split(m.a, sx.xs, sx.xsh, sx.xsq, sx.dp, gamma, st.s);
+  return m.result(st, outer);
+}
+
+WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<float>& f,
+                                      const std::vector<float>& alpha, const std::vector<float>& y,
+                                      const std::vector<int32_t>& apply_idx, const std::vector<float>& apply_coef,
+                                      float gamma, float C, int done) {
+  check_split_x(x, n, d);
+  DPSVM_CHECK((int64_t)f.size() == n && (int64_t)alpha.size() == n && (int64_t)y.size() == n,
+              "ws_fupdate_split_probe: f / alpha / y of n rows");
+  DPSVM_CHECK(apply_idx.size() == apply_coef.size() && apply_idx.size() <= (size_t)kWsMax,
+              "ws_fupdate_split_probe: <= 192 apply rows, a coefficient each");
+  for (int32_t r : apply_idx) DPSVM_CHECK(r >= 0 && r < n, "ws_fupdate_split_probe: apply row out of range");
+  DPSVM_CHECK(done >= kRunning && done <= kCommFail, "ws_fupdate_split_probe: done is a DoneCode");
+  int32_t G = 0, rpt = 0;
+  launch::ws_geometry(n, 1, &G, &rpt);
+  DPSVM_CHECK(rpt <= kWsMaxRPT, "ws_fupdate_split_probe: too many rows");
+  Stream st;
+  SplitX sx(st, x, n, d);
+  auto c = blank_ctrl();
+  c->outer = 1;
+  c->done = done;
+  c->n_apply = (int32_t)apply_idx.size();
+  // past the list: what an earlier, longer round left there (the kernel pads the
+  // list to a multiple of 32 rows and must give the padding a zero coefficient)
+  for (int k = 0; k < kWsMax; ++k) c->apply_coef[k] = 3.f;
+  for (size_t k = 0; k < apply_idx.size(); ++k) {
+    c->apply_idx[k] = c->apply_line[k] = apply_idx[k];
+    c->apply_coef[k] = apply_coef[k];
+  }
+  std::vector<WsCtrl> hc(1);
+  memcpy(&hc[0], c.get(), sizeof(WsCtrl));
+  WsArgs a{};
+  a.ctrl = st.up(hc, 1);
+  a.f = st.up(f, (size_t)n);
+  a.alpha = st.up(alpha, (size_t)n);
+  a.y = st.up(y, (size_t)n);
+  const size_t nc = (size_t)G * 2 * kWsCand;
+  a.cand = a.cand_out = st.up(std::vector<uint64_t>(nc, kWsProbeKey), nc);
+  a.n = a.nl = n;
+  a.off = 0;
+  a.G = a.G_all = G;
+  a.rpt = rpt;
+  a.world = 1;
+  a.blocks = 1;
+  a.q_max = kWsMax;
+  a.C = C;
+  DPSVM_CHECK(launch::ws_recompute_supported(a, sx.dp), "ws_fupdate_split_probe: shape not supported");
+  launch::ws_fupdate_split(a, sx.xs, sx.xsh, sx.xsq, sx.dp, gamma, st.s);
+  const WsCtrl o = download(a.ctrl, 1, st.s)[0];
+  WsFupdateProbe r;
+  r.f = download(a.f, (size_t)n, st.s);
+  r.cand = download(a.cand_out, nc, st.s);
+  r.nonfinite = o.nonfinite;
+  r.rows_computed = o.rows_computed;
+  r.G = G;
+  r.rpt = rpt;
   return r;
 }
 

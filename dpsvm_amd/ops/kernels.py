@@ -291,6 +291,73 @@ def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float
                               row_C=None if row_C is None else f32(row_C))
 
 
+def _merge_round_args(cand, prev_set, f, alpha, y):
+    import numpy as np
+
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32)).reshape(-1)  # noqa: E731
+    c = np.ascontiguousarray(np.asarray(cand, dtype=np.uint64).reshape(-1, 2, WS_CAND))
+    return c.reshape(-1), np.asarray(list(prev_set), dtype=np.int32), f32(f), f32(alpha), f32(y)
+
+
+def _merge_round_result(r: dict, q_max: int) -> dict:
+    r["subg"] = r["subg"].reshape(q_max, q_max)
+    r["aux"] = r["aux"].reshape(3, -1)
+    return r
+
+
+def ws_gather(gram, cand, prev_set, f, alpha, y, q_max: int, n_new: int, eps: float, iteration: int = 0,
+              max_iter: int = 1 << 40, nonfinite: int = 0, outer: int = 1) -> dict:
+    """One launch of the dense one-block round's first kernel (ws_gather_kernel:
+    the one-block merge of ws_merge.hpp in each of q_max workgroups, then one
+    sub-Gram row each) on crafted lists ``cand`` [G][2][WS_CAND] (the merge reads
+    the first 4 keys a side), the previous set (newest first) and a resident
+    ``gram`` [n][ldg >= n].  subg / aux / idx hold a sentinel (NaN / -1) before
+    the launch.  Returns done, q, idx[:q], b_hi, b_lo, n_apply (kWsProbeApply
+    before the launch: a stop sets 0), subg [q_max][q_max], aux [3][192]."""
+    import numpy as np
+
+    g = np.ascontiguousarray(np.asarray(gram, dtype=np.float32))
+    c, prev, f_, a_, y_ = _merge_round_args(cand, prev_set, f, alpha, y)
+    r = load().k_ws_gather(g.reshape(-1), g.shape[0], g.shape[1], c, prev, f_, a_, y_, int(q_max), int(n_new),
+                           float(eps), int(iteration), int(max_iter), int(nonfinite), int(outer))
+    return _merge_round_result(r, q_max)
+
+
+def ws_subgram_split(x, cand, prev_set, f, alpha, y, gamma: float, q_max: int, n_new: int, eps: float,
+                     iteration: int = 0, max_iter: int = 1 << 40, nonfinite: int = 0, outer: int = 1) -> dict:
+    """One launch of the recompute round's first kernel (ws_subgram_split_kernel:
+    the same merge, then 64 x 64 tiles of the sub-Gram from the members' split X
+    rows) on the state ws_gather takes, with ``x`` [n][d] (d <= 64 padded; |x|^2
+    and the split operands are built as the solver builds them) in place of the
+    Gram.  Returns ws_gather's fields."""
+    import numpy as np
+
+    xx = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+    c, prev, f_, a_, y_ = _merge_round_args(cand, prev_set, f, alpha, y)
+    r = load().k_ws_subgram_split(xx.reshape(-1), xx.shape[0], xx.shape[1], c, prev, f_, a_, y_, float(gamma),
+                                  int(q_max), int(n_new), float(eps), int(iteration), int(max_iter), int(nonfinite),
+                                  int(outer))
+    return _merge_round_result(r, q_max)
+
+
+def ws_fupdate_split(x, f, alpha, y, apply_idx, apply_coef, gamma: float, C_: float, done: int = 0) -> dict:
+    """One launch of the recompute round's selection pass (ws_fupdate_split_kernel)
+    on ``x`` [n][d] (d <= 64 padded): f_j += sum_k apply_coef[k] K(apply_idx[k], j)
+    with the kernel rows recomputed, then each selection group's candidate lists.
+    ``done``: the run's DoneCode when the pass starts (0 running).  cand is
+    prefilled with kWsProbeKey.  Returns f, cand [G][2][WS_CAND], nonfinite,
+    rows_computed, G, rpt (launch::ws_geometry's)."""
+    import numpy as np
+
+    xx = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32)).reshape(-1)  # noqa: E731
+    r = load().k_ws_fupdate_split(xx.reshape(-1), xx.shape[0], xx.shape[1], f32(f), f32(alpha), f32(y),
+                                  np.asarray(apply_idx, dtype=np.int32).reshape(-1), f32(apply_coef), float(gamma),
+                                  float(C_), int(done))
+    r["cand"] = np.asarray(r["cand"], dtype=np.uint64).reshape(r["G"], 2, WS_CAND)
+    return r
+
+
 def fused_select(f: torch.Tensor, alpha: torch.Tensor, y: torch.Tensor, C_: float, rows_per_group: int = 256):
     """Per-workgroup (up, low) selection keys of the fused / persistent engines
     (classification + wave-64 DPP minimum + LDS across waves): [groups, 2] u64

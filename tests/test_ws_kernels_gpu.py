@@ -6,7 +6,11 @@ assignment), the one-wave LDS pair loop (the reference's pair rule
 svmTrainMain.cpp:255-299 in both clipping modes, eta floor), and the two-pass
 f update with the line search (d_f, d'Qd, g'd, t, f, alpha, candidates).
 The end-to-end solves (tests/test_ws_gpu.py) cannot tell which kernel a
-compensating bug sits in; these can."""
+compensating bug sits in; these can.  The model of the one-block merge
+(merge1_model) and its crafted inputs live here beside merge_model; the tests
+that run them are test_ws_merge1_model_cpu.py (the model's invariants, no GPU)
+and test_ws_recompute_kernels_gpu.py (ws_gather, ws_subgram_split,
+ws_fupdate_split)."""
 import numpy as np
 import pytest
 import torch
@@ -90,6 +94,203 @@ def merge_model(cand, blocks, p_act, q_max, n_new, eps, prev):
         idx[b, la] = row
         qb[b] = max(qb[b], la + 1)
     return dict(done=0, b_hi=b_hi, b_lo=b_lo, uidx=union, idx=idx, qb=qb, P=P)
+
+
+def merge1_model(cand, prev, q_max, n_new, eps, iteration=0, max_iter=1 << 40, nonfinite=0):
+    """The one-block merge (ws_merge.hpp) from its rule: the lists folded four to
+    a merge thread, the stop test, per side the 16-bit prefix threshold, the
+    class order, the interleave with first-position-wins, then the previous set.
+    Returns what the kernel must leave, and counters the tests use to show that
+    an input reached a branch: d, m, T (per side), folded lists, boundary-class
+    rows dropped, duplicate positions dropped, distinct depth-d prefixes sharing
+    T's top byte."""
+    c = np.asarray(cand, dtype=np.uint64).reshape(-1, 2, KC)[:, :, :KC1]  # 1. only kWsCand1 keys a side are read
+    G = c.shape[0]
+    Gl = min(G, 256)
+    lists = [[np.sort(np.concatenate([c[g, sd] for g in range(t, G, 256)]))[:KC1] for t in range(Gl)]
+             for sd in (0, 1)]
+    gmin = [min(int(lst[0]) for lst in lists[sd]) for sd in (0, 1)]
+    b_hi, b_lo = (np.float32(s) * key_value(np.array([g], dtype=np.uint64))[0] for s, g in zip((1, -1), gmin))
+    out = dict(b_hi=b_hi, b_lo=b_lo, n_apply=0, q=0, idx=[], folded=max(0, G - 256))
+    # 2. the stop test, in the kernel's order
+    if nonfinite:
+        return dict(out, done=4)
+    if gmin[0] == int(NONE) or gmin[1] == int(NONE):
+        return dict(out, done=3)
+    if not (np.isfinite(b_hi) and np.isfinite(b_lo)):
+        return dict(out, done=4)
+    if not (np.float32(b_lo) > np.float32(np.float32(b_hi) + np.float32(np.float32(2.0) * np.float32(eps)))):
+        return dict(out, done=1)
+    if iteration >= max_iter:
+        return dict(out, done=2)
+    # 3. the threshold
+    want = q_max if len(prev) == 0 else min(n_new, q_max)
+    half = (want + 1) // 2
+    d = min(KC1 - 1, (half + Gl - 1) // Gl - 1)
+    m = (half + d) // (d + 1)
+    T, order, same_byte = [], [], []
+    for sd in (0, 1):
+        pre = sorted(int(lst[d]) >> 48 for lst in lists[sd] if int(lst[d]) != int(NONE))
+        t = pre[m - 1] if len(pre) >= m else 0xFFFF
+        T.append(t)
+        same_byte.append(len({p for p in pre if p >> 8 == t >> 8}))
+        # 4. the side's order: the global extreme, then prefix < T, then prefix == T, each in (thread, rank) order
+        rest = [int(k) for lst in lists[sd] for k in lst if int(k) != int(NONE) and int(k) != gmin[sd]]
+        order.append([gmin[sd]] + [k for k in rest if k >> 48 < t] + [k for k in rest if k >> 48 == t])
+    # 5. interleave up rank r / low rank r over the first `want` ranks; a row's first position wins
+    row = lambda k: int(k) & 0xFFFFFFFF  # noqa: E731
+    new, src, dups = [], [], 0
+    for r in range(want):
+        for sd in (0, 1):
+            if r < len(order[sd]):
+                if row(order[sd][r]) in new:
+                    dups += 1
+                else:
+                    new.append(row(order[sd][r]))
+                    src.append("ul"[sd])
+    new, src = new[:want], src[:want]
+    boundary_dropped = sum(1 for sd in (0, 1) for k in order[sd][1:] if k >> 48 == T[sd] and row(k) not in new)
+    # 6. the previous set's rows not chosen again, newest first, up to q_max
+    kept = [int(p) for p in prev if int(p) not in new][: q_max - len(new)]
+    idx = new + kept
+    return dict(out, done=0, n_apply=None, q=len(idx), idx=idx, src=src + ["p"] * len(kept), n_chosen=len(new),
+                want=want, d=d, m=m, T=T, boundary_dropped=boundary_dropped, dups=dups, same_byte=same_byte)
+
+
+def lists_from_state(f, alpha, y, C, G, fill=8):
+    """[G][2][KC] candidate lists of G contiguous row groups: each side's `fill`
+    smallest keys (the one-block merge must ignore those past KC1)."""
+    n = len(f)
+    R = (n + G - 1) // G
+    cand = np.full((G, 2, KC), NONE, dtype=np.uint64)
+    for g in range(G):
+        j = np.arange(g * R, min(n, (g + 1) * R))
+        if len(j) == 0:
+            continue
+        up, lo = in_up(alpha[j], y[j], C), in_low(alpha[j], y[j], C)
+        u = np.sort(make_key(f[j][up], j[up]))[:fill]
+        l_ = np.sort(make_key(-f[j][lo], j[lo]))[:fill]
+        cand[g, 0, : len(u)] = u
+        cand[g, 1, : len(l_)] = l_
+    return cand
+
+
+MERGE1_C = 2.0
+
+
+def merge1_state(name, n, G, fgen, interior=0.3, up_only_from=None, seed=0):
+    """f / alpha / y of n rows (alpha: zeros, interior values, values exactly at
+    C; rows from up_only_from on: alpha 0, y +1, so I_up only) and the G lists
+    they give."""
+    rng = np.random.default_rng(1000 + seed)
+    y = np.where(rng.random(n) < 0.5, 1.0, -1.0).astype(np.float32)
+    u = rng.random(n)
+    alpha = np.where(u < interior, rng.uniform(0.1, 1.9, n), np.where(u < interior + (1 - interior) / 2, 0.0,
+                                                                     MERGE1_C)).astype(np.float32)
+    if up_only_from is not None:
+        alpha[up_only_from:] = 0.0
+        y[up_only_from:] = 1.0
+    f = fgen(rng, n).astype(np.float32)
+    return dict(name=name, n=n, G=G, f=f, alpha=alpha, y=y, cand=lists_from_state(f, alpha, y, MERGE1_C, G))
+
+
+MERGE1_EPS = 1e-4
+
+
+def _prev_rows(st, rng, q_max, n_new, n_prev, overlap):
+    """a previous set: `overlap` rows the merge picks again (they must leave the
+    retained tail), the rest rows no list holds"""
+    c = st["cand"][:, :, :KC1].ravel()
+    held = np.unique((c[c != NONE] & np.uint64(0xFFFFFFFF)).astype(np.int64))
+    free = np.setdiff1d(np.arange(st["n"]), held)
+    # the new rows depend on whether there is a previous set, not on its rows
+    probe = merge1_model(st["cand"], [int(free[0])], q_max, n_new, MERGE1_EPS)
+    new = np.asarray(probe["idx"][: probe["n_chosen"]])
+    k = min(overlap, len(new))
+    rows = np.concatenate([rng.choice(new, size=k, replace=False), rng.choice(free, size=n_prev - k, replace=False)])
+    return [int(v) for v in rng.permutation(rows)]
+
+
+_normal = lambda rng, n: rng.normal(size=n)  # noqa: E731
+
+# name -> (state arguments, q_max, n_new, previous rows, of them held by the lists); the branch each must reach
+# is asserted from the model's counters in merge1_case_reaches_its_branch
+MERGE1_CASES = {
+    "g256-d0": (dict(n=3072, G=256, fgen=_normal), 192, 192, 0, 0),
+    "g256-prev-overlap": (dict(n=3072, G=256, fgen=_normal), 192, 144, 150, 60),
+    "g256-nnew1": (dict(n=3072, G=256, fgen=_normal), 192, 1, 100, 10),
+    "g256-q96": (dict(n=3072, G=256, fgen=_normal), 96, 72, 96, 30),
+    "g256-q40": (dict(n=3072, G=256, fgen=_normal), 40, 30, 40, 5),
+    "g40-d1": (dict(n=3080, G=40, fgen=_normal), 192, 144, 120, 40),
+    "g3-too-few": (dict(n=3072, G=3, fgen=_normal), 192, 192, 0, 0),
+    "g600-fold": (dict(n=3600, G=600, fgen=_normal), 192, 192, 0, 0),
+    "g600-fold-prev": (dict(n=3600, G=600, fgen=_normal), 192, 144, 192, 80),
+    "top-byte": (dict(n=3072, G=256, fgen=lambda rng, n: rng.uniform(1.0, 2.0, n)), 192, 192, 0, 0),
+    "boundary-cut": (dict(n=3072, G=256, fgen=lambda rng, n: 1.0 + rng.permutation(n) * 2.0 ** -20), 192, 192, 0,
+                     0),
+    "boundary-cut-prev": (dict(n=3072, G=256, fgen=lambda rng, n: 1.0 + rng.permutation(n) * 2.0 ** -20), 192, 144,
+                          100, 50),
+    "both-sides": (dict(n=40, G=10, fgen=_normal, interior=1.0), 40, 40, 0, 0),
+    # groups of 6 rows: the first 10 hold rows of both sides (each side lists 4 of the 6), the last 10 I_up rows only
+    "both-sides-prev": (dict(n=120, G=20, fgen=_normal, interior=1.0, up_only_from=60), 96, 72, 24, 8),
+    "ties": (dict(n=3072, G=256, fgen=lambda rng, n: np.round(rng.normal(size=n) * 2) / 2), 192, 192, 0, 0),
+    "ties-prev": (dict(n=3072, G=256, fgen=lambda rng, n: np.round(rng.normal(size=n) * 2) / 2), 192, 144, 120, 60),
+}
+
+
+def merge1_case(name, table=None):
+    """(state, q_max, n_new, prev) of a crafted one-block merge input"""
+    table = MERGE1_CASES if table is None else table
+    kw, q_max, n_new, n_prev, overlap = table[name]
+    seed = sorted(table).index(name)
+    st = merge1_state(name, seed=seed, **kw)
+    prev = _prev_rows(st, np.random.default_rng(2000 + seed), q_max, n_new, n_prev, overlap) if n_prev else []
+    return st, q_max, n_new, prev
+
+
+def merge1_case_reaches_its_branch(name, st, prev, ref):
+    """from the model's own counters: the input exercises what its name says"""
+    assert ref["done"] == 0
+    if name.startswith("g256"):
+        assert ref["d"] == 0 and max(ref["T"]) < 0xFFFF
+    if name.startswith("g40"):
+        assert ref["want"] == 144 and ref["d"] == 1 and max(ref["T"]) < 0xFFFF
+    if name.startswith("g3"):
+        assert ref["T"] == [0xFFFF, 0xFFFF] and ref["d"] == 3
+    if name.startswith("g600"):
+        assert ref["folded"] == 600 - 256
+    if name == "top-byte":
+        assert min(ref["same_byte"]) >= 2  # several prefixes in the first pass's bin: the second pass decides
+    if name.startswith("boundary-cut"):
+        assert ref["boundary_dropped"] >= 1 and ref["n_chosen"] == ref["want"]
+    if name.startswith("both-sides"):
+        assert ref["dups"] >= 1
+    if name.startswith("ties"):
+        k = st["cand"][:, :, :KC1].ravel()
+        k = k[k != NONE]
+        assert len(np.unique(k >> np.uint64(32))) < len(k)  # equal f values: the row index orders them
+    if prev:  # some previous rows are retained, some were picked again
+        assert "p" in ref["src"] and set(prev) & set(ref["idx"][: ref["n_chosen"]])
+    else:
+        assert ref["want"] == ref["q"] or ref["n_chosen"] == ref["q"]
+
+
+# stop codes of the one-block merge: (f, alpha, y, eps, iteration, max_iter, nonfinite) -> done
+def merge1_stop_cases():
+    eps = np.float32(1e-3)
+    gap = np.float32(np.float32(2.0) * eps)
+    two = lambda f_low: (np.array([0.0, f_low], np.float32), np.array([0.0, 0.0], np.float32),  # noqa: E731
+                         np.array([1.0, -1.0], np.float32))  # row 0 up only (b_hi = 0), row 1 low only (b_lo = f_low)
+    return {
+        "nonfinite-flag": (*two(1.0), eps, 0, 100, 1, 4),
+        "empty-low-side": (np.array([0.0, 1.0], np.float32), np.zeros(2, np.float32), np.ones(2, np.float32), eps, 0,
+                           100, 0, 3),
+        "inf-b": (*two(np.inf), eps, 0, 100, 0, 4),
+        "gap-inside": (*two(gap), eps, 0, 100, 0, 1),                      # b_lo == b_hi + 2 eps: converged
+        "gap-outside": (*two(np.nextafter(gap, np.float32(1.0))), eps, 0, 100, 0, 0),  # one ulp more: runs
+        "max-iter": (*two(1.0), eps, 100, 100, 0, 2),
+        "before-max-iter": (*two(1.0), eps, 99, 100, 0, 0),
+    }
 
 
 def crafted_candidates(rng, G, n_rows, ties=True):

@@ -4,8 +4,14 @@ With short rows (d <= 64 padded) the round's kernel rows are recomputed inside
 the f update and the sub-Gram comes straight from the split X rows.  The K
 values are the split GEMMs' bits, the f update sums them per column instead of
 per changed row, so the run must stop at the resident-Gram engine's optimum
-(same stop test, intercept, support set and decisions to rounding), and the
-sub-Gram kernel must reproduce the Gram's entries bit for bit."""
+(same stop test, intercept, support set and decisions to rounding).  The
+sub-Gram kernel must reproduce the Gram's entries bit for bit, and the f update
+must sum them in its documented order: both are checked on the kernels alone by
+test_ws_recompute_kernels_gpu.py
+(test_ws_subgram_split_set_sizes_bit_identical_to_the_split_gram,
+test_ws_fupdate_split_bit_exact_against_the_summation_order_model); here, f at
+the end of a run is held to f recomputed from alpha (DPSVM_VERIFY), as for every
+pair-at-a-time engine (test_solver_gpu.py test_verify_invariants_every_engine)."""
 import numpy as np
 import pytest
 import torch
@@ -49,6 +55,35 @@ def test_recompute_rounds_reach_the_resident_gram_optimum(case):
     assert abs(rec.n_support_ - dense.n_support_) <= max(3, dense.n_support_ // 100)
     if clip == "box":  # unique optimum
         assert np.abs(rec.alpha_ - dense.alpha_).max() < 0.05 * C_
+
+
+WS_ENGINES = {
+    "ws-dense": (dict(), "ws-dense", "gram"),
+    "ws-cache": (dict(force_cache=True, cache_lines=2048, ws_recompute="off"), "ws-cache", "cache"),
+    "recompute": (dict(force_cache=True, cache_lines=2048), "ws-cache", "recompute"),
+    "recompute-partial": (dict(force_cache=True, cache_lines=2048, max_iter=777), "ws-cache", "recompute"),
+}
+
+
+@pytest.mark.parametrize("clip", ["independent", "box"])
+@pytest.mark.parametrize("engine", sorted(WS_ENGINES))
+def test_verify_invariants_working_set_engines(monkeypatch, engine, clip):
+    """DPSVM_VERIFY=1: alpha in [0, C] and the incrementally updated f equals f
+    recomputed from alpha (predict GEMM), at the end of a run and after a
+    max_iter stop.  In the recompute rounds f alone carries the kernel rows:
+    nothing downstream repairs an error in it."""
+    monkeypatch.setenv("DPSVM_VERIFY", "1")
+    extra, iteration, rows = WS_ENGINES[engine]
+    X, y = synthetic("covtype", n=6000, d=54, seed=5)
+    clf = SVC(C=4.0, gamma=0.5, eps=1e-3, clip=clip, device="cuda", solver="ws", ws_blocks=1, **extra).fit(X, y)
+    assert clf.setup_info_["iteration"] == iteration and clf.setup_info_["ws_rows"] == rows
+    if "max_iter" in extra:
+        assert clf.n_iter_ == 777 and not clf.converged_
+    else:
+        assert clf.converged_
+    err = clf.stats_["verify_f_err"]
+    print(f"verify_f_err {engine}/{clip}: {err:.3e} after {clf.n_iter_} steps in {clf.n_rounds_} rounds")
+    assert 0.0 <= err < 1e-4
 
 
 def test_recompute_modes_and_fallbacks():

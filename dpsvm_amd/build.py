@@ -42,6 +42,7 @@ LIB_SOURCES = [
     "comm/comm_host.cpp",
     "comm/comm_rccl.cpp",
     "solver/smo_cpu.cpp",
+    "solver/platt_cpu.cpp",
     "solver/checkpoint.cpp",
     "solver/gpu_setup.hip",
     "solver/gpu_exchange.hip",
@@ -64,6 +65,7 @@ LIB_SOURCES = [
     "kernels/ws_merge.hip",
     "kernels/ws_solve.hip",
     "kernels/ws_recompute.hip",
+    "kernels/platt.hip",
 ]
 # the quarantined engines (solver/gpu_engines_pairq.hip registers them): a plugin
 # library for the Python module, linked into the CLIs (svmTrain --engines all)

@@ -188,6 +188,15 @@ struct SolveResult {
   bool converged() const { return status == 1; }
 };
 
+// One machine's Platt sigmoid P(y = +1 | d) = 1 / (1 + exp(A d + B)) and how its fit went (platt.hip /
+// platt_fit_cpu): Newton steps taken, objective evaluations (the start's included), the final objective
+struct PlattFit {
+  double A = 0.0, B = 0.0, fval = 0.0;
+  int32_t iters = 0, evals = 0;
+  int32_t status = 0;  // 0 converged, 1 line search failed, 2 stopped at 100 steps
+  int32_t pad = 0;
+};
+
 // ---------------------------------------------------------------------------
 // Order-preserving selection keys.
 //

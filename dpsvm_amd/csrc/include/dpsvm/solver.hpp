@@ -56,6 +56,11 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
 std::vector<float> decision_cpu(const Model& m, const float* x, int64_t n, int d, int threads = 0);
 // One-vs-rest decision values [n][k]: column c = sum_sv coef[sv][c] K(sv, x) - b[c] (k passes of decision_cpu)
 std::vector<float> decision_multi_cpu(const MultiModel& m, const float* x, int64_t n, int d, int threads = 0);
+// Platt scaling on the host in plain double, the twins of platt.hip (device="cpu"): the sigmoid fit of one
+// machine on n decisions (y > 0: the positive class; unweighted, LIBSVM's targets and Newton method), and
+// dec [n][k] decisions to probabilities [n][k]: p = 1 / (1 + exp(A_c d + B_c)), k > 2 divided by the row's sum
+PlattFit platt_fit_cpu(const float* dec, const float* y, int64_t n);
+std::vector<float> proba_cpu(const float* dec, int64_t n, int k, const double* A, const double* B);
 // fraction of rows with sign(decision) == y  (>= 0 -> +1)
 double accuracy_from_decision(const std::vector<float>& dec, const float* y, int64_t n);
 
@@ -119,6 +124,14 @@ class GpuSolver {
   // after solve(): the whole gradient on every rank (the shards all-gathered;
   // a collective at world > 1)
   std::vector<float> gradient_all();
+  // After solve() (one rank, X replicated): the decision values f_i + y_i - b of `rows` (nr global row
+  // indices: the fold the solve held out by C_i = 0) into entry i of slot `slot` of the solver's own
+  // [slots][n] device buffer (grown to slot + 1 zeroed slots on demand); the gradient stays on the device.
+  // holdout(slot): that slot downloaded.  platt_fit(slot): the sigmoid fit (platt.hip) of the slot's n
+  // decisions against the labels current on the device (setup / set_labels).
+  void holdout_decisions(const int32_t* rows, int64_t nr, double b, int slot);
+  std::vector<float> holdout(int slot) const;
+  PlattFit platt_fit(int slot);
   // After setup(): other labels on the same rows (host, global n; mapped to +1 / -1 as setup does).  X, |x|^2,
   // the split operands, the engine, the round plan and the captured graphs stay (they hold the label buffer's
   // address, which does not move).  The next solve() on a dense engine then keeps the resident Gram — it
@@ -198,6 +211,9 @@ class GpuPredictor {
   // [n][k] decision values of a multi-class model (launch::rbf_predict_multi), chunked like decision()
   std::vector<float> decision_multi(const float* x_host, int64_t n, int d);
   int k() const;  // columns of decision_multi (0: a binary model)
+  // the decisions of decision() / decision_multi() turned into probabilities on the device, per chunk before
+  // the download (launch::proba_rows): [n][max(k, 1)]; A, B: the machines' sigmoids (host, max(k, 1) each)
+  std::vector<float> proba(const float* x_host, int64_t n, int d, const double* A, const double* B);
   // device pointers, stream = hipStream_t as void*
   void decision_device(const float* x_dev, int64_t n, int d, int ld, float* out_dev, void* stream);
   struct Impl;
@@ -257,6 +273,17 @@ void xpass_rows(const float* x, const float* xsq, int64_t n, int ld, const int* 
 // the (up, low) keys of its rows -> keys_out[2 * groups]
 void fused_select(const float* f, const float* alpha, const float* y, int64_t n, float C, int rows_per_group,
                   uint64_t* keys_out, void* stream);
+// probability estimates (platt.hip), host vectors in and out, one launch each.  holdout_decision: dec
+// [slots][n] with slot `slot`'s entries at `rows` (each in [0, n)) replaced by float(double(f) + y - b).
+// platt_fit: m machines (dec and y [m][n]) in one launch.  proba_rows: dec [n][k] -> probabilities [n][k].
+std::vector<float> holdout_decision(const std::vector<float>& f, const std::vector<float>& y,
+                                    const std::vector<int32_t>& rows, double b, std::vector<float> dec, int slot);
+std::vector<PlattFit> platt_fit(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n);
+std::vector<float> proba_rows(const std::vector<float>& dec, int64_t n, int k, const std::vector<double>& A,
+                              const std::vector<double>& B);
+// diagnostics (bench/platt_probe.py): ms per launch, event-timed, of platt_fit on device-resident inputs
+std::vector<float> platt_fit_bench(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n,
+                                   int reps);
 
 // ---- working-set kernels (ws_*.hip), one launch each on crafted state
 // (host vectors in and out; ws_kernel_entry.hip).  Reference counterparts:

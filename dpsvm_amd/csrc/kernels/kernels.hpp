@@ -211,6 +211,17 @@ void rbf_predict_multi(const float* A, const float* Asq, int64_t M, int lda, con
                        const float* coef, int ldc, int k, int64_t N, int ldb, int dp, float gamma, const float* b,
                        float* scratch, float* dec, int64_t ldd, hipStream_t s, int precision = 0);
 
+// Probability estimates (platt.hip).  holdout_decision: dec[i] = float(double(f_i) + y_i - b) for the nr rows
+// i = rows[r] (device indices < the length of f / y / dec; the other entries of dec are left alone).
+// platt_fit: one workgroup per machine fits machine c's sigmoid on dec[c ldd + i], y[c ldy + i], i < n (y > 0:
+// the positive class) into out[c] (device); bit-reproducible.  proba_rows: dec [n][k] decisions to
+// probabilities in place, p = 1 / (1 + exp(A_c d + B_c)), for k > 2 divided by the row's sum (A, B: device)
+void holdout_decision(const float* f, const float* y, const int32_t* rows, int64_t nr, double b, float* dec,
+                      hipStream_t s);
+void platt_fit(const float* dec, int64_t ldd, const float* y, int64_t ldy, int64_t n, int machines, PlattFit* out,
+               hipStream_t s);
+void proba_rows(float* dec, int64_t n, int k, const double* A, const double* B, hipStream_t s);
+
 // SV compaction: idx_out[k] = i for the k-th alpha[i] > 0 (index order)
 // scratch: >= compact_scratch_ints(n) ints; count written to *count_dev
 int64_t compact_scratch_ints(int64_t n);

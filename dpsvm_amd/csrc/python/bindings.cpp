@@ -182,6 +182,24 @@ py::dict setup_dict(const GpuSetupInfo& i) {
   return d;
 }
 
+py::dict platt_dict(const PlattFit& r) {
+  py::dict d;
+  d["A"] = r.A;
+  d["B"] = r.B;
+  d["iters"] = r.iters;
+  d["evals"] = r.evals;
+  d["fval"] = r.fval;
+  d["status"] = r.status;
+  return d;
+}
+
+using F64 = py::array_t<double, py::array::c_style | py::array::forcecast>;
+// the k sigmoids (A, B) of decisions with `cols` columns
+void check_sigmoids(const F64& A, const F64& B, int64_t cols) {
+  if (A.ndim() != 1 || B.ndim() != 1 || A.shape(0) != cols || B.shape(0) != cols)
+    throw py::value_error("A and B must hold one value per decision column");
+}
+
 ProgressFn wrap_progress(py::object cb) {
   if (cb.is_none()) return {};
   py::function fn = cb;
@@ -474,6 +492,23 @@ PYBIND11_MODULE(_C, m) {
   m.def("decision_cpu", [](const Model& md, F32 x, int threads) {
     return decide(x, 0, [&](const float* xd, int64_t n, int d) { return decision_cpu(md, xd, n, d, threads); });
   }, py::arg("model"), py::arg("x"), py::arg("threads") = 0);
+  m.def("platt_fit_cpu", [](F32 dec, F32 y) {
+    if (dec.ndim() != 1 || y.ndim() != 1 || dec.shape(0) != y.shape(0) || dec.shape(0) < 1)
+      throw py::value_error("dec and y must be 1-D with the same n >= 1 entries");
+    PlattFit r;
+    {
+      py::gil_scoped_release rel;
+      r = platt_fit_cpu(dec.data(), y.data(), dec.shape(0));
+    }
+    return platt_dict(r);
+  }, py::arg("dec"), py::arg("y"),
+        "the Platt sigmoid of one machine's decisions (y > 0: the positive class) in plain double on the host");
+  m.def("proba_cpu", [](F32 dec, F64 A, F64 B) {
+    if (dec.ndim() != 2) throw py::value_error("dec must be 2-D (n, k)");
+    check_sigmoids(A, B, dec.shape(1));
+    return to_np2(proba_cpu(dec.data(), dec.shape(0), (int)dec.shape(1), A.data(), B.data()), dec.shape(0),
+                  (int)dec.shape(1));
+  }, py::arg("dec"), py::arg("A"), py::arg("B"));
 
   // ---------------- solvers ----------------
   m.def("solve_cpu", [](F32 x, F32 y, const SolverParams& p, std::shared_ptr<Communicator> comm,
@@ -571,6 +606,30 @@ PYBIND11_MODULE(_C, m) {
         }
         return to_np(g);
       }, "after solve(): this rank's gradient f_j = sum_i alpha_i y_i K(i, j) - y_j as the solver maintained it")
+      .def("holdout_decisions", [](GpuSolver& s, py::array_t<int32_t, py::array::c_style | py::array::forcecast> rows,
+                                   double b, int slot) {
+        if (rows.ndim() != 1) throw py::value_error("rows must be 1-D");
+        py::gil_scoped_release rel;
+        s.holdout_decisions(rows.data(), rows.shape(0), b, slot);
+      }, py::arg("rows"), py::arg("b"), py::arg("slot") = 0,
+           "after solve(): the decisions f_i + y_i - b of the held-out rows into slot `slot` of the solver's "
+           "device buffer")
+      .def("holdout", [](GpuSolver& s, int slot) {
+        std::vector<float> v;
+        {
+          py::gil_scoped_release rel;
+          v = s.holdout(slot);
+        }
+        return to_np(v);
+      }, py::arg("slot") = 0)
+      .def("platt_fit", [](GpuSolver& s, int slot) {
+        PlattFit r;
+        {
+          py::gil_scoped_release rel;
+          r = s.platt_fit(slot);
+        }
+        return platt_dict(r);
+      }, py::arg("slot") = 0, "the sigmoid fit of slot `slot`'s decisions against the labels current on the device")
       .def("release_cache", [](GpuSolver& s) {
         py::gil_scoped_release rel;
         s.release_cache();
@@ -645,6 +704,12 @@ PYBIND11_MODULE(_C, m) {
       .def("decision", [](GpuPredictor& p, F32 x) {
         return decide(x, 0, [&](const float* xd, int64_t n, int d) { return p.decision(xd, n, d); });
       })
+      .def("proba", [](GpuPredictor& p, F32 x, F64 A, F64 B) {
+        const int cols = std::max(p.k(), 1);
+        check_sigmoids(A, B, cols);
+        return decide(x, cols, [&](const float* xd, int64_t n, int d) { return p.proba(xd, n, d, A.data(), B.data()); });
+      }, py::arg("x"), py::arg("A"), py::arg("B"),
+           "(n, max(k, 1)) probabilities: the decision GEMM, then the sigmoids on the device before the download")
       .def("decision_device", [](GpuPredictor& p, uintptr_t x, int64_t n, int d, int ld, uintptr_t out,
                                  uintptr_t stream) {
         py::gil_scoped_release rel;
@@ -865,6 +930,40 @@ PYBIND11_MODULE(_C, m) {
     return d_;
   }, py::arg("x"), py::arg("n"), py::arg("d"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("apply_idx"),
         py::arg("apply_coef"), py::arg("gamma"), py::arg("C"), py::arg("done"));
+  // probability estimates (platt.hip), one launch each on host arrays
+  m.def("k_holdout_decision", [vi](const F32& f, const F32& y, const I32& rows, double b, const F32& dec, int slot) {
+    if (dec.ndim() != 2 || dec.shape(1) != f.size()) throw py::value_error("dec must be (slots, n)");
+    return to_np2(kernels::holdout_decision(from_np(f), from_np(y), vi(rows), b, from_np(dec), slot), dec.shape(0),
+                  (int)dec.shape(1));
+  }, py::arg("f"), py::arg("y"), py::arg("rows"), py::arg("b"), py::arg("dec"), py::arg("slot"));
+  m.def("k_platt_fit", [](const F32& dec, const F32& y) {
+    if (dec.ndim() != 2 || y.ndim() != 2 || dec.shape(0) != y.shape(0) || dec.shape(1) != y.shape(1))
+      throw py::value_error("dec and y must be (m, n)");
+    std::vector<PlattFit> r;
+    {
+      const std::vector<float> d = from_np(dec), yy = from_np(y);
+      const int mm = (int)dec.shape(0);
+      const int64_t n = dec.shape(1);
+      py::gil_scoped_release rel;
+      r = kernels::platt_fit(d, yy, mm, n);
+    }
+    py::list out;
+    for (const PlattFit& q : r) out.append(platt_dict(q));
+    return out;
+  }, py::arg("dec"), py::arg("y"));
+  m.def("k_platt_fit_bench", [](const F32& dec, const F32& y, int reps) {
+    if (dec.ndim() != 2 || y.ndim() != 2 || dec.shape(0) != y.shape(0) || dec.shape(1) != y.shape(1))
+      throw py::value_error("dec and y must be (m, n)");
+    return kernels::platt_fit_bench(from_np(dec), from_np(y), (int)dec.shape(0), dec.shape(1), reps);
+  }, py::arg("dec"), py::arg("y"), py::arg("reps"), "diagnostics: ms per launch of the fit on resident decisions");
+  m.def("k_proba_rows", [](const F32& dec, const F64& A, const F64& B) {
+    if (dec.ndim() != 2) throw py::value_error("dec must be (n, k)");
+    check_sigmoids(A, B, dec.shape(1));
+    return to_np2(kernels::proba_rows(from_np(dec), dec.shape(0), (int)dec.shape(1),
+                                      std::vector<double>(A.data(), A.data() + A.size()),
+                                      std::vector<double>(B.data(), B.data() + B.size())),
+                  dec.shape(0), (int)dec.shape(1));
+  }, py::arg("dec"), py::arg("A"), py::arg("B"));
   m.attr("kWsProbeKey") = kernels::kWsProbeKey;
   m.attr("kWsProbeApply") = kernels::kWsProbeApply;
   m.def("production_line_cap", &production_line_cap, py::arg("cache_lines"), py::arg("ws_size"),

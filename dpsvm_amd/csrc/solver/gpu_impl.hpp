@@ -142,6 +142,11 @@ struct GpuSolver::Impl {
   // arguments and the captured graphs) and the host values (the post-solve box check); wsa.c_row = row_c or null
   float* row_c = nullptr;
   std::vector<float> h_row_c;
+  // held-out decisions (GpuSolver::holdout_decisions): [holdout_slots][n], a fold's row indices [n], one fit
+  float* holdout = nullptr;
+  int holdout_slots = 0;
+  int32_t* holdout_rows = nullptr;
+  PlattFit* platt_out = nullptr;
 
   hipGraphExec_t gexec = nullptr;
   hipGraph_t graph = nullptr;

@@ -44,10 +44,11 @@ struct DeviceSvs {
 // Decision values of a host matrix [nt][d] in chunks of 2^20 rows: upload (rows zero-padded to dp, whole tiles
 // zeroed), |x|^2, launch(dx, dsq, rows, scratch, ddec) writes the chunk's [rows][cols] values, download.
 // scratch_floats(rows) is what one launch of `rows` rows needs: its split count depends on the row count, so the
-// scratch is sized for the larger of the full chunk's and the tail's.
-template <class ScratchFn, class LaunchFn>
+// scratch is sized for the larger of the full chunk's and the tail's.  post(ddec, rows) runs on the chunk's values
+// before their download (the probability epilogue).
+template <class ScratchFn, class LaunchFn, class PostFn>
 std::vector<float> predict_host_chunks(const float* xh, int64_t nt, int d, int dp, int cols, hipStream_t stream,
-                                       ScratchFn scratch_floats, LaunchFn launch) {
+                                       ScratchFn scratch_floats, LaunchFn launch, PostFn post) {
   std::vector<float> out((size_t)nt * cols);
   if (nt == 0) return out;
   const int64_t chunk = 1 << 20;
@@ -66,12 +67,18 @@ std::vector<float> predict_host_chunks(const float* xh, int64_t nt, int d, int d
                                hipMemcpyHostToDevice, stream));
     launch::row_sqnorm(dx, rows, dp, dp, dsq, stream);
     launch(dx, dsq, rows, scratch, ddec);
+    post(ddec, rows);
     HIP_CHECK(hipMemcpyAsync(out.data() + (size_t)r0 * cols, ddec, (size_t)rows * cols * 4, hipMemcpyDeviceToHost,
                              stream));
   }
   HIP_CHECK(hipStreamSynchronize(stream));
   for (void* p : {(void*)dx, (void*)dsq, (void*)ddec, (void*)scratch}) (void)hipFree(p);
   return out;
+}
+template <class ScratchFn, class LaunchFn>
+std::vector<float> predict_host_chunks(const float* xh, int64_t nt, int d, int dp, int cols, hipStream_t stream,
+                                       ScratchFn scratch_floats, LaunchFn launch) {
+  return predict_host_chunks(xh, nt, d, dp, cols, stream, scratch_floats, launch, [](float*, int64_t) {});
 }
 
 }  // namespace
@@ -184,6 +191,67 @@ std::vector<float> GpuSolver::gradient() const {
   return f;
 }
 
+// ---------------------------------------------------------------------------
+// Held-out decisions and the sigmoid fit on them (platt.hip): a fold's rows never leave the device
+// ---------------------------------------------------------------------------
+void GpuSolver::holdout_decisions(const int32_t* rows, int64_t nr, double b, int slot) {
+  auto& m = *impl_;
+  DPSVM_CHECK(m.engine && m.f && m.world == 1 && m.nl == m.n,
+              "holdout_decisions: after setup() on one rank with all rows");
+  DPSVM_CHECK(slot >= 0 && slot < (1 << 20) && nr >= 0 && nr <= m.n && (rows || nr == 0),
+              "holdout_decisions: slot >= 0, at most n rows");
+  for (int64_t r = 0; r < nr; ++r) DPSVM_CHECK(rows[r] >= 0 && rows[r] < m.n, "holdout_decisions: a row outside [0, n)");
+  HIP_CHECK(hipSetDevice(m.device));
+  if (slot >= m.holdout_slots) {  // grow: the slots written so far move over, the new ones are zero
+    float* grown = dmalloc<float>((size_t)(slot + 1) * m.n, &m.bytes);
+    HIP_CHECK(hipMemsetAsync(grown, 0, (size_t)(slot + 1) * m.n * 4, m.stream));
+    if (m.holdout) {
+      HIP_CHECK(hipMemcpyAsync(grown, m.holdout, (size_t)m.holdout_slots * m.n * 4, hipMemcpyDeviceToDevice,
+                               m.stream));
+      HIP_CHECK(hipStreamSynchronize(m.stream));
+      HIP_CHECK(hipFree(m.holdout));
+      m.bytes -= (size_t)m.holdout_slots * m.n * 4;
+    }
+    m.holdout = grown;
+    m.holdout_slots = slot + 1;
+    m.info.bytes_device = m.bytes;
+  }
+  if (!m.holdout_rows) {
+    m.holdout_rows = dmalloc<int32_t>((size_t)m.n, &m.bytes);
+    m.info.bytes_device = m.bytes;
+  }
+  if (nr == 0) return;
+  HIP_CHECK(hipMemcpyAsync(m.holdout_rows, rows, (size_t)nr * 4, hipMemcpyHostToDevice, m.stream));
+  launch::holdout_decision(m.f, m.y, m.holdout_rows, nr, b, m.holdout + (size_t)slot * m.n, m.stream);
+  HIP_CHECK(hipStreamSynchronize(m.stream));  // rows is the caller's memory
+}
+
+std::vector<float> GpuSolver::holdout(int slot) const {
+  const auto& m = *impl_;
+  DPSVM_CHECK(slot >= 0 && slot < m.holdout_slots, "holdout: no such slot (holdout_decisions first)");
+  HIP_CHECK(hipSetDevice(m.device));
+  std::vector<float> out((size_t)m.n);
+  HIP_CHECK(hipMemcpyAsync(out.data(), m.holdout + (size_t)slot * m.n, (size_t)m.n * 4, hipMemcpyDeviceToHost,
+                           m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  return out;
+}
+
+PlattFit GpuSolver::platt_fit(int slot) {
+  auto& m = *impl_;
+  DPSVM_CHECK(slot >= 0 && slot < m.holdout_slots, "platt_fit: no such slot (holdout_decisions first)");
+  HIP_CHECK(hipSetDevice(m.device));
+  if (!m.platt_out) {
+    m.platt_out = dmalloc<PlattFit>(1, &m.bytes);
+    m.info.bytes_device = m.bytes;
+  }
+  launch::platt_fit(m.holdout + (size_t)slot * m.n, m.n, m.y, m.n, m.n, 1, m.platt_out, m.stream);
+  PlattFit r;
+  HIP_CHECK(hipMemcpyAsync(&r, m.platt_out, sizeof(r), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  return r;
+}
+
 std::vector<float> GpuSolver::decision(const SolveResult& r, const float* xh, int64_t nt, int d) {
   auto& m = *impl_;
   DPSVM_CHECK(d == m.d, "feature count mismatch");
@@ -260,31 +328,58 @@ GpuPredictor::~GpuPredictor() = default;
 
 int GpuPredictor::k() const { return impl_->k; }
 
-std::vector<float> GpuPredictor::decision_multi(const float* xh, int64_t nt, int d) {
-  auto& m = *impl_;
-  DPSVM_CHECK(m.k > 0, "decision_multi: this predictor holds a binary model");
+// the model's decision GEMM over a host matrix in chunks ([nt][max(k, 1)]), post(ddec, rows) before each download
+template <class PostFn>
+static std::vector<float> predictor_chunks(GpuPredictor::Impl& m, const float* xh, int64_t nt, int d, PostFn post) {
   DPSVM_CHECK(d == m.d || m.s.nsv == 0, "feature count mismatch between model and data");
   HIP_CHECK(hipSetDevice(m.device));
-  return predict_host_chunks(
-      xh, nt, d, m.dp, m.k, m.stream,
-      [&](int64_t rows) { return launch::predict_multi_scratch_floats(rows, m.s.nsv, m.k); },
-      [&](const float* dx, const float* dsq, int64_t rows, float* scratch, float* ddec) {
-        launch::rbf_predict_multi(dx, dsq, rows, m.dp, m.s.sv, m.s.svsq, m.s.coef, m.k, m.k, m.s.nsv, m.dp, m.dp,
-                                  m.gamma, m.s.bk, scratch, ddec, m.k, m.stream, m.precision);
-      });
-}
-
-std::vector<float> GpuPredictor::decision(const float* xh, int64_t nt, int d) {
-  auto& m = *impl_;
-  DPSVM_CHECK(m.k == 0, "decision: this predictor holds a multi-class model (decision_multi)");
-  DPSVM_CHECK(d == m.d || m.s.nsv == 0, "feature count mismatch between model and data");
-  HIP_CHECK(hipSetDevice(m.device));
+  if (m.k > 0)
+    return predict_host_chunks(
+        xh, nt, d, m.dp, m.k, m.stream,
+        [&](int64_t rows) { return launch::predict_multi_scratch_floats(rows, m.s.nsv, m.k); },
+        [&](const float* dx, const float* dsq, int64_t rows, float* scratch, float* ddec) {
+          launch::rbf_predict_multi(dx, dsq, rows, m.dp, m.s.sv, m.s.svsq, m.s.coef, m.k, m.k, m.s.nsv, m.dp, m.dp,
+                                    m.gamma, m.s.bk, scratch, ddec, m.k, m.stream, m.precision);
+        },
+        post);
   return predict_host_chunks(
       xh, nt, d, m.dp, 1, m.stream, [&](int64_t rows) { return launch::predict_scratch_floats(rows, m.s.nsv); },
       [&](const float* dx, const float* dsq, int64_t rows, float* part, float* ddec) {
         launch::rbf_predict(dx, dsq, rows, m.dp, m.s.sv, m.s.svsq, m.s.coef, m.s.nsv, m.dp, m.dp, m.gamma, m.b, part,
                             ddec, nullptr, nullptr, m.stream, m.precision);
-      });
+      },
+      post);
+}
+
+std::vector<float> GpuPredictor::decision_multi(const float* xh, int64_t nt, int d) {
+  DPSVM_CHECK(impl_->k > 0, "decision_multi: this predictor holds a binary model");
+  return predictor_chunks(*impl_, xh, nt, d, [](float*, int64_t) {});
+}
+
+std::vector<float> GpuPredictor::decision(const float* xh, int64_t nt, int d) {
+  DPSVM_CHECK(impl_->k == 0, "decision: this predictor holds a multi-class model (decision_multi)");
+  return predictor_chunks(*impl_, xh, nt, d, [](float*, int64_t) {});
+}
+
+std::vector<float> GpuPredictor::proba(const float* xh, int64_t nt, int d, const double* A, const double* B) {
+  auto& m = *impl_;
+  const int cols = std::max(m.k, 1);
+  HIP_CHECK(hipSetDevice(m.device));
+  size_t tb = 0;
+  double* ab = dmalloc<double>((size_t)2 * cols, &tb);
+  HIP_CHECK(hipMemcpyAsync(ab, A, (size_t)cols * 8, hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipMemcpyAsync(ab + cols, B, (size_t)cols * 8, hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));  // A, B are the caller's memory
+  std::vector<float> out;
+  try {
+    out = predictor_chunks(m, xh, nt, d,
+                           [&](float* ddec, int64_t rows) { launch::proba_rows(ddec, rows, cols, ab, ab + cols, m.stream); });
+  } catch (...) {
+    (void)hipFree(ab);
+    throw;
+  }
+  (void)hipFree(ab);
+  return out;
 }
 
 void GpuPredictor::decision_device(const float* x_dev, int64_t nt, int d, int ld, float* out_dev, void* stream) {

@@ -46,7 +46,8 @@ GpuSolver::Impl::~Impl() {
                     (void*)key_of, (void*)ref, (void*)hslot_of, (void*)hkey_of, (void*)partials, (void*)ctrl,
                     (void*)records, (void*)my_record, (void*)pf, (void*)rf, (void*)rcf, (void*)stamps,
                     (void*)plru_meta, (void*)plru_stats, (void*)wsctrl, (void*)wscand, (void*)wssub, (void*)wsdfs, (void*)wsdalpha, (void*)wspart, (void*)wssorted,
-                    (void*)wsxq, (void*)wsxqsq, (void*)wsiota, xs, (void*)xsh, wsxs, (void*)wsxsh, (void*)row_c})
+                    (void*)wsxq, (void*)wsxqsq, (void*)wsiota, xs, (void*)xsh, wsxs, (void*)wsxsh, (void*)row_c,
+                    (void*)holdout, (void*)holdout_rows, (void*)platt_out})
     if (ptr) (void)hipFree(ptr);
   if (status_h) (void)hipHostFree(status_h);
   if (hlines_h) (void)hipHostFree(hlines_h);

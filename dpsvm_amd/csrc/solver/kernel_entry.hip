@@ -296,6 +296,89 @@ int64_t compact_nonzero(const float* alpha, int64_t n, int* idx_out, void* strea
   return h;
 }
 
+// ---- probability estimates (platt.hip): host vectors in and out on the null stream ----
+namespace {
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t count;
+  explicit DevBuf(size_t c) : count(std::max<size_t>(c, 1)) {
+    size_t tb = 0;
+    p = dmalloc<T>(count, &tb);
+    HIP_CHECK(hipMemset(p, 0, count * sizeof(T)));
+  }
+  explicit DevBuf(const std::vector<T>& h) : DevBuf(h.size()) {
+    if (!h.empty()) HIP_CHECK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  }
+  DevBuf(const DevBuf&) = delete;
+  ~DevBuf() { (void)hipFree(p); }
+  std::vector<T> down(size_t c) const {
+    std::vector<T> h(c);
+    if (c) HIP_CHECK(hipMemcpy(h.data(), p, c * sizeof(T), hipMemcpyDeviceToHost));
+    return h;
+  }
+};
+}  // namespace
+
+std::vector<float> holdout_decision(const std::vector<float>& f, const std::vector<float>& y,
+                                    const std::vector<int32_t>& rows, double b, std::vector<float> dec, int slot) {
+  const int64_t n = (int64_t)f.size();
+  DPSVM_CHECK(n > 0 && (int64_t)y.size() == n, "holdout_decision: f and y of n > 0 rows");
+  DPSVM_CHECK(slot >= 0 && (int64_t)dec.size() % n == 0 && (int64_t)slot < (int64_t)dec.size() / n,
+              "holdout_decision: dec [slots][n] with slot < slots");
+  for (int32_t r : rows) DPSVM_CHECK(r >= 0 && r < n, "holdout_decision: a row outside [0, n)");
+  DevBuf<float> df(f), dy(y), dd(dec);
+  DevBuf<int32_t> dr(rows);
+  launch::holdout_decision(df.p, dy.p, dr.p, (int64_t)rows.size(), b, dd.p + (size_t)slot * n, nullptr);
+  HIP_CHECK(hipStreamSynchronize(nullptr));
+  return dd.down(dec.size());
+}
+
+std::vector<PlattFit> platt_fit(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n) {
+  DPSVM_CHECK(m >= 1 && n >= 1 && (int64_t)dec.size() == m * n && (int64_t)y.size() == m * n,
+              "platt_fit: dec and y [m][n], m, n >= 1");
+  DevBuf<float> dd(dec), dy(y);
+  DevBuf<PlattFit> out((size_t)m);
+  launch::platt_fit(dd.p, n, dy.p, n, n, m, out.p, nullptr);
+  HIP_CHECK(hipStreamSynchronize(nullptr));
+  return out.down((size_t)m);
+}
+
+std::vector<float> platt_fit_bench(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n,
+                                   int reps) {
+  DPSVM_CHECK(m >= 1 && n >= 1 && reps > 0 && (int64_t)dec.size() == m * n && (int64_t)y.size() == m * n,
+              "platt_fit_bench: dec and y [m][n], m, n >= 1, reps > 0");
+  DevBuf<float> dd(dec), dy(y);
+  DevBuf<PlattFit> out((size_t)m);
+  hipEvent_t e0, e1;
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
+  std::vector<float> ms;
+  for (int r = 0; r < reps; ++r) {
+    HIP_CHECK(hipEventRecord(e0, nullptr));
+    launch::platt_fit(dd.p, n, dy.p, n, n, m, out.p, nullptr);
+    HIP_CHECK(hipEventRecord(e1, nullptr));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float t = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+    ms.push_back(t);
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return ms;
+}
+
+std::vector<float> proba_rows(const std::vector<float>& dec, int64_t n, int k, const std::vector<double>& A,
+                              const std::vector<double>& B) {
+  DPSVM_CHECK(n >= 1 && k >= 1 && (int64_t)dec.size() == n * k && (int)A.size() == k && (int)B.size() == k,
+              "proba_rows: dec [n][k], A and B of k values");
+  DevBuf<float> dd(dec);
+  DevBuf<double> dA(A), dB(B);
+  launch::proba_rows(dd.p, n, k, dA.p, dB.p, nullptr);
+  HIP_CHECK(hipStreamSynchronize(nullptr));
+  return dd.down(dec.size());
+}
+
 }  // namespace kernels
 
 }  // namespace dpsvm

@@ -93,6 +93,56 @@ def _pick(table: dict, value: str, name: str) -> int:
     return table[value]
 
 
+def _predict_proba(gp, model, multi: bool, X: np.ndarray, A, B) -> np.ndarray:
+    """What SVC and the loaded models share: the machines' sigmoids (A, B) on the decision values of X — on the
+    device predictor ``gp`` before the download, else (gp None) on the host; ``model()``: the native model."""
+    C = load()
+    A = np.atleast_1d(np.asarray(A, dtype=np.float64))
+    B = np.atleast_1d(np.asarray(B, dtype=np.float64))
+    if gp is not None:
+        p = gp.proba(X, A, B)
+    elif multi:
+        p = C.proba_cpu(C.decision_multi_cpu(model(), X, 0), A, B)
+    else:
+        p = C.proba_cpu(C.decision_cpu(model(), X, 0).reshape(-1, 1), A, B)
+    return p if multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
+
+
+def _write_platt(path: str, A, B) -> None:
+    """the sidecar ``path + ".platt"`` of a model file: "dpsvm-platt <k>", the k A values, the k B values
+    (comma-separated, 17 significant digits); without sigmoids a stale one is removed"""
+    import os
+
+    side = path + ".platt"
+    if A is None:
+        if os.path.exists(side):
+            os.remove(side)
+        return
+    A, B = np.atleast_1d(A), np.atleast_1d(B)
+    with open(side, "w") as f:
+        f.write(f"dpsvm-platt {len(A)}\n")
+        for v in (A, B):
+            f.write(",".join("%.17g" % float(x) for x in v) + "\n")
+
+
+def _read_platt(path: str, k: int):
+    """(A, B) float64 (k,) of the sidecar of the model file ``path``, None when there is none"""
+    import os
+
+    side = path + ".platt"
+    if not os.path.exists(side):
+        return None
+    with open(side) as f:
+        lines = f.read().split("\n")
+    head = lines[0].split()
+    if len(lines) < 3 or len(head) != 2 or head[0] != "dpsvm-platt" or int(head[1]) != k:
+        raise ValueError(f"{side}: not the Platt sidecar of a model of {k} machine(s)")
+    A, B = (np.array([float(v) for v in ln.split(",")], dtype=np.float64) for ln in lines[1:3])
+    if len(A) != k or len(B) != k:
+        raise ValueError(f"{side}: needs {k} A and {k} B values")
+    return A, B
+
+
 @dataclass
 class SVCConfig:
     """Solver configuration (mirrors the svmTrain flags)."""
@@ -257,6 +307,14 @@ class SVC:
     box is ``0 <= alpha_i <= C * w_i``; ``row_C_`` holds the bounds ((n,), or
     (k, n)), ``n_bounded_`` counts ``alpha_i == C_i > 0``.  ``cross_val_decision``
     / ``cross_val_score``: k folds as k solves on one resident Gram.
+
+    Probabilities (``fit(probability=cv)``, docs/DESIGN.md §16): per machine the
+    full-data solve and ``cv`` fold solves on that Gram; ``cv_decision_`` holds the
+    out-of-fold decisions ((n,), or (n, k)), ``probA_`` / ``probB_`` the Platt
+    sigmoids fitted on them (float64; (k,) for k machines), ``platt_stats_`` the
+    fits' ``iters`` / ``evals`` / ``fval`` / ``status``, ``cv_stats_`` the fold
+    solves' dicts (per machine); ``stats_`` stays the full-data solves.
+    ``predict_proba`` needs them; ``save`` writes them to ``path + ".platt"``.
     """
 
     def __init__(self, C: float = 1.0, gamma: Optional[float] = None, eps: float = 1e-3,
@@ -356,18 +414,22 @@ class SVC:
         return p, RC, self.config.weighted_params(p, comm, resume, rank_rows)
 
     # ------------------------------------------------------------------ fit
-    def _solve_machines(self, X: np.ndarray, Ys: np.ndarray, RC: Optional[np.ndarray], p, note=None, comm=None,
-                        resume=None, progress=None, rank_rows=None, hook=None, keep=False):
+    def _solve_machines(self, X: np.ndarray, Ys: np.ndarray, RC, p, note=None, comm=None,
+                        resume=None, progress=None, rank_rows=None, hook=None, keep=False, lab=None):
         """The solves of one fit on one X: machine c has the labels ``Ys[c]`` and the row bounds ``RC[c]`` (RC None:
-        the scalar C); ``Ys`` (1, n) under more rows of RC is one set of labels for all of them (the folds of a
-        cross-validation).  On the GPU one solver: setup() (X upload, norms, operand prep, engine choice) once, then
-        per machine set_labels (after the first), set_row_C (with RC) and solve; the resident Gram built by the
-        first solve is kept by the swaps after it.  ``hook(c, solver)`` runs after machine c's solve on the live
-        GpuSolver.  Returns the alphas, the info dicts, the setup info (None on the CPU) and, with ``keep``, the
-        GpuSolver (else it is dropped here, with its Gram)."""
+        the scalar C; an entry None: the scalar C for that solve); ``Ys`` (1, n) under more rows of RC is one set
+        of labels for all of them (the folds of a cross-validation); ``lab[c]``: the row of Ys that solve c uses
+        (the full-data solve and the folds of each machine of a probability fit).  On the GPU one solver: setup()
+        (X upload, norms, operand prep, engine choice) once, then per machine set_labels (after the first),
+        set_row_C (with RC) and solve; the resident Gram built by the first solve is kept by the swaps after it.
+        ``hook(c, solver, info)`` runs after solve c on the live GpuSolver.  Returns the alphas, the info dicts,
+        the setup info (None on the CPU) and, with ``keep``, the GpuSolver (else it is dropped here, with its
+        Gram)."""
         C = load()
         k, n = Ys.shape
         m = k if RC is None else len(RC)
+        if lab is None:
+            lab = list(range(m)) if k > 1 else [0] * m
         ck = C.read_checkpoint(resume) if isinstance(resume, str) else resume
         kind, dev = self.config.device_kind()
         alphas, infos, setup, solver = [], [], None, None
@@ -390,50 +452,161 @@ class SVC:
                 en = setup.get("engine_note", "")
                 setup["engine_note"] = (en + "; " if en else "") + note
             for c in range(m):
-                if c and k > 1:
-                    solver.set_labels(Ys[c])
+                if c and lab[c] != lab[c - 1]:
+                    solver.set_labels(Ys[lab[c]])
                 if RC is not None:
                     solver.set_row_C(RC[c])
                 a, info = solver.solve(ck, progress)
                 if hook is not None:
-                    hook(c, solver)
+                    hook(c, solver, info)
                 alphas.append(a)
                 infos.append(dict(info))
         else:
             if rank_rows is not None:
                 raise ValueError("partitioned X needs the GPU solver")
             for c in range(m):
-                a, info = C.solve_cpu(X, Ys[c if k > 1 else 0], p, comm, ck, progress, None if RC is None else RC[c])
+                a, info = C.solve_cpu(X, Ys[lab[c]], p, comm, ck, progress, None if RC is None else RC[c])
                 alphas.append(a)
                 infos.append(dict(info))
         return alphas, infos, setup, solver if keep else None
 
+    def _cv_solves(self, X: np.ndarray, Ys: np.ndarray, W: Optional[np.ndarray], p, cv: int, seed: int,
+                   full: Optional[list] = None, note=None, progress=None, keep=False):
+        """Per machine c (labels ``Ys[c]``, weights ``W[c]`` or ones): with ``full`` the full-data solve under the
+        bounds ``full[c]`` (None: the scalar C), then the ``cv`` fold solves, each with the fold's weights zeroed
+        (C_i = 0: alpha_i stays 0, the row is out of the problem) — all through _solve_machines, so on the GPU on
+        one solver, one setup() and one resident Gram.  There a held-out row's decision value is f_i + y_i - b,
+        its gradient entry as every round's f update kept it: written on the device into the solver's slot c
+        (holdout_decision_kernel), downloaded once per machine, and with ``full`` fitted there by
+        platt_fit_kernel against the machine's labels.  On the CPU the decisions come from decision_cpu and the
+        fit from platt_fit_cpu.  Folds: ``cv_folds(n, cv, seed)``, the same for every machine.  Returns the
+        out-of-fold decisions (k, n), the folds, the Platt fits (k dicts; None without ``full``), the full-data
+        solves' alphas and dicts, the folds' dicts per machine, the setup info and the kept GpuSolver."""
+        C = load()
+        k, n = Ys.shape
+        folds = self.cv_folds(n, cv, seed)
+        RC, lab, role = [], [], []  # solve i: machine role[i][0], fold role[i][1] (-1: the full-data solve)
+        for c in range(k):
+            if full is not None:
+                RC.append(full[c])
+                lab.append(c)
+                role.append((c, -1))
+            w = np.ones(n, dtype=np.float64) if W is None else W[c]
+            for j, fold in enumerate(folds):
+                wf = w.copy()
+                wf[fold] = 0.0
+                RC.append(self._row_C(wf, Ys[c]))
+                lab.append(c)
+                role.append((c, j))
+        rows = [np.ascontiguousarray(fold, dtype=np.int32) for fold in folds]
+        dec = np.zeros((k, n), dtype=np.float32)
+        platt = [None] * k
+        on_device = []
+
+        def hook(i, solver, info):  # cold solves (alpha = 0, f = -y): the gradient is the whole decision
+            c, j = role[i]
+            if j >= 0:
+                solver.holdout_decisions(rows[j], float(info["b"]), c)
+            if i + 1 == len(role) or role[i + 1][0] != c:  # machine c's last solve: its labels are still current
+                if full is not None:
+                    platt[c] = dict(solver.platt_fit(c))
+                dec[c] = solver.holdout(c)
+                on_device.append(c)
+
+        alphas, infos, setup, solver = self._solve_machines(X, Ys, RC, p, note, progress=progress, hook=hook,
+                                                            keep=keep, lab=lab)
+        if not on_device:
+            for i, (c, j) in enumerate(role):
+                if j >= 0:
+                    model = C.make_model(X, Ys[c], alphas[i], float(infos[i]["b"]), p.gamma)
+                    dec[c, folds[j]] = C.decision_cpu(model, np.ascontiguousarray(X[folds[j]]), 0)
+            if full is not None:
+                platt = [dict(C.platt_fit_cpu(dec[c], Ys[c])) for c in range(k)]
+        is_full = [j < 0 for _, j in role]
+        f_alphas = [a for a, f in zip(alphas, is_full) if f]
+        f_infos = [s for s, f in zip(infos, is_full) if f]
+        cv_infos = [[s for s, (cc, j) in zip(infos, role) if cc == c and j >= 0] for c in range(k)]
+        return dec, folds, (platt if full is not None else None), f_alphas, f_infos, cv_infos, setup, solver
+
+    def _fit_solves(self, X, y, Ys, sample_weight, probability: int, seed: int, comm, resume, progress, rank_rows,
+                    keep: bool):
+        """The solves of fit(): the machines of Ys, or with ``probability`` folds each machine's full-data solve
+        and fold solves on one Gram (_cv_solves) with the Platt fits.  Returns the native params, the machines'
+        row bounds, the alphas, the full-data solves' dicts, the setup info, the kept GpuSolver and the
+        probability results (None without)."""
+        p, RC, note = self._problem(X.shape[1], y, Ys, sample_weight, comm, resume, rank_rows)
+        if not probability:
+            alphas, infos, setup, solver = self._solve_machines(X, Ys, RC, p, note, comm, resume, progress,
+                                                                rank_rows, keep=keep)
+            return p, RC, alphas, infos, setup, solver, None
+        if RC is None:  # resolved as a weighted fit; the full-data solves keep the scalar C
+            note = self.config.weighted_params(p, comm, resume, rank_rows)
+        full = [None] * len(Ys) if RC is None else list(RC)
+        W = self._weights(y, Ys, sample_weight)
+        dec, folds, platt, alphas, infos, cv_infos, setup, solver = self._cv_solves(
+            X, Ys, W, p, probability, seed, full, note, progress, keep)
+        return p, RC, alphas, infos, setup, solver, (dec, folds, platt, cv_infos)
+
+    def _publish_proba(self, proba) -> None:
+        """cv_decision_, cv_stats_, cv_folds_, probA_, probB_, platt_stats_ of a probability fit (else cleared)"""
+        if proba is None:
+            self.probA_ = self.probB_ = self.platt_stats_ = self.cv_decision_ = None
+            return
+        dec, folds, platt, cv_infos = proba
+        multi = self._multi
+        self.cv_decision_ = np.ascontiguousarray(dec.T) if multi else dec[0]
+        self.cv_stats_ = cv_infos if multi else cv_infos[0]
+        self.cv_folds_ = folds
+        A = np.array([f["A"] for f in platt], dtype=np.float64)
+        B = np.array([f["B"] for f in platt], dtype=np.float64)
+        self.probA_, self.probB_ = (A, B) if multi else (np.float64(A[0]), np.float64(B[0]))
+        stats = [{key: f[key] for key in ("iters", "evals", "fval", "status")} for f in platt]
+        self.platt_stats_ = stats if multi else stats[0]
+        bad = [(c, f["status"]) for c, f in enumerate(platt) if f["status"] != 0]
+        if bad:
+            import warnings
+
+            why = {1: "its line search failed", 2: "it stopped at 100 Newton steps"}
+            warnings.warn("the Platt sigmoid fit did not converge: " +
+                          "; ".join(f"machine {c}: {why.get(s, s)}" for c, s in bad), RuntimeWarning, stacklevel=3)
+
     def fit(self, X, y, comm=None, resume=None, progress: Optional[Callable] = None,
-            rank_rows: Optional[int] = None, sample_weight=None) -> "SVC":
+            rank_rows: Optional[int] = None, sample_weight=None, probability: int = 0,
+            probability_seed: int = 0) -> "SVC":
         """Train.  ``comm``: a native communicator (see dpsvm_amd.parallel) for
         multi-rank training; ``resume``: checkpoint path or native Checkpoint;
-        ``sample_weight``: per-row multipliers of C (with ``class_weight``)."""
+        ``sample_weight``: per-row multipliers of C (with ``class_weight``);
+        ``probability``: folds of the cross-validation whose out-of-fold
+        decisions fit each machine's Platt sigmoid for ``predict_proba`` (0: off;
+        LIBSVM uses 5; folds ``cv_folds(n, probability, probability_seed)``).
+        The settings then resolve as for a weighted fit, and the full-data solve
+        and the folds of every machine run on one resident Gram."""
+        probability = int(probability)
+        if probability != 0 and probability < 2:
+            raise ValueError(f"probability is the number of folds: 0 (off) or >= 2, got {probability}")
         if self.config.engines == "all" or self.config.host_cache_lines or self.config.cache_engine == "chain":
             load_quarantine()  # the quarantined pair-at-a-time cache engines (plugin)
         X = _as_f32_2d(X)
         y1 = _as_1d(y)
         if len(np.unique(y1)) > 2:
-            return self._fit_multi(X, y1, comm, resume, progress, rank_rows, sample_weight)
+            return self._fit_multi(X, y1, comm, resume, progress, rank_rows, sample_weight, probability,
+                                   probability_seed)
         self._multi = False
         ys = self._encode(y)
         n, d = X.shape[0], X.shape[1]
         if rank_rows is None and ys.shape[0] != n:
             raise ValueError("len(y) != X.shape[0]")
         cfg = self.config
-        p, RC, note = self._problem(d, y1, ys[None, :], sample_weight, comm, resume, rank_rows)
         if cfg.log_every and progress is None:
             def progress(it, bh, bl, el, hits, misses):  # noqa: E306
                 print(f"iter {it}  b_hi {bh:.6g}  b_lo {bl:.6g}  gap {bl - bh:.3g}  "
                       f"{it / max(el, 1e-9):.0f} it/s  hits {hits} misses {misses}", flush=True)
         t0 = time.perf_counter()
-        (alpha,), (info,), setup, self._solver = self._solve_machines(X, ys[None, :], RC, p, note, comm, resume,
-                                                                      progress, rank_rows, keep=True)
+        p, RC, (alpha,), (info,), setup, self._solver, proba = self._fit_solves(
+            X, y1, ys[None, :], sample_weight, probability, probability_seed, comm, resume, progress, rank_rows,
+            keep=True)
         self._publish(p, d, time.perf_counter() - t0, setup)
+        self._publish_proba(proba)
         self.alpha_ = alpha
         self.b_ = float(info["b"])
         self.intercept_ = -self.b_
@@ -475,7 +648,7 @@ class SVC:
         self._gpu_pred = None
 
     def _fit_multi(self, X: np.ndarray, y: np.ndarray, comm, resume, progress, rank_rows,
-                   sample_weight=None) -> "SVC":
+                   sample_weight=None, probability: int = 0, probability_seed: int = 0) -> "SVC":
         """One-vs-rest: k machines on one X, the GpuSolver dropped (with its resident Gram) after the last."""
         for name, val in (("comm", comm), ("resume", resume), ("rank_rows", rank_rows)):
             if val is not None:
@@ -486,11 +659,12 @@ class SVC:
             raise ValueError("len(y) != X.shape[0]")
         classes = np.unique(y)
         Ys = np.stack([np.where(y == c, 1.0, -1.0).astype(np.float32) for c in classes])
-        p, RC, note = self._problem(d, y, Ys, sample_weight)
         t0 = time.perf_counter()
-        alphas, infos, setup, self._solver = self._solve_machines(X, Ys, RC, p, note, progress=progress)
+        p, RC, alphas, infos, setup, self._solver, proba = self._fit_solves(
+            X, y, Ys, sample_weight, probability, probability_seed, None, None, progress, None, keep=False)
         self._publish(p, d, time.perf_counter() - t0, setup)
         self._multi = True
+        self._publish_proba(proba)
         self.classes_ = classes
         self.alpha_ = np.stack(alphas).astype(np.float32)
         self.b_ = np.array([i["b"] for i in infos], dtype=np.float32)
@@ -534,7 +708,6 @@ class SVC:
         f_i + y_i - b, read from the solver's gradient — no sub-Gram, no second upload, no predict pass.
         Folds: ``cv_folds(n, cv, seed)``.  ``class_weight='balanced'`` is computed on all n rows.  Settings
         resolve as for a weighted fit.  ``cv_stats_``: the per-fold solve dicts."""
-        C = load()
         X = _as_f32_2d(X)
         y1 = _as_1d(y)
         if len(np.unique(y1)) != 2:
@@ -545,32 +718,15 @@ class SVC:
             raise ValueError("len(y) != X.shape[0]")
         p = self.config.to_native(d)
         W = self._weights(y1, ys[None, :], sample_weight)
-        w = np.ones(n, dtype=np.float64) if W is None else W[0]
         self.config.weighted_params(p)
-        folds = self.cv_folds(n, cv, seed)
-        rcs = []
-        for fold in folds:
-            wf = w.copy()
-            wf[fold] = 0.0
-            rcs.append(self._row_C(wf, ys))
-        grads = []  # the GPU solves' gradients: cold solves (alpha = 0, f = -y)
         t0 = time.perf_counter()
-        alphas, stats, setup, _ = self._solve_machines(X, ys[None, :], np.stack(rcs), p,
-                                                       hook=lambda c, solver: grads.append(solver.gradient()))
-        dec = np.zeros(n, dtype=np.float32)
-        for c, fold in enumerate(folds):
-            b = float(stats[c]["b"])
-            if grads:
-                dec[fold] = (grads[c][fold].astype(np.float64) + ys[fold] - b).astype(np.float32)
-            else:
-                model = C.make_model(X, ys, alphas[c], b, p.gamma)
-                dec[fold] = C.decision_cpu(model, np.ascontiguousarray(X[fold]), 0)
+        dec, folds, _, _, _, stats, setup, _ = self._cv_solves(X, ys[None, :], W, p, cv, seed)
         if setup is not None:
             self.cv_setup_info_ = setup
         self.cv_wall_time_ = time.perf_counter() - t0
-        self.cv_stats_ = stats
+        self.cv_stats_ = stats[0]
         self.cv_folds_ = folds
-        return dec
+        return dec[0]
 
     def cross_val_score(self, X, y, cv: int = 5, seed: int = 0, sample_weight=None) -> float:
         """accuracy of the signs of cross_val_decision (>= 0 -> the positive class)"""
@@ -608,8 +764,9 @@ class SVC:
                 raise ValueError("the multi-class model file holds numeric class labels exactly representable in "
                                  "float32")
             load().write_multi_model(path, model, precision)
-            return
-        load().write_model(path, self.to_model(), precision, legacy)
+        else:
+            load().write_model(path, self.to_model(), precision, legacy)
+        _write_platt(path, getattr(self, "probA_", None), getattr(self, "probB_", None))
 
     # ------------------------------------------------------------------ predict
     def _predictor(self):
@@ -637,6 +794,19 @@ class SVC:
             return self.classes_[np.argmax(dec, axis=1)]  # ties: the lowest class index
         return self._decode(np.where(dec < 0, -1.0, 1.0))  # d >= 0 -> +1 (svmTrain.cu:654-657)
 
+    def predict_proba(self, X) -> np.ndarray:
+        """(n, k) float32 class probabilities, columns in the order of ``classes_``, after
+        ``fit(probability=cv)``: machine c's Platt sigmoid p = 1 / (1 + exp(probA_ d + probB_)) of its decision
+        value; two classes: [1 - p, p] with p = P(classes_[-1]); more: the k values divided by their sum (a row
+        whose sum is 0: 1 / k each).  On the GPU the sigmoids run on the decision GEMM's output before its
+        download.  ``predict`` stays the sign / the argmax of the decision values."""
+        X = _as_f32_2d(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, model has {self.n_features_in_}")
+        if getattr(self, "probA_", None) is None:
+            raise RuntimeError("predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
+        return _predict_proba(self._predictor(), self.to_model, self._multi, X, self.probA_, self.probB_)
+
     def score(self, X, y) -> float:
         yy = _as_1d(y)
         return float(np.mean(self.predict(X) == yy))
@@ -656,12 +826,23 @@ class SVC:
 class _Loaded:
     """What the loaded models share: the device, the GpuPredictor built on first use, the model's scalars."""
 
-    def __init__(self, model, device: str = "auto"):
+    _multi = False
+
+    def __init__(self, model, device: str = "auto", platt=None):
         self.model = model
         self.device = device
         if device != "auto":
             _parse_device(device)  # an unknown string fails here, not at the first prediction
         self._gpu = None
+        self.probA_, self.probB_ = platt if platt is not None else (None, None)  # the sidecar's sigmoids
+
+    def predict_proba(self, X) -> np.ndarray:
+        """SVC.predict_proba on the sigmoids read from the model file's ``.platt`` sidecar"""
+        if self.probA_ is None:
+            raise RuntimeError("predict_proba needs the model file's .platt sidecar (a model saved after "
+                               "fit(probability=cv))")
+        return _predict_proba(self._predictor(), lambda: self.model, self._multi, _as_f32_2d(X), self.probA_,
+                              self.probB_)
 
     @property
     def gamma(self) -> float:
@@ -701,8 +882,10 @@ class LoadedModel(_Loaded):
 class LoadedMultiModel(_Loaded):
     """A one-vs-rest model read from a multi-class model file."""
 
-    def __init__(self, model, device: str = "auto"):
-        super().__init__(model, device)
+    _multi = True
+
+    def __init__(self, model, device: str = "auto", platt=None):
+        super().__init__(model, device, platt)
         self.classes_ = np.asarray(model.classes)
 
     def decision_function(self, X) -> np.ndarray:
@@ -718,8 +901,10 @@ class LoadedMultiModel(_Loaded):
 
 
 def load_model(path: str, device: str = "auto", legacy: bool = False):
-    """A LoadedModel, or a LoadedMultiModel for a multi-class (one-vs-rest) file."""
+    """A LoadedModel, or a LoadedMultiModel for a multi-class (one-vs-rest) file; with the Platt sigmoids of the
+    ``path + ".platt"`` sidecar when there is one (``predict_proba``)."""
     C = load()
     if not legacy and C.is_multi_model(path):
-        return LoadedMultiModel(C.read_multi_model(path), device)
-    return LoadedModel(C.read_model(path, legacy), device)
+        model = C.read_multi_model(path)
+        return LoadedMultiModel(model, device, _read_platt(path, model.k))
+    return LoadedModel(C.read_model(path, legacy), device, _read_platt(path, 1))

@@ -358,6 +358,40 @@ def ws_fupdate_split(x, f, alpha, y, apply_idx, apply_coef, gamma: float, C_: fl
     return r
 
 
+def holdout_decision(f, y, rows, b: float, dec, slot: int = 0):
+    """One launch of holdout_decision_kernel (platt.hip): ``dec`` [slots][n] with
+    dec[slot, i] = float32(float64(f[i]) + y[i] - b) for the rows i of ``rows``
+    (a fold's indices, each in [0, n), any order); every other entry is left as
+    it was."""
+    import numpy as np
+
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))  # noqa: E731
+    return load().k_holdout_decision(f32(f), f32(y), np.asarray(rows, dtype=np.int32).reshape(-1), float(b),
+                                     np.atleast_2d(f32(dec)), int(slot))
+
+
+def platt_fit(dec, y) -> list:
+    """One launch of platt_fit_kernel on ``dec`` and ``y`` [m][n]: a workgroup
+    per machine fits P(y > 0 | d) = 1 / (1 + exp(A d + B)) on its n decisions
+    (Lin, Lin and Weng's Newton method in fp64; fixed summation order, so the
+    result is bit-reproducible).  Returns per machine a dict A, B, iters, evals,
+    fval, status (0 converged, 1 line search failed, 2 stopped at 100 steps)."""
+    import numpy as np
+
+    f32 = lambda a: np.atleast_2d(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))  # noqa: E731
+    return [dict(r) for r in load().k_platt_fit(f32(dec), f32(y))]
+
+
+def proba_rows(dec, A, B):
+    """One launch of proba_rows_kernel on decisions ``dec`` [n][k]: the
+    probabilities p = 1 / (1 + exp(A_c d + B_c)) computed in fp64 and rounded
+    to float32 once; k > 2: divided by the row's sum (a sum of 0: 1 / k each)."""
+    import numpy as np
+
+    f64 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)).reshape(-1)  # noqa: E731
+    return load().k_proba_rows(np.ascontiguousarray(np.asarray(dec, dtype=np.float32)), f64(A), f64(B))
+
+
 def fused_select(f: torch.Tensor, alpha: torch.Tensor, y: torch.Tensor, C_: float, rows_per_group: int = 256):
     """Per-workgroup (up, low) selection keys of the fused / persistent engines
     (classification + wave-64 DPP minimum + LDS across waves): [groups, 2] u64

@@ -156,6 +156,12 @@ struct SolverParams {
   // sample's elements all pass the bound), 1 on, 2 off
   int gram_adapt = 0;
   float gram_cold_tau = 0x1p-22f;
+  // the problem: 0 classification (y = +-1, linear term -1), 1 epsilon-SVR — `y` holds real targets z and the
+  // solvers run the folded 2n-row dual (rows j: alpha_j, y = +1; rows j + n: alpha*_j, y = -1; the n x n Gram
+  // read modulo n; start f = [eps - z, -eps - z]; docs/DESIGN.md §17).  Box clipping, one rank, no resume;
+  // the device solver: one-block working-set rounds on the resident Gram.  SolveResult::alpha has 2n entries.
+  int problem = 0;
+  float svr_epsilon = 0.1f;   // epsilon-SVR: half width of the tube, >= 0
 };
 
 

@@ -427,6 +427,10 @@ struct WsArgs {
                        // kWsAutoUnion rows, kWsCand beyond; 0 = kWsCand); the tail of a list is kKeyNone
   const float* c_row;  // [n] global per-row bounds C_i = C w_i (GpuSolver::set_row_C); nullptr: the scalar C.
                        // Read by the kRowC instantiations of ws_select / ws_solve only (one rank)
+  int64_t fold;        // epsilon-SVR (one rank, one block, resident Gram): the Gram's rows and columns number
+                       // fold = n_x while the state (f / alpha / y: n = nl = 2 fold) holds alpha_j at j and
+                       // alpha*_j at j + fold, K~(a, b) = K(a mod fold, b mod fold); 0: off.  Read by the fold
+                       // kernels of ws_select / ws_merge only
 };
 // keys per side and list of the multi-block selection (ws_select pass 2, the peer exchange)
 constexpr int ws_ncand(int ncand) { return ncand > 0 && ncand < kWsCand ? ncand : kWsCand; }

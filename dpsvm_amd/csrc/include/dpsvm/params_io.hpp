@@ -66,6 +66,8 @@ void for_each_param(SolverParams& p, F&& f) {
   f("gram_precision", p.gram_precision);
   f("gram_adapt", p.gram_adapt);
   f("gram_cold_tau", p.gram_cold_tau);
+  f("problem", p.problem);
+  f("svr_epsilon", p.svr_epsilon);
 }
 
 inline std::string num(double v) {

@@ -330,6 +330,7 @@ struct WsSelectProbe {
   float t = 1.f;
   int64_t p1_round = 0;
   std::vector<float> pass1_us;  // reps > 0: event times of repeated pass-1 launches
+  std::vector<float> select_us; // one block, reps > 0: event times of repeated one-pass launches (plain or fold)
 };
 WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t ldg, const std::vector<float>& f,
                               const std::vector<float>& alpha, const std::vector<float>& y,
@@ -337,7 +338,10 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               const std::vector<float>& apply_coef, const std::vector<int32_t>& nab, int blocks,
                               int p_round, int p_act, int q_max, float C, int64_t outer, int ks = 0,
                               int reps = 0, bool wide = false,
-                              const std::vector<float>& row_C = {});  // [n] per-row bounds (empty: scalar C)
+                              const std::vector<float>& row_C = {},  // [n] per-row bounds (empty: scalar C)
+                              // fold > 0: the epsilon-SVR kernel — f / alpha / y of 2 fold state rows on gram
+                              // [L][ldg >= fold]; done: the run's state (DoneCode) the launch finds
+                              int64_t fold = 0, int done = 0);
 // The one-block merge (ws_merge.hpp) through the two round kernels that run it
 // in every workgroup, one launch each: round `outer` builds parity outer & 1
 // from cand = [G][2][kWsCand] lists (the merge reads the first kWsCand1 keys a
@@ -353,13 +357,15 @@ struct WsGatherProbe {
   int done = 0, q = 0, n_apply = 0;
   float b_hi = 0.f, b_lo = 0.f;
   std::vector<int32_t> idx;  // [q] the set, newest first
+  std::vector<int32_t> line; // [q] the members' Gram lines as the round recorded them (WsCtrl::line)
   std::vector<float> subg;   // [q_max][q_max]
   std::vector<float> aux;    // [3][kWsMax] f / alpha / y of the set
 };
 WsGatherProbe ws_gather_probe(const std::vector<float>& gram, int64_t n, int64_t ldg, const std::vector<uint64_t>& cand,
                               const std::vector<int32_t>& prev_set, const std::vector<float>& f,
                               const std::vector<float>& alpha, const std::vector<float>& y, int q_max, int n_new,
-                              float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer);
+                              float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer,
+                              int64_t fold = 0);  // fold > 0: n = 2 fold state rows on gram [fold][ldg >= fold]
 WsGatherProbe ws_subgram_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<uint64_t>& cand,
                                      const std::vector<int32_t>& prev_set, const std::vector<float>& f,
                                      const std::vector<float>& alpha, const std::vector<float>& y, float gamma,

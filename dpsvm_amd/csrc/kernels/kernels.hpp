@@ -12,6 +12,8 @@ namespace launch {
 
 void row_sqnorm(const float* x, int64_t n, int d, int ld, float* out, hipStream_t s);
 void init_f(const float* y, int64_t off, int64_t nl, float* f, hipStream_t s);
+// epsilon-SVR start of the folded dual: f[j] = eps - z[j], f[j + n] = -eps - z[j] (f: 2 n floats)
+void init_f_svr(const float* z, float eps, int64_t n, float* f, hipStream_t s);
 void fill_i32(int32_t* p, int64_t n, int32_t v, hipStream_t s);
 
 // One SMO iteration's kernels (see device_state.hpp)

@@ -31,6 +31,17 @@ __global__ void init_f_kernel(const float* __restrict__ y, int64_t off, int64_t 
   if (j < nl) f[j] = -y[off + j];  // f = -y (svmTrain.cu:380)
 }
 
+// epsilon-SVR on the folded 2n-row dual: f = y o (Q alpha + p) at alpha = 0 with p = [eps - z, eps + z], i.e.
+// f[j] = eps - z_j (the alpha_j rows, y = +1) and f[j + n] = -eps - z_j (the alpha*_j rows, y = -1)
+__global__ void init_f_svr_kernel(const float* __restrict__ z, float eps, int64_t n, float* __restrict__ f) {
+  int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) {
+    const float zj = z[j];
+    f[j] = eps - zj;
+    f[j + n] = -eps - zj;
+  }
+}
+
 __global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -50,6 +61,12 @@ void init_f(const float* y, int64_t off, int64_t nl, float* f, hipStream_t s) {
   if (nl <= 0) return;
   dev::init_f_kernel<<<dim3((unsigned)((nl + 255) / 256)), 256, 0, s>>>(y, off, nl, f);
   post_launch("init_f", s);
+}
+
+void init_f_svr(const float* z, float eps, int64_t n, float* f, hipStream_t s) {
+  if (n <= 0) return;
+  dev::init_f_svr_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(z, eps, n, f);
+  post_launch("init_f_svr", s);
 }
 
 void fill_i32(int32_t* p, int64_t n, int32_t v, hipStream_t s) {

@@ -27,6 +27,10 @@ namespace dev {
 // are zeroed.
 // Peer exchange: xr is the row's slot in the receive buffers (block p's row
 // ra of a multi-block round: p q_max + ra).
+// kFold (epsilon-SVR, WsArgs::fold = n_x: one rank, the state rows number 2 n_x):
+// the line holds the n_x Gram columns, state row gj reads column gj mod n_x;
+// f / alpha / y come from the 2 n_x-long vectors by the state row.
+template <bool kFold = false>
 __device__ __forceinline__ void ws_gather_row(const WsArgs& a, WsCtrl* c, const int32_t* s_idx, int q, int ra,
                                               const float* line, int xr) {
   const int tid = threadIdx.x;
@@ -69,7 +73,8 @@ __device__ __forceinline__ void ws_gather_row(const WsArgs& a, WsCtrl* c, const 
   }
   for (int b = tid; b < a.q_max; b += kWsGatherThreads) {
     const int64_t gj = b < q ? (int64_t)s_idx[b] : -1;
-    dst[b] = gj >= lo && gj < hi ? line[gj - lo] : 0.f;
+    if constexpr (kFold) dst[b] = gj >= 0 && gj < hi ? line[gj >= a.fold ? gj - a.fold : gj] : 0.f;
+    else dst[b] = gj >= lo && gj < hi ? line[gj - lo] : 0.f;
   }
   if (tid == 0) {
     const int64_t gi = s_idx[ra];
@@ -84,6 +89,7 @@ __device__ __forceinline__ void ws_gather_row(const WsArgs& a, WsCtrl* c, const 
 // workgroup (row a: q random columns of Gram row idx_a — one load per thread;
 // the whole grid issues the scattered reads a single CU could not)
 // ---------------------------------------------------------------------------
+template <bool kFold = false>
 __global__ __launch_bounds__(kWsGatherThreads) void ws_gather_kernel(WsArgs a) {
   __shared__ int32_t s_idx[kWsMax];
   __shared__ WsMergeLds L;
@@ -99,7 +105,8 @@ __global__ __launch_bounds__(kWsGatherThreads) void ws_gather_kernel(WsArgs a) {
   if (blockIdx.x == 0) {
     for (int t = tid; t < q; t += kWsGatherThreads) {
       c->idx[par][t] = s_idx[t];
-      c->line[par][t] = s_idx[t];  // the resident Gram: line i is row i
+      if constexpr (kFold) c->line[par][t] = s_idx[t] >= a.fold ? s_idx[t] - (int32_t)a.fold : s_idx[t];
+      else c->line[par][t] = s_idx[t];  // the resident Gram: line i is row i
     }
     if (tid == 0) {
       c->q[par] = q;
@@ -107,8 +114,9 @@ __global__ __launch_bounds__(kWsGatherThreads) void ws_gather_kernel(WsArgs a) {
       c->b_lo = b_lo;
     }
   }
-  ws_gather_row(a, c, s_idx, q, blockIdx.x, blockIdx.x < q ? a.gram + (int64_t)s_idx[blockIdx.x] * a.ldg : nullptr,
-                blockIdx.x);
+  int64_t gline = blockIdx.x < q ? (int64_t)s_idx[blockIdx.x] : 0;
+  if constexpr (kFold) gline = gline >= a.fold ? gline - a.fold : gline;
+  ws_gather_row<kFold>(a, c, s_idx, q, blockIdx.x, blockIdx.x < q ? a.gram + gline * a.ldg : nullptr, blockIdx.x);
   if (lead) WS_STAMP(8);
 }
 
@@ -878,6 +886,7 @@ void ws_xcollect_cand(const WsArgs& a, hipStream_t s) {
 }
 
 void ws_merge_multi(const WsArgs& a, hipStream_t s) {
+  DPSVM_CHECK(a.fold == 0, "ws_merge_multi: multi-block rounds are not implemented for regression (fold)");
   DPSVM_CHECK(a.blocks > 1 && a.blocks <= kWsMaxBlocks && a.blocks * a.q_max <= kWsMaxAll && a.G_all <= kWsMaxGroups && a.q_max % 2 == 0 &&
                   (!a.cache || (ws_cache_multi_supported(a.L, a.blocks, a.q_max) && a.blocks * a.q_max <= dev::kMH / 2)),
               "ws_merge_multi: multi-block rounds need <= 256 candidate lists, an even q_max and "
@@ -889,6 +898,14 @@ void ws_merge_multi(const WsArgs& a, hipStream_t s) {
 }
 
 void ws_gather(const WsArgs& a, hipStream_t s) {
+  if (a.fold > 0) {  // epsilon-SVR: the dense one-block gather with Gram access modulo fold
+    DPSVM_CHECK(a.blocks == 1 && !a.cache && a.world == 1 && a.xpeer == nullptr && a.off == 0 && a.n == 2 * a.fold &&
+                    a.nl == a.n && a.ldg >= a.fold,
+                "ws_gather: regression (fold) runs one-block rounds on the resident Gram, one rank");
+    dev::ws_gather_kernel<true><<<dim3(a.q_max), dev::kWsGatherThreads, 0, s>>>(a);
+    post_launch("ws_gather_fold", s);
+    return;
+  }
   if (a.blocks > 1) {
     dev::ws_gather_multi_kernel<<<dim3(a.blocks * a.q_max), dev::kWsGatherThreads, 0, s>>>(a);
     post_launch("ws_gather_multi", s);
@@ -896,12 +913,13 @@ void ws_gather(const WsArgs& a, hipStream_t s) {
     dev::ws_gather_lines_kernel<<<dim3(a.q_max), dev::kWsGatherThreads, 0, s>>>(a);
     post_launch("ws_gather_lines", s);
   } else {
-    dev::ws_gather_kernel<<<dim3(a.q_max), dev::kWsGatherThreads, 0, s>>>(a);
+    dev::ws_gather_kernel<false><<<dim3(a.q_max), dev::kWsGatherThreads, 0, s>>>(a);
     post_launch("ws_gather", s);
   }
 }
 
 void ws_merge(const WsArgs& a, hipStream_t s) {
+  DPSVM_CHECK(a.fold == 0, "ws_merge: the kernel-row cache is not implemented for regression (fold)");
   dev::ws_merge_kernel<<<1, dev::kWsGatherThreads, 0, s>>>(a);
   post_launch("ws_merge", s);
 }

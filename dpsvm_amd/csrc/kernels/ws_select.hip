@@ -532,6 +532,173 @@ __global__ __launch_bounds__(kP1Threads) void ws_pass1_v4_kernel(WsArgs a) {
   }
 }
 
+// epsilon-SVR (a.fold = n_x > 0): MODE 0 on the folded 2 n_x-row dual.  The
+// kernel matrix of the state rows is the n_x x n_x Gram tiled 2 x 2, so the
+// grid covers the n_x Gram columns (ws_geometry(n_x, 1)) and the thread owning
+// column j sums acc = sum_k coef_k gram[line_k][j] once — MODE 0's partitions,
+// list order and f_add1 — then adds the same acc to f[j] and f[j + n_x]: every
+// Gram element is loaded once a round for both halves.  Both variables are
+// classified (alpha / y at j and j + n_x), two key slots per side per column:
+// slot 2 r is row j, slot 2 r + 1 row j + n_x; the extraction is MODE 0's
+// generic one (nc rounds of wave minima) over 2 RPT slots.  One rank, one
+// block, scalar C, no peer exchange.
+template <int RPT>
+__global__ __launch_bounds__((kWsSelThreads * ws_parts<RPT>())) void ws_select_fold_kernel(WsArgs a) {
+  constexpr int PARTS = ws_parts<RPT>();
+  constexpr int CH = 48 / RPT;  // Gram loads in flight per thread (RPT <= 4)
+  constexpr int KS2 = 2 * RPT;  // key slots per side
+  static_assert(RPT <= 4, "fold: the resident Gram bounds n_x (rpt <= 4)");
+  __shared__ int32_t s_idx[kWsMax];  // lines of the changed rows
+  __shared__ float s_coef[kWsMax];
+  __shared__ float s_part[PARTS - 1][kWsSelThreads * RPT];
+  __shared__ uint64_t s_wc[kWsSelThreads / 64][2][kWsCand];
+  WsCtrl* c = a.ctrl;
+  const int tid = threadIdx.x & (kWsSelThreads - 1), part = threadIdx.x / kWsSelThreads;
+  if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(6);
+  const int na = c->n_apply;
+  const int done = c->done;
+  if (na == 0 && done != kRunning) return;
+  for (int k = threadIdx.x; k < na; k += kWsSelThreads * PARTS) {
+    s_idx[k] = c->apply_line[k];
+    s_coef[k] = c->apply_coef[k];
+  }
+  __syncthreads();
+  const int64_t nx = a.fold;
+  const int64_t base = (int64_t)blockIdx.x * a.rpt * kWsSelThreads + tid;
+  float f0[RPT], f1[RPT];  // f[j], f[j + nx]
+  bool has[RPT];
+#pragma unroll
+  for (int r = 0; r < RPT; ++r) {
+    const int64_t j = base + (int64_t)r * kWsSelThreads;
+    has[r] = r < a.rpt && j < nx;
+    f0[r] = has[r] && part == 0 ? a.f[j] : 0.f;
+    f1[r] = has[r] && part == 0 ? a.f[j + nx] : 0.f;
+  }
+  if (na > 0) {
+    float acc[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) acc[r] = 0.f;
+    const int per = (na + PARTS - 1) / PARTS;
+    const int k_lo = min(na, part * per), k_hi = min(na, k_lo + per);
+    for (int k0 = k_lo; k0 < k_hi; k0 += CH) {
+      float kv[CH][RPT];
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        const int kk = min(k0 + u, k_hi - 1);
+        const float* row = a.gram + (int64_t)s_idx[kk] * a.ldg;
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) kv[u][r] = has[r] ? row[base + r * kWsSelThreads] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        if (k0 + u < k_hi) {
+          const float cc = s_coef[k0 + u];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) acc[r] = f_add1(acc[r], cc, kv[u][r]);
+        }
+      }
+    }
+    if (part > 0) {
+#pragma unroll
+      for (int r = 0; r < RPT; ++r) s_part[part - 1][r * kWsSelThreads + tid] = acc[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 1; p < PARTS; ++p) {
+#pragma unroll
+      for (int r = 0; r < RPT; ++r) {
+#pragma clang fp contract(off)
+        acc[r] = acc[r] + s_part[p - 1][r * kWsSelThreads + tid];
+      }
+    }
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+#pragma clang fp contract(off)
+      f0[r] = f0[r] + acc[r];
+      f1[r] = f1[r] + acc[r];
+      if (has[r] && part == 0) {
+        const int64_t j = base + r * kWsSelThreads;
+        a.f[j] = f0[r];
+        a.f[j + nx] = f1[r];
+        bad |= !isfinite(f0[r]) || !isfinite(f1[r]);
+      }
+    }
+    if (bad) atomicOr(&c->nonfinite, 1);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(10);
+  if (done != kRunning) return;  // uniform
+
+  // partition 0 classifies both halves and extracts; the other waves idle to the barrier
+  uint64_t ku[KS2], kl[KS2];
+#pragma unroll
+  for (int r = 0; r < RPT; ++r) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      ku[2 * r + h] = kl[2 * r + h] = kKeyNone;
+      if (has[r] && part == 0) {
+        const int64_t gj = base + r * kWsSelThreads + (h ? nx : 0);
+        const float av = a.alpha[gj], yv = a.y[gj], fv = h ? f1[r] : f0[r];
+        if (in_up(av, yv, a.C)) ku[2 * r + h] = make_key(fv, (uint32_t)gj);
+        if (in_low(av, yv, a.C)) kl[2 * r + h] = make_key(-fv, (uint32_t)gj);
+      }
+    }
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+  constexpr int NC = kWsCand1;
+  constexpr int W = kWsSelThreads / 64;
+  const uint64_t below = (1ull << lane) - 1ull;
+  auto place = [&](uint64_t k, int smaller) {
+    const uint64_t none = __ballot(k == kKeyNone);
+    return k == kKeyNone ? 64 - __popcll(none) + __popcll(none & below) : smaller;
+  };
+  for (int round = 0; round < NC && part == 0; ++round) {
+    uint64_t mu = kKeyNone, ml = kKeyNone;
+#pragma unroll
+    for (int r = 0; r < KS2; ++r) {
+      mu = ku[r] < mu ? ku[r] : mu;
+      ml = kl[r] < ml ? kl[r] : ml;
+    }
+    mu = wave_min_u64(mu);
+    ml = wave_min_u64(ml);
+    if (lane == 0) {
+      s_wc[wave][0][round] = mu;
+      s_wc[wave][1][round] = ml;
+    }
+#pragma unroll
+    for (int r = 0; r < KS2; ++r) {
+      if (ku[r] == mu) ku[r] = kKeyNone;
+      if (kl[r] == ml) kl[r] = kKeyNone;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    // lane l: entry l % kWsCand of wave l / kWsCand's list, as MODE 0's merge of the four lists
+    static_assert(W * kWsCand == 64, "one merge entry per lane");
+    __shared__ uint64_t s_top[2][NC];
+    const bool have = lane % kWsCand < NC;
+    const uint64_t eu = have ? s_wc[lane / kWsCand][0][lane % kWsCand] : kKeyNone;
+    const uint64_t el = have ? s_wc[lane / kWsCand][1][lane % kWsCand] : kKeyNone;
+    int cu = 0, cl = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+#pragma unroll
+      for (int r = 0; r < NC; ++r) {
+        cu += s_wc[w][0][r] < eu ? 1 : 0;
+        cl += s_wc[w][1][r] < el ? 1 : 0;
+      }
+    }
+    const int pu = place(eu, cu), pl = place(el, cl);
+    if (pu < NC) s_top[0][pu] = eu;
+    if (pl < NC) s_top[1][pl] = el;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    uint64_t* out = a.cand_out + (size_t)blockIdx.x * 2 * kWsCand;
+    if (lane < NC) out[lane] = s_top[0][lane];
+    else if (lane >= 32 && lane < 32 + NC) out[kWsCand + lane - 32] = s_top[1][lane - 32];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(7);
+}
+
 // Multi-block rounds over the peer exchange: every rank's line-search partials
 // (pushed by pass 1 into this rank's receive buffer) into a.part, the layout the
 // all-gather leaves — pass 2 then reads them as from the collective.  Runs when
@@ -602,7 +769,24 @@ static void ws_select_mode(const WsArgs& a, hipStream_t s) {
   ws_select_rpt<MODE, false>(a, s);
 }
 
+// epsilon-SVR: the folded one-pass kernel, grid over the fold Gram columns
+static void ws_select_fold(const WsArgs& a, hipStream_t s) {
+  int32_t G = 0, rpt = 0;
+  ws_geometry(a.fold, 1, &G, &rpt);
+  DPSVM_CHECK(a.blocks == 1 && a.world == 1 && a.xpeer == nullptr && a.c_row == nullptr && a.cache == 0,
+              "ws_select: regression (fold) runs one-block rounds on the resident Gram, one rank, scalar C");
+  DPSVM_CHECK(a.n == 2 * a.fold && a.nl == a.n && a.off == 0 && a.G == G && a.rpt == rpt && a.ldg >= a.fold,
+              "ws_select: fold needs 2 fold state rows and the selection geometry of the fold Gram columns");
+  DPSVM_CHECK(a.rpt <= 4, "ws_select: fold takes <= 262,144 Gram columns (4 a selection thread)");
+  const dim3 grid(a.G), threads(kWsSelThreads * 4);
+  if (a.rpt <= 1) dev::ws_select_fold_kernel<1><<<grid, threads, 0, s>>>(a);
+  else if (a.rpt <= 2) dev::ws_select_fold_kernel<2><<<grid, threads, 0, s>>>(a);
+  else dev::ws_select_fold_kernel<4><<<grid, threads, 0, s>>>(a);
+  post_launch("ws_select_fold", s);
+}
+
 void ws_select(const WsArgs& a, hipStream_t s) {
+  if (a.fold > 0) return ws_select_fold(a, s);
   if (a.blocks > 1) {
     ws_select_pass(a, 1, s);  // d_f + line-search partials
     ws_select_mode<2>(a, s);  // f += t d_f, candidates
@@ -622,6 +806,7 @@ static bool ws_pass1_nt(const WsArgs& a) {
 }
 
 void ws_select_pass(const WsArgs& a, int pass, hipStream_t s) {
+  DPSVM_CHECK(a.fold == 0, "ws_select_pass: multi-block rounds are not implemented for regression (fold)");
   if (pass == 1 && a.p1v4) {
     const dim3 g(a.p1G * std::max(1, a.ks));
     if (ws_pass1_nt(a)) dev::ws_pass1_v4_kernel<true><<<g, dev::kP1Threads, 0, s>>>(a);

@@ -274,6 +274,8 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("gram_precision", &SolverParams::gram_precision)
       .def_readwrite("gram_adapt", &SolverParams::gram_adapt)
       .def_readwrite("gram_cold_tau", &SolverParams::gram_cold_tau)
+      .def_readwrite("problem", &SolverParams::problem)
+      .def_readwrite("svr_epsilon", &SolverParams::svr_epsilon)
       .def("to_json", [](const SolverParams& p) { return params_json(p); })
       .def("update_from_json", [](SolverParams& p, const std::string& t) { apply_params_json(t, p); });
 
@@ -523,7 +525,8 @@ PYBIND11_MODULE(_C, m) {
     }
     ds.x = from_np(x);
     ds.y = from_np(y);
-    for (auto& v : ds.y) v = v > 0 ? 1.f : -1.f;
+    if (p.problem == 0)  // epsilon-SVR (problem 1): y holds the real targets
+      for (auto& v : ds.y) v = v > 0 ? 1.f : -1.f;
     auto prog = wrap_progress(progress);
     SolveResult r;
     {
@@ -859,11 +862,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("k_ws_select", [vi](const F32& gram, int64_t L, int64_t ldg, const F32& f, const F32& alpha, const F32& y,
                             const F32& dalpha, const I32& lines, const F32& coef, const I32& nab, int blocks,
                             int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps, bool wide,
-                            py::object row_C) {
+                            py::object row_C, int64_t fold, int done) {
     const auto r = kernels::ws_select_probe(from_np(gram), L, ldg, from_np(f), from_np(alpha), from_np(y),
                                             from_np(dalpha), vi(lines), from_np(coef), vi(nab), blocks, p_round, p_act,
                                             q_max, C, outer, ks, reps, wide,
-                                            row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()));
+                                            row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()), fold,
+                                            done);
     py::dict d;
     d["f"] = to_np(r.f);
     d["alpha"] = to_np(r.alpha);
@@ -876,6 +880,7 @@ PYBIND11_MODULE(_C, m) {
     d["p1G"] = r.p1G;
     d["t"] = r.t;
     d["pass1_us"] = r.pass1_us;
+    d["select_us"] = r.select_us;
     d["p_act"] = r.p_act;
     d["n_damped"] = r.n_damped;
     d["p1_round"] = r.p1_round;
@@ -884,13 +889,14 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("gram"), py::arg("L"), py::arg("ldg"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("dalpha"),
         py::arg("lines"), py::arg("coef"), py::arg("nab"), py::arg("blocks"), py::arg("p_round"), py::arg("p_act"),
         py::arg("q_max"), py::arg("C"), py::arg("outer"), py::arg("ks") = 0, py::arg("reps") = 0,
-        py::arg("wide") = false, py::arg("row_C") = py::none());
+        py::arg("wide") = false, py::arg("row_C") = py::none(), py::arg("fold") = 0, py::arg("done") = 0);
   auto vu = [](const U64& a) { return std::vector<uint64_t>(a.data(), a.data() + a.size()); };
   auto gather_dict = [](const kernels::WsGatherProbe& r) {
     py::dict d;
     d["done"] = r.done;
     d["q"] = r.q;
     d["idx"] = r.idx;
+    d["line"] = r.line;
     d["b_hi"] = r.b_hi;
     d["b_lo"] = r.b_lo;
     d["n_apply"] = r.n_apply;
@@ -900,12 +906,14 @@ PYBIND11_MODULE(_C, m) {
   };
   m.def("k_ws_gather", [vi, vu, gather_dict](const F32& gram, int64_t n, int64_t ldg, const U64& cand, const I32& prev,
                                              const F32& f, const F32& alpha, const F32& y, int q_max, int n_new,
-                                             float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer) {
+                                             float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer,
+                                             int64_t fold) {
     return gather_dict(kernels::ws_gather_probe(from_np(gram), n, ldg, vu(cand), vi(prev), from_np(f), from_np(alpha),
-                                                from_np(y), q_max, n_new, eps, iter, max_iter, nonfinite, outer));
+                                                from_np(y), q_max, n_new, eps, iter, max_iter, nonfinite, outer,
+                                                fold));
   }, py::arg("gram"), py::arg("n"), py::arg("ldg"), py::arg("cand"), py::arg("prev"), py::arg("f"), py::arg("alpha"),
         py::arg("y"), py::arg("q_max"), py::arg("n_new"), py::arg("eps"), py::arg("iter"), py::arg("max_iter"),
-        py::arg("nonfinite"), py::arg("outer"));
+        py::arg("nonfinite"), py::arg("outer"), py::arg("fold") = 0);
   m.def("k_ws_subgram_split", [vi, vu, gather_dict](const F32& x, int64_t n, int d, const U64& cand, const I32& prev,
                                                     const F32& f, const F32& alpha, const F32& y, float gamma,
                                                     int q_max, int n_new, float eps, int64_t iter, int64_t max_iter,

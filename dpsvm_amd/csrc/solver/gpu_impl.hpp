@@ -129,6 +129,13 @@ struct GpuSolver::Impl {
   SmoArgs args{};
   float gamma = 0.f;
   int64_t n = 0, nl = 0, off = 0, x_rows = 0, G = 0, ldl = 0, L = 0;
+  // state rows: the length of alpha / y / f and of SolveResult::alpha.  n, except epsilon-SVR (p.problem == 1:
+  // one rank, ws-dense, one block) where the folded dual has 2n of them while X, |x|^2, the split operands, the
+  // Gram and every shard / geometry quantity above stay n-sized (wsa.fold = n); z: the targets (device, host)
+  int64_t ns = 0;
+  float* z = nullptr;
+  std::vector<float> h_z;
+  bool svr() const { return p.problem == 1; }
   int d = 0, dp = 0;
   bool replicated = true, dense = false;
   EngineKind kind = EngineKind::Chain;

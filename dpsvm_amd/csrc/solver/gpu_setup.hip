@@ -47,7 +47,7 @@ GpuSolver::Impl::~Impl() {
                     (void*)records, (void*)my_record, (void*)pf, (void*)rf, (void*)rcf, (void*)stamps,
                     (void*)plru_meta, (void*)plru_stats, (void*)wsctrl, (void*)wscand, (void*)wssub, (void*)wsdfs, (void*)wsdalpha, (void*)wspart, (void*)wssorted,
                     (void*)wsxq, (void*)wsxqsq, (void*)wsiota, xs, (void*)xsh, wsxs, (void*)wsxsh, (void*)row_c,
-                    (void*)holdout, (void*)holdout_rows, (void*)platt_out})
+                    (void*)holdout, (void*)holdout_rows, (void*)platt_out, (void*)z})
     if (ptr) (void)hipFree(ptr);
   if (status_h) (void)hipHostFree(status_h);
   if (hlines_h) (void)hipHostFree(hlines_h);
@@ -144,6 +144,17 @@ void GpuSolver::set_labels(const float* y) {
   auto& m = *impl_;
   DPSVM_CHECK(m.engine && m.y, "set_labels: call setup() first");
   DPSVM_CHECK(y != nullptr, "set_labels: y is null");
+  if (m.svr()) {
+    // epsilon-SVR: other targets on the same rows; y (+1 / -1 per half) stays, the next solve starts f from z
+    for (int64_t i = 0; i < m.n; ++i) DPSVM_CHECK(std::isfinite(y[i]), "set_labels: regression targets must be finite");
+    HIP_CHECK(hipSetDevice(m.device));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+    m.h_z.assign(y, y + m.n);
+    HIP_CHECK(hipMemcpyAsync(m.z, m.h_z.data(), m.n * 4, hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+    m.problem_swapped = true;
+    return;
+  }
   HIP_CHECK(hipSetDevice(m.device));
   HIP_CHECK(hipStreamSynchronize(m.stream));
   m.h_y.assign(y, y + m.n);
@@ -156,6 +167,7 @@ void GpuSolver::set_labels(const float* y) {
 void GpuSolver::set_row_C(const float* c) {
   auto& m = *impl_;
   DPSVM_CHECK(m.engine && m.y, "set_row_C: call setup() first");
+  DPSVM_CHECK(!m.svr(), "set_row_C: per-row C is not implemented for regression (epsilon-SVR)");
   DPSVM_CHECK(m.working_set() && m.world == 1 && !m.ws_recompute,
               "set_row_C: per-row C runs on the working-set engines (ws-dense, ws-cache with the row cache) on one "
               "rank");
@@ -354,7 +366,30 @@ void check_and_choose_policy(GpuSolver::Impl& m, SetupState& s, int64_t n, int d
   DPSVM_CHECK(m.p.C > 0.f, "C must be > 0");
   DPSVM_CHECK(m.p.rows_per_group % kFusedThreads == 0 && m.p.rows_per_group >= 0,
               "rows_per_group must be a multiple of 256");
+  DPSVM_CHECK(m.p.problem == 0 || m.p.problem == 1, "problem must be 0 (classification) or 1 (epsilon-SVR)");
+  if (m.svr()) {
+    // epsilon-SVR: the folded 2n-row dual on one-block working-set rounds over the resident Gram; everything
+    // else is refused here, before any device state exists (docs/DESIGN.md §17)
+    const SolverParams& p = m.p;
+    DPSVM_CHECK(p.svr_epsilon >= 0.f && std::isfinite(p.svr_epsilon), "epsilon-SVR: svr_epsilon must be >= 0");
+    DPSVM_CHECK(p.clip == ClipMode::Box,
+                "epsilon-SVR runs with box clipping (clip=box): a pair (j, j + n) has eta = 0 and only the joint "
+                "box removes its common part");
+    DPSVM_CHECK(m.outer_world == 1 && !p.force_collectives && p.exchange != 2,
+                "epsilon-SVR: multi-rank solves, forced collectives and the peer exchange are not implemented");
+    DPSVM_CHECK(p.solver == 2 && p.engines == 0,
+                "epsilon-SVR: not implemented on the pair-at-a-time engines (solver must be ws, engines production)");
+    DPSVM_CHECK(p.ws_blocks == 1, "epsilon-SVR: multi-block rounds are not implemented (ws_blocks must be 1)");
+    DPSVM_CHECK(!p.force_cache && p.cache_lines == 0 && p.host_cache_lines == 0 && p.ws_recompute != 1,
+                "epsilon-SVR: the kernel-row cache (ws-cache) and recompute rounds are not implemented: the Gram "
+                "must be resident");
+    DPSVM_CHECK(p.x_mode != 2 && s.n_x_rows == n, "epsilon-SVR: partitioned X is not implemented");
+    DPSVM_CHECK(p.checkpoint_every == 0, "epsilon-SVR: checkpoints and resume are not implemented");
+    DPSVM_CHECK(n < (int64_t)1 << 30, "epsilon-SVR: 2 n must fit in 31 bits (packed selection keys)");
+    for (int64_t i = 0; i < n; ++i) DPSVM_CHECK(std::isfinite(s.yh[i]), "epsilon-SVR: targets must be finite");
+  }
   m.n = n;
+  m.ns = m.svr() ? 2 * n : n;
   m.d = d;
   m.dp = pad_features(d);
   m.gamma = resolve_gamma(m.p.gamma, d);
@@ -479,19 +514,31 @@ void row_norms(GpuSolver::Impl& m) {
 // cache is sized from the free memory
 void place_vectors(GpuSolver::Impl& m, SetupState& s) {
   const int64_t n = m.n;
-  const int64_t n_pad = round_up(std::max<int64_t>(n, m.off + m.ldl), 128) + 512;
+  // (state rows: y / alpha / f hold m.ns entries — 2n in regression; xsq is an X-row vector, same padding)
+  const int64_t n_pad = round_up(std::max<int64_t>(m.ns, m.off + m.ldl), 128) + 512;
   m.xsq = dmalloc<float>((size_t)n_pad, &m.bytes);
   m.y = dmalloc<float>((size_t)n_pad, &m.bytes);
   m.alpha = dmalloc<float>((size_t)n_pad, &m.bytes);
   HIP_CHECK(hipMemsetAsync(m.xsq, 0, n_pad * 4, m.stream));
   HIP_CHECK(hipMemsetAsync(m.y, 0, n_pad * 4, m.stream));
   HIP_CHECK(hipMemsetAsync(m.alpha, 0, n_pad * 4, m.stream));
-  m.h_y.assign(s.yh, s.yh + n);
-  for (auto& v : m.h_y) v = v > 0 ? 1.f : -1.f;
-  HIP_CHECK(hipMemcpyAsync(m.y, m.h_y.data(), n * 4, hipMemcpyHostToDevice, m.stream));
+  if (m.svr()) {
+    // the folded dual's labels: +1 for the alpha rows, -1 for the alpha* rows; the targets beside them
+    m.h_y.assign((size_t)m.ns, 1.f);
+    std::fill(m.h_y.begin() + n, m.h_y.end(), -1.f);
+    m.h_z.assign(s.yh, s.yh + n);
+    m.z = dmalloc<float>((size_t)n, &m.bytes);
+    HIP_CHECK(hipMemcpyAsync(m.z, m.h_z.data(), n * 4, hipMemcpyHostToDevice, m.stream));
+  } else {
+    m.h_y.assign(s.yh, s.yh + n);
+    for (auto& v : m.h_y) v = v > 0 ? 1.f : -1.f;
+  }
+  HIP_CHECK(hipMemcpyAsync(m.y, m.h_y.data(), m.ns * 4, hipMemcpyHostToDevice, m.stream));
   row_norms(m);
-  m.f = dmalloc<float>((size_t)m.ldl, &m.bytes);
-  HIP_CHECK(hipMemsetAsync(m.f, 0, m.ldl * 4, m.stream));
+  // the local gradient: ldl padded shard rows; regression (one rank): the 2n state rows
+  const int64_t f_rows = m.svr() ? std::max(m.ldl, m.ns) : m.ldl;
+  m.f = dmalloc<float>((size_t)f_rows, &m.bytes);
+  HIP_CHECK(hipMemsetAsync(m.f, 0, f_rows * 4, m.stream));
   m.partials = dmalloc<uint64_t>((size_t)2 * m.G, &m.bytes);
   m.ctrl = dmalloc<SmoCtrl>(1, &m.bytes);
   HIP_CHECK(hipHostMalloc((void**)&m.status_h, sizeof(SmoStatus), hipHostMallocMapped));
@@ -797,6 +844,9 @@ void pick_engine(GpuSolver::Impl& m, const SetupState& s) {
     if (!m.info.engine_note.empty()) why += " (" + m.info.engine_note + ")";
     DPSVM_CHECK(false, why + "; the pair-at-a-time cache / partitioned-X engines are quarantined: set engines=all");
   }
+  DPSVM_CHECK(!m.svr() || m.kind == EngineKind::WsDense,
+              "epsilon-SVR: the Gram must be resident (ws-dense); the kernel-row cache (ws-cache), recompute "
+              "rounds and the pair-at-a-time engines are not implemented for regression");
   if (m.persistent() && !m.census(m.kind)) {
     DPSVM_CHECK(m.p.persist != 2, "persistent engine requested (persist=on) but its grid is not co-resident (" +
                                       m.info.engine_note + ")");
@@ -876,6 +926,16 @@ void fill_ws_args(GpuSolver::Impl& m, const SetupState& s) {
   w.n = m.n;
   w.nl = m.nl;
   w.off = m.off;
+  if (m.svr()) {
+    // the folded dual: 2n state rows on the n x n Gram; the selection geometry (s.ws_G, s.ws_rpt) is that of
+    // the n Gram columns, each carrying two state rows
+    DPSVM_CHECK(shape.blocks == 1 && !m.xch && m.world == 1 && m.nl == m.n && m.off == 0,
+                "epsilon-SVR: one-block rounds on one rank only");
+    DPSVM_CHECK(s.ws_rpt <= 4, "epsilon-SVR: at most 262,144 rows (4 Gram columns a selection thread)");
+    w.n = w.nl = m.ns;
+    w.fold = m.n;
+    m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + "epsilon-SVR: folded 2n, one block";
+  }
   w.G = s.ws_G;
   w.p1G = s.ws_G;  // multi-block rounds take the wide pass-1 geometry below
   w.rpt = s.ws_rpt;

@@ -218,6 +218,7 @@ ShrinkingSolver::~ShrinkingSolver() = default;
 GpuSetupInfo ShrinkingSolver::setup(const float* x, int64_t n, int d, const float* y_in) {
   auto& m = *impl_;
   DPSVM_CHECK(n >= 2 && d >= 1, "shrinking: need at least 2 samples and 1 feature");
+  DPSVM_CHECK(m.p.problem == 0, "shrinking is not implemented for regression (epsilon-SVR)");
   m.x = x;
   m.n = n;
   m.d = d;

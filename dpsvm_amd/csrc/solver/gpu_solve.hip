@@ -50,6 +50,11 @@ void GpuSolver::Impl::snapshot(const SmoStatus& st) {
 
 // every rank: the whole gradient (the solve's f shards all-gathered)
 std::vector<float> GpuSolver::Impl::gather_f() {
+  if (svr()) {  // one rank: the 2n state rows as they lie
+    std::vector<float> out((size_t)ns);
+    HIP_CHECK(hipMemcpy(out.data(), f, ns * 4, hipMemcpyDeviceToHost));
+    return out;
+  }
   std::vector<float> floc((size_t)ldl, 0.f), fall((size_t)ldl * world);
   HIP_CHECK(hipMemcpy(floc.data(), f, nl * 4, hipMemcpyDeviceToHost));
   if (world > 1) {
@@ -90,6 +95,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
 
   // per-row C: refused combinations before any state changes (a refused call keeps a requested Gram reuse)
   DPSVM_CHECK(!(m.wsa.c_row && resume), "per-row C (set_row_C): resume is not supported");
+  DPSVM_CHECK(!(m.svr() && resume), "epsilon-SVR: resume is not implemented");
   if (m.wsa.c_row) {
     // the bounds were validated against the labels current at set_row_C; set_labels may have come after
     bool pos = false, neg = false;
@@ -111,7 +117,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   // ---- state init (alpha = 0, f = -y, empty cache) or resume ----
   int64_t iter0 = 0;
   float b_hi0 = 0.f, b_lo0 = 0.f;
-  HIP_CHECK(hipMemsetAsync(m.alpha, 0, m.n * 4, m.stream));
+  HIP_CHECK(hipMemsetAsync(m.alpha, 0, m.ns * 4, m.stream));
   if (resume) {
     check_resume(*resume, m.n, m.d, m.p, m.gamma);
     HIP_CHECK(hipMemcpyAsync(m.alpha, resume->alpha.data(), m.n * 4, hipMemcpyHostToDevice, m.stream));
@@ -128,6 +134,8 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
     HIP_CHECK(hipMemcpy(fh.data(), m.f, m.nl * 4, hipMemcpyDeviceToHost));
     for (int64_t j = 0; j < m.nl; ++j) fh[j] -= m.h_y[m.off + j];
     HIP_CHECK(hipMemcpy(m.f, fh.data(), m.nl * 4, hipMemcpyHostToDevice));
+  } else if (m.svr()) {
+    launch::init_f_svr(m.z, m.p.svr_epsilon, m.n, m.f, m.stream);  // f = [eps - z, -eps - z]
   } else {
     launch::init_f(m.y, m.off, m.nl, m.f, m.stream);
   }
@@ -271,7 +279,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   }
   // ================= end of timed region =================
 
-  if (trace::verify_enabled()) {
+  if (trace::verify_enabled() && !m.svr()) {  // (regression: skipped — the predict GEMM takes n-row alphas)
     // invariants: alpha in [0, C]; f consistent with alpha, i.e. the
     // incrementally updated f_j equals sum_i alpha_i y_i K(i, j) - y_j recomputed
     // from scratch (MFMA predict GEMM); float drift over 10^5 updates stays ~1e-5.
@@ -351,8 +359,8 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
       fclose(fp);
     }
   }
-  res.alpha.resize((size_t)m.n);
-  HIP_CHECK(hipMemcpy(res.alpha.data(), m.alpha, m.n * 4, hipMemcpyDeviceToHost));
+  res.alpha.resize((size_t)m.ns);  // regression: [alpha | alpha*]
+  HIP_CHECK(hipMemcpy(res.alpha.data(), m.alpha, m.ns * 4, hipMemcpyDeviceToHost));
   // the solve ended by its own stop rules: the lines hold a whole Gram (no engine writes them after the GEMM)
   m.gram_valid = m.dense && (st.done == kConverged || st.done == kMaxIter || st.done == kNoPair);
   return res;

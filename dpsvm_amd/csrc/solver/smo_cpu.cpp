@@ -100,6 +100,22 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   const float* Y = ds.y.data();
   // per-row bounds C_i (global n; nullptr: the scalar C): the compare-form sets and the two-bound pair step
   const float* Cr = row_C;
+  // epsilon-SVR (p.problem == 1): ds.y holds the targets z; the folded dual has ns = 2n state rows (alpha_j at
+  // j with y = +1, alpha*_j at j + n with y = -1) over kernel rows of n columns: K~(a, b) = K(a mod n, b mod n)
+  const bool svr = p.problem == 1;
+  DPSVM_CHECK(p.problem == 0 || p.problem == 1, "problem must be 0 (classification) or 1 (epsilon-SVR)");
+  if (svr) {
+    DPSVM_CHECK(p.svr_epsilon >= 0.f && std::isfinite(p.svr_epsilon), "epsilon-SVR: svr_epsilon must be >= 0");
+    DPSVM_CHECK(p.clip == ClipMode::Box, "epsilon-SVR runs with box clipping (clip=box): a pair (j, j + n) has "
+                                         "eta = 0 and only the joint box removes its common part");
+    DPSVM_CHECK(world == 1, "epsilon-SVR: multi-rank solves are not implemented");
+    DPSVM_CHECK(!Cr, "epsilon-SVR: per-row C is not implemented");
+    DPSVM_CHECK(!resume && p.checkpoint_every == 0, "epsilon-SVR: resume and checkpoints are not implemented");
+    DPSVM_CHECK(n < (int64_t)1 << 30, "epsilon-SVR: 2 n must fit in 31 bits (packed selection keys)");
+    for (int64_t i = 0; i < n; ++i) DPSVM_CHECK(std::isfinite(Y[i]), "epsilon-SVR: targets must be finite");
+  }
+  const int64_t ns = svr ? 2 * n : n;  // state rows
+  auto y_of = [&](int64_t g) { return svr ? (g < n ? 1.f : -1.f) : Y[g]; };
   if (Cr) {
     bool pos = false, neg = false;
     for (int64_t i = 0; i < n; ++i) {
@@ -124,9 +140,16 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
     for (int64_t i = b; i < e; ++i) xsq[i] = dot_f32(X + (size_t)i * d, X + (size_t)i * d, d);
   }, 1024);
 
-  std::vector<float> alpha((size_t)n, 0.f);
-  std::vector<float> f((size_t)nl);
-  for (int64_t j = 0; j < nl; ++j) f[j] = -Y[off + j];  // f = -y (svmTrain.cu:380)
+  std::vector<float> alpha((size_t)ns, 0.f);
+  std::vector<float> f((size_t)(svr ? ns : nl));
+  if (svr) {
+    for (int64_t j = 0; j < n; ++j) {  // f = y o p at alpha = 0, p = [eps - z, eps + z]
+      f[j] = p.svr_epsilon - Y[j];
+      f[j + n] = -p.svr_epsilon - Y[j];
+    }
+  } else {
+    for (int64_t j = 0; j < nl; ++j) f[j] = -Y[off + j];  // f = -y (svmTrain.cu:380)
+  }
   // f_j = sum_i alpha_i y_i K(i, j) - y_j from scratch (resume without f, DPSVM_VERIFY)
   auto recompute_f = [&](std::vector<float>& out) {
     pool.run(nl, [&](int, int64_t b, int64_t e) {
@@ -134,11 +157,17 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
         const float* xj = X + (size_t)(off + j) * d;
         float s = 0.f;
         for (int64_t i = 0; i < n; ++i) {
-          if (alpha[i] == 0.f) continue;
+          const float ai = svr ? alpha[i] - alpha[i + n] : alpha[i] * Y[i];
+          if (ai == 0.f) continue;
           float d2 = xsq[i] + xsq[off + j] - 2.f * dot_f32(X + (size_t)i * d, xj, d);
-          s += alpha[i] * Y[i] * std::exp(-gamma * std::max(d2, 0.f));
+          s += ai * std::exp(-gamma * std::max(d2, 0.f));
         }
-        out[j] = s - Y[off + j];
+        if (svr) {
+          out[j] = s + (p.svr_epsilon - Y[j]);
+          out[j + n] = s + (-p.svr_epsilon - Y[j]);
+        } else {
+          out[j] = s - Y[off + j];
+        }
       }
     }, 64);
   };
@@ -203,12 +232,14 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   auto select_rows = [&](int t, int64_t b, int64_t e) {
     uint64_t kh = kKeyNone, kl = kKeyNone;
     for (int64_t j = b; j < e; ++j) {
-      const int64_t g = off + j;
-      const float a = alpha[g], yj = Y[g], fj = f[j];
-      const bool up = Cr ? in_up_w(a, yj, Cr[g]) : in_up(a, yj, C);
-      const bool low = Cr ? in_low_w(a, yj, Cr[g]) : in_low(a, yj, C);
-      if (up) kh = std::min(kh, make_key(fj, (uint32_t)g));
-      if (low) kl = std::min(kl, make_key(-fj, (uint32_t)g));
+      for (int h = 0; h < (svr ? 2 : 1); ++h) {  // epsilon-SVR: column j carries state rows j and j + n
+        const int64_t g = off + j + (h ? n : 0);
+        const float a = alpha[g], yj = y_of(g), fj = f[g - off];
+        const bool up = Cr ? in_up_w(a, yj, Cr[g]) : in_up(a, yj, C);
+        const bool low = Cr ? in_low_w(a, yj, Cr[g]) : in_low(a, yj, C);
+        if (up) kh = std::min(kh, make_key(fj, (uint32_t)g));
+        if (low) kl = std::min(kl, make_key(-fj, (uint32_t)g));
+      }
     }
     th_hi[t] = kh;
     th_lo[t] = kl;
@@ -237,8 +268,9 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
       break;
     }
     // ---- eta from the explicit difference (reference host rbf_kernel) ----
-    const float* xh = X + (size_t)i_hi * d;
-    const float* xl = X + (size_t)i_lo * d;
+    const int64_t r_hi = svr && i_hi >= n ? i_hi - n : i_hi, r_lo = svr && i_lo >= n ? i_lo - n : i_lo;  // X rows
+    const float* xh = X + (size_t)r_hi * d;
+    const float* xl = X + (size_t)r_lo * d;
     float dist2 = 0.f;
     for (int k = 0; k < d; ++k) {
       float t = xh[k] - xl[k];
@@ -248,7 +280,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
     const float a_hi_old = alpha[i_hi], a_lo_old = alpha[i_lo];
     PairUpdate u = Cr ? pair_update_w(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, Cr[i_hi], Cr[i_lo],
                                       p.tau, (int)p.clip, i_hi == i_lo)
-                      : pair_update(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, C, p.tau,
+                      : pair_update(a_hi_old, a_lo_old, y_of(i_hi), y_of(i_lo), b_hi, b_lo, k_hl, C, p.tau,
                                     (int)p.clip, i_hi == i_lo);
     alpha[i_lo] = u.a_lo_new;
     alpha[i_hi] = u.a_hi_new;  // hi written last: wins if i_hi == i_lo
@@ -256,13 +288,14 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
     float* khi = nullptr;
     float* klo = nullptr;
     if (u.c_hi != 0.f) {
-      auto [ptr, hit] = cache.get(i_hi);
-      if (hit) ++res.cache_hits; else { ++res.cache_misses; ++res.rows_computed; compute_row(i_hi, ptr); }
+      auto [ptr, hit] = cache.get(r_hi);
+      if (hit) ++res.cache_hits; else { ++res.cache_misses; ++res.rows_computed; compute_row(r_hi, ptr); }
       khi = ptr;
     }
     if (u.c_lo != 0.f) {
-      auto [ptr, hit] = cache.get(i_lo);
-      if (hit) ++res.cache_hits; else { ++res.cache_misses; ++res.rows_computed; compute_row(i_lo, ptr); }
+      // epsilon-SVR, pair (j, j + n): one kernel row serves both (the same line again)
+      auto [ptr, hit] = cache.get(r_lo);
+      if (hit) ++res.cache_hits; else { ++res.cache_misses; ++res.rows_computed; compute_row(r_lo, ptr); }
       klo = ptr;  // capacity >= 2 and the hi line is MRU -> never the victim here
     }
     if (khi || klo) {
@@ -277,6 +310,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
           else if (khi) delta = ch * khi[j];
           else delta = cl * klo[j];
           f[j] += delta;
+          if (svr) f[j + n] += delta;  // each kernel value once for both halves
         }
         select_rows(t, b, e);
       });
@@ -320,13 +354,13 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   res.t_solve = secs_since(t0);
   if (trace::verify_enabled()) {
     // invariants: alpha in [0, C]; incremental f == f recomputed from alpha
-    for (int64_t i = 0; i < n; ++i)
+    for (int64_t i = 0; i < ns; ++i)
       if (!(alpha[i] >= 0.f && alpha[i] <= (Cr ? Cr[i] : C)))
         fail("DPSVM_VERIFY: alpha[" + std::to_string(i) + "] outside [0, C]");
-    std::vector<float> fr((size_t)nl);
+    std::vector<float> fr(f.size());
     recompute_f(fr);
     double err = 0.0;
-    for (int64_t j = 0; j < nl; ++j) {
+    for (int64_t j = 0; j < (int64_t)f.size(); ++j) {
       const double e = std::fabs((double)f[j] - fr[j]) / (1.0 + std::fabs((double)fr[j]));
       err = std::isfinite(e) ? std::max(err, e) : INFINITY;
     }

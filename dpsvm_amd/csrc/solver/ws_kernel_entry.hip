@@ -25,6 +25,7 @@
 // (svmTrainMain.cpp:282-299), the f update (svmTrain.cu:98-137).
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>
 #include <limits>
 
@@ -216,11 +217,16 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               const std::vector<float>& dalpha, const std::vector<int32_t>& apply_line,
                               const std::vector<float>& apply_coef, const std::vector<int32_t>& nab, int blocks,
                               int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps,
-                              bool wide, const std::vector<float>& row_C) {
+                              bool wide, const std::vector<float>& row_C, int64_t fold, int done) {
   const int64_t n = (int64_t)f.size();
+  // fold > 0 (epsilon-SVR): n = 2 fold state rows on gram [L][ldg >= fold], geometry of the fold columns
+  DPSVM_CHECK(fold == 0 || (n == 2 * fold && blocks == 1 && row_C.empty()),
+              "ws_select_probe: fold needs 2 fold state rows, one block, scalar C");
+  DPSVM_CHECK(done >= kRunning && done <= kCommFail, "ws_select_probe: done is a DoneCode");
+  const int64_t ncol = fold > 0 ? fold : n;
   DPSVM_CHECK(n >= 1 && (int64_t)alpha.size() == n && (int64_t)y.size() == n && (int64_t)dalpha.size() == n,
               "ws_select_probe: f / alpha / y / dalpha of n rows");
-  DPSVM_CHECK(ldg >= n && (int64_t)gram.size() == L * ldg, "ws_select_probe: gram [L][ldg >= n]");
+  DPSVM_CHECK(ldg >= ncol && (int64_t)gram.size() == L * ldg, "ws_select_probe: gram [L][ldg >= n]");
   DPSVM_CHECK(blocks >= 1 && blocks <= kWsMaxBlocks && (int)nab.size() == blocks && q_max >= 2 && q_max <= kWsMax,
               "ws_select_probe: nab per block, q_max <= 192");
   DPSVM_CHECK(apply_line.size() == apply_coef.size(), "ws_select_probe: apply lines / coefficients");
@@ -233,11 +239,12 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   DPSVM_CHECK(tot == (int64_t)apply_line.size(), "ws_select_probe: sum(nab) apply rows");
   for (int32_t l : apply_line) DPSVM_CHECK(l >= 0 && l < L, "ws_select_probe: apply line out of range");
   int32_t G = 0, rpt = 0;
-  launch::ws_geometry(n, 1, &G, &rpt);
+  launch::ws_geometry(ncol, 1, &G, &rpt);
   DPSVM_CHECK(rpt <= kWsMaxRPT, "ws_select_probe: too many rows");
   Stream st;
   auto c = blank_ctrl();
   c->outer = outer;
+  c->done = done;
   c->n_apply = (int32_t)tot;
   c->p_round = p_round;
   c->p_act = p_act;
@@ -280,6 +287,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   a.C = C;
   if (!row_C.empty()) a.c_row = st.up(row_C, (size_t)n);
   a.blocks = blocks;
+  a.fold = fold;
   a.t_halve = 0.9f;
   a.clip_fallback = 1;
   WsSelectProbe r;
@@ -296,6 +304,33 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
       float ms = 0.f;
       HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
       r.pass1_us.push_back(1e3 * ms);
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  if (blocks == 1 && reps > 0) {
+    // timing (bench/svr_probe.py): the one-pass kernel (plain or fold) repeated, rep i on the lines
+    // apply_line[k] + (i mod (L / na)) na — a Gram of many times the list's lines keeps the rows out of the
+    // caches from one launch to the next.  The launches update f: the state returned below includes them.
+    const int64_t groups = std::max<int64_t>(1, tot > 0 ? L / tot : 1);
+    int32_t* dline = (int32_t*)((char*)a.ctrl + offsetof(WsCtrl, apply_line));
+    std::vector<int32_t> hl((size_t)tot);
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    for (int i = 0; i <= reps; ++i) {  // the last pass restores the caller's lines
+      const int64_t shift = i < reps ? (i % groups) * tot : 0;
+      for (int64_t k = 0; k < tot; ++k) hl[k] = (int32_t)((apply_line[k] + shift) % L);
+      if (tot > 0) HIP_CHECK(hipMemcpyAsync(dline, hl.data(), tot * 4, hipMemcpyHostToDevice, st.s));
+      HIP_CHECK(hipStreamSynchronize(st.s));
+      if (i == reps) break;
+      HIP_CHECK(hipEventRecord(e0, st.s));
+      launch::ws_select(a, st.s);
+      HIP_CHECK(hipEventRecord(e1, st.s));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      r.select_us.push_back(1e3 * ms);
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
@@ -421,6 +456,7 @@ struct MergeRound {
     r.b_lo = o.b_lo;
     r.q = o.q[par];
     r.idx.assign(o.idx[par], o.idx[par] + std::max(0, std::min(r.q, (int)kWsMax)));
+    r.line.assign(o.line[par], o.line[par] + std::max(0, std::min(r.q, (int)kWsMax)));
     r.subg = download(a.subg, (size_t)a.q_max * a.q_max, st.s);
     r.aux = download(a.aux, (size_t)3 * kWsMax, st.s);
     return r;
@@ -432,13 +468,17 @@ struct MergeRound {
 WsGatherProbe ws_gather_probe(const std::vector<float>& gram, int64_t n, int64_t ldg, const std::vector<uint64_t>& cand,
                               const std::vector<int32_t>& prev_set, const std::vector<float>& f,
                               const std::vector<float>& alpha, const std::vector<float>& y, int q_max, int n_new,
-                              float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer) {
+                              float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer, int64_t fold) {
   check_merge_state(n, cand, prev_set, f, alpha, y, q_max, n_new, nonfinite);
-  DPSVM_CHECK(ldg >= n && (int64_t)gram.size() == n * ldg && outer >= 0, "ws_gather_probe: gram [n][ldg >= n]");
+  // fold > 0 (epsilon-SVR): n = 2 fold state rows, gram [fold][ldg >= fold]
+  DPSVM_CHECK(fold == 0 || n == 2 * fold, "ws_gather_probe: fold needs n = 2 fold state rows");
+  const int64_t ng = fold > 0 ? fold : n;
+  DPSVM_CHECK(ldg >= ng && (int64_t)gram.size() == ng * ldg && outer >= 0, "ws_gather_probe: gram [n][ldg >= n]");
   Stream st;
   MergeRound m(st, n, cand, prev_set, f, alpha, y, q_max, n_new, eps, iter, max_iter, nonfinite, outer);
   m.a.gram = st.up(gram, gram.size());
   m.a.ldg = ldg;
+  m.a.fold = fold;
   launch::ws_gather(m.a, st.s);  // dense, one block: ws_gather_kernel
   return m.result(st, outer);
 }

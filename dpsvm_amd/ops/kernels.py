@@ -270,7 +270,7 @@ def ws_solve(K, f, alpha, y, qb, q_max: int, C_: float, clip: str = "independent
 
 def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float, q_max: int = 192,
               p_round: int | None = None, p_act: int | None = None, outer: int = 1, ks: int = 0,
-              wide: bool = False, row_C=None) -> dict:
+              wide: bool = False, row_C=None, fold: int = 0, done: int = 0, reps: int = 0) -> dict:
     """The working-set f update + candidate selection (ws_select_kernel) on a
     dense gram [L][ldg >= n] (rows = lines).  len(nab) == 1: the one-pass
     kernel; more blocks: pass 1 (d_f, d'Qd / g'd partials) and pass 2 (line
@@ -278,7 +278,12 @@ def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float
     ks > 1: pass 1 split into ks list slices per selection group (dfs then
     holds slice 0, part [G][ks][2]).  wide: the wide pass 1 (1024-column
     groups, 16-B row loads; part [p1G][ks][2]).  row_C: per-row bounds C_i
-    [n] (None: the scalar C_)."""
+    [n] (None: the scalar C_).  fold > 0: the epsilon-SVR kernel
+    (ws_select_fold_kernel) — f / alpha / y hold 2 fold state rows, gram is
+    [L][ldg >= fold], the grid covers the fold columns.  done: the run's
+    DoneCode when the launch starts (0 running).  reps > 0 (one block):
+    ``select_us``, the event times of reps launches before the returned one,
+    launch i on the lines apply_lines + (i mod (L // na)) na (bench/svr_probe.py)."""
     import numpy as np
 
     g = np.ascontiguousarray(np.asarray(gram, dtype=np.float32))
@@ -288,7 +293,8 @@ def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float
                               np.asarray(apply_lines, dtype=np.int32), f32(apply_coef), np.asarray(nab, dtype=np.int32),
                               P, P if p_round is None else p_round, P if p_act is None else p_act, q_max, float(C_),
                               int(outer), ks=int(ks), wide=bool(wide),
-                              row_C=None if row_C is None else f32(row_C))
+                              row_C=None if row_C is None else f32(row_C), fold=int(fold), done=int(done),
+                              reps=int(reps))
 
 
 def _merge_round_args(cand, prev_set, f, alpha, y):
@@ -306,20 +312,24 @@ def _merge_round_result(r: dict, q_max: int) -> dict:
 
 
 def ws_gather(gram, cand, prev_set, f, alpha, y, q_max: int, n_new: int, eps: float, iteration: int = 0,
-              max_iter: int = 1 << 40, nonfinite: int = 0, outer: int = 1) -> dict:
+              max_iter: int = 1 << 40, nonfinite: int = 0, outer: int = 1, fold: int = 0) -> dict:
     """One launch of the dense one-block round's first kernel (ws_gather_kernel:
     the one-block merge of ws_merge.hpp in each of q_max workgroups, then one
     sub-Gram row each) on crafted lists ``cand`` [G][2][WS_CAND] (the merge reads
     the first 4 keys a side), the previous set (newest first) and a resident
     ``gram`` [n][ldg >= n].  subg / aux / idx hold a sentinel (NaN / -1) before
-    the launch.  Returns done, q, idx[:q], b_hi, b_lo, n_apply (kWsProbeApply
-    before the launch: a stop sets 0), subg [q_max][q_max], aux [3][192]."""
+    the launch.  Returns done, q, idx[:q], line[:q] (the members' Gram lines
+    as the round recorded them), b_hi, b_lo, n_apply (kWsProbeApply
+    before the launch: a stop sets 0), subg [q_max][q_max], aux [3][192].
+    fold > 0: the epsilon-SVR instantiation — f / alpha / y and the candidates'
+    rows number 2 fold, ``gram`` is [fold][ldg >= fold] and read modulo fold."""
     import numpy as np
 
     g = np.ascontiguousarray(np.asarray(gram, dtype=np.float32))
     c, prev, f_, a_, y_ = _merge_round_args(cand, prev_set, f, alpha, y)
-    r = load().k_ws_gather(g.reshape(-1), g.shape[0], g.shape[1], c, prev, f_, a_, y_, int(q_max), int(n_new),
-                           float(eps), int(iteration), int(max_iter), int(nonfinite), int(outer))
+    r = load().k_ws_gather(g.reshape(-1), 2 * g.shape[0] if fold else g.shape[0], g.shape[1], c, prev, f_, a_, y_,
+                           int(q_max), int(n_new), float(eps), int(iteration), int(max_iter), int(nonfinite),
+                           int(outer), fold=int(fold))
     return _merge_round_result(r, q_max)
 
 

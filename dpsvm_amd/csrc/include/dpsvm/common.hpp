@@ -162,6 +162,12 @@ struct SolverParams {
   // the device solver: one-block working-set rounds on the resident Gram.  SolveResult::alpha has 2n entries.
   int problem = 0;
   float svr_epsilon = 0.1f;   // epsilon-SVR: half width of the tube, >= 0
+  // one-class SVM (problem 0 with one_class_nu in (0, 1); 0 = off): min 1/2 a'Ka, 0 <= a_i <= 1, sum a = nu n.
+  // Every label is +1 (y is ignored), C must be 1, and the solve starts from the feasible point a = [1 .. 1,
+  // nu n - floor(nu n), 0 .. 0] with f = K a — on the device a weighted sum of the resident Gram's first
+  // ceil(nu n) rows (gram_rows_wsum, docs/DESIGN.md §18).  b is rho.  Box clipping, one rank, no resume, no
+  // per-row C; the device solver: one-block working-set rounds on the resident Gram.
+  float one_class_nu = 0.f;
 };
 
 
@@ -175,6 +181,11 @@ struct SolveResult {
   double t_gram = 0.0;  // device time of the resident Gram GEMM inside t_solve (dense mode)
   // the solve ran on the resident Gram an earlier solve of the same GpuSolver built (set_labels: t_gram = 0)
   bool gram_reused = false;
+  // one-class: device time of the start f = K alpha_0 read from the resident Gram (gram_rows_wsum), inside t_solve
+  double t_start = 0.0;
+  // solve_cpu, one-class: the final gradient f = K alpha (f - b: the training decisions); the device solver
+  // serves it by GpuSolver::gradient()
+  std::vector<float> f;
   // adaptive split Gram (gram_adapt, docs/DESIGN.md §13): tiles of the one-product pass and how many of them
   // held an element the error bound rejected (recomputed with all three products); -1: not adaptive
   int64_t gram_tiles = -1, gram_hot_tiles = -1;

@@ -68,6 +68,7 @@ void for_each_param(SolverParams& p, F&& f) {
   f("gram_cold_tau", p.gram_cold_tau);
   f("problem", p.problem);
   f("svr_epsilon", p.svr_epsilon);
+  f("one_class_nu", p.one_class_nu);
 }
 
 inline std::string num(double v) {

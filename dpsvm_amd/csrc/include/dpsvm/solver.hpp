@@ -151,6 +151,10 @@ class GpuSolver {
   // then current again (a set_labels after set_row_C may leave a label without a row of positive C_i: refused),
   // and refuses a resume, before it touches any state.
   void set_row_C(const float* c);
+  // One-class (set up with one_class_nu in (0, 1)): the nu of the next solve(), in (0, 1).  nu changes the start
+  // alone, so like set_labels it asks that solve to keep a completed resident Gram (gram_reused, t_gram = 0): a
+  // sweep over nu is k solves on one setup and one Gram.
+  void set_nu(float nu);
   // the stop tolerance of the next solve() (kernel arguments updated, captured graphs rebuilt)
   void set_eps(float eps);
   // free the kernel-row cache / resident Gram until the next solve() (which
@@ -342,6 +346,20 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               // fold > 0: the epsilon-SVR kernel — f / alpha / y of 2 fold state rows on gram
                               // [L][ldg >= fold]; done: the run's state (DoneCode) the launch finds
                               int64_t fold = 0, int done = 0);
+// gram_rows_wsum (gram_wsum.hip): out[j] = float(sum_r double(coef[r]) double(gram[line(r)][j]) + base[j]), j < n,
+// on gram [L][ldg].  lines empty: identity lines (row r), m = coef.size() <= L; base empty: none.  out is
+// round_up(n, 4) + kGramWsumProbePad floats filled with kGramWsumProbeFill before the launch: the entries from n
+// on must come back as they were.  reps > 0: event times (us) of reps launches before the returned one.
+constexpr int kGramWsumProbePad = 64;
+constexpr float kGramWsumProbeFill = -12345.f;
+struct GramWsumProbe {
+  std::vector<float> out;
+  int slices = 0;  // S = gram_wsum_slices(n, m)
+  std::vector<float> us;
+};
+GramWsumProbe gram_rows_wsum_probe(const std::vector<float>& gram, int64_t L, int64_t ldg, int64_t n,
+                                   const std::vector<int32_t>& lines, const std::vector<float>& coef,
+                                   const std::vector<float>& base, int reps = 0);
 // The one-block merge (ws_merge.hpp) through the two round kernels that run it
 // in every workgroup, one launch each: round `outer` builds parity outer & 1
 // from cand = [G][2][kWsCand] lists (the merge reads the first kWsCand1 keys a

@@ -15,6 +15,17 @@ void init_f(const float* y, int64_t off, int64_t nl, float* f, hipStream_t s);
 // epsilon-SVR start of the folded dual: f[j] = eps - z[j], f[j + n] = -eps - z[j] (f: 2 n floats)
 void init_f_svr(const float* z, float eps, int64_t n, float* f, hipStream_t s);
 void fill_i32(int32_t* p, int64_t n, int32_t v, hipStream_t s);
+// A weighted sum of Gram rows, accumulated in fp64 and rounded once (gram_wsum.hip, docs/DESIGN.md §18):
+//   out[j] = float(sum_{r < m} double(coef[r]) double(gram[line(r) ldg + j]) + (base ? double(base[j]) : 0)), j < n
+// line(r) = lines[r] (device, each in [0, L)), or r when lines == nullptr (m <= L).  gram: [L][ldg], ldg % 4 == 0,
+// ldg >= n; gram / base / out / part 16-B aligned; m = 0 yields base (or zeros).  Two launches, no atomics: the
+// list is cut into gram_wsum_slices(n, m) contiguous slices (a function of the shape alone: bit-equal results),
+// each summed in list order into part (>= gram_wsum_scratch_doubles(n) doubles, enough for every m), the slices
+// then in order.
+int gram_wsum_slices(int64_t n, int64_t m);
+int64_t gram_wsum_scratch_doubles(int64_t n);
+void gram_rows_wsum(const float* gram, int64_t L, int64_t ldg, int64_t n, const int32_t* lines, const float* coef,
+                    int64_t m, const float* base, float* out, double* part, hipStream_t s);
 
 // One SMO iteration's kernels (see device_state.hpp)
 void smo_rows(const SmoArgs& a, hipStream_t s);

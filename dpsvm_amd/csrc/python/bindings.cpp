@@ -123,6 +123,7 @@ py::dict result_dict(const SolveResult& r) {
   d["t_solve"] = r.t_solve;
   d["t_gram"] = r.t_gram;
   d["gram_reused"] = r.gram_reused;
+  d["t_start"] = r.t_start;
   d["gram_tiles"] = r.gram_tiles;
   d["gram_hot_tiles"] = r.gram_hot_tiles;
   d["verify_f_err"] = r.verify_f_err;
@@ -142,6 +143,7 @@ py::dict result_dict(const SolveResult& r) {
   d["host_cache_lines"] = r.host_cache_lines;
   d["cache_lines"] = r.cache_lines;
   d["world"] = r.world;
+  if (!r.f.empty()) d["f"] = to_np(r.f);  // solve_cpu, one-class: the final gradient K alpha
   return d;
 }
 
@@ -276,6 +278,7 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("gram_cold_tau", &SolverParams::gram_cold_tau)
       .def_readwrite("problem", &SolverParams::problem)
       .def_readwrite("svr_epsilon", &SolverParams::svr_epsilon)
+      .def_readwrite("one_class_nu", &SolverParams::one_class_nu)
       .def("to_json", [](const SolverParams& p) { return params_json(p); })
       .def("update_from_json", [](SolverParams& p, const std::string& t) { apply_params_json(t, p); });
 
@@ -526,7 +529,7 @@ PYBIND11_MODULE(_C, m) {
     ds.x = from_np(x);
     ds.y = from_np(y);
     if (p.problem == 0)  // epsilon-SVR (problem 1): y holds the real targets
-      for (auto& v : ds.y) v = v > 0 ? 1.f : -1.f;
+      for (auto& v : ds.y) v = v > 0 || p.one_class_nu != 0.f ? 1.f : -1.f;  // one-class: every row is +1
     auto prog = wrap_progress(progress);
     SolveResult r;
     {
@@ -601,6 +604,10 @@ PYBIND11_MODULE(_C, m) {
         s.set_row_C(a.data());
       }, py::arg("row_C"), "per-row bounds C_i of the next solves (None: the scalar C); the next solve() keeps the "
                            "resident Gram")
+      .def("set_nu", [](GpuSolver& s, float nu) {
+        py::gil_scoped_release rel;
+        s.set_nu(nu);
+      }, py::arg("nu"), "one-class: nu of the next solve(), which keeps the resident Gram (nu changes the start only)")
       .def("gradient", [](GpuSolver& s) {
         std::vector<float> g;
         {
@@ -890,6 +897,21 @@ PYBIND11_MODULE(_C, m) {
         py::arg("lines"), py::arg("coef"), py::arg("nab"), py::arg("blocks"), py::arg("p_round"), py::arg("p_act"),
         py::arg("q_max"), py::arg("C"), py::arg("outer"), py::arg("ks") = 0, py::arg("reps") = 0,
         py::arg("wide") = false, py::arg("row_C") = py::none(), py::arg("fold") = 0, py::arg("done") = 0);
+  m.def("k_gram_wsum_slices", [](int64_t n, int64_t m) { return launch::gram_wsum_slices(n, m); }, py::arg("n"),
+        py::arg("m"), "row slices S of gram_rows_wsum for n columns and m rows (a function of the shape alone)");
+  m.def("k_gram_rows_wsum", [vi](const F32& gram, int64_t L, int64_t ldg, int64_t n, py::object lines, const F32& coef,
+                                 py::object base, int reps) {
+    const auto r = kernels::gram_rows_wsum_probe(
+        from_np(gram), L, ldg, n, lines.is_none() ? std::vector<int32_t>() : vi(lines.cast<I32>()), from_np(coef),
+        base.is_none() ? std::vector<float>() : from_np(base.cast<F32>()), reps);
+    py::dict d;
+    d["out"] = to_np(r.out);
+    d["S"] = r.slices;
+    d["us"] = r.us;
+    d["fill"] = kernels::kGramWsumProbeFill;
+    return d;
+  }, py::arg("gram"), py::arg("L"), py::arg("ldg"), py::arg("n"), py::arg("lines"), py::arg("coef"),
+        py::arg("base") = py::none(), py::arg("reps") = 0);
   auto vu = [](const U64& a) { return std::vector<uint64_t>(a.data(), a.data() + a.size()); };
   auto gather_dict = [](const kernels::WsGatherProbe& r) {
     py::dict d;

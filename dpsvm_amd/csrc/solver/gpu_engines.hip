@@ -426,10 +426,23 @@ struct WsRounds : Base {
 
 struct WsDense final : WsRounds<DenseBase, false> {
   EngineKind kind() const override { return EngineKind::WsDense; }
+  std::unique_ptr<EventTimer> start_timer;  // one-class solves only
+  bool start_ran = false;
   void seed(GpuSolver::Impl& m, int64_t iter0, float b_hi, float b_lo, SolveResult& res) override {
     gram(m, res);
+    start_ran = m.one_class();
+    if (start_ran) {
+      // one-class: f = K alpha_0 before the first selection — alpha_0's ceil(nu n) leading entries weigh the
+      // Gram's leading rows (docs/DESIGN.md §18); also on a reused Gram (set_nu)
+      if (!start_timer) start_timer = std::make_unique<EventTimer>();
+      start_timer->start(m.stream);
+      launch::gram_rows_wsum(m.lines, m.L, m.ldl, m.n, nullptr, m.alpha, m.start_rows, nullptr, m.f, m.wsum_part,
+                             m.stream);
+      start_timer->stop(m.stream);
+    }
     seed_rounds(m, iter0, b_hi, b_lo);
   }
+  double start_seconds() override { return start_ran ? start_timer->seconds() : 0.0; }
 };
 
 // ws-cache: the X pass of a round computes all of its set's missing rows in one

@@ -136,6 +136,13 @@ struct GpuSolver::Impl {
   float* z = nullptr;
   std::vector<float> h_z;
   bool svr() const { return p.problem == 1; }
+  // one-class (p.one_class_nu != 0, checked to lie in (0, 1): one rank, ws-dense, one block; set_nu changes it).
+  // solve() uploads the start alpha_0 = [1 .. 1, frac, 0 .. 0]; its first start_rows = ceil(nu n) entries are
+  // the weights of the Gram rows gram_rows_wsum sums into f.  wsum_part: the kernel's slice partials, allocated
+  // once for every nu
+  int64_t start_rows = 0;
+  double* wsum_part = nullptr;
+  bool one_class() const { return p.one_class_nu != 0.f; }
   int d = 0, dp = 0;
   bool replicated = true, dense = false;
   EngineKind kind = EngineKind::Chain;
@@ -238,6 +245,7 @@ struct Engine {
   virtual void observe(GpuSolver::Impl&, const SmoStatus&, int64_t /*launched*/) {}
   virtual Pending pending(GpuSolver::Impl&) { return {}; }
   virtual double gram_seconds() { return 0.0; }
+  virtual double start_seconds() { return 0.0; }  // one-class: the start's gram_rows_wsum (device time)
 };
 
 std::unique_ptr<Engine> make_engine(EngineKind k);

@@ -169,6 +169,7 @@ void gpu_local_decision(GpuSolver::Impl& m, const std::vector<float>& alpha, flo
 double GpuSolver::train_accuracy(const SolveResult& r) {
   auto& m = *impl_;
   DPSVM_CHECK(m.p.problem == 0, "train_accuracy: not implemented for regression (epsilon-SVR: predict by the model)");
+  DPSVM_CHECK(!m.one_class(), "train_accuracy: not implemented for one-class (one-class has no labels to score against)");
   HIP_CHECK(hipSetDevice(m.device));
   DeviceSvs s;
   build_svs(m, r.alpha, s);
@@ -199,6 +200,7 @@ std::vector<float> GpuSolver::gradient() const {
 void GpuSolver::holdout_decisions(const int32_t* rows, int64_t nr, double b, int slot) {
   auto& m = *impl_;
   DPSVM_CHECK(m.p.problem == 0, "holdout_decisions: not implemented for regression (epsilon-SVR: predict by the model)");
+  DPSVM_CHECK(!m.one_class(), "holdout_decisions: not implemented for one-class (held-out decisions belong to the classifier)");
   DPSVM_CHECK(m.engine && m.f && m.world == 1 && m.nl == m.n,
               "holdout_decisions: after setup() on one rank with all rows");
   DPSVM_CHECK(slot >= 0 && slot < (1 << 20) && nr >= 0 && nr <= m.n && (rows || nr == 0),
@@ -243,6 +245,7 @@ std::vector<float> GpuSolver::holdout(int slot) const {
 PlattFit GpuSolver::platt_fit(int slot) {
   auto& m = *impl_;
   DPSVM_CHECK(m.p.problem == 0, "platt_fit: not implemented for regression (epsilon-SVR: predict by the model)");
+  DPSVM_CHECK(!m.one_class(), "platt_fit: not implemented for one-class (probabilities belong to the classifier)");
   DPSVM_CHECK(slot >= 0 && slot < m.holdout_slots, "platt_fit: no such slot (holdout_decisions first)");
   HIP_CHECK(hipSetDevice(m.device));
   if (!m.platt_out) {

@@ -47,7 +47,7 @@ GpuSolver::Impl::~Impl() {
                     (void*)records, (void*)my_record, (void*)pf, (void*)rf, (void*)rcf, (void*)stamps,
                     (void*)plru_meta, (void*)plru_stats, (void*)wsctrl, (void*)wscand, (void*)wssub, (void*)wsdfs, (void*)wsdalpha, (void*)wspart, (void*)wssorted,
                     (void*)wsxq, (void*)wsxqsq, (void*)wsiota, xs, (void*)xsh, wsxs, (void*)wsxsh, (void*)row_c,
-                    (void*)holdout, (void*)holdout_rows, (void*)platt_out, (void*)z})
+                    (void*)holdout, (void*)holdout_rows, (void*)platt_out, (void*)z, (void*)wsum_part})
     if (ptr) (void)hipFree(ptr);
   if (status_h) (void)hipHostFree(status_h);
   if (hlines_h) (void)hipHostFree(hlines_h);
@@ -144,6 +144,7 @@ void GpuSolver::set_labels(const float* y) {
   auto& m = *impl_;
   DPSVM_CHECK(m.engine && m.y, "set_labels: call setup() first");
   DPSVM_CHECK(y != nullptr, "set_labels: y is null");
+  DPSVM_CHECK(!m.one_class(), "set_labels: one-class has no labels (every row is +1); set_nu swaps the problem");
   if (m.svr()) {
     // epsilon-SVR: other targets on the same rows; y (+1 / -1 per half) stays, the next solve starts f from z
     for (int64_t i = 0; i < m.n; ++i) DPSVM_CHECK(std::isfinite(y[i]), "set_labels: regression targets must be finite");
@@ -164,9 +165,19 @@ void GpuSolver::set_labels(const float* y) {
   m.problem_swapped = true;
 }
 
+void GpuSolver::set_nu(float nu) {
+  auto& m = *impl_;
+  DPSVM_CHECK(m.engine && m.y, "set_nu: call setup() first");
+  DPSVM_CHECK(m.one_class(), "set_nu: the solver was not set up for one-class (one_class_nu > 0)");
+  DPSVM_CHECK(nu > 0.f && nu < 1.f, "set_nu: one-class nu must lie in (0, 1)");
+  m.p.one_class_nu = nu;  // read by the next solve(): nu changes the start only
+  m.problem_swapped = true;
+}
+
 void GpuSolver::set_row_C(const float* c) {
   auto& m = *impl_;
   DPSVM_CHECK(m.engine && m.y, "set_row_C: call setup() first");
+  DPSVM_CHECK(!(m.one_class() && c), "set_row_C: per-row C is not implemented for one-class");
   DPSVM_CHECK(!m.svr(), "set_row_C: per-row C is not implemented for regression (epsilon-SVR)");
   DPSVM_CHECK(m.working_set() && m.world == 1 && !m.ws_recompute,
               "set_row_C: per-row C runs on the working-set engines (ws-dense, ws-cache with the row cache) on one "
@@ -367,6 +378,26 @@ void check_and_choose_policy(GpuSolver::Impl& m, SetupState& s, int64_t n, int d
   DPSVM_CHECK(m.p.rows_per_group % kFusedThreads == 0 && m.p.rows_per_group >= 0,
               "rows_per_group must be a multiple of 256");
   DPSVM_CHECK(m.p.problem == 0 || m.p.problem == 1, "problem must be 0 (classification) or 1 (epsilon-SVR)");
+  if (m.one_class()) {
+    // one-class: the classifier's one-block working-set rounds on the resident Gram from a non-zero start read
+    // off that Gram; everything else is refused here, before any device state exists (docs/DESIGN.md §18)
+    const SolverParams& p = m.p;
+    DPSVM_CHECK(p.one_class_nu > 0.f && p.one_class_nu < 1.f, "one-class: one_class_nu must lie in (0, 1)");
+    DPSVM_CHECK(p.problem == 0, "one-class: problem must be 0 (one_class_nu > 0 selects the one-class dual)");
+    DPSVM_CHECK(p.C == 1.f, "one-class: the box is [0, 1] (C must be 1)");
+    DPSVM_CHECK(p.clip == ClipMode::Box,
+                "one-class runs with box clipping (clip=box): independent clipping lets sum(alpha) drift from nu n");
+    DPSVM_CHECK(m.outer_world == 1 && !p.force_collectives && p.exchange != 2,
+                "one-class: multi-rank solves, forced collectives and the peer exchange are not implemented");
+    DPSVM_CHECK(p.solver == 2 && p.engines == 0,
+                "one-class: not implemented on the pair-at-a-time engines (solver must be ws, engines production)");
+    DPSVM_CHECK(p.ws_blocks == 1, "one-class: multi-block rounds are not implemented (ws_blocks must be 1)");
+    DPSVM_CHECK(!p.force_cache && p.cache_lines == 0 && p.host_cache_lines == 0 && p.ws_recompute != 1,
+                "one-class: the kernel-row cache (ws-cache) and recompute rounds are not implemented: the start is "
+                "read from the resident Gram");
+    DPSVM_CHECK(p.x_mode != 2 && s.n_x_rows == n, "one-class: partitioned X is not implemented");
+    DPSVM_CHECK(p.checkpoint_every == 0, "one-class: checkpoints and resume are not implemented");
+  }
   if (m.svr()) {
     // epsilon-SVR: the folded 2n-row dual on one-block working-set rounds over the resident Gram; everything
     // else is refused here, before any device state exists (docs/DESIGN.md §17)
@@ -529,6 +560,8 @@ void place_vectors(GpuSolver::Impl& m, SetupState& s) {
     m.h_z.assign(s.yh, s.yh + n);
     m.z = dmalloc<float>((size_t)n, &m.bytes);
     HIP_CHECK(hipMemcpyAsync(m.z, m.h_z.data(), n * 4, hipMemcpyHostToDevice, m.stream));
+  } else if (m.one_class()) {
+    m.h_y.assign((size_t)n, 1.f);  // one class: whatever y holds
   } else {
     m.h_y.assign(s.yh, s.yh + n);
     for (auto& v : m.h_y) v = v > 0 ? 1.f : -1.f;
@@ -844,6 +877,9 @@ void pick_engine(GpuSolver::Impl& m, const SetupState& s) {
     if (!m.info.engine_note.empty()) why += " (" + m.info.engine_note + ")";
     DPSVM_CHECK(false, why + "; the pair-at-a-time cache / partitioned-X engines are quarantined: set engines=all");
   }
+  DPSVM_CHECK(!m.one_class() || m.kind == EngineKind::WsDense,
+              "one-class: the Gram must be resident (ws-dense): the start is read from it; the kernel-row cache "
+              "(ws-cache), recompute rounds and the pair-at-a-time engines are not implemented");
   DPSVM_CHECK(!m.svr() || m.kind == EngineKind::WsDense,
               "epsilon-SVR: the Gram must be resident (ws-dense); the kernel-row cache (ws-cache), recompute "
               "rounds and the pair-at-a-time engines are not implemented for regression");
@@ -936,6 +972,11 @@ void fill_ws_args(GpuSolver::Impl& m, const SetupState& s) {
     w.fold = m.n;
     m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + "epsilon-SVR: folded 2n, one block";
   }
+  if (m.one_class()) {
+    DPSVM_CHECK(shape.blocks == 1 && !m.xch && m.world == 1 && m.nl == m.n && m.off == 0,
+                "one-class: one-block rounds on one rank only");
+    m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + "one-class: nu start, one block";
+  }
   w.G = s.ws_G;
   w.p1G = s.ws_G;  // multi-block rounds take the wide pass-1 geometry below
   w.rpt = s.ws_rpt;
@@ -1006,6 +1047,8 @@ void alloc_round_buffers(GpuSolver::Impl& m, const SetupState& s) {
   w.subg = m.wssub;
   w.aux = m.wssub + (size_t)w.blocks * w.q_max * w.q_max;
   w.ctrl = m.wsctrl;
+  // one-class: the slice partials of the start's Gram-row sum, sized for every nu (set_nu)
+  if (m.one_class()) m.wsum_part = dmalloc<double>((size_t)launch::gram_wsum_scratch_doubles(n), &m.bytes);
   if (w.blocks > 1) {
     m.wsdfs = dmalloc<float>((size_t)w.ks * m.nl, &m.bytes);
     m.wsdalpha = dmalloc<float>((size_t)n, &m.bytes);

@@ -219,6 +219,7 @@ GpuSetupInfo ShrinkingSolver::setup(const float* x, int64_t n, int d, const floa
   auto& m = *impl_;
   DPSVM_CHECK(n >= 2 && d >= 1, "shrinking: need at least 2 samples and 1 feature");
   DPSVM_CHECK(m.p.problem == 0, "shrinking is not implemented for regression (epsilon-SVR)");
+  DPSVM_CHECK(m.p.one_class_nu == 0.f, "shrinking is not implemented for one-class");
   m.x = x;
   m.n = n;
   m.d = d;

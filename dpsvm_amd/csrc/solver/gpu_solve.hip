@@ -96,6 +96,8 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   // per-row C: refused combinations before any state changes (a refused call keeps a requested Gram reuse)
   DPSVM_CHECK(!(m.wsa.c_row && resume), "per-row C (set_row_C): resume is not supported");
   DPSVM_CHECK(!(m.svr() && resume), "epsilon-SVR: resume is not implemented");
+  DPSVM_CHECK(!(m.one_class() && resume), "one-class: resume is not implemented");
+  DPSVM_CHECK(!(m.one_class() && m.wsa.c_row), "one-class: per-row C (set_row_C) is not implemented");
   if (m.wsa.c_row) {
     // the bounds were validated against the labels current at set_row_C; set_labels may have come after
     bool pos = false, neg = false;
@@ -136,6 +138,16 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
     HIP_CHECK(hipMemcpy(m.f, fh.data(), m.nl * 4, hipMemcpyHostToDevice));
   } else if (m.svr()) {
     launch::init_f_svr(m.z, m.p.svr_epsilon, m.n, m.f, m.stream);  // f = [eps - z, -eps - z]
+  } else if (m.one_class()) {
+    // the feasible start of LIBSVM's one-class solver, built in double: alpha = 1 on the first floor(nu n) rows,
+    // the remainder on the next one.  f = K alpha_0 is the seed's (gram_rows_wsum, once the Gram is there)
+    const double total = (double)m.p.one_class_nu * (double)m.n;
+    const int64_t full = std::min<int64_t>(m.n, (int64_t)total);
+    std::vector<float> a0((size_t)std::min<int64_t>(m.n, full + 1), 1.f);
+    if (full < m.n) a0[(size_t)full] = (float)(total - (double)full);
+    m.start_rows = full < m.n && a0[(size_t)full] > 0.f ? full + 1 : full;
+    HIP_CHECK(hipMemcpyAsync(m.alpha, a0.data(), a0.size() * 4, hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));  // a0 is a local
   } else {
     launch::init_f(m.y, m.off, m.nl, m.f, m.stream);
   }
@@ -272,6 +284,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   HIP_CHECK(hipStreamSynchronize(m.stream));
   res.t_solve = secs_since(t0);
   res.t_gram = m.engine->gram_seconds();
+  res.t_start = m.engine->start_seconds();
   if (m.gram_cold_tau > 0.f && !res.gram_reused) launch::gram_adapt_last(&res.gram_tiles, &res.gram_hot_tiles);
   if (m.p.checkpoint_every > 0 && !m.p.checkpoint_path.empty()) {
     st = m.read_status();
@@ -297,7 +310,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
     (void)hipFree(dref);
     double err = 0.0;
     for (int64_t j = 0; j < m.nl; ++j) {
-      const double ref = (double)fr[j] - m.h_y[m.off + j];
+      const double ref = (double)fr[j] - (m.one_class() ? 0.0 : (double)m.h_y[m.off + j]);  // one-class: f = K alpha
       const double e = std::fabs((double)fd[j] - ref) / (1.0 + std::fabs(ref));
       err = std::isfinite(e) ? std::max(err, e) : INFINITY;
     }

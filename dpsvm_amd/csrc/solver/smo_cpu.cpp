@@ -98,12 +98,30 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   const float C = p.C;
   const float* X = ds.x.data();
   const float* Y = ds.y.data();
+  // one-class (p.one_class_nu != 0; docs/DESIGN.md §18): every label is +1 whatever ds.y holds, the linear term
+  // is 0 and the solve starts from LIBSVM's feasible point (below, once the kernel rows can be computed)
+  const bool oc = p.one_class_nu != 0.f;
+  std::vector<float> ones;
+  if (oc) {
+    ones.assign((size_t)n, 1.f);
+    Y = ones.data();
+  }
   // per-row bounds C_i (global n; nullptr: the scalar C): the compare-form sets and the two-bound pair step
   const float* Cr = row_C;
   // epsilon-SVR (p.problem == 1): ds.y holds the targets z; the folded dual has ns = 2n state rows (alpha_j at
   // j with y = +1, alpha*_j at j + n with y = -1) over kernel rows of n columns: K~(a, b) = K(a mod n, b mod n)
   const bool svr = p.problem == 1;
   DPSVM_CHECK(p.problem == 0 || p.problem == 1, "problem must be 0 (classification) or 1 (epsilon-SVR)");
+  if (oc) {
+    DPSVM_CHECK(p.one_class_nu > 0.f && p.one_class_nu < 1.f, "one-class: one_class_nu must lie in (0, 1)");
+    DPSVM_CHECK(p.problem == 0, "one-class: problem must be 0 (one_class_nu > 0 selects the one-class dual)");
+    DPSVM_CHECK(C == 1.f, "one-class: the box is [0, 1] (C must be 1)");
+    DPSVM_CHECK(p.clip == ClipMode::Box,
+                "one-class runs with box clipping (clip=box): independent clipping lets sum(alpha) drift from nu n");
+    DPSVM_CHECK(world == 1, "one-class: multi-rank solves (comm) are not implemented");
+    DPSVM_CHECK(!Cr, "one-class: per-row C is not implemented");
+    DPSVM_CHECK(!resume && p.checkpoint_every == 0, "one-class: resume and checkpoints are not implemented");
+  }
   if (svr) {
     DPSVM_CHECK(p.svr_epsilon >= 0.f && std::isfinite(p.svr_epsilon), "epsilon-SVR: svr_epsilon must be >= 0");
     DPSVM_CHECK(p.clip == ClipMode::Box, "epsilon-SVR runs with box clipping (clip=box): a pair (j, j + n) has "
@@ -166,7 +184,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
           out[j] = s + (p.svr_epsilon - Y[j]);
           out[j + n] = s + (-p.svr_epsilon - Y[j]);
         } else {
-          out[j] = s - Y[off + j];
+          out[j] = oc ? s : s - Y[off + j];
         }
       }
     }, 64);
@@ -216,6 +234,25 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
       }
     }, 512);
   };
+
+  if (oc) {
+    // alpha = 1 on the first floor(nu n) rows, the remainder on the next (built in double, as LIBSVM does);
+    // f = K alpha from those kernel rows, accumulated in double and rounded once — what gram_rows_wsum reads
+    // off the resident Gram on the device
+    const double total = (double)p.one_class_nu * (double)n;
+    const int64_t full = std::min<int64_t>(n, (int64_t)total);
+    for (int64_t i = 0; i < full; ++i) alpha[i] = 1.f;
+    if (full < n) alpha[full] = (float)(total - (double)full);
+    std::vector<double> acc((size_t)nl, 0.0);
+    std::vector<float> row((size_t)nl);
+    for (int64_t r = 0; r < n && alpha[r] > 0.f; ++r) {
+      compute_row(r, row.data());
+      ++res.rows_computed;
+      const double a = alpha[r];
+      for (int64_t j = 0; j < nl; ++j) acc[j] += a * (double)row[j];
+    }
+    for (int64_t j = 0; j < nl; ++j) f[j] = (float)acc[j];
+  }
 
   const int T = pool.size();
   std::vector<uint64_t> th_hi(T), th_lo(T);
@@ -382,6 +419,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   res.b_lo = b_lo;
   res.b = (b_lo + b_hi) / 2.0f;  // svmTrainMain.cpp:329
   res.alpha = std::move(alpha);
+  if (oc) res.f = std::move(f);  // f - b: the training decisions
   return res;
 }
 

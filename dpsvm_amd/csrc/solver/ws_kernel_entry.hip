@@ -79,6 +79,49 @@ std::unique_ptr<WsCtrl> blank_ctrl() {
 
 }  // namespace
 
+GramWsumProbe gram_rows_wsum_probe(const std::vector<float>& gram, int64_t L, int64_t ldg, int64_t n,
+                                   const std::vector<int32_t>& lines, const std::vector<float>& coef,
+                                   const std::vector<float>& base, int reps) {
+  DPSVM_CHECK(n >= 1 && L >= 0 && ldg >= n && (int64_t)gram.size() == L * ldg,
+              "gram_rows_wsum_probe: gram [L][ldg >= n], n >= 1");
+  DPSVM_CHECK(lines.empty() || lines.size() == coef.size(), "gram_rows_wsum_probe: one coefficient per line");
+  DPSVM_CHECK(base.empty() || (int64_t)base.size() == n, "gram_rows_wsum_probe: base of n entries (or none)");
+  const int64_t m = (int64_t)coef.size();
+  DPSVM_CHECK(!lines.empty() || m <= L, "gram_rows_wsum_probe: identity lines need m <= L");
+  for (int32_t l : lines) DPSVM_CHECK(l >= 0 && l < L, "gram_rows_wsum_probe: line out of range");
+  DPSVM_CHECK(reps >= 0, "gram_rows_wsum_probe: reps >= 0");
+  Stream st;
+  const float* dg = st.up(gram, gram.size());
+  const int32_t* dl = lines.empty() ? nullptr : st.up(lines, lines.size());
+  const float* dc = st.up(coef, coef.size());
+  const float* db = base.empty() ? nullptr : st.up(base, base.size());
+  const size_t n_out = (size_t)((n + 3) / 4 * 4) + kGramWsumProbePad;
+  const std::vector<float> fill(n_out, kGramWsumProbeFill);
+  float* dout = st.up(fill, n_out);
+  double* part = st.up(std::vector<double>(), (size_t)launch::gram_wsum_scratch_doubles(n));
+  GramWsumProbe r;
+  r.slices = launch::gram_wsum_slices(n, m);
+  if (reps > 0) {
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    for (int i = 0; i < reps; ++i) {
+      HIP_CHECK(hipEventRecord(e0, st.s));
+      launch::gram_rows_wsum(dg, L, ldg, n, dl, dc, m, db, dout, part, st.s);
+      HIP_CHECK(hipEventRecord(e1, st.s));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      r.us.push_back(1e3f * ms);
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  launch::gram_rows_wsum(dg, L, ldg, n, dl, dc, m, db, dout, part, st.s);
+  r.out = download(dout, n_out, st.s);
+  return r;
+}
+
 WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int blocks, int p_act, int q_max,
                                   int n_new, float eps, const std::vector<int32_t>& prev_union, int64_t iter,
                                   int64_t max_iter) {

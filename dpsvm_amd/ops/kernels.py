@@ -297,6 +297,27 @@ def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float
                               reps=int(reps))
 
 
+def gram_rows_wsum(gram, n: int, coef, lines=None, base=None, reps: int = 0) -> dict:
+    """A weighted sum of Gram rows accumulated in fp64 and rounded once
+    (gram_wsum.hip): out[j] = float(sum_r coef[r] gram[line(r), j] + base[j]),
+    j < n, on ``gram`` [L][ldg >= n] with ldg a multiple of 4.  lines=None: the
+    identity (row r, the one-class start's contiguous prefix).  Returns ``out``
+    [n], ``pad`` (the entries behind out[n - 1] of the padded device buffer),
+    ``fill`` (what they held before the launch), ``S`` (the row slices) and,
+    for reps > 0, ``us``: the event times of reps launches before the returned
+    one (bench/oneclass_probe.py)."""
+    import numpy as np
+
+    g = np.ascontiguousarray(np.asarray(gram, dtype=np.float32))
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32)).reshape(-1)  # noqa: E731
+    r = load().k_gram_rows_wsum(g.reshape(-1), g.shape[0], g.shape[1], int(n),
+                                None if lines is None else np.ascontiguousarray(np.asarray(lines, dtype=np.int32)),
+                                f32(coef), None if base is None else f32(base), reps=int(reps))
+    out = np.asarray(r["out"])
+    return {"out": out[:n].copy(), "pad": out[n:].copy(), "fill": float(r["fill"]), "S": int(r["S"]),
+            "us": list(r["us"])}
+
+
 def _merge_round_args(cand, prev_set, f, alpha, y):
     import numpy as np
 

@@ -10,6 +10,7 @@
 #include "dpsvm/comm.hpp"
 #include "dpsvm/common.hpp"
 #include "dpsvm/io.hpp"
+#include "dpsvm/problem.hpp"
 #include "dpsvm/solver.hpp"
 #include "dpsvm/ws_plan.hpp"
 #include "kernels/kernels.hpp"
@@ -330,6 +331,132 @@ static void test_ws_plan() {
   }
 }
 
+template <class F>
+static std::string thrown(F&& call) {
+  try {
+    call();
+  } catch (const std::exception& e) {
+    return e.what();
+  }
+  return "";
+}
+static bool has(const std::string& s, const char* part) { return s.find(part) != std::string::npos; }
+
+static void test_problem() {
+  using K = ProblemKind;
+  auto params = [](int problem, float nu) {
+    SolverParams p;
+    p.problem = problem;
+    p.one_class_nu = nu;
+    return p;
+  };
+  EXPECT(resolve_problem(params(0, 0.f)) == K::Classify);
+  EXPECT(resolve_problem(params(1, 0.f)) == K::Svr);
+  EXPECT(resolve_problem(params(0, 0.2f)) == K::OneClass);
+  EXPECT(has(thrown([&] { resolve_problem(params(1, 0.2f)); }), "one-class: problem must be 0"));
+  EXPECT(has(thrown([&] { resolve_problem(params(2, 0.f)); }), "problem must be 0 (classification) or 1"));
+  EXPECT(state_rows(K::Classify, 5) == 5 && state_rows(K::Svr, 5) == 10 && state_rows(K::OneClass, 5) == 5);
+
+  const float y[4] = {2.5f, -1.f, 0.f, 1.f};
+  std::vector<float> out;
+  problem_labels(K::Classify, y, 4, out);
+  EXPECT((out == std::vector<float>{1.f, -1.f, -1.f, 1.f}));
+  problem_labels(K::Svr, y, 4, out);
+  EXPECT((out == std::vector<float>{1.f, 1.f, 1.f, 1.f, -1.f, -1.f, -1.f, -1.f}));
+  problem_labels(K::OneClass, y, 4, out);
+  EXPECT((out == std::vector<float>{1.f, 1.f, 1.f, 1.f}));
+
+  OneClassStart st = one_class_start(0.25f, 8);
+  EXPECT(st.full == 2 && st.rest == 0.f && st.start_rows == 2);
+  st = one_class_start(0.3f, 7);  // 0.3f * 7 = 2.100000083446502685546875 in double
+  EXPECT(st.full == 2 && st.rest == 0.100000083446502685546875f && st.start_rows == 3);
+  st = one_class_start(0.999f, 3);  // 0.999f * 3 = 2.997000038623809814453125
+  EXPECT(st.full == 2 && st.rest == 0.997000038623809814453125f && st.start_rows == 3);
+  st = one_class_start(0x1.fffffep-1f, (int64_t)1 << 24);  // (1 - 2^-24) 2^24 = 2^24 - 1: never past n
+  EXPECT(st.full == ((int64_t)1 << 24) - 1 && st.rest == 0.f && st.start_rows == st.full);
+
+  // check_problem: a valid parameter set of each kind passes on the device and on the CPU; every refused setting
+  // throws on both where it applies, naming the kind and the setting
+  const int64_t n = 8;
+  const float z[8] = {0.f, 1.f, -2.f, 3.f, 0.5f, 0.f, 1.f, 2.f};
+  float z_inf[8];
+  std::copy(z, z + 8, z_inf);
+  z_inf[5] = INFINITY;
+  auto valid = [](K kind) {
+    SolverParams p;
+    p.clip = ClipMode::Box;
+    p.solver = 2;
+    p.ws_blocks = 1;
+    if (kind == K::Svr) p.problem = 1, p.svr_epsilon = 0.1f, p.C = 10.f;
+    if (kind == K::OneClass) p.one_class_nu = 0.2f, p.C = 1.f;
+    return p;
+  };
+  auto site = [&](bool device) { return ProblemSite{n, 1, false, false, n, z, device}; };
+  struct Refusal {
+    const char* keyword;
+    int kinds;     // 1 epsilon-SVR, 2 one-class, 3 both
+    bool cpu;      // refused by solve_cpu too (else: an engine-level row)
+    std::function<void(SolverParams&, ProblemSite&)> set;
+  };
+  const Refusal table[] = {
+      {"box", 3, true, [](SolverParams& p, ProblemSite&) { p.clip = ClipMode::Independent; }},
+      {"comm", 3, true, [](SolverParams&, ProblemSite& s) { s.world = 2; }},
+      {"per-row C", 3, true, [](SolverParams&, ProblemSite& s) { s.row_C = true; }},
+      {"resume", 3, true, [](SolverParams&, ProblemSite& s) { s.resume = true; }},
+      {"checkpoints", 3, true, [](SolverParams& p, ProblemSite&) { p.checkpoint_every = 5; }},
+      {"collectives", 3, false, [](SolverParams& p, ProblemSite&) { p.force_collectives = true; }},
+      {"peer exchange", 3, false, [](SolverParams& p, ProblemSite&) { p.exchange = 2; }},
+      {"solver", 3, false, [](SolverParams& p, ProblemSite&) { p.solver = 1; }},
+      {"solver", 3, false, [](SolverParams& p, ProblemSite&) { p.solver = 0; }},
+      {"solver", 3, false, [](SolverParams& p, ProblemSite&) { p.engines = 1; }},
+      {"ws_blocks", 3, false, [](SolverParams& p, ProblemSite&) { p.ws_blocks = 8; }},
+      {"ws_blocks", 3, false, [](SolverParams& p, ProblemSite&) { p.ws_blocks = 0; }},
+      {"cache", 3, false, [](SolverParams& p, ProblemSite&) { p.force_cache = true; }},
+      {"cache", 3, false, [](SolverParams& p, ProblemSite&) { p.cache_lines = 1000; }},
+      {"cache", 3, false, [](SolverParams& p, ProblemSite&) { p.host_cache_lines = 10; }},
+      {"cache", 3, false, [](SolverParams& p, ProblemSite&) { p.ws_recompute = 1; }},
+      {"partitioned", 3, false, [](SolverParams& p, ProblemSite&) { p.x_mode = 2; }},
+      {"partitioned", 3, false, [](SolverParams&, ProblemSite& s) { s.n_x_rows = 4; }},
+      {"svr_epsilon", 1, true, [](SolverParams& p, ProblemSite&) { p.svr_epsilon = -1.f; }},
+      {"svr_epsilon", 1, true, [](SolverParams& p, ProblemSite&) { p.svr_epsilon = NAN; }},
+      {"31 bits", 1, true, [](SolverParams&, ProblemSite& s) { s.n = s.n_x_rows = (int64_t)1 << 30, s.targets = nullptr; }},
+      {"finite", 1, true, [&](SolverParams&, ProblemSite& s) { s.targets = z_inf; }},
+      {"(0, 1)", 2, true, [](SolverParams& p, ProblemSite&) { p.one_class_nu = 1.f; }},
+      {"(0, 1)", 2, true, [](SolverParams& p, ProblemSite&) { p.one_class_nu = -0.1f; }},
+      {"C must be 1", 2, true, [](SolverParams& p, ProblemSite&) { p.C = 2.f; }},
+  };
+  for (K kind : {K::Svr, K::OneClass})
+    for (bool device : {true, false}) {
+      EXPECT(thrown([&] { check_problem(kind, valid(kind), site(device)); }).empty());
+      for (const Refusal& r : table) {
+        if (!(r.kinds & (kind == K::Svr ? 1 : 2))) continue;
+        SolverParams p = valid(kind);
+        ProblemSite s = site(device);
+        r.set(p, s);
+        const std::string msg = thrown([&] { check_problem(kind, p, s); });
+        if (device || r.cpu) {
+          EXPECT(has(msg, problem_name(kind)) && has(msg, r.keyword));
+          EXPECT(msg.find(problem_name(kind)) < msg.find(r.keyword));
+        } else {
+          EXPECT(msg.empty());  // an engine-level setting: nothing of the CPU solver's
+        }
+      }
+    }
+  {  // a classifier is refused nothing here, whatever the settings
+    SolverParams p;
+    p.clip = ClipMode::Independent, p.ws_blocks = 8, p.x_mode = 2, p.checkpoint_every = 5;
+    EXPECT(thrown([&] { check_problem(K::Classify, p, ProblemSite{n, 4, true, true, 2, nullptr, true}); }).empty());
+  }
+
+  EXPECT(thrown([] { require_classifier(K::Classify, "platt_fit"); }).empty());
+  for (K kind : {K::Svr, K::OneClass}) {
+    const std::string msg = thrown([&] { require_classifier(kind, "platt_fit"); });
+    EXPECT(has(msg, "platt_fit") && has(msg, problem_name(kind)));
+  }
+  EXPECT(std::string(problem_note(K::Classify)).empty());
+  EXPECT(has(problem_note(K::Svr), "epsilon-SVR") && has(problem_note(K::OneClass), "one-class"));
+}
+
 static void test_gpu() {
   if (device_count() == 0) {
     printf("  (no GPU: device tests skipped)\n");
@@ -371,6 +498,7 @@ int main(int argc, char** argv) {
       {"cpu_checkpoint_resume", test_cpu_checkpoint_resume},
       {"gram_path", test_gram_path},
       {"ws_plan", test_ws_plan},
+      {"problem", test_problem},
   };
   if (gpu) tests.push_back({"gpu", test_gpu});
   for (auto& [name, fn] : tests) {

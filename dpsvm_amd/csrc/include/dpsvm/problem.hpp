@@ -1,0 +1,86 @@
+// The problem kind — classification, epsilon-SVR, one-class — and everything the device solver and the CPU solver
+// share about it: the one table of refusals, the state rows, the labels, the one-class start, the engine note
+// (docs/DESIGN.md §19).  Host-only C++.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "dpsvm/common.hpp"
+
+namespace dpsvm {
+
+enum class ProblemKind { Classify, Svr, OneClass };
+// by kind: the prefix of every refusal, and what GpuSetupInfo::engine_note says about it
+constexpr const char* kProblemName[] = {"classification", "epsilon-SVR", "one-class"};
+constexpr const char* kProblemNote[] = {"", "epsilon-SVR: folded 2n, one block", "one-class: nu start, one block"};
+inline const char* problem_name(ProblemKind k) { return kProblemName[(int)k]; }
+inline const char* problem_note(ProblemKind k) { return kProblemNote[(int)k]; }
+
+// The only reader of (problem, one_class_nu): one_class_nu == 0 is off (a plain classifier), anything else one-class.
+inline ProblemKind resolve_problem(const SolverParams& p) {
+  DPSVM_CHECK(p.problem == 0 || p.problem == 1, "problem must be 0 (classification) or 1 (epsilon-SVR)");
+  if (p.one_class_nu == 0.f) return p.problem == 1 ? ProblemKind::Svr : ProblemKind::Classify;
+  DPSVM_CHECK(p.problem == 0, "one-class: problem must be 0 (one_class_nu > 0 selects the one-class dual)");
+  return ProblemKind::OneClass;
+}
+// What the caller of check_problem knows: per-row bounds / a checkpoint to resume from given; the X rows this rank
+// holds (!= n: partitioned); epsilon-SVR's n targets, scanned for finiteness (nullptr: not scanned); device: GpuSolver
+// (the engine-level rows apply), else solve_cpu
+struct ProblemSite { int64_t n; int world; bool row_C, resume; int64_t n_x_rows; const float* targets; bool device; };
+// The one table of refusals: epsilon-SVR and one-class run the classifier's one-block working-set rounds on the
+// resident Gram of one rank with the joint box, and nothing else.  Throws "<kind>...<setting>".
+inline void check_problem(ProblemKind kind, const SolverParams& p, const ProblemSite& s) {
+  if (kind == ProblemKind::Classify) return;
+  const bool svr = kind == ProblemKind::Svr, oc = !svr, dev = s.device;
+  const bool finite =
+      !svr || !s.targets || std::all_of(s.targets, s.targets + s.n, [](float z) { return std::isfinite(z); });
+  const struct { bool ok; const char* text; } rows[] = {
+      {!svr || (p.svr_epsilon >= 0.f && std::isfinite(p.svr_epsilon)), ": svr_epsilon must be >= 0"},
+      {!svr || s.n < (int64_t)1 << 30, ": 2 n must fit in 31 bits (packed selection keys)"},
+      {finite, ": targets must be finite"},
+      {!oc || (p.one_class_nu > 0.f && p.one_class_nu < 1.f), ": one_class_nu must lie in (0, 1)"},
+      {!oc || p.C == 1.f, ": the box is [0, 1] (C must be 1)"},
+      {p.clip == ClipMode::Box,
+       svr ? " runs with box clipping (clip=box): a pair (j, j + n) has eta = 0 and only the joint box removes its "
+             "common part"
+           : " runs with box clipping (clip=box): independent clipping lets sum(alpha) drift from nu n"},
+      {s.world == 1 && (!dev || (!p.force_collectives && p.exchange != 2)),
+       ": multi-rank solves (comm), forced collectives and the peer exchange are not implemented"},
+      {!s.row_C, ": per-row C is not implemented"},
+      {!s.resume && p.checkpoint_every == 0, ": checkpoints and resume are not implemented"},
+      {!dev || (p.solver == 2 && p.engines == 0),
+       ": not implemented on the pair-at-a-time engines (solver must be ws, engines production)"},
+      {!dev || p.ws_blocks == 1, ": multi-block rounds are not implemented (ws_blocks must be 1)"},
+      {!dev || (!p.force_cache && p.cache_lines == 0 && p.host_cache_lines == 0 && p.ws_recompute != 1),
+       ": the kernel-row cache (ws-cache) and recompute rounds are not implemented: the Gram must be resident"},
+      {!dev || (p.x_mode != 2 && s.n_x_rows == s.n), ": partitioned X is not implemented"},
+  };
+  for (const auto& r : rows) DPSVM_CHECK(r.ok, std::string(problem_name(kind)) + r.text);
+}
+// a call that serves the classifier alone
+inline void require_classifier(ProblemKind kind, const char* call) {
+  DPSVM_CHECK(kind == ProblemKind::Classify, std::string(call) + ": serves the classifier, not implemented for " +
+                                                 problem_name(kind) + (kind == ProblemKind::Svr ? " (regression)" : ""));
+}
+// rows of alpha / y / f: n, or the folded dual's 2n
+inline int64_t state_rows(ProblemKind kind, int64_t n) { return kind == ProblemKind::Svr ? 2 * n : n; }
+// their labels: y > 0 ? +1 : -1; epsilon-SVR (y_in holds targets): n times +1, n times -1; one-class: all ones
+inline void problem_labels(ProblemKind kind, const float* y_in, int64_t n, std::vector<float>& out) {
+  out.assign((size_t)state_rows(kind, n), 1.f);
+  if (kind == ProblemKind::Svr) std::fill(out.begin() + n, out.end(), -1.f);
+  if (kind == ProblemKind::Classify)
+    std::transform(y_in, y_in + n, out.begin(), [](float v) { return v > 0 ? 1.f : -1.f; });
+}
+// LIBSVM's feasible one-class start, built in double: alpha = 1 on the first full = floor(nu n) rows, rest on the
+// next one (if there is one); start_rows: the rows with alpha > 0
+struct OneClassStart { int64_t full; float rest; int64_t start_rows; };
+inline OneClassStart one_class_start(float nu, int64_t n) {
+  const double total = (double)nu * (double)n;
+  const int64_t full = std::min<int64_t>(n, (int64_t)total);
+  const float rest = full < n ? (float)(total - (double)full) : 0.f;
+  return {full, rest, rest > 0.f ? full + 1 : full};
+}
+
+}  // namespace dpsvm

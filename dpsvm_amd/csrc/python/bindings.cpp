@@ -15,6 +15,7 @@
 #include "dpsvm/io.hpp"
 #include "dpsvm/solver.hpp"
 #include "dpsvm/params_io.hpp"
+#include "dpsvm/problem.hpp"
 #include "dpsvm/ws_plan.hpp"
 #include "../kernels/kernels.hpp"
 
@@ -528,8 +529,6 @@ PYBIND11_MODULE(_C, m) {
     }
     ds.x = from_np(x);
     ds.y = from_np(y);
-    if (p.problem == 0)  // epsilon-SVR (problem 1): y holds the real targets
-      for (auto& v : ds.y) v = v > 0 || p.one_class_nu != 0.f ? 1.f : -1.f;  // one-class: every row is +1
     auto prog = wrap_progress(progress);
     SolveResult r;
     {
@@ -540,6 +539,7 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("x"), py::arg("y"), py::arg("params"), py::arg("comm") = nullptr, py::arg("resume") = nullptr,
      py::arg("progress") = py::none(), py::arg("row_C") = py::none());
 
+  m.def("problem_note", [](const SolverParams& p) { return std::string(problem_note(resolve_problem(p))); });
   m.def("solve_shrinking", [](F32 x, F32 y, const SolverParams& p, int device, const Checkpoint* resume,
                               py::object progress, std::shared_ptr<Communicator> comm) {
     int64_t n = 0;

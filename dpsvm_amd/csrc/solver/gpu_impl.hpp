@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "dpsvm/device_state.hpp"
+#include "dpsvm/problem.hpp"
 #include "dpsvm/solver.hpp"
 #include "dpsvm/ws_plan.hpp"
 #include "../kernels/kernels.hpp"
@@ -129,20 +130,21 @@ struct GpuSolver::Impl {
   SmoArgs args{};
   float gamma = 0.f;
   int64_t n = 0, nl = 0, off = 0, x_rows = 0, G = 0, ldl = 0, L = 0;
-  // state rows: the length of alpha / y / f and of SolveResult::alpha.  n, except epsilon-SVR (p.problem == 1:
-  // one rank, ws-dense, one block) where the folded dual has 2n of them while X, |x|^2, the split operands, the
+  ProblemKind problem = ProblemKind::Classify;  // resolved once by setup (check_and_choose_policy)
+  // state rows: the length of alpha / y / f and of SolveResult::alpha.  n, except epsilon-SVR (one
+  // rank, ws-dense, one block) where the folded dual has 2n of them while X, |x|^2, the split operands, the
   // Gram and every shard / geometry quantity above stay n-sized (wsa.fold = n); z: the targets (device, host)
   int64_t ns = 0;
   float* z = nullptr;
   std::vector<float> h_z;
-  bool svr() const { return p.problem == 1; }
-  // one-class (p.one_class_nu != 0, checked to lie in (0, 1): one rank, ws-dense, one block; set_nu changes it).
+  bool svr() const { return problem == ProblemKind::Svr; }
+  // one-class (p.one_class_nu in (0, 1): one rank, ws-dense, one block; set_nu changes it).
   // solve() uploads the start alpha_0 = [1 .. 1, frac, 0 .. 0]; its first start_rows = ceil(nu n) entries are
   // the weights of the Gram rows gram_rows_wsum sums into f.  wsum_part: the kernel's slice partials, allocated
   // once for every nu
   int64_t start_rows = 0;
   double* wsum_part = nullptr;
-  bool one_class() const { return p.one_class_nu != 0.f; }
+  bool one_class() const { return problem == ProblemKind::OneClass; }
   int d = 0, dp = 0;
   bool replicated = true, dense = false;
   EngineKind kind = EngineKind::Chain;

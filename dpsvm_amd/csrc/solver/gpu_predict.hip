@@ -168,8 +168,7 @@ void gpu_local_decision(GpuSolver::Impl& m, const std::vector<float>& alpha, flo
 // ---------------------------------------------------------------------------
 double GpuSolver::train_accuracy(const SolveResult& r) {
   auto& m = *impl_;
-  DPSVM_CHECK(m.p.problem == 0, "train_accuracy: not implemented for regression (epsilon-SVR: predict by the model)");
-  DPSVM_CHECK(!m.one_class(), "train_accuracy: not implemented for one-class (one-class has no labels to score against)");
+  require_classifier(m.problem, "train_accuracy");
   HIP_CHECK(hipSetDevice(m.device));
   DeviceSvs s;
   build_svs(m, r.alpha, s);
@@ -188,7 +187,7 @@ double GpuSolver::train_accuracy(const SolveResult& r) {
 std::vector<float> GpuSolver::gradient() const {
   const auto& m = *impl_;
   HIP_CHECK(hipSetDevice(m.device));
-  const int64_t rows = m.p.problem == 1 ? m.ns : m.nl;  // epsilon-SVR: the 2n state rows (one rank)
+  const int64_t rows = m.svr() ? m.ns : m.nl;  // epsilon-SVR: the 2n state rows (one rank)
   std::vector<float> f((size_t)rows);
   if (rows > 0) HIP_CHECK(hipMemcpy(f.data(), m.f, (size_t)rows * 4, hipMemcpyDeviceToHost));
   return f;
@@ -199,8 +198,7 @@ std::vector<float> GpuSolver::gradient() const {
 // ---------------------------------------------------------------------------
 void GpuSolver::holdout_decisions(const int32_t* rows, int64_t nr, double b, int slot) {
   auto& m = *impl_;
-  DPSVM_CHECK(m.p.problem == 0, "holdout_decisions: not implemented for regression (epsilon-SVR: predict by the model)");
-  DPSVM_CHECK(!m.one_class(), "holdout_decisions: not implemented for one-class (held-out decisions belong to the classifier)");
+  require_classifier(m.problem, "holdout_decisions");
   DPSVM_CHECK(m.engine && m.f && m.world == 1 && m.nl == m.n,
               "holdout_decisions: after setup() on one rank with all rows");
   DPSVM_CHECK(slot >= 0 && slot < (1 << 20) && nr >= 0 && nr <= m.n && (rows || nr == 0),
@@ -244,8 +242,7 @@ std::vector<float> GpuSolver::holdout(int slot) const {
 
 PlattFit GpuSolver::platt_fit(int slot) {
   auto& m = *impl_;
-  DPSVM_CHECK(m.p.problem == 0, "platt_fit: not implemented for regression (epsilon-SVR: predict by the model)");
-  DPSVM_CHECK(!m.one_class(), "platt_fit: not implemented for one-class (probabilities belong to the classifier)");
+  require_classifier(m.problem, "platt_fit");
   DPSVM_CHECK(slot >= 0 && slot < m.holdout_slots, "platt_fit: no such slot (holdout_decisions first)");
   HIP_CHECK(hipSetDevice(m.device));
   if (!m.platt_out) {
@@ -261,7 +258,7 @@ PlattFit GpuSolver::platt_fit(int slot) {
 
 std::vector<float> GpuSolver::decision(const SolveResult& r, const float* xh, int64_t nt, int d) {
   auto& m = *impl_;
-  DPSVM_CHECK(m.p.problem == 0, "decision: not implemented for regression (epsilon-SVR: predict by the model)");
+  if (m.svr()) require_classifier(m.problem, "decision");  // (one-class: the same decision, served)
   DPSVM_CHECK(d == m.d, "feature count mismatch");
   HIP_CHECK(hipSetDevice(m.device));
   DeviceSvs s;

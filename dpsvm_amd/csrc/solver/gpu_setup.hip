@@ -144,23 +144,17 @@ void GpuSolver::set_labels(const float* y) {
   auto& m = *impl_;
   DPSVM_CHECK(m.engine && m.y, "set_labels: call setup() first");
   DPSVM_CHECK(y != nullptr, "set_labels: y is null");
-  DPSVM_CHECK(!m.one_class(), "set_labels: one-class has no labels (every row is +1); set_nu swaps the problem");
-  if (m.svr()) {
-    // epsilon-SVR: other targets on the same rows; y (+1 / -1 per half) stays, the next solve starts f from z
-    for (int64_t i = 0; i < m.n; ++i) DPSVM_CHECK(std::isfinite(y[i]), "set_labels: regression targets must be finite");
-    HIP_CHECK(hipSetDevice(m.device));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-    m.h_z.assign(y, y + m.n);
-    HIP_CHECK(hipMemcpyAsync(m.z, m.h_z.data(), m.n * 4, hipMemcpyHostToDevice, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-    m.problem_swapped = true;
-    return;
-  }
+  // epsilon-SVR: other targets on the same rows, y (+1 / -1 per half) stays; one-class has no labels (set_nu)
+  const bool svr = m.svr();
+  if (!svr) require_classifier(m.problem, "set_labels");
+  for (int64_t i = 0; svr && i < m.n; ++i)
+    DPSVM_CHECK(std::isfinite(y[i]), "set_labels: regression targets must be finite");
   HIP_CHECK(hipSetDevice(m.device));
   HIP_CHECK(hipStreamSynchronize(m.stream));
-  m.h_y.assign(y, y + m.n);
-  for (auto& v : m.h_y) v = v > 0 ? 1.f : -1.f;  // as place_vectors
-  HIP_CHECK(hipMemcpyAsync(m.y, m.h_y.data(), m.n * 4, hipMemcpyHostToDevice, m.stream));
+  if (svr) m.h_z.assign(y, y + m.n);
+  else problem_labels(m.problem, y, m.n, m.h_y);
+  HIP_CHECK(hipMemcpyAsync(svr ? m.z : m.y, svr ? m.h_z.data() : m.h_y.data(), m.n * 4, hipMemcpyHostToDevice,
+                           m.stream));
   HIP_CHECK(hipStreamSynchronize(m.stream));
   m.problem_swapped = true;
 }
@@ -168,7 +162,7 @@ void GpuSolver::set_labels(const float* y) {
 void GpuSolver::set_nu(float nu) {
   auto& m = *impl_;
   DPSVM_CHECK(m.engine && m.y, "set_nu: call setup() first");
-  DPSVM_CHECK(m.one_class(), "set_nu: the solver was not set up for one-class (one_class_nu > 0)");
+  DPSVM_CHECK(m.one_class(), std::string("set_nu: set up for ") + problem_name(m.problem) + ", not for one-class");
   DPSVM_CHECK(nu > 0.f && nu < 1.f, "set_nu: one-class nu must lie in (0, 1)");
   m.p.one_class_nu = nu;  // read by the next solve(): nu changes the start only
   m.problem_swapped = true;
@@ -177,8 +171,7 @@ void GpuSolver::set_nu(float nu) {
 void GpuSolver::set_row_C(const float* c) {
   auto& m = *impl_;
   DPSVM_CHECK(m.engine && m.y, "set_row_C: call setup() first");
-  DPSVM_CHECK(!(m.one_class() && c), "set_row_C: per-row C is not implemented for one-class");
-  DPSVM_CHECK(!m.svr(), "set_row_C: per-row C is not implemented for regression (epsilon-SVR)");
+  if (c || m.svr()) require_classifier(m.problem, "set_row_C (per-row C)");
   DPSVM_CHECK(m.working_set() && m.world == 1 && !m.ws_recompute,
               "set_row_C: per-row C runs on the working-set engines (ws-dense, ws-cache with the row cache) on one "
               "rank");
@@ -377,50 +370,11 @@ void check_and_choose_policy(GpuSolver::Impl& m, SetupState& s, int64_t n, int d
   DPSVM_CHECK(m.p.C > 0.f, "C must be > 0");
   DPSVM_CHECK(m.p.rows_per_group % kFusedThreads == 0 && m.p.rows_per_group >= 0,
               "rows_per_group must be a multiple of 256");
-  DPSVM_CHECK(m.p.problem == 0 || m.p.problem == 1, "problem must be 0 (classification) or 1 (epsilon-SVR)");
-  if (m.one_class()) {
-    // one-class: the classifier's one-block working-set rounds on the resident Gram from a non-zero start read
-    // off that Gram; everything else is refused here, before any device state exists (docs/DESIGN.md §18)
-    const SolverParams& p = m.p;
-    DPSVM_CHECK(p.one_class_nu > 0.f && p.one_class_nu < 1.f, "one-class: one_class_nu must lie in (0, 1)");
-    DPSVM_CHECK(p.problem == 0, "one-class: problem must be 0 (one_class_nu > 0 selects the one-class dual)");
-    DPSVM_CHECK(p.C == 1.f, "one-class: the box is [0, 1] (C must be 1)");
-    DPSVM_CHECK(p.clip == ClipMode::Box,
-                "one-class runs with box clipping (clip=box): independent clipping lets sum(alpha) drift from nu n");
-    DPSVM_CHECK(m.outer_world == 1 && !p.force_collectives && p.exchange != 2,
-                "one-class: multi-rank solves, forced collectives and the peer exchange are not implemented");
-    DPSVM_CHECK(p.solver == 2 && p.engines == 0,
-                "one-class: not implemented on the pair-at-a-time engines (solver must be ws, engines production)");
-    DPSVM_CHECK(p.ws_blocks == 1, "one-class: multi-block rounds are not implemented (ws_blocks must be 1)");
-    DPSVM_CHECK(!p.force_cache && p.cache_lines == 0 && p.host_cache_lines == 0 && p.ws_recompute != 1,
-                "one-class: the kernel-row cache (ws-cache) and recompute rounds are not implemented: the start is "
-                "read from the resident Gram");
-    DPSVM_CHECK(p.x_mode != 2 && s.n_x_rows == n, "one-class: partitioned X is not implemented");
-    DPSVM_CHECK(p.checkpoint_every == 0, "one-class: checkpoints and resume are not implemented");
-  }
-  if (m.svr()) {
-    // epsilon-SVR: the folded 2n-row dual on one-block working-set rounds over the resident Gram; everything
-    // else is refused here, before any device state exists (docs/DESIGN.md §17)
-    const SolverParams& p = m.p;
-    DPSVM_CHECK(p.svr_epsilon >= 0.f && std::isfinite(p.svr_epsilon), "epsilon-SVR: svr_epsilon must be >= 0");
-    DPSVM_CHECK(p.clip == ClipMode::Box,
-                "epsilon-SVR runs with box clipping (clip=box): a pair (j, j + n) has eta = 0 and only the joint "
-                "box removes its common part");
-    DPSVM_CHECK(m.outer_world == 1 && !p.force_collectives && p.exchange != 2,
-                "epsilon-SVR: multi-rank solves, forced collectives and the peer exchange are not implemented");
-    DPSVM_CHECK(p.solver == 2 && p.engines == 0,
-                "epsilon-SVR: not implemented on the pair-at-a-time engines (solver must be ws, engines production)");
-    DPSVM_CHECK(p.ws_blocks == 1, "epsilon-SVR: multi-block rounds are not implemented (ws_blocks must be 1)");
-    DPSVM_CHECK(!p.force_cache && p.cache_lines == 0 && p.host_cache_lines == 0 && p.ws_recompute != 1,
-                "epsilon-SVR: the kernel-row cache (ws-cache) and recompute rounds are not implemented: the Gram "
-                "must be resident");
-    DPSVM_CHECK(p.x_mode != 2 && s.n_x_rows == n, "epsilon-SVR: partitioned X is not implemented");
-    DPSVM_CHECK(p.checkpoint_every == 0, "epsilon-SVR: checkpoints and resume are not implemented");
-    DPSVM_CHECK(n < (int64_t)1 << 30, "epsilon-SVR: 2 n must fit in 31 bits (packed selection keys)");
-    for (int64_t i = 0; i < n; ++i) DPSVM_CHECK(std::isfinite(s.yh[i]), "epsilon-SVR: targets must be finite");
-  }
+  // epsilon-SVR, one-class: whatever they do not run is refused here, before any device state exists
+  m.problem = resolve_problem(m.p);
+  check_problem(m.problem, m.p, {n, m.outer_world, false, false, s.n_x_rows, s.yh, true});
   m.n = n;
-  m.ns = m.svr() ? 2 * n : n;
+  m.ns = state_rows(m.problem, n);
   m.d = d;
   m.dp = pad_features(d);
   m.gamma = resolve_gamma(m.p.gamma, d);
@@ -553,18 +507,11 @@ void place_vectors(GpuSolver::Impl& m, SetupState& s) {
   HIP_CHECK(hipMemsetAsync(m.xsq, 0, n_pad * 4, m.stream));
   HIP_CHECK(hipMemsetAsync(m.y, 0, n_pad * 4, m.stream));
   HIP_CHECK(hipMemsetAsync(m.alpha, 0, n_pad * 4, m.stream));
-  if (m.svr()) {
-    // the folded dual's labels: +1 for the alpha rows, -1 for the alpha* rows; the targets beside them
-    m.h_y.assign((size_t)m.ns, 1.f);
-    std::fill(m.h_y.begin() + n, m.h_y.end(), -1.f);
+  problem_labels(m.problem, s.yh, n, m.h_y);
+  if (m.svr()) {  // the targets beside the folded dual's labels
     m.h_z.assign(s.yh, s.yh + n);
     m.z = dmalloc<float>((size_t)n, &m.bytes);
     HIP_CHECK(hipMemcpyAsync(m.z, m.h_z.data(), n * 4, hipMemcpyHostToDevice, m.stream));
-  } else if (m.one_class()) {
-    m.h_y.assign((size_t)n, 1.f);  // one class: whatever y holds
-  } else {
-    m.h_y.assign(s.yh, s.yh + n);
-    for (auto& v : m.h_y) v = v > 0 ? 1.f : -1.f;
   }
   HIP_CHECK(hipMemcpyAsync(m.y, m.h_y.data(), m.ns * 4, hipMemcpyHostToDevice, m.stream));
   row_norms(m);
@@ -877,12 +824,10 @@ void pick_engine(GpuSolver::Impl& m, const SetupState& s) {
     if (!m.info.engine_note.empty()) why += " (" + m.info.engine_note + ")";
     DPSVM_CHECK(false, why + "; the pair-at-a-time cache / partitioned-X engines are quarantined: set engines=all");
   }
-  DPSVM_CHECK(!m.one_class() || m.kind == EngineKind::WsDense,
-              "one-class: the Gram must be resident (ws-dense): the start is read from it; the kernel-row cache "
-              "(ws-cache), recompute rounds and the pair-at-a-time engines are not implemented");
-  DPSVM_CHECK(!m.svr() || m.kind == EngineKind::WsDense,
-              "epsilon-SVR: the Gram must be resident (ws-dense); the kernel-row cache (ws-cache), recompute "
-              "rounds and the pair-at-a-time engines are not implemented for regression");
+  DPSVM_CHECK(m.problem == ProblemKind::Classify || m.kind == EngineKind::WsDense,
+              std::string(problem_name(m.problem)) +
+                  ": the Gram must be resident (ws-dense); the kernel-row cache (ws-cache), recompute rounds and "
+                  "the pair-at-a-time engines are not implemented");
   if (m.persistent() && !m.census(m.kind)) {
     DPSVM_CHECK(m.p.persist != 2, "persistent engine requested (persist=on) but its grid is not co-resident (" +
                                       m.info.engine_note + ")");
@@ -962,20 +907,17 @@ void fill_ws_args(GpuSolver::Impl& m, const SetupState& s) {
   w.n = m.n;
   w.nl = m.nl;
   w.off = m.off;
+  if (m.problem != ProblemKind::Classify) {
+    DPSVM_CHECK(shape.blocks == 1 && !m.xch && m.world == 1 && m.nl == m.n && m.off == 0,
+                std::string(problem_name(m.problem)) + ": one-block rounds on one rank only");
+    m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + problem_note(m.problem);
+  }
   if (m.svr()) {
     // the folded dual: 2n state rows on the n x n Gram; the selection geometry (s.ws_G, s.ws_rpt) is that of
     // the n Gram columns, each carrying two state rows
-    DPSVM_CHECK(shape.blocks == 1 && !m.xch && m.world == 1 && m.nl == m.n && m.off == 0,
-                "epsilon-SVR: one-block rounds on one rank only");
     DPSVM_CHECK(s.ws_rpt <= 4, "epsilon-SVR: at most 262,144 rows (4 Gram columns a selection thread)");
     w.n = w.nl = m.ns;
     w.fold = m.n;
-    m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + "epsilon-SVR: folded 2n, one block";
-  }
-  if (m.one_class()) {
-    DPSVM_CHECK(shape.blocks == 1 && !m.xch && m.world == 1 && m.nl == m.n && m.off == 0,
-                "one-class: one-block rounds on one rank only");
-    m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + "one-class: nu start, one block";
   }
   w.G = s.ws_G;
   w.p1G = s.ws_G;  // multi-block rounds take the wide pass-1 geometry below

@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dpsvm/device_state.hpp"
+#include "dpsvm/problem.hpp"
 #include "dpsvm/solver.hpp"
 #include "../kernels/kernels.hpp"
 #include "../runtime/hip_check.hpp"
@@ -218,8 +219,7 @@ ShrinkingSolver::~ShrinkingSolver() = default;
 GpuSetupInfo ShrinkingSolver::setup(const float* x, int64_t n, int d, const float* y_in) {
   auto& m = *impl_;
   DPSVM_CHECK(n >= 2 && d >= 1, "shrinking: need at least 2 samples and 1 feature");
-  DPSVM_CHECK(m.p.problem == 0, "shrinking is not implemented for regression (epsilon-SVR)");
-  DPSVM_CHECK(m.p.one_class_nu == 0.f, "shrinking is not implemented for one-class");
+  require_classifier(resolve_problem(m.p), "shrinking");
   m.x = x;
   m.n = n;
   m.d = d;

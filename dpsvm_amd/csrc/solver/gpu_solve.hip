@@ -95,9 +95,7 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
 
   // per-row C: refused combinations before any state changes (a refused call keeps a requested Gram reuse)
   DPSVM_CHECK(!(m.wsa.c_row && resume), "per-row C (set_row_C): resume is not supported");
-  DPSVM_CHECK(!(m.svr() && resume), "epsilon-SVR: resume is not implemented");
-  DPSVM_CHECK(!(m.one_class() && resume), "one-class: resume is not implemented");
-  DPSVM_CHECK(!(m.one_class() && m.wsa.c_row), "one-class: per-row C (set_row_C) is not implemented");
+  if (resume || m.wsa.c_row) require_classifier(m.problem, "solve: resume / per-row C (set_row_C)");
   if (m.wsa.c_row) {
     // the bounds were validated against the labels current at set_row_C; set_labels may have come after
     bool pos = false, neg = false;
@@ -139,13 +137,11 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   } else if (m.svr()) {
     launch::init_f_svr(m.z, m.p.svr_epsilon, m.n, m.f, m.stream);  // f = [eps - z, -eps - z]
   } else if (m.one_class()) {
-    // the feasible start of LIBSVM's one-class solver, built in double: alpha = 1 on the first floor(nu n) rows,
-    // the remainder on the next one.  f = K alpha_0 is the seed's (gram_rows_wsum, once the Gram is there)
-    const double total = (double)m.p.one_class_nu * (double)m.n;
-    const int64_t full = std::min<int64_t>(m.n, (int64_t)total);
-    std::vector<float> a0((size_t)std::min<int64_t>(m.n, full + 1), 1.f);
-    if (full < m.n) a0[(size_t)full] = (float)(total - (double)full);
-    m.start_rows = full < m.n && a0[(size_t)full] > 0.f ? full + 1 : full;
+    // LIBSVM's feasible start (one_class_start); f = K alpha_0 is the seed's (gram_rows_wsum, once the Gram is there)
+    const OneClassStart st = one_class_start(m.p.one_class_nu, m.n);
+    std::vector<float> a0((size_t)std::min<int64_t>(m.n, st.full + 1), 1.f);
+    if (st.full < m.n) a0[(size_t)st.full] = st.rest;
+    m.start_rows = st.start_rows;
     HIP_CHECK(hipMemcpyAsync(m.alpha, a0.data(), a0.size() * 4, hipMemcpyHostToDevice, m.stream));
     HIP_CHECK(hipStreamSynchronize(m.stream));  // a0 is a local
   } else {

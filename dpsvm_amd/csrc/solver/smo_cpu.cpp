@@ -20,6 +20,7 @@
 #include <unordered_map>
 
 #include "dpsvm/common.hpp"
+#include "dpsvm/problem.hpp"
 #include "dpsvm/solver.hpp"
 #include "../runtime/thread_pool.hpp"
 #include <unistd.h>
@@ -97,43 +98,19 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   const float gamma = resolve_gamma(p.gamma, d);
   const float C = p.C;
   const float* X = ds.x.data();
-  const float* Y = ds.y.data();
-  // one-class (p.one_class_nu != 0; docs/DESIGN.md §18): every label is +1 whatever ds.y holds, the linear term
-  // is 0 and the solve starts from LIBSVM's feasible point (below, once the kernel rows can be computed)
-  const bool oc = p.one_class_nu != 0.f;
-  std::vector<float> ones;
-  if (oc) {
-    ones.assign((size_t)n, 1.f);
-    Y = ones.data();
-  }
   // per-row bounds C_i (global n; nullptr: the scalar C): the compare-form sets and the two-bound pair step
   const float* Cr = row_C;
-  // epsilon-SVR (p.problem == 1): ds.y holds the targets z; the folded dual has ns = 2n state rows (alpha_j at
-  // j with y = +1, alpha*_j at j + n with y = -1) over kernel rows of n columns: K~(a, b) = K(a mod n, b mod n)
-  const bool svr = p.problem == 1;
-  DPSVM_CHECK(p.problem == 0 || p.problem == 1, "problem must be 0 (classification) or 1 (epsilon-SVR)");
-  if (oc) {
-    DPSVM_CHECK(p.one_class_nu > 0.f && p.one_class_nu < 1.f, "one-class: one_class_nu must lie in (0, 1)");
-    DPSVM_CHECK(p.problem == 0, "one-class: problem must be 0 (one_class_nu > 0 selects the one-class dual)");
-    DPSVM_CHECK(C == 1.f, "one-class: the box is [0, 1] (C must be 1)");
-    DPSVM_CHECK(p.clip == ClipMode::Box,
-                "one-class runs with box clipping (clip=box): independent clipping lets sum(alpha) drift from nu n");
-    DPSVM_CHECK(world == 1, "one-class: multi-rank solves (comm) are not implemented");
-    DPSVM_CHECK(!Cr, "one-class: per-row C is not implemented");
-    DPSVM_CHECK(!resume && p.checkpoint_every == 0, "one-class: resume and checkpoints are not implemented");
-  }
-  if (svr) {
-    DPSVM_CHECK(p.svr_epsilon >= 0.f && std::isfinite(p.svr_epsilon), "epsilon-SVR: svr_epsilon must be >= 0");
-    DPSVM_CHECK(p.clip == ClipMode::Box, "epsilon-SVR runs with box clipping (clip=box): a pair (j, j + n) has "
-                                         "eta = 0 and only the joint box removes its common part");
-    DPSVM_CHECK(world == 1, "epsilon-SVR: multi-rank solves are not implemented");
-    DPSVM_CHECK(!Cr, "epsilon-SVR: per-row C is not implemented");
-    DPSVM_CHECK(!resume && p.checkpoint_every == 0, "epsilon-SVR: resume and checkpoints are not implemented");
-    DPSVM_CHECK(n < (int64_t)1 << 30, "epsilon-SVR: 2 n must fit in 31 bits (packed selection keys)");
-    for (int64_t i = 0; i < n; ++i) DPSVM_CHECK(std::isfinite(Y[i]), "epsilon-SVR: targets must be finite");
-  }
-  const int64_t ns = svr ? 2 * n : n;  // state rows
-  auto y_of = [&](int64_t g) { return svr ? (g < n ? 1.f : -1.f) : Y[g]; };
+  // the problem kind and its refusals (dpsvm/problem.hpp).  One-class (docs/DESIGN.md §18): labels +1, linear term 0,
+  // the start LIBSVM's feasible point (below).  epsilon-SVR (§17): ds.y holds the targets Z; the folded dual has
+  // ns = 2n state rows (alpha_j at j, alpha*_j at j + n) over kernel rows of n columns: K~(a, b) = K(a mod n, b mod n)
+  const ProblemKind kind = resolve_problem(p);
+  const bool oc = kind == ProblemKind::OneClass, svr = kind == ProblemKind::Svr;
+  check_problem(kind, p, {n, world, Cr != nullptr, resume != nullptr, n, ds.y.data(), false});
+  const int64_t ns = state_rows(kind, n);
+  const float* Z = ds.y.data();
+  std::vector<float> labels;
+  problem_labels(kind, Z, n, labels);
+  const float* Y = labels.data();  // the ns state rows' labels
   if (Cr) {
     bool pos = false, neg = false;
     for (int64_t i = 0; i < n; ++i) {
@@ -162,8 +139,8 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   std::vector<float> f((size_t)(svr ? ns : nl));
   if (svr) {
     for (int64_t j = 0; j < n; ++j) {  // f = y o p at alpha = 0, p = [eps - z, eps + z]
-      f[j] = p.svr_epsilon - Y[j];
-      f[j + n] = -p.svr_epsilon - Y[j];
+      f[j] = p.svr_epsilon - Z[j];
+      f[j + n] = -p.svr_epsilon - Z[j];
     }
   } else {
     for (int64_t j = 0; j < nl; ++j) f[j] = -Y[off + j];  // f = -y (svmTrain.cu:380)
@@ -181,8 +158,8 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
           s += ai * std::exp(-gamma * std::max(d2, 0.f));
         }
         if (svr) {
-          out[j] = s + (p.svr_epsilon - Y[j]);
-          out[j + n] = s + (-p.svr_epsilon - Y[j]);
+          out[j] = s + (p.svr_epsilon - Z[j]);
+          out[j + n] = s + (-p.svr_epsilon - Z[j]);
         } else {
           out[j] = oc ? s : s - Y[off + j];
         }
@@ -236,16 +213,14 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   };
 
   if (oc) {
-    // alpha = 1 on the first floor(nu n) rows, the remainder on the next (built in double, as LIBSVM does);
-    // f = K alpha from those kernel rows, accumulated in double and rounded once — what gram_rows_wsum reads
-    // off the resident Gram on the device
-    const double total = (double)p.one_class_nu * (double)n;
-    const int64_t full = std::min<int64_t>(n, (int64_t)total);
-    for (int64_t i = 0; i < full; ++i) alpha[i] = 1.f;
-    if (full < n) alpha[full] = (float)(total - (double)full);
+    // LIBSVM's feasible start (one_class_start); f = K alpha from those kernel rows, accumulated in double and
+    // rounded once — what gram_rows_wsum reads off the resident Gram on the device
+    const OneClassStart st = one_class_start(p.one_class_nu, n);
+    for (int64_t i = 0; i < st.full; ++i) alpha[i] = 1.f;
+    if (st.full < n) alpha[st.full] = st.rest;
     std::vector<double> acc((size_t)nl, 0.0);
     std::vector<float> row((size_t)nl);
-    for (int64_t r = 0; r < n && alpha[r] > 0.f; ++r) {
+    for (int64_t r = 0; r < st.start_rows; ++r) {
       compute_row(r, row.data());
       ++res.rows_computed;
       const double a = alpha[r];
@@ -271,7 +246,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
     for (int64_t j = b; j < e; ++j) {
       for (int h = 0; h < (svr ? 2 : 1); ++h) {  // epsilon-SVR: column j carries state rows j and j + n
         const int64_t g = off + j + (h ? n : 0);
-        const float a = alpha[g], yj = y_of(g), fj = f[g - off];
+        const float a = alpha[g], yj = Y[g], fj = f[g - off];
         const bool up = Cr ? in_up_w(a, yj, Cr[g]) : in_up(a, yj, C);
         const bool low = Cr ? in_low_w(a, yj, Cr[g]) : in_low(a, yj, C);
         if (up) kh = std::min(kh, make_key(fj, (uint32_t)g));
@@ -317,7 +292,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
     const float a_hi_old = alpha[i_hi], a_lo_old = alpha[i_lo];
     PairUpdate u = Cr ? pair_update_w(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, Cr[i_hi], Cr[i_lo],
                                       p.tau, (int)p.clip, i_hi == i_lo)
-                      : pair_update(a_hi_old, a_lo_old, y_of(i_hi), y_of(i_lo), b_hi, b_lo, k_hl, C, p.tau,
+                      : pair_update(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, C, p.tau,
                                     (int)p.clip, i_hi == i_lo);
     alpha[i_lo] = u.a_lo_new;
     alpha[i_hi] = u.a_hi_new;  // hi written last: wins if i_hi == i_lo

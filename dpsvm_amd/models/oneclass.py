@@ -17,22 +17,14 @@ scikit-learn names: ``offset_`` is rho, ``eps`` stays this project's stop tolera
 """
 from __future__ import annotations
 
-import dataclasses
 import time
 from typing import Any, Callable, Optional, Sequence
 
 import numpy as np
 
 from .._native import load
-from .svc import SVCConfig, _as_f32_2d, _parse_device
-
-# what one-class runs on: one-block working-set rounds on the resident Gram, one rank, joint-box clipping
-_NOTE = "one-class: nu start, one block"
-
-
-def _refuse(what: str) -> None:
-    raise NotImplementedError(f"OneClassSVM: {what} is not implemented for one-class (it runs one-block "
-                              "working-set rounds on the resident Gram of one rank, with box clipping and C = 1)")
+from ._base import _OneBlockEstimator, _as_f32_2d
+from .svc import LoadedModel
 
 
 def _check_nu(nu: float) -> float:
@@ -42,7 +34,23 @@ def _check_nu(nu: float) -> float:
     return nu
 
 
-class OneClassSVM:
+class _OneClassDecisions:
+    """what the estimator and the loaded model derive from the decision sum_sv alpha K(sv, x) - rho"""
+
+    def decision_function(self, X) -> np.ndarray:
+        """float32: >= 0 inside the estimated support"""
+        return self._decision(X)
+
+    def score_samples(self, X) -> np.ndarray:
+        """the decision without the offset: sum_sv alpha K(sv, x)"""
+        return (self.decision_function(X) + np.float32(self._rho())).astype(np.float32)
+
+    def predict(self, X) -> np.ndarray:
+        """+1 where the decision is >= 0 (inlier), else -1"""
+        return np.where(self.decision_function(X) >= 0, 1, -1).astype(np.int32)
+
+
+class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
     """RBF one-class SVM: ``min 1/2 |w|^2 - rho + 1/(nu n) sum max(0, rho - w.phi(x_i))``.
 
     Attributes after ``fit(X)``: ``alpha_`` ((n,), LIBSVM's scale: 0 <= alpha <= 1, sum = nu n), ``dual_coef_``
@@ -56,66 +64,31 @@ class OneClassSVM:
     from nu n, so the joint box only.  nu = 1 (every alpha at its bound: nothing to solve) is refused.
     """
 
+    _NAME, _KIND, _EXTRA = "OneClassSVM", "one-class", "nu"
+    _RUNS = "it runs one-block working-set rounds on the resident Gram of one rank, with box clipping and C = 1"
+    _CLIP_WHY = "independent clipping lets sum(alpha) drift from nu n"
+
     def __init__(self, nu: float = 0.5, gamma: Optional[float] = None, eps: float = 1e-3, max_iter: int = 150000,
                  device: str = "auto", **kwargs: Any):
-        kwargs.setdefault("clip", "box")
-        if kwargs.get("C", 1.0) != 1.0:
-            _refuse(f"C={kwargs['C']} (the box is [0, 1])")
-        kwargs.pop("C", None)
-        self.config = SVCConfig(C=1.0, gamma=gamma, eps=eps, max_iter=max_iter, device=device, **kwargs)
         self.nu = nu
-        self._resolve()
-        self._model = None
-        self._gpu_pred = None
+        C = kwargs.pop("C", 1.0)
+        if C != 1.0:
+            self._refuse(f"C={C} (the box is [0, 1])")
+        super().__init__(C=1.0, gamma=gamma, eps=eps, max_iter=max_iter, device=device, **kwargs)
 
-    # ------------------------------------------------------------------ settings
-    def _resolve(self) -> None:
-        """refuse what one-class does not run, resolve the rest (before any native or device state exists)"""
-        cfg = self.config
+    def _check_extra(self) -> None:
         self.nu = _check_nu(self.nu)
-        _parse_device(cfg.device)
-        if cfg.C != 1.0:
-            _refuse(f"C={cfg.C} (the box is [0, 1])")
-        if cfg.clip != "box":
-            _refuse(f"clip={cfg.clip!r} (independent clipping lets sum(alpha) drift from nu n)")
-        if cfg.solver not in ("auto", "ws"):
-            _refuse(f"solver={cfg.solver!r} (the pair-at-a-time engines)")
-        if cfg.ws_blocks not in (0, 1):
-            _refuse(f"ws_blocks={cfg.ws_blocks} (multi-block rounds)")
-        if cfg.shrink_mode() == "on":
-            _refuse("shrink='on'")
-        if cfg.ws_recompute == "on":
-            _refuse("ws_recompute='on'")
-        if cfg.class_weight is not None:
-            _refuse("class_weight (per-row C)")
-        if cfg.force_cache or cfg.cache_lines or cfg.host_cache_lines:
-            _refuse("the kernel-row cache (force_cache / cache_lines / host_cache_lines)")
-        if cfg.engines != "production":
-            _refuse("engines='all'")
-        if cfg.x_mode == "partitioned" or cfg.dp != "auto":
-            _refuse("partitioned X / a data-parallel policy")
-        if cfg.exchange == "peer" or cfg.force_collectives:
-            _refuse("the peer exchange / forced collectives")
-        if cfg.checkpoint_path or cfg.checkpoint_every:
-            _refuse("checkpoints")
-        cfg.solver = "ws"
-        cfg.ws_blocks = 1
-        cfg.shrink = "off"
-        cfg.ws_recompute = "off"
+        if self.config.C != 1.0:
+            self._refuse(f"C={self.config.C} (the box is [0, 1])")
 
     def _params(self, d: int, nu: Optional[float] = None):
         p = self.config.to_native(d)
         p.one_class_nu = self.nu if nu is None else nu
         return p
 
-    @staticmethod
-    def _refuse_fit_args(comm, resume, rank_rows, sample_weight) -> None:
-        for name, val in (("comm", comm), ("resume", resume), ("rank_rows", rank_rows),
-                          ("sample_weight", sample_weight)):
-            if val is not None:
-                _refuse(name)
+    def _rho(self) -> float:
+        return self.offset_
 
-    # ------------------------------------------------------------------ fit
     def fit(self, X, y=None, comm=None, resume=None, progress: Optional[Callable] = None, rank_rows=None,
             sample_weight=None) -> "OneClassSVM":
         """Train on the rows of ``X`` (``y`` is ignored).  One rank, from the nu start, unweighted."""
@@ -123,56 +96,15 @@ class OneClassSVM:
         self._resolve()
         X = _as_f32_2d(X)
         n, d = X.shape
-        C = load()
         p = self._params(d)
-        ones = np.ones(n, dtype=np.float32)
-        kind, dev = self.config.device_kind()
         t0 = time.perf_counter()
-        if kind == "cuda":
-            solver = C.GpuSolver(p, None, dev)  # dropped after the solve, with its resident Gram
-            self.setup_info_ = solver.setup(X, n, ones)
-            alpha, info = solver.solve(None, progress)
-            f = np.asarray(solver.gradient(), dtype=np.float32)
-            del solver
-            info = dict(info)
-        else:
-            self.setup_info_ = {"iteration": "cpu", "engine_note": _NOTE}
-            alpha, info = C.solve_cpu(X, ones, p, None, None, progress, None)
-            info = dict(info)
-            f = np.asarray(info.pop("f"), dtype=np.float32)
+        alpha, info, f, setup = self._run(X, np.ones(n, dtype=np.float32), p, progress, want_gradient=True)
         self.wall_time_ = time.perf_counter() - t0
-        self._publish(X, alpha, info, f, p.gamma)
-        self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
-        return self
-
-    def _publish(self, X: np.ndarray, alpha: np.ndarray, info: dict, f: np.ndarray, gamma: float) -> None:
-        n, d = X.shape
         self.alpha_ = np.ascontiguousarray(np.asarray(alpha, dtype=np.float32).reshape(n))
-        self.b_ = float(info["b"])
-        self.offset_ = self.b_
-        self.intercept_ = -self.b_
-        self.train_decision_ = (f.astype(np.float64) - self.b_).astype(np.float32)
-        self.n_iter_ = int(info["iters"])
-        self.n_rounds_ = int(info.get("outer", 0))
-        self.status_ = int(info["status"])
-        self.converged_ = bool(info["converged"])
-        self.fit_time_ = float(info["t_solve"])
-        self.setup_time_ = float(info["t_setup"])
-        self.stats_ = info
-        self.gamma_ = gamma
-        self.n_features_in_ = d
-        self.support_ = np.nonzero(self.alpha_ > 0)[0]
-        self.support_vectors_ = X[self.support_]
-        self.dual_coef_ = self.alpha_[self.support_].astype(np.float32)
-        self.n_support_ = int(len(self.support_))
-        self._X_train = X
-        self._model = None
-        self._gpu_pred = None
-        if self.status_ == 2:
-            import warnings
-
-            warnings.warn(f"stopped at max_iter with gap {info['b_lo'] - info['b_hi']:.3g} > 2 eps: raise max_iter "
-                          "to converge", RuntimeWarning, stacklevel=3)
+        self.offset_ = float(info["b"])
+        self.train_decision_ = (f.astype(np.float64) - self.offset_).astype(np.float32)
+        self._publish_fit(X, self.alpha_, info, p.gamma, setup)
+        return self
 
     def nu_path(self, X, nus: Sequence[float], progress: Optional[Callable] = None) -> dict:
         """One solve per nu on one solver, one ``setup()`` and one resident Gram (``set_nu`` per nu; on the CPU k
@@ -215,90 +147,16 @@ class OneClassSVM:
         self.path_alpha_ = np.stack(alphas)
         return {"nu": list(nus), "rho": rho, "n_support": nsv, "outlier_fraction": out}
 
-    # ------------------------------------------------------------------ model
-    def to_model(self):
-        """the binary model of alpha with y = +1 (rows with alpha = 0 are no SVs), b = rho"""
-        if self._model is None:
-            if getattr(self, "alpha_", None) is None:
-                raise RuntimeError("to_model() needs a fitted OneClassSVM")
-            y = np.ones(len(self.alpha_), dtype=np.float32)
-            self._model = load().make_model(self._X_train, y, self.alpha_, self.b_, self.gamma_)
-        return self._model
 
-    def save(self, path: str, precision: int = 9) -> None:
-        """Write the binary text model (gamma, rho, then alpha, +1, x per SV); ``load_one_class`` reads it."""
-        load().write_model(path, self.to_model(), precision, False)
-
-    # ------------------------------------------------------------------ predict
-    def _predictor(self):
-        if self._gpu_pred is None:
-            kind, dev = self.config.device_kind()
-            if kind == "cuda":
-                self._gpu_pred = load().GpuPredictor(self.to_model(), dev)
-        return self._gpu_pred
-
-    def decision_function(self, X) -> np.ndarray:
-        """sum_sv alpha K(sv, x) - rho, float32: >= 0 inside the estimated support"""
-        X = _as_f32_2d(X)
-        if X.shape[1] != self.n_features_in_:
-            raise ValueError(f"X has {X.shape[1]} features, model has {self.n_features_in_}")
-        gp = self._predictor()
-        out = gp.decision(X) if gp is not None else load().decision_cpu(self.to_model(), X, 0)
-        return np.asarray(out, dtype=np.float32)
-
-    def score_samples(self, X) -> np.ndarray:
-        """the decision without the offset: sum_sv alpha K(sv, x)"""
-        return (self.decision_function(X) + np.float32(self.offset_)).astype(np.float32)
-
-    def predict(self, X) -> np.ndarray:
-        """+1 where the decision is >= 0 (inlier), else -1"""
-        return np.where(self.decision_function(X) >= 0, 1, -1).astype(np.int32)
-
-    def get_params(self, deep: bool = True) -> dict:
-        out = dataclasses.asdict(self.config)
-        out["nu"] = self.nu
-        return out
-
-
-class LoadedOneClass:
+class LoadedOneClass(_OneClassDecisions, LoadedModel):
     """A one-class model read from the binary text model file."""
-
-    def __init__(self, model, device: str = "auto"):
-        self.model = model
-        self.device = device
-        if device != "auto":
-            _parse_device(device)
-        self._gpu = None
-
-    @property
-    def gamma(self) -> float:
-        return self.model.gamma
 
     @property
     def offset(self) -> float:
         return self.model.b
 
-    @property
-    def n_support(self) -> int:
-        return self.model.nsv
-
-    def _predictor(self):
-        kind, dev = _parse_device(self.device)
-        if kind == "cuda" and self._gpu is None:
-            self._gpu = load().GpuPredictor(self.model, dev)
-        return self._gpu
-
-    def decision_function(self, X) -> np.ndarray:
-        X = _as_f32_2d(X)
-        gp = self._predictor()
-        out = gp.decision(X) if gp is not None else load().decision_cpu(self.model, X, 0)
-        return np.asarray(out, dtype=np.float32)
-
-    def score_samples(self, X) -> np.ndarray:
-        return (self.decision_function(X) + np.float32(self.offset)).astype(np.float32)
-
-    def predict(self, X) -> np.ndarray:
-        return np.where(self.decision_function(X) >= 0, 1, -1).astype(np.int32)
+    def _rho(self) -> float:
+        return self.model.b
 
 
 def load_one_class(path: str, device: str = "auto") -> LoadedOneClass:

@@ -20,32 +20,8 @@ from typing import Any, Callable, Optional
 
 import numpy as np
 
-from .._native import gpu_available, load, load_quarantine
-
-
-def _as_f32_2d(X) -> np.ndarray:
-    try:
-        import torch
-
-        if isinstance(X, torch.Tensor):
-            X = X.detach().to("cpu", dtype=torch.float32).numpy()
-    except ImportError:
-        pass
-    X = np.ascontiguousarray(np.asarray(X, dtype=np.float32))
-    if X.ndim != 2:
-        raise ValueError(f"X must be 2-D (n_samples, n_features), got shape {X.shape}")
-    return X
-
-
-def _as_1d(y) -> np.ndarray:
-    try:
-        import torch
-
-        if isinstance(y, torch.Tensor):
-            y = y.detach().cpu().numpy()
-    except ImportError:
-        pass
-    return np.asarray(y).reshape(-1)
+from .._native import load, load_quarantine
+from ._base import _Predicts, _as_1d, _as_f32_2d, _parse_device, _pick, _publish_solves  # noqa: F401 (re-exported)
 
 
 _CLIP = {"independent": 0, "box": 1}
@@ -74,23 +50,6 @@ _PLAIN = {
           "census_groups", "ws_size", "ws_new", "ws_blocks", "ws_inner", "ws_wss", "ws_block"),
     bool: ("use_graph", "verbose", "force_collectives", "force_cache", "verify_ranks"),
 }
-
-
-def _parse_device(dev: str) -> tuple[str, int]:
-    """auto | cpu | cuda | cuda:N -> ("cuda", N) or ("cpu", 0); anything else is a ValueError"""
-    if dev == "auto":
-        return ("cuda", 0) if gpu_available() else ("cpu", 0)
-    if dev == "cpu":
-        return ("cpu", 0)
-    if dev.startswith("cuda"):
-        return ("cuda", int(dev.split(":")[1]) if ":" in dev else 0)
-    raise ValueError(f"unknown device {dev!r}")
-
-
-def _pick(table: dict, value: str, name: str) -> int:
-    if value not in table:
-        raise ValueError(f"{name} must be one of {list(table)}, got {value!r}")
-    return table[value]
 
 
 def _predict_proba(gp, model, multi: bool, X: np.ndarray, A, B) -> np.ndarray:
@@ -286,7 +245,7 @@ class SVCConfig:
         return _parse_device(self.device)
 
 
-class SVC:
+class SVC(_Predicts):
     """RBF C-SVM trained by modified SMO on MI355X (or the CPU).
 
     Attributes after fit: ``alpha_`` (dual variables, len n), ``b_`` (threshold:
@@ -321,7 +280,6 @@ class SVC:
                  max_iter: int = 150000, device: str = "auto", **kwargs: Any):
         self.config = SVCConfig(C=C, gamma=gamma, eps=eps, max_iter=max_iter, device=device, **kwargs)
         self._model = None
-        self._gpu_pred = None
         self._multi = False
         self.classes_ = np.array([-1.0, 1.0], dtype=np.float32)
 
@@ -608,15 +566,7 @@ class SVC:
         self._publish(p, d, time.perf_counter() - t0, setup)
         self._publish_proba(proba)
         self.alpha_ = alpha
-        self.b_ = float(info["b"])
-        self.intercept_ = -self.b_
-        self.n_iter_ = int(info["iters"])
-        self.n_rounds_ = int(info.get("outer", 0))
-        self.status_ = int(info["status"])
-        self.converged_ = bool(info["converged"])
-        self.fit_time_ = float(info["t_solve"])
-        self.setup_time_ = float(info["t_setup"])
-        self.stats_ = info
+        _publish_solves(self, [info])
         self.row_C_ = row_C = None if RC is None else RC[0]
         bound = row_C if row_C is not None else np.float32(cfg.C)
         self.n_bounded_ = int(np.sum((alpha == bound) & (alpha > 0))) if rank_rows is None else None
@@ -645,7 +595,7 @@ class SVC:
         self.gamma_ = p.gamma
         self.n_features_in_ = d
         self._model = None
-        self._gpu_pred = None
+        self._gpu = None
 
     def _fit_multi(self, X: np.ndarray, y: np.ndarray, comm, resume, progress, rank_rows,
                    sample_weight=None, probability: int = 0, probability_seed: int = 0) -> "SVC":
@@ -667,15 +617,7 @@ class SVC:
         self._publish_proba(proba)
         self.classes_ = classes
         self.alpha_ = np.stack(alphas).astype(np.float32)
-        self.b_ = np.array([i["b"] for i in infos], dtype=np.float32)
-        self.intercept_ = -self.b_
-        self.n_iter_ = np.array([i["iters"] for i in infos], dtype=np.int64)
-        self.n_rounds_ = np.array([i.get("outer", 0) for i in infos], dtype=np.int64)
-        self.status_ = int(max(i["status"] for i in infos))
-        self.converged_ = bool(all(i["converged"] for i in infos))
-        self.fit_time_ = float(sum(i["t_solve"] for i in infos))
-        self.setup_time_ = float(infos[0]["t_setup"])
-        self.stats_ = infos
+        _publish_solves(self, infos, multi=True)
         self.row_C_ = RC
         bound = RC if RC is not None else np.float32(self.config.C)
         self.n_bounded_ = int(np.sum((self.alpha_ == bound) & (self.alpha_ > 0)))
@@ -769,24 +711,9 @@ class SVC:
         _write_platt(path, getattr(self, "probA_", None), getattr(self, "probB_", None))
 
     # ------------------------------------------------------------------ predict
-    def _predictor(self):
-        if self._gpu_pred is None:
-            kind, dev = self.config.device_kind()
-            if kind == "cuda":
-                self._gpu_pred = load().GpuPredictor(self.to_model(), dev)
-        return self._gpu_pred
-
     def decision_function(self, X) -> np.ndarray:
         """sum_sv alpha y K(sv, x) - b  (svmTrain.cu:646-652)."""
-        X = _as_f32_2d(X)
-        if X.shape[1] != self.n_features_in_:
-            raise ValueError(f"X has {X.shape[1]} features, model has {self.n_features_in_}")
-        gp = self._predictor()
-        if self._multi:
-            return gp.decision_multi(X) if gp is not None else load().decision_multi_cpu(self.to_model(), X, 0)
-        if gp is not None:
-            return gp.decision(X)
-        return load().decision_cpu(self.to_model(), X, 0)
+        return self._decision(X)
 
     def predict(self, X) -> np.ndarray:
         dec = self.decision_function(X)
@@ -823,17 +750,13 @@ class SVC:
         return dataclasses.asdict(self.config)
 
 
-class _Loaded:
-    """What the loaded models share: the device, the GpuPredictor built on first use, the model's scalars."""
-
-    _multi = False
+class _Loaded(_Predicts):
+    """What the loaded models share: the predictor holder, the Platt sidecar's sigmoids, the model's scalars."""
 
     def __init__(self, model, device: str = "auto", platt=None):
         self.model = model
         self.device = device
-        if device != "auto":
-            _parse_device(device)  # an unknown string fails here, not at the first prediction
-        self._gpu = None
+        self._check_device()
         self.probA_, self.probB_ = platt if platt is not None else (None, None)  # the sidecar's sigmoids
 
     def predict_proba(self, X) -> np.ndarray:
@@ -856,21 +779,18 @@ class _Loaded:
     def n_support(self) -> int:
         return self.model.nsv
 
-    def _predictor(self):
-        """the device predictor, None on the CPU"""
-        kind, dev = _parse_device(self.device)
-        if kind == "cuda" and self._gpu is None:
-            self._gpu = load().GpuPredictor(self.model, dev)
-        return self._gpu
+    def _device(self) -> str:
+        return self.device
+
+    def _native_model(self):
+        return self.model
 
 
 class LoadedModel(_Loaded):
     """A model read from a reference-format file (svmTest path)."""
 
     def decision_function(self, X) -> np.ndarray:
-        X = _as_f32_2d(X)
-        gp = self._predictor()
-        return gp.decision(X) if gp is not None else load().decision_cpu(self.model, X, 0)
+        return self._decision(X)
 
     def predict(self, X) -> np.ndarray:
         return np.where(self.decision_function(X) < 0, -1.0, 1.0).astype(np.float32)
@@ -889,9 +809,7 @@ class LoadedMultiModel(_Loaded):
         self.classes_ = np.asarray(model.classes)
 
     def decision_function(self, X) -> np.ndarray:
-        X = _as_f32_2d(X)
-        gp = self._predictor()
-        return gp.decision_multi(X) if gp is not None else load().decision_multi_cpu(self.model, X, 0)
+        return self._decision(X)
 
     def predict(self, X) -> np.ndarray:
         return self.classes_[np.argmax(self.decision_function(X), axis=1)]

@@ -18,7 +18,15 @@ EPS = 1e-3
 PRED_TOL = 1e-2
 B_TOL = 1e-2
 BAND = 1e-2   # decisions within BAND of 0 are undecided at these tolerances
-NOTE = "one-class: nu start, one block"
+
+
+def note():
+    """what engine_note says about one-class: the native problem_note"""
+    from dpsvm_amd._native import load
+
+    p = load().SolverParams()
+    p.one_class_nu = 0.5
+    return load().problem_note(p)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -47,7 +55,7 @@ def check_setup(m):
     si = m.setup_info_
     assert si["iteration"] == "ws-dense" and si["ws_rows"] == "gram"
     assert si["ws_blocks"] == 1
-    assert NOTE in si["engine_note"]
+    assert note() in si["engine_note"]
 
 
 def check_invariants(m, nu, n):
@@ -179,7 +187,7 @@ def test_oneclass_gpu_nu_path_reuses_the_gram(fx):
         assert path["rho"][i] == fresh.offset_ and m.path_stats_[i]["iters"] == fresh.n_iter_
         assert path["n_support"][i] == fresh.n_support_
         assert path["outlier_fraction"][i] == float(np.mean(fresh.train_decision_ < 0))
-    assert NOTE in m.path_setup_info_["engine_note"]
+    assert note() in m.path_setup_info_["engine_note"]
 
 
 @pytest.mark.parametrize("kw,msg", [

@@ -55,7 +55,11 @@ def check_setup(m):
     si = m.setup_info_
     assert si["iteration"] == "ws-dense" and si["ws_rows"] == "gram"
     assert si["ws_blocks"] == 1
-    assert "epsilon-SVR: folded 2n, one block" in si["engine_note"]
+    from dpsvm_amd._native import load
+
+    p = load().SolverParams()
+    p.problem = 1
+    assert load().problem_note(p) and load().problem_note(p) in si["engine_note"]
     assert si["n"] == m.alpha_.shape[1]  # the Gram's rows: n, not 2n
 
 
@@ -218,6 +222,7 @@ def test_svr_gpu_refuses_classifier_only_calls(fx, C):
                  lambda: solver.decision(alpha[:n], info["b"], fx["X_test"]),
                  lambda: solver.holdout_decisions(np.arange(5, dtype=np.int32), 0.0, 0),
                  lambda: solver.platt_fit(0),
+                 lambda: solver.set_nu(0.2),
                  lambda: solver.solve(C.Checkpoint())):
         with pytest.raises(RuntimeError, match="regression|epsilon-SVR"):
             call()

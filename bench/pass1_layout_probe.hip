@@ -1,6 +1,7 @@
 // Probe: how fast can the working-set f update (pass 1: d_f_j = sum over the
 // round's changed rows k of c_k K(line_k, j)) stream its Gram rows, by access
-// layout?  The production kernel (kernels/ws_select.hip, MODE 1) gives each
+// layout?  The production kernel of round 3 (the selection-geometry pass 1,
+// since replaced by ws_pass1_v4_kernel, the dwordx4 layout found here) gave each
 // thread one column (dword loads, 256 B per wave instruction), four
 // partitions of the changed-row list per 1024-thread workgroup and 48 loads in
 // flight per thread: 161 us for 3,072 rows x 60,000 columns (4.6 TB/s of row

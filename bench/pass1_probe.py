@@ -4,8 +4,11 @@ sharded headline: a rank of P owns n = 60000 / P columns of every Gram row and
 a round changes up to 6,144 rows (the default union: 128 blocks x 48).  Times ws_select pass 1 alone
 (event-timed, repeated: it only reads the state) on crafted state through the
 ws_select probe, for several list-slice counts ks (pass-1 workgroups per
-selection group), to see whether the G = ceil(n / 256) workgroups of the
-selection geometry can drive the memory system at small n.
+column group), to see how many slices the p1G = ceil(n / 1024) column groups
+need to drive the memory system at small n.  Columns per rank must be a
+multiple of 4 (16-byte row loads).  Every record carries "wide": true, so
+bench/project_shard.py reads these and older records (which also timed a
+selection-geometry pass 1, "wide": false) alike.
 
   python bench/pass1_probe.py [--rows 60000] [--reps 20] [--out file.jsonl]
 """
@@ -27,7 +30,6 @@ def main() -> int:
     ap.add_argument("--changed", type=int, default=6144)
     ap.add_argument("--blocks", type=int, default=128)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--wide", action="store_true", help="the wide pass 1 (ws_pass1_v4_kernel, the default)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from dpsvm_amd._native import load
@@ -48,10 +50,10 @@ def main() -> int:
         nab = np.full(blocks, q, dtype=np.int32)
         for ks in [int(v) for v in a.ks.split(",")]:
             r = C.k_ws_select(gram.reshape(-1), L, n, f, alpha, y, dalpha, lines, coef, nab, blocks, blocks, blocks, q,
-                              10.0, 1, ks=ks, reps=a.reps, wide=a.wide)
+                              10.0, 1, ks=ks, reps=a.reps)
             t = np.array(r["pass1_us"][2:])
             rec = {"cols": n, "rows": L, "changed": int(blocks * q), "G": int(r["G"]), "ks": ks,
-                   "wide": bool(a.wide), "p1G": int(r["p1G"]), "workgroups": int(r["p1G"]) * ks, "pass1_us_median": round(float(np.median(t)), 2),
+                   "wide": True, "p1G": int(r["p1G"]), "workgroups": int(r["p1G"]) * ks, "pass1_us_median": round(float(np.median(t)), 2),
                    "pass1_us_min": round(float(t.min()), 2),
                    "GBps": round(blocks * q * n * 4 / (float(np.median(t)) * 1e-6) / 1e9, 1)}
             print(json.dumps(rec), flush=True)

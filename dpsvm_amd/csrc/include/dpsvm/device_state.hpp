@@ -418,8 +418,7 @@ struct WsArgs {
   float t_halve;       // multi-block: a round damped to t < t_halve halves the block count
   int32_t clip_fallback;  // multi-block, independent clipping: a clip event drops to one block (1) or not (0)
   int32_t ks;          // multi-block pass 1: list slices over workgroups (dfs [ks][nl], part [world p1G][ks][2])
-  int32_t p1G;         // multi-block pass 1: column groups per rank (= G; the wide pass 1: ceil(nl_max / 1024))
-  int32_t p1v4;        // multi-block pass 1: 1 = wide column groups, 4 columns (16-B loads) per thread
+  int32_t p1G;         // multi-block pass 1: column groups per rank, ceil(nl_max / 1024) (ws_pass1_v4_groups)
   uint64_t* sorted;    // multi-block: [2][kWsMaxGroups * kWsCand] every candidate key per side, ascending (ws_rank)
   int32_t direct_sub;  // multi-block solve loads its sub-Gram / f / alpha / y straight from the resident Gram
                        // (world 1, dense, blocks of <= 64 rows: no ws_gather launch)
@@ -442,7 +441,7 @@ constexpr int64_t ws_xch_words(int64_t G_all, int64_t q_max) {
 // multi-block engine (P blocks of q rows; its one-block rounds use q1 rows):
 // candidates (kWsCand keys per side), line-search partials, sub-Gram rows
 constexpr int64_t ws_xch_cand_words_multi(int64_t G_all) { return 2 * G_all * 4 * kWsCand; }
-// (P1_all = world x p1G pass-1 groups: the selection groups, or the wide pass 1's)
+// (P1_all = world x p1G pass-1 groups)
 constexpr int64_t ws_xch_part_words(int64_t P1_all, int64_t ks) { return 2 * P1_all * ks * 4; }
 constexpr int64_t ws_xch_sub_words(int64_t P, int64_t q, int64_t q1) {
   return 2 * ((P * q * (q + 1)) > (q1 * (q1 + 1)) ? P * q * (q + 1) : q1 * (q1 + 1));

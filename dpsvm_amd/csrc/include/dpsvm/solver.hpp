@@ -324,13 +324,14 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
 // ws_select: the f update of a round's alpha changes (apply rows: lines into
 // gram [L][ldg], coefficients) and the per-workgroup candidates.  blocks == 1:
 // the one-pass kernel; blocks > 1: pass 1 (d_f, line-search partials) and pass 2
-// (t, f += t d_f, alpha fix-up, candidates) with p_round blocks this round.
+// (t, f += t d_f, alpha fix-up, candidates) with p_round blocks this round;
+// pass 1 loads 16 bytes a thread, so blocks > 1 needs ldg % 4 == 0 and ldg >= round_up(n, 4).
 struct WsSelectProbe {
   std::vector<float> f, alpha, dalpha, dfs;
-  std::vector<double> part;      // [G][2] d'Qd, g'd partials (two-pass mode)
+  std::vector<double> part;      // [p1G][ks][2] d'Qd, g'd partials (two-pass mode)
   std::vector<uint64_t> cand;    // [G][2][kWsCand]
   int G = 0, rpt = 0, p_act = 0, n_damped = 0, nonfinite = 0;
-  int p1G = 0;                   // pass-1 groups (= G; the wide pass 1: ceil(n / 1024)); part is [p1G][ks][2]
+  int p1G = 0;                   // pass-1 groups (blocks > 1: ceil(n / 1024), else G); part is [p1G][ks][2]
   float t = 1.f;
   int64_t p1_round = 0;
   std::vector<float> pass1_us;  // reps > 0: event times of repeated pass-1 launches
@@ -341,7 +342,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               const std::vector<float>& dalpha, const std::vector<int32_t>& apply_line,
                               const std::vector<float>& apply_coef, const std::vector<int32_t>& nab, int blocks,
                               int p_round, int p_act, int q_max, float C, int64_t outer, int ks = 0,
-                              int reps = 0, bool wide = false,
+                              int reps = 0,
                               const std::vector<float>& row_C = {},  // [n] per-row bounds (empty: scalar C)
                               // fold > 0: the epsilon-SVR kernel — f / alpha / y of 2 fold state rows on gram
                               // [L][ldg >= fold]; done: the run's state (DoneCode) the launch finds

@@ -1,7 +1,9 @@
 // Working-set engine, selection pass (ws_select): the round's alpha changes
-// applied to every f_j — one pass, or the two passes around the multi-block
-// line search — then each workgroup's candidate keys per side.  Round
-// structure and shared helpers: ws_common.hpp.
+// applied to every f_j, then each workgroup's candidate keys per side.  One-block
+// rounds: ws_select_kernel (one pass) or its epsilon-SVR form ws_select_fold_kernel,
+// both on the list sum WsListSum; multi-block rounds: ws_pass1_v4_kernel, then
+// ws_select_kernel as pass 2.  Every selecting kernel extracts by ws_extract.
+// Round structure and shared helpers: ws_common.hpp.
 #include <hip/hip_runtime.h>
 
 #include "dpsvm/common.hpp"
@@ -28,71 +30,187 @@ constexpr int ws_parts() {
   return RPT <= 4 ? 4 : RPT <= 16 ? 2 : 1;
 }
 
-// MODE 0: one pass (f += the round's change, then candidates).  Multi-block
-// rounds split it: MODE 1 computes the change d_f into a.dfs and per-workgroup
-// partial sums of the line search (d'Qd = sum_j c_j d_f_j and g'd = -sum_j c_j
-// f_j over the changed rows j, c_j = d_alpha_j y_j), MODE 2 takes
-// t = min(1, g'd / d'Qd) from the partials (fixed order: every workgroup the
-// same t), applies f += t d_f and alpha = alpha_new - (1 - t) d_alpha, then
-// selects the candidates.  Pass 2 walks no list: one partition, 256 threads.
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
-template <int RPT, int MODE>
-constexpr int ws_sel_parts() {
-  return MODE == 2 ? 1 : ws_parts<RPT>();
+// The changed-row list sum of the one-block kernels, a workgroup's LDS state
+// (__shared__) and the two steps on it: load() the round's list, then sum()
+// acc[r] = sum_k coef_k gram[line_k][base + 256 r] by kWsSelThreads * PARTS
+// threads, thread (tid, part) over partition part's slice.
+template <int RPT>
+struct WsListSum {
+  static constexpr int PARTS = ws_parts<RPT>();
+  static constexpr int CH = RPT >= 32 ? 1 : RPT >= 8 ? 4 : 48 / RPT;  // Gram loads in flight per thread (vmcnt <= 63)
+  int32_t idx[kWsMax];  // lines of the changed rows
+  float coef[kWsMax];
+  float part[PARTS > 1 ? PARTS - 1 : 1][PARTS > 1 ? kWsSelThreads * RPT : 1];
+
+  __device__ __forceinline__ void load(const WsCtrl* c, int na) {
+    for (int k = threadIdx.x; k < na; k += kWsSelThreads * PARTS) {
+      idx[k] = c->apply_line[k];
+      coef[k] = c->apply_coef[k];
+    }
+    __syncthreads();
+  }
+
+  // every thread of the workgroup calls it (one barrier); partition 0 holds the sum
+  __device__ __forceinline__ void sum(const WsArgs& a, int na, int64_t base, const bool (&has)[RPT], float (&acc)[RPT]) {
+    const int tid = threadIdx.x & (kWsSelThreads - 1), p_own = threadIdx.x / kWsSelThreads;
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) acc[r] = 0.f;
+    const int per = (na + PARTS - 1) / PARTS;
+    const int k_lo = min(na, p_own * per), k_hi = min(na, k_lo + per);
+    for (int k0 = k_lo; k0 < k_hi; k0 += CH) {
+      float kv[CH][RPT];
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        const int kk = min(k0 + u, k_hi - 1);
+        const float* row = a.gram + (int64_t)idx[kk] * a.ldg;
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) kv[u][r] = has[r] ? row[base + r * kWsSelThreads] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        if (k0 + u < k_hi) {
+          const float cc = coef[k0 + u];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) acc[r] = f_add1(acc[r], cc, kv[u][r]);
+        }
+      }
+    }
+    if constexpr (PARTS > 1) {
+      if (p_own > 0) {
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) part[p_own - 1][r * kWsSelThreads + tid] = acc[r];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int p = 1; p < PARTS; ++p) {
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+#pragma clang fp contract(off)
+          acc[r] = acc[r] + part[p - 1][r * kWsSelThreads + tid];
+        }
+      }
+    }
+  }
+};
+
+// Candidate extraction: the workgroup's nc smallest keys per side (ku: I_up,
+// kl: I_low; NK key slots a thread of partition 0, the other threads only meet
+// the barrier) to out[0 .. NC) and out[kWsCand .. kWsCand + NC), the tail past
+// nc kKeyNone.  Each wave's nc smallest keys per side, then wave 0 merges the
+// four lists.  Keys are unique (the global index is in the low bits) except
+// kKeyNone, the largest: a key's place is the count of smaller keys,
+// kKeyNone's the real keys' count plus its order among the lanes holding
+// kKeyNone — a permutation, so every place is written once.  One slot per
+// thread (RPT 1, every rank of up to 60,160 rows): each lane counts over its
+// wave's 64 keys (broadcast LDS reads, no barrier) instead of nc rounds of
+// wave minima.  Returns the merged lists [2][NC] in LDS, for wave 0 to read.
+template <int NK, int NC>
+__device__ __forceinline__ auto ws_extract(uint64_t (&ku)[NK], uint64_t (&kl)[NK], int nc, uint64_t* out) {
+  constexpr int W = kWsSelThreads / 64;
+  __shared__ uint64_t s_wc[W][2][kWsCand];
+  __shared__ uint64_t s_top[2][NC];
+  const bool part0 = threadIdx.x < kWsSelThreads;
+  const int lane = threadIdx.x & 63, wave = (threadIdx.x & (kWsSelThreads - 1)) >> 6;
+  const uint64_t below = (1ull << lane) - 1ull;
+  // place of key k among the wave's keys, given the count of smaller ones
+  auto place = [&](uint64_t k, int smaller) {
+    const uint64_t none = __ballot(k == kKeyNone);
+    return k == kKeyNone ? 64 - __popcll(none) + __popcll(none & below) : smaller;
+  };
+  if constexpr (NK == 1) {
+    __shared__ u64x2 s_kk[W][2][32];  // [wave][side] the wave's 64 keys
+    if (part0) {
+      const uint64_t mu = ku[0], ml = kl[0];
+      ((uint64_t*)s_kk[wave][0])[lane] = mu;
+      ((uint64_t*)s_kk[wave][1])[lane] = ml;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own stores, read by its lanes
+      int cu = 0, cl = 0;
+#pragma unroll 8
+      for (int m = 0; m < 32; ++m) {
+        const u64x2 vu = s_kk[wave][0][m], vl = s_kk[wave][1][m];
+        cu += (vu.x < mu ? 1 : 0) + (vu.y < mu ? 1 : 0);
+        cl += (vl.x < ml ? 1 : 0) + (vl.y < ml ? 1 : 0);
+      }
+      const int pu = place(mu, cu), pl = place(ml, cl);
+      if (pu < nc) s_wc[wave][0][pu] = mu;
+      if (pl < nc) s_wc[wave][1][pl] = ml;
+    }
+  } else {
+    for (int round = 0; round < nc && part0; ++round) {
+      uint64_t mu = kKeyNone, ml = kKeyNone;
+#pragma unroll
+      for (int r = 0; r < NK; ++r) {
+        mu = ku[r] < mu ? ku[r] : mu;
+        ml = kl[r] < ml ? kl[r] : ml;
+      }
+      mu = wave_min_u64(mu);
+      ml = wave_min_u64(ml);
+      if (lane == 0) {
+        s_wc[wave][0][round] = mu;
+        s_wc[wave][1][round] = ml;
+      }
+#pragma unroll
+      for (int r = 0; r < NK; ++r) {
+        if (ku[r] == mu) ku[r] = kKeyNone;
+        if (kl[r] == ml) kl[r] = kKeyNone;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    // lane l: entry l % kWsCand of wave l / kWsCand's list (W x kWsCand = 64)
+    static_assert(W * kWsCand == 64, "one merge entry per lane");
+    const bool have = lane % kWsCand < nc;  // the waves' nc entries
+    const uint64_t eu = have ? s_wc[lane / kWsCand][0][lane % kWsCand] : kKeyNone;
+    const uint64_t el = have ? s_wc[lane / kWsCand][1][lane % kWsCand] : kKeyNone;
+    int cu = 0, cl = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+#pragma unroll
+      for (int r = 0; r < NC; ++r) {
+        if (r < nc) {  // uniform
+          cu += s_wc[w][0][r] < eu ? 1 : 0;
+          cl += s_wc[w][1][r] < el ? 1 : 0;
+        }
+      }
+    }
+    const int pu = place(eu, cu), pl = place(el, cl);
+    if (pu < NC) s_top[0][pu] = pu < nc ? eu : kKeyNone;  // multi-block lists: the tail past nc is kKeyNone
+    if (pl < NC) s_top[1][pl] = pl < nc ? el : kKeyNone;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane < NC) out[lane] = s_top[0][lane];
+    else if (lane >= 32 && lane < 32 + NC) out[kWsCand + lane - 32] = s_top[1][lane - 32];
+  }
+  return s_top;
 }
 
+// P2 = false: one pass (f += the round's change, then candidates).  Multi-block
+// rounds split it: ws_pass1_v4_kernel below computes the change d_f into a.dfs
+// and per-workgroup partial sums of the line search (d'Qd = sum_j c_j d_f_j and
+// g'd = -sum_j c_j f_j over the changed rows j, c_j = d_alpha_j y_j); pass 2
+// (P2 = true) takes t = min(1, g'd / d'Qd) from the partials (fixed order:
+// every workgroup the same t), applies f += t d_f and alpha = alpha_new -
+// (1 - t) d_alpha, then selects the candidates.  Pass 2 walks no list: one
+// partition, 256 threads.
+//
 // kRowC: per-row bounds C_i (WsArgs::c_row, global [n]) — the classification reads c_row[gj] beside alpha / y
 // (one more coalesced 4-byte stream of n per round) in the compare form (in_up_w / in_low_w: a C_i = 0 row is
 // in neither set), and the line-search fix-ups clip a row to its own bound.  Separate instantiations: the
 // scalar ones keep their code.
-template <int RPT, int MODE, bool kRowC = false>
-__global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void ws_select_kernel(WsArgs a) {
-  constexpr int PARTS = ws_sel_parts<RPT, MODE>();
-  constexpr int CH = RPT >= 32 ? 1 : RPT >= 8 ? 4 : 48 / RPT;  // Gram loads in flight per thread (vmcnt <= 63)
-  constexpr int LMAX = MODE == 1 ? kWsMaxAll : MODE == 0 ? kWsMax : 1;
-  __shared__ int32_t s_idx[LMAX];  // lines of the changed rows
-  __shared__ float s_coef[LMAX];
-  __shared__ double s_red[2][kWsSelThreads * PARTS / 64];
-  __shared__ double s_red_tot[2];
-  __shared__ float s_part[PARTS > 1 ? PARTS - 1 : 1][PARTS > 1 ? kWsSelThreads * RPT : 1];
-  __shared__ uint64_t s_wc[kWsSelThreads / 64][2][kWsCand];
+template <int RPT, bool P2, bool kRowC = false>
+__global__ __launch_bounds__((kWsSelThreads * (P2 ? 1 : ws_parts<RPT>()))) void ws_select_kernel(WsArgs a) {
+  __shared__ WsListSum<RPT> s_list;  // one pass only
   WsCtrl* c = a.ctrl;
   const int tid = threadIdx.x & (kWsSelThreads - 1), part = threadIdx.x / kWsSelThreads;
-  if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(MODE == 1 ? 22 : 6);  // pass 1: own slots (22, 23)
+  if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(6);
   const int na = c->n_apply;
   const int done = c->done;
-  if (na == 0 && (done != kRunning || MODE == 1)) return;
-  if constexpr (MODE == 0) {
-    for (int k = threadIdx.x; k < na; k += kWsSelThreads * PARTS) {
-      s_idx[k] = c->apply_line[k];
-      s_coef[k] = c->apply_coef[k];
-    }
-  }
-  // a workgroup owns a.rpt x 256 rows (ws_geometry); RPT (>= a.rpt) only sizes the registers.
-  // MODE 1 runs KS = a.ks workgroups per row group, each over its KS-th of the
-  // changed-row list (pass 1 fills the device when G is small: 30 groups per rank at
-  // 8 ranks on the headline); pass 2 sums the KS partial changes in slice order.
-  const int KS = MODE == 1 ? max(1, a.ks) : 1;
-  const int grp = MODE == 1 ? (int)(blockIdx.x % a.G) : (int)blockIdx.x, ksi = MODE == 1 ? (int)(blockIdx.x / a.G) : 0;
-  if constexpr (MODE == 1) {
-    // the blocks' apply segments, concatenated in block order; this workgroup
-    // loads only its slice [e_lo, e_hi) of the list (at their list positions)
-    const int per_wg = PARTS * ((na + PARTS * KS - 1) / (PARTS * KS));
-    const int e_lo = min(na, ksi * per_wg), e_hi = min(na, e_lo + per_wg);
-    int at = 0;
-    for (int p = 0; p < a.blocks && at < e_hi; ++p) {
-      const int nb = c->nab[p];
-      const int k0 = max(0, e_lo - at), k1 = min(nb, e_hi - at);
-      for (int k = k0 + threadIdx.x; k < k1; k += kWsSelThreads * PARTS) {
-        s_idx[at + k] = c->apply_line[p * a.q_max + k];
-        s_coef[at + k] = c->apply_coef[p * a.q_max + k];
-      }
-      at += nb;
-    }
-  }
-  __syncthreads();
-  const int64_t base = (int64_t)grp * a.rpt * kWsSelThreads + tid;
+  if (na == 0 && done != kRunning) return;
+  if constexpr (!P2) s_list.load(c, na);
+  // a workgroup owns a.rpt x 256 rows (ws_geometry); RPT (>= a.rpt) only sizes the registers
+  const int64_t base = (int64_t)(int)blockIdx.x * a.rpt * kWsSelThreads + tid;
   float f[RPT];
   bool has[RPT];
 #pragma unroll
@@ -103,95 +221,11 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
   }
   if (na > 0) {
     float acc[RPT];
+    if constexpr (!P2) {
+      s_list.sum(a, na, base, has, acc);
+    } else {
 #pragma unroll
-    for (int r = 0; r < RPT; ++r) acc[r] = 0.f;
-    if constexpr (MODE != 2) {
-    const int per = (na + PARTS * KS - 1) / (PARTS * KS);
-    const int k_lo = min(na, (ksi * PARTS + part) * per), k_hi = min(na, k_lo + per);
-    for (int k0 = k_lo; k0 < k_hi; k0 += CH) {
-      float kv[CH][RPT];
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        const int kk = min(k0 + u, k_hi - 1);
-        const float* row = a.gram + (int64_t)s_idx[kk] * a.ldg;
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) kv[u][r] = has[r] ? row[base + r * kWsSelThreads] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        if (k0 + u < k_hi) {
-          const float cc = s_coef[k0 + u];
-#pragma unroll
-          for (int r = 0; r < RPT; ++r) acc[r] = f_add1(acc[r], cc, kv[u][r]);
-        }
-      }
-    }
-    if (PARTS > 1) {
-      if (part > 0) {
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) s_part[part - 1][r * kWsSelThreads + tid] = acc[r];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int p = 1; p < PARTS; ++p) {
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-#pragma clang fp contract(off)
-          acc[r] = acc[r] + s_part[p - 1][r * kWsSelThreads + tid];
-        }
-      }
-    }
-    }  // MODE != 2
-    if constexpr (MODE == 1) {
-      double sq = 0.0, sg = 0.0;
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) {
-        if (has[r] && part == 0) {
-          const int64_t j = base + r * kWsSelThreads;
-          a.dfs[(int64_t)ksi * a.nl + j] = acc[r];
-          const float dj = a.dalpha[a.off + j];
-          if (dj != 0.f) {
-            const double cj = (double)dj * (double)a.y[a.off + j];
-            sq += cj * (double)acc[r];  // d'Qd is linear in the KS partial changes
-            if (ksi == 0) sg -= cj * (double)f[r];
-          }
-        }
-      }
-      // fixed-order block sums (butterfly per wave, waves in order)
-      sq = wave_sum_f64(sq);
-      sg = wave_sum_f64(sg);
-      const int w = threadIdx.x >> 6;
-      if ((threadIdx.x & 63) == 0) {
-        s_red[0][w] = sq;
-        s_red[1][w] = sg;
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        double tq = 0.0, tg = 0.0;
-        for (int k = 0; k < kWsSelThreads * PARTS / 64; ++k) {
-          tq += s_red[0][k];
-          tg += s_red[1][k];
-        }
-        s_red_tot[0] = tq;
-        s_red_tot[1] = tg;
-        const int64_t slot = ((int64_t)a.rank * a.p1G + grp) * KS + ksi;
-        a.part[2 * slot] = tq;
-        a.part[2 * slot + 1] = tg;
-        if (blockIdx.x == 0) WS_STAMP(23);
-      }
-      __syncthreads();  // s_red_tot
-      if (a.xpeer != nullptr && threadIdx.x < 64 && (threadIdx.x >> 1) < a.world) {
-        // peer exchange: the slot's two doubles to every rank (lanes 2 p, 2 p + 1: rank p)
-        const int64_t slot = ((int64_t)a.rank * a.p1G + grp) * KS + ksi;
-        const int64_t R = c->outer;  // committed by this round's solve
-        const uint64_t t = xtag((uint32_t)R + 1u);
-        const int pr = threadIdx.x >> 1, h = threadIdx.x & 1;
-        const double v = h ? s_red_tot[1] : s_red_tot[0];
-        ws_put64(a.xpeer[pr] + ws_xpart(a, (int)(R & 1), slot) + 2 * h, t, (uint64_t)__double_as_longlong(v));
-      }
-      return;
-    }
-    if constexpr (MODE == 2) {
+      for (int r = 0; r < RPT; ++r) acc[r] = 0.f;
       const int pr = c->p_round;  // written by this round's merge (p_act may change below)
       const float t = ws_line_search(a, pr);
       if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -212,7 +246,7 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
         // (the P segments' slots flat over the threads: every count and row load
         // in flight at once, not one block's count after another)
         const int slots = a.blocks * a.q_max;
-        for (int i = threadIdx.x; i < slots; i += kWsSelThreads * PARTS) {
+        for (int i = threadIdx.x; i < slots; i += kWsSelThreads) {
           const int p = i / a.q_max, k = i - p * a.q_max;
           if (k >= c->nab[p]) continue;
           const int64_t gi = c->apply_idx[i];
@@ -225,10 +259,10 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
       }
 #pragma unroll
       for (int r = 0; r < RPT; ++r) {
-        if (has[r] && part == 0) {
+        if (has[r]) {
           const int64_t j = base + r * kWsSelThreads;
           float d = a.dfs[j];
-          for (int k = 1; k < a.ks; ++k) {
+          for (int k = 1; k < a.ks; ++k) {  // the pass-1 list slices' changes, in slice order
 #pragma clang fp contract(off)
             d = d + a.dfs[(int64_t)k * a.nl + j];
           }
@@ -260,7 +294,7 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
   if (done != kRunning) return;  // uniform
 
   // partition 0 (waves 0..3) classifies and extracts; the other waves idle to
-  // the one barrier below (no wave leaves before it)
+  // the one barrier of the extraction (no wave leaves before it)
   uint64_t ku[RPT], kl[RPT];
 #pragma unroll
   for (int r = 0; r < RPT; ++r) {
@@ -278,118 +312,39 @@ __global__ __launch_bounds__((kWsSelThreads * ws_sel_parts<RPT, MODE>())) void w
       }
     }
   }
-  // each wave's nc smallest keys per side, then wave 0 merges the four lists.
-  // Keys are unique (the global index is in the low bits) except kKeyNone, the
-  // largest: a key's place is the count of smaller keys, kKeyNone's the real
-  // keys' count plus its order among the lanes holding kKeyNone — a
-  // permutation, so every place is written once.  One row per thread (RPT 1,
-  // every rank of up to 60,160 rows): each lane counts over its wave's 64 keys
-  // (broadcast LDS reads, no barrier) instead of nc rounds of wave minima
-  const int lane = tid & 63, wave = tid >> 6;
-  // multi-block merges read ws_ncand keys per list (MODE 2: every multi-block
+  // multi-block merges read ws_ncand keys per list (pass 2: every multi-block
   // round, the seed included; the list's tail is kKeyNone), the one-block
-  // merge kWsCand1 (MODE 0)
-  constexpr int NC = MODE == 0 ? kWsCand1 : kWsCand;  // register capacity
-  const int nc = MODE == 0 ? kWsCand1 : ws_ncand(a.ncand);
-  constexpr int W = kWsSelThreads / 64;
-  const uint64_t below = (1ull << lane) - 1ull;
-  // place of key k among the wave's keys, given the count of smaller ones
-  auto place = [&](uint64_t k, int smaller) {
-    const uint64_t none = __ballot(k == kKeyNone);
-    return k == kKeyNone ? 64 - __popcll(none) + __popcll(none & below) : smaller;
-  };
-  if constexpr (RPT == 1) {
-    __shared__ u64x2 s_kk[W][2][32];  // [wave][side] the wave's 64 keys
-    if (part == 0) {
-      const uint64_t mu = ku[0], ml = kl[0];
-      ((uint64_t*)s_kk[wave][0])[lane] = mu;
-      ((uint64_t*)s_kk[wave][1])[lane] = ml;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own stores, read by its lanes
-      int cu = 0, cl = 0;
-#pragma unroll 8
-      for (int m = 0; m < 32; ++m) {
-        const u64x2 vu = s_kk[wave][0][m], vl = s_kk[wave][1][m];
-        cu += (vu.x < mu ? 1 : 0) + (vu.y < mu ? 1 : 0);
-        cl += (vl.x < ml ? 1 : 0) + (vl.y < ml ? 1 : 0);
-      }
-      const int pu = place(mu, cu), pl = place(ml, cl);
-      if (pu < nc) s_wc[wave][0][pu] = mu;
-      if (pl < nc) s_wc[wave][1][pl] = ml;
-    }
-  } else {
-    for (int round = 0; round < nc && part == 0; ++round) {
-      uint64_t mu = kKeyNone, ml = kKeyNone;
+  // merge kWsCand1
+  constexpr int NC = P2 ? kWsCand : kWsCand1;  // register capacity
+  const int nc = P2 ? ws_ncand(a.ncand) : kWsCand1;
+  const auto s_top = ws_extract<RPT, NC>(ku, kl, nc, a.cand_out + (size_t)blockIdx.x * 2 * kWsCand);
+  if (threadIdx.x < 64 && a.xpeer != nullptr && threadIdx.x < a.world) {
+    // lane p publishes to rank p: the nc keys per side the merge of this
+    // engine reads (slot width a.xcw: up keys at 0, low keys at a.xcw / 2)
+    uint64_t* dst = a.xpeer[threadIdx.x] + ws_xcand(a, (int)(c->outer & 1), a.xrank * a.G + blockIdx.x);
+    const uint64_t t = xtag((uint32_t)c->outer + 1u);
+    const int lo = a.xcw / 2;
 #pragma unroll
-      for (int r = 0; r < RPT; ++r) {
-        mu = ku[r] < mu ? ku[r] : mu;
-        ml = kl[r] < ml ? kl[r] : ml;
-      }
-      mu = wave_min_u64(mu);
-      ml = wave_min_u64(ml);
-      if (lane == 0) {
-        s_wc[wave][0][round] = mu;
-        s_wc[wave][1][round] = ml;
-      }
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) {
-        if (ku[r] == mu) ku[r] = kKeyNone;
-        if (kl[r] == ml) kl[r] = kKeyNone;
-      }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    // lane l: entry l % kWsCand of wave l / kWsCand's list (W x kWsCand = 64)
-    static_assert(W * kWsCand == 64, "one merge entry per lane");
-    __shared__ uint64_t s_top[2][NC];
-    const bool have = lane % kWsCand < nc;  // the waves' nc entries
-    const uint64_t eu = have ? s_wc[lane / kWsCand][0][lane % kWsCand] : kKeyNone;
-    const uint64_t el = have ? s_wc[lane / kWsCand][1][lane % kWsCand] : kKeyNone;
-    int cu = 0, cl = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-#pragma unroll
-      for (int r = 0; r < NC; ++r) {
-        if (r < nc) {  // uniform
-          cu += s_wc[w][0][r] < eu ? 1 : 0;
-          cl += s_wc[w][1][r] < el ? 1 : 0;
-        }
-      }
-    }
-    const int pu = place(eu, cu), pl = place(el, cl);
-    if (pu < NC) s_top[0][pu] = pu < nc ? eu : kKeyNone;  // multi-block lists: the tail past nc is kKeyNone
-    if (pl < NC) s_top[1][pl] = pl < nc ? el : kKeyNone;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    uint64_t* out = a.cand_out + (size_t)blockIdx.x * 2 * kWsCand;
-    if (lane < NC) out[lane] = s_top[0][lane];
-    else if (lane >= 32 && lane < 32 + NC) out[kWsCand + lane - 32] = s_top[1][lane - 32];
-    if (a.xpeer != nullptr && lane < a.world) {
-      // lane p publishes to rank p: the nc keys per side the merge of this
-      // engine reads (slot width a.xcw: up keys at 0, low keys at a.xcw / 2)
-      uint64_t* dst = a.xpeer[lane] + ws_xcand(a, (int)(c->outer & 1), a.xrank * a.G + blockIdx.x);
-      const uint64_t t = xtag((uint32_t)c->outer + 1u);
-      const int lo = a.xcw / 2;
-#pragma unroll
-      for (int r = 0; r < NC; ++r) {
-        if (r < nc) {
-          ws_put64(dst + 2 * r, t, s_top[0][r]);
-          ws_put64(dst + lo + 2 * r, t, s_top[1][r]);
-        }
+    for (int r = 0; r < NC; ++r) {
+      if (r < nc) {
+        ws_put64(dst + 2 * r, t, s_top[0][r]);
+        ws_put64(dst + lo + 2 * r, t, s_top[1][r]);
       }
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(7);
 }
 
-// Multi-block pass 1, wide layout (a.p1v4): the same sums as MODE 1 — d_f_j =
-// sum_k c_k K(k, j) over the round's changed rows, each partition over a
-// contiguous slice of the list in list order, partitions combined in order,
-// slices summed in order by pass 2 — but a workgroup owns 1024 columns and a
-// thread 4 adjacent ones (16-B row loads): each wave reads 1 KiB of a changed
-// Gram row per load instead of 256 B (HBM row-buffer locality of the scattered
-// rows), and p1G = ceil(nl_max / 1024) groups x ks list slices fill the device.
-// Four partitions of 256 threads = 1024 threads; a workgroup owns kWsPass1Cols
-// (1024) columns.  NT: the Gram rows
+// Multi-block pass 1: d_f_j = sum_k c_k K(k, j) over the round's changed rows,
+// the blocks' apply segments concatenated in block order, by the list sum's
+// rule — each partition over a contiguous slice of the list in list order,
+// partitions combined in order, the ks list slices summed in order by pass 2
+// — in a wide layout: a workgroup owns 1024 columns and a thread 4 adjacent
+// ones (16-B row loads; ldg is a multiple of 4 and >= round_up(nl, 4)), so each
+// wave reads 1 KiB of a changed Gram row per load (HBM row-buffer locality of
+// the scattered rows), and p1G = ceil(nl_max / 1024) groups x ks list slices
+// fill the device.  Four partitions of 256 threads = 1024 threads; a workgroup
+// owns kWsPass1Cols (1024) columns.  NT: the Gram rows
 // by non-temporal loads (each changed row is read once a round: no L2 / MALL
 // reuse to keep; ws_pass1_nt picks it)
 constexpr int kP1Threads = 4 * kWsSelThreads;
@@ -532,37 +487,27 @@ __global__ __launch_bounds__(kP1Threads) void ws_pass1_v4_kernel(WsArgs a) {
   }
 }
 
-// epsilon-SVR (a.fold = n_x > 0): MODE 0 on the folded 2 n_x-row dual.  The
-// kernel matrix of the state rows is the n_x x n_x Gram tiled 2 x 2, so the
-// grid covers the n_x Gram columns (ws_geometry(n_x, 1)) and the thread owning
-// column j sums acc = sum_k coef_k gram[line_k][j] once — MODE 0's partitions,
-// list order and f_add1 — then adds the same acc to f[j] and f[j + n_x]: every
+// epsilon-SVR (a.fold = n_x > 0): the one-pass kernel on the folded 2 n_x-row
+// dual.  The kernel matrix of the state rows is the n_x x n_x Gram tiled 2 x 2,
+// so the grid covers the n_x Gram columns (ws_geometry(n_x, 1)) and the thread
+// owning column j sums acc = sum_k coef_k gram[line_k][j] once — the one-pass
+// kernel's WsListSum — then adds the same acc to f[j] and f[j + n_x]: every
 // Gram element is loaded once a round for both halves.  Both variables are
 // classified (alpha / y at j and j + n_x), two key slots per side per column:
-// slot 2 r is row j, slot 2 r + 1 row j + n_x; the extraction is MODE 0's
-// generic one (nc rounds of wave minima) over 2 RPT slots.  One rank, one
-// block, scalar C, no peer exchange.
+// slot 2 r is row j, slot 2 r + 1 row j + n_x; ws_extract over 2 RPT slots
+// (nc rounds of wave minima at every RPT).  One rank, one block, scalar C, no
+// peer exchange.
 template <int RPT>
 __global__ __launch_bounds__((kWsSelThreads * ws_parts<RPT>())) void ws_select_fold_kernel(WsArgs a) {
-  constexpr int PARTS = ws_parts<RPT>();
-  constexpr int CH = 48 / RPT;  // Gram loads in flight per thread (RPT <= 4)
-  constexpr int KS2 = 2 * RPT;  // key slots per side
   static_assert(RPT <= 4, "fold: the resident Gram bounds n_x (rpt <= 4)");
-  __shared__ int32_t s_idx[kWsMax];  // lines of the changed rows
-  __shared__ float s_coef[kWsMax];
-  __shared__ float s_part[PARTS - 1][kWsSelThreads * RPT];
-  __shared__ uint64_t s_wc[kWsSelThreads / 64][2][kWsCand];
+  __shared__ WsListSum<RPT> s_list;
   WsCtrl* c = a.ctrl;
   const int tid = threadIdx.x & (kWsSelThreads - 1), part = threadIdx.x / kWsSelThreads;
   if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(6);
   const int na = c->n_apply;
   const int done = c->done;
   if (na == 0 && done != kRunning) return;
-  for (int k = threadIdx.x; k < na; k += kWsSelThreads * PARTS) {
-    s_idx[k] = c->apply_line[k];
-    s_coef[k] = c->apply_coef[k];
-  }
-  __syncthreads();
+  s_list.load(c, na);
   const int64_t nx = a.fold;
   const int64_t base = (int64_t)blockIdx.x * a.rpt * kWsSelThreads + tid;
   float f0[RPT], f1[RPT];  // f[j], f[j + nx]
@@ -576,41 +521,7 @@ __global__ __launch_bounds__((kWsSelThreads * ws_parts<RPT>())) void ws_select_f
   }
   if (na > 0) {
     float acc[RPT];
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) acc[r] = 0.f;
-    const int per = (na + PARTS - 1) / PARTS;
-    const int k_lo = min(na, part * per), k_hi = min(na, k_lo + per);
-    for (int k0 = k_lo; k0 < k_hi; k0 += CH) {
-      float kv[CH][RPT];
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        const int kk = min(k0 + u, k_hi - 1);
-        const float* row = a.gram + (int64_t)s_idx[kk] * a.ldg;
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) kv[u][r] = has[r] ? row[base + r * kWsSelThreads] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        if (k0 + u < k_hi) {
-          const float cc = s_coef[k0 + u];
-#pragma unroll
-          for (int r = 0; r < RPT; ++r) acc[r] = f_add1(acc[r], cc, kv[u][r]);
-        }
-      }
-    }
-    if (part > 0) {
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) s_part[part - 1][r * kWsSelThreads + tid] = acc[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 1; p < PARTS; ++p) {
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) {
-#pragma clang fp contract(off)
-        acc[r] = acc[r] + s_part[p - 1][r * kWsSelThreads + tid];
-      }
-    }
+    s_list.sum(a, na, base, has, acc);
     bool bad = false;
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
@@ -629,8 +540,8 @@ __global__ __launch_bounds__((kWsSelThreads * ws_parts<RPT>())) void ws_select_f
   if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(10);
   if (done != kRunning) return;  // uniform
 
-  // partition 0 classifies both halves and extracts; the other waves idle to the barrier
-  uint64_t ku[KS2], kl[KS2];
+  // partition 0 classifies both halves and extracts; the other waves idle to the extraction's barrier
+  uint64_t ku[2 * RPT], kl[2 * RPT];
 #pragma unroll
   for (int r = 0; r < RPT; ++r) {
 #pragma unroll
@@ -644,58 +555,7 @@ __global__ __launch_bounds__((kWsSelThreads * ws_parts<RPT>())) void ws_select_f
       }
     }
   }
-  const int lane = tid & 63, wave = tid >> 6;
-  constexpr int NC = kWsCand1;
-  constexpr int W = kWsSelThreads / 64;
-  const uint64_t below = (1ull << lane) - 1ull;
-  auto place = [&](uint64_t k, int smaller) {
-    const uint64_t none = __ballot(k == kKeyNone);
-    return k == kKeyNone ? 64 - __popcll(none) + __popcll(none & below) : smaller;
-  };
-  for (int round = 0; round < NC && part == 0; ++round) {
-    uint64_t mu = kKeyNone, ml = kKeyNone;
-#pragma unroll
-    for (int r = 0; r < KS2; ++r) {
-      mu = ku[r] < mu ? ku[r] : mu;
-      ml = kl[r] < ml ? kl[r] : ml;
-    }
-    mu = wave_min_u64(mu);
-    ml = wave_min_u64(ml);
-    if (lane == 0) {
-      s_wc[wave][0][round] = mu;
-      s_wc[wave][1][round] = ml;
-    }
-#pragma unroll
-    for (int r = 0; r < KS2; ++r) {
-      if (ku[r] == mu) ku[r] = kKeyNone;
-      if (kl[r] == ml) kl[r] = kKeyNone;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    // lane l: entry l % kWsCand of wave l / kWsCand's list, as MODE 0's merge of the four lists
-    static_assert(W * kWsCand == 64, "one merge entry per lane");
-    __shared__ uint64_t s_top[2][NC];
-    const bool have = lane % kWsCand < NC;
-    const uint64_t eu = have ? s_wc[lane / kWsCand][0][lane % kWsCand] : kKeyNone;
-    const uint64_t el = have ? s_wc[lane / kWsCand][1][lane % kWsCand] : kKeyNone;
-    int cu = 0, cl = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-#pragma unroll
-      for (int r = 0; r < NC; ++r) {
-        cu += s_wc[w][0][r] < eu ? 1 : 0;
-        cl += s_wc[w][1][r] < el ? 1 : 0;
-      }
-    }
-    const int pu = place(eu, cu), pl = place(el, cl);
-    if (pu < NC) s_top[0][pu] = eu;
-    if (pl < NC) s_top[1][pl] = el;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    uint64_t* out = a.cand_out + (size_t)blockIdx.x * 2 * kWsCand;
-    if (lane < NC) out[lane] = s_top[0][lane];
-    else if (lane >= 32 && lane < 32 + NC) out[kWsCand + lane - 32] = s_top[1][lane - 32];
-  }
+  ws_extract<2 * RPT, kWsCand1>(ku, kl, kWsCand1, a.cand_out + (size_t)blockIdx.x * 2 * kWsCand);
   if (blockIdx.x == 0 && threadIdx.x == 0) WS_STAMP(7);
 }
 
@@ -748,25 +608,24 @@ bool ws_supported(int64_t nl_max, int world, int q_max) {
   return q_max >= 2 && q_max <= kWsMax && rpt <= kWsMaxRPT && nl_max < (int64_t)1 << 31 && world <= kWsMaxGroups;
 }
 
-template <int MODE, bool kRowC>
+template <bool P2, bool kRowC>
 static void ws_select_rpt(const WsArgs& a, hipStream_t s) {
-  const dim3 grid(a.G * (MODE == 1 ? std::max(1, a.ks) : 1));
-  auto threads = [](int rpt) { return dim3(MODE == 2 ? kWsSelThreads : kWsSelThreads * (rpt <= 4 ? 4 : rpt <= 16 ? 2 : 1)); };
-  if (a.rpt <= 1) dev::ws_select_kernel<1, MODE, kRowC><<<grid, threads(1), 0, s>>>(a);
-  else if (a.rpt <= 2) dev::ws_select_kernel<2, MODE, kRowC><<<grid, threads(2), 0, s>>>(a);
-  else if (a.rpt <= 4) dev::ws_select_kernel<4, MODE, kRowC><<<grid, threads(4), 0, s>>>(a);
-  else if (a.rpt <= 8) dev::ws_select_kernel<8, MODE, kRowC><<<grid, threads(8), 0, s>>>(a);
-  else if (a.rpt <= 16) dev::ws_select_kernel<16, MODE, kRowC><<<grid, threads(16), 0, s>>>(a);
-  else dev::ws_select_kernel<32, MODE, kRowC><<<grid, threads(32), 0, s>>>(a);
+  const dim3 grid(a.G);
+  auto threads = [](int rpt) { return dim3(P2 ? kWsSelThreads : kWsSelThreads * (rpt <= 4 ? 4 : rpt <= 16 ? 2 : 1)); };
+  if (a.rpt <= 1) dev::ws_select_kernel<1, P2, kRowC><<<grid, threads(1), 0, s>>>(a);
+  else if (a.rpt <= 2) dev::ws_select_kernel<2, P2, kRowC><<<grid, threads(2), 0, s>>>(a);
+  else if (a.rpt <= 4) dev::ws_select_kernel<4, P2, kRowC><<<grid, threads(4), 0, s>>>(a);
+  else if (a.rpt <= 8) dev::ws_select_kernel<8, P2, kRowC><<<grid, threads(8), 0, s>>>(a);
+  else if (a.rpt <= 16) dev::ws_select_kernel<16, P2, kRowC><<<grid, threads(16), 0, s>>>(a);
+  else dev::ws_select_kernel<32, P2, kRowC><<<grid, threads(32), 0, s>>>(a);
   post_launch("ws_select", s);
 }
 
-template <int MODE>
+// the one-pass kernel (P2 = false) or pass 2
+template <bool P2>
 static void ws_select_mode(const WsArgs& a, hipStream_t s) {
-  if constexpr (MODE != 1) {  // pass 1 neither classifies nor clips: one instantiation
-    if (a.c_row != nullptr) return ws_select_rpt<MODE, true>(a, s);  // per-row C
-  }
-  ws_select_rpt<MODE, false>(a, s);
+  if (a.c_row != nullptr) return ws_select_rpt<P2, true>(a, s);  // per-row C
+  ws_select_rpt<P2, false>(a, s);
 }
 
 // epsilon-SVR: the folded one-pass kernel, grid over the fold Gram columns
@@ -789,13 +648,13 @@ void ws_select(const WsArgs& a, hipStream_t s) {
   if (a.fold > 0) return ws_select_fold(a, s);
   if (a.blocks > 1) {
     ws_select_pass(a, 1, s);  // d_f + line-search partials
-    ws_select_mode<2>(a, s);  // f += t d_f, candidates
+    ws_select_pass(a, 2, s);  // f += t d_f, candidates
   } else {
-    ws_select_mode<0>(a, s);
+    ws_select_mode<false>(a, s);
   }
 }
 
-// the wide pass 1's Gram row loads: non-temporal where the Gram is far larger
+// pass 1's Gram row loads: non-temporal where the Gram is far larger
 // than the 256 MB MALL (> 1 GiB: the rows of a round are not read again before
 // they would be evicted) — headline 0.0170 -> 0.0160 s, same trajectory
 // (profiles/r6_p1_nt_ab.txt); default policy below, where a small Gram's rows
@@ -807,15 +666,13 @@ static bool ws_pass1_nt(const WsArgs& a) {
 
 void ws_select_pass(const WsArgs& a, int pass, hipStream_t s) {
   DPSVM_CHECK(a.fold == 0, "ws_select_pass: multi-block rounds are not implemented for regression (fold)");
-  if (pass == 1 && a.p1v4) {
+  if (pass == 1) {
     const dim3 g(a.p1G * std::max(1, a.ks));
     if (ws_pass1_nt(a)) dev::ws_pass1_v4_kernel<true><<<g, dev::kP1Threads, 0, s>>>(a);
     else dev::ws_pass1_v4_kernel<false><<<g, dev::kP1Threads, 0, s>>>(a);
     post_launch("ws_pass1_v4", s);
-  } else if (pass == 1) {
-    ws_select_mode<1>(a, s);
   } else {
-    ws_select_mode<2>(a, s);
+    ws_select_mode<true>(a, s);
   }
 }
 

@@ -868,11 +868,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("wss"), py::arg("row_C") = py::none());
   m.def("k_ws_select", [vi](const F32& gram, int64_t L, int64_t ldg, const F32& f, const F32& alpha, const F32& y,
                             const F32& dalpha, const I32& lines, const F32& coef, const I32& nab, int blocks,
-                            int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps, bool wide,
+                            int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps,
                             py::object row_C, int64_t fold, int done) {
     const auto r = kernels::ws_select_probe(from_np(gram), L, ldg, from_np(f), from_np(alpha), from_np(y),
                                             from_np(dalpha), vi(lines), from_np(coef), vi(nab), blocks, p_round, p_act,
-                                            q_max, C, outer, ks, reps, wide,
+                                            q_max, C, outer, ks, reps,
                                             row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()), fold,
                                             done);
     py::dict d;
@@ -896,7 +896,7 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("gram"), py::arg("L"), py::arg("ldg"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("dalpha"),
         py::arg("lines"), py::arg("coef"), py::arg("nab"), py::arg("blocks"), py::arg("p_round"), py::arg("p_act"),
         py::arg("q_max"), py::arg("C"), py::arg("outer"), py::arg("ks") = 0, py::arg("reps") = 0,
-        py::arg("wide") = false, py::arg("row_C") = py::none(), py::arg("fold") = 0, py::arg("done") = 0);
+        py::arg("row_C") = py::none(), py::arg("fold") = 0, py::arg("done") = 0);
   m.def("k_gram_wsum_slices", [](int64_t n, int64_t m) { return launch::gram_wsum_slices(n, m); }, py::arg("n"),
         py::arg("m"), "row slices S of gram_rows_wsum for n columns and m rows (a function of the shape alone)");
   m.def("k_gram_rows_wsum", [vi](const F32& gram, int64_t L, int64_t ldg, int64_t n, py::object lines, const F32& coef,

@@ -920,7 +920,7 @@ void fill_ws_args(GpuSolver::Impl& m, const SetupState& s) {
     w.fold = m.n;
   }
   w.G = s.ws_G;
-  w.p1G = s.ws_G;  // multi-block rounds take the wide pass-1 geometry below
+  w.p1G = s.ws_G;  // multi-block rounds take the pass-1 geometry below
   w.rpt = s.ws_rpt;
   w.world = m.world;
   w.G_all = w.G * m.world;
@@ -937,7 +937,6 @@ void fill_ws_args(GpuSolver::Impl& m, const SetupState& s) {
   if (w.blocks > 1) {
     w.ks = p.ks;
     w.p1G = p.p1G;
-    w.p1v4 = 1;
   }
   DPSVM_CHECK(m.p.ws_wss >= 0 && m.p.ws_wss <= 2, "ws_wss must be 0 (auto), 1 (first order) or 2 (second order)");
   if (m.p.ws_wss > 0) {

@@ -260,7 +260,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
                               const std::vector<float>& dalpha, const std::vector<int32_t>& apply_line,
                               const std::vector<float>& apply_coef, const std::vector<int32_t>& nab, int blocks,
                               int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps,
-                              bool wide, const std::vector<float>& row_C, int64_t fold, int done) {
+                              const std::vector<float>& row_C, int64_t fold, int done) {
   const int64_t n = (int64_t)f.size();
   // fold > 0 (epsilon-SVR): n = 2 fold state rows on gram [L][ldg >= fold], geometry of the fold columns
   DPSVM_CHECK(fold == 0 || (n == 2 * fold && blocks == 1 && row_C.empty()),
@@ -270,6 +270,8 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   DPSVM_CHECK(n >= 1 && (int64_t)alpha.size() == n && (int64_t)y.size() == n && (int64_t)dalpha.size() == n,
               "ws_select_probe: f / alpha / y / dalpha of n rows");
   DPSVM_CHECK(ldg >= ncol && (int64_t)gram.size() == L * ldg, "ws_select_probe: gram [L][ldg >= n]");
+  DPSVM_CHECK(blocks == 1 || (ldg % 4 == 0 && ldg >= (n + 3) / 4 * 4),
+              "ws_select_probe: pass 1 loads 16 bytes a thread: ldg a multiple of 4 and >= round_up(n, 4)");
   DPSVM_CHECK(blocks >= 1 && blocks <= kWsMaxBlocks && (int)nab.size() == blocks && q_max >= 2 && q_max <= kWsMax,
               "ws_select_probe: nab per block, q_max <= 192");
   DPSVM_CHECK(apply_line.size() == apply_coef.size(), "ws_select_probe: apply lines / coefficients");
@@ -312,11 +314,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   a.y = st.up(y, (size_t)n);
   a.dalpha = st.up(dalpha, (size_t)n);
   a.ks = std::max(1, ks);
-  a.p1G = G;
-  if (wide && blocks > 1) {  // the wide pass 1 (ws_pass1_v4_kernel)
-    a.p1v4 = 1;
-    a.p1G = ws_pass1_v4_groups(n);
-  }
+  a.p1G = blocks > 1 ? ws_pass1_v4_groups(n) : G;
   a.dfs = st.up(std::vector<float>(), (size_t)n * a.ks);
   a.part = st.up(std::vector<double>(), (size_t)2 * a.p1G * a.ks);
   a.cand = a.cand_out = st.up(std::vector<uint64_t>(), (size_t)G * 2 * kWsCand);

@@ -270,14 +270,17 @@ def ws_solve(K, f, alpha, y, qb, q_max: int, C_: float, clip: str = "independent
 
 def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float, q_max: int = 192,
               p_round: int | None = None, p_act: int | None = None, outer: int = 1, ks: int = 0,
-              wide: bool = False, row_C=None, fold: int = 0, done: int = 0, reps: int = 0) -> dict:
-    """The working-set f update + candidate selection (ws_select_kernel) on a
-    dense gram [L][ldg >= n] (rows = lines).  len(nab) == 1: the one-pass
-    kernel; more blocks: pass 1 (d_f, d'Qd / g'd partials) and pass 2 (line
-    search t, f += t d_f, alpha = alpha_new - (1 - t) d_alpha, candidates).
-    ks > 1: pass 1 split into ks list slices per selection group (dfs then
-    holds slice 0, part [G][ks][2]).  wide: the wide pass 1 (1024-column
-    groups, 16-B row loads; part [p1G][ks][2]).  row_C: per-row bounds C_i
+              row_C=None, fold: int = 0, done: int = 0, reps: int = 0) -> dict:
+    """The working-set f update + candidate selection on a dense gram
+    [L][ldg >= n] (rows = lines; n = len(f), ldg = gram.shape[1]).
+    len(nab) == 1: the one-pass kernel (ws_select_kernel); more blocks: the
+    passes every multi-block round runs — pass 1 (ws_pass1_v4_kernel: d_f,
+    d'Qd / g'd partials; p1G = ceil(n / 1024) column groups, 16-byte row loads,
+    so ldg must be a multiple of 4 and >= round_up(n, 4): pad the gram's
+    columns, a bad shape raises) and pass 2 (line search t, f += t d_f,
+    alpha = alpha_new - (1 - t) d_alpha, candidates).  ks > 1: pass 1 split
+    into ks list slices per column group (dfs then holds slice 0); part is
+    [p1G][ks][2].  row_C: per-row bounds C_i
     [n] (None: the scalar C_).  fold > 0: the epsilon-SVR kernel
     (ws_select_fold_kernel) — f / alpha / y hold 2 fold state rows, gram is
     [L][ldg >= fold], the grid covers the fold columns.  done: the run's
@@ -292,7 +295,7 @@ def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float
     return load().k_ws_select(g.reshape(-1), g.shape[0], g.shape[1], f32(f), f32(alpha), f32(y), f32(dalpha),
                               np.asarray(apply_lines, dtype=np.int32), f32(apply_coef), np.asarray(nab, dtype=np.int32),
                               P, P if p_round is None else p_round, P if p_act is None else p_act, q_max, float(C_),
-                              int(outer), ks=int(ks), wide=bool(wide),
+                              int(outer), ks=int(ks),
                               row_C=None if row_C is None else f32(row_C), fold=int(fold), done=int(done),
                               reps=int(reps))
 

@@ -620,7 +620,7 @@ def test_ws_select_two_pass_line_search_matches_model(K, target, P, p_act):
                       p_round=P, p_act=p_act)
     G, rpt = got["G"], got["rpt"]
     np.testing.assert_allclose(got["dfs"], d_f, rtol=1e-4, atol=2e-5)
-    part = np.asarray(got["part"]).reshape(G, 2)
+    part = np.asarray(got["part"]).reshape(got["p1G"], 2)
     qk, gk = part[:, 0].sum(), part[:, 1].sum()
     # the partials: d'Qd over the kernel's own d_f, g'd over f (float64 sums)
     assert qk == pytest.approx(float(np.sum(c[ch] * got["dfs"].astype(np.float64)[ch])), rel=1e-9)
@@ -666,7 +666,7 @@ def test_ws_select_pass1_list_slices_match_model(K, ks):
     kw = dict(q_max=q_max)
     got = K.ws_select(gram, f, a_new, y, dal, ch, c[ch].astype(np.float32), nab, C, ks=ks, **kw)
     one = K.ws_select(gram, f, a_new, y, dal, ch, c[ch].astype(np.float32), nab, C, ks=1, **kw)
-    part = np.asarray(got["part"]).reshape(got["G"] * ks, 2)
+    part = np.asarray(got["part"]).reshape(got["p1G"] * ks, 2)
     assert part[:, 0].sum() == pytest.approx(q, rel=1e-4)
     assert part[:, 1].sum() == pytest.approx(g, rel=1e-6, abs=1e-9)
     assert got["t"] == pytest.approx(float(line_search_rule(part[:, 0].sum(), part[:, 1].sum(), P)), rel=1e-6)
@@ -731,33 +731,66 @@ def test_ws_solve_second_order_matches_model(K, clip):
         assert bl2 <= bh2 + 2 * eps_in + 1e-4
 
 
-@pytest.mark.parametrize("ks", [1, 3])
-def test_ws_select_wide_pass1_matches_model(K, ks):
-    """The wide pass 1 (ws_pass1_v4_kernel: 1024-column groups, four columns per
-    thread, 16-B row loads, ks list slices): d_f, the d'Qd / g'd partials and f
-    after pass 2 match the float64 model and the selection-geometry kernel;
-    n not a multiple of 1024 (the last group is partial)."""
-    rng = np.random.default_rng(70 + ks)
-    n, C, q_max, P = 3000, 2.0, 96, 4
-    gram, f, a_new, y, dal, ch = select_state(rng, n, C, 160)
+def check_wide_pass1(K, n, ldg, nab, ks, seed):
+    """Pass 1 (ws_pass1_v4_kernel) and pass 2 on a gram [n][ldg] whose columns
+    past n are NaN (the 16-byte loads read them, no sum may take them in),
+    against the float64 model: d_f, the d'Qd / g'd partials, t, f after pass 2,
+    the candidates.  At ks = 1 and rpt <= 4 the change is also the one-pass
+    kernel's, bit for bit: both sum four partitions of per = ceil(na / 4)
+    rows by f_add1 in list order and combine them in partition order, so the
+    same rows in one block through the one-pass kernel leave f = f + d_f."""
+    rng = np.random.default_rng(seed)
+    C, q_max, P = 2.0, 96, len(nab)
+    gram, f, a_new, y, dal, ch = select_state(rng, n, C, sum(nab))
+    gram = np.concatenate([gram, np.full((n, ldg - n), np.nan, np.float32)], axis=1)
     c = dal.astype(np.float64) * y
-    d_f = gram.astype(np.float64).T @ c
+    d_f = gram[:, :n].astype(np.float64).T @ c
     q = float(np.sum(c[ch] * d_f[ch]))
     g = -float(np.sum(c[ch] * f.astype(np.float64)[ch]))
-    nab = [40] * P
-    got = K.ws_select(gram, f, a_new, y, dal, ch, c[ch].astype(np.float32), nab, C, q_max=q_max, ks=ks, wide=True)
-    ref = K.ws_select(gram, f, a_new, y, dal, ch, c[ch].astype(np.float32), nab, C, q_max=q_max, ks=ks)
+    coef = c[ch].astype(np.float32)
+    got = K.ws_select(gram, f, a_new, y, dal, ch, coef, nab, C, q_max=q_max, ks=ks)
     assert got["p1G"] == (n + 1023) // 1024
     part = np.asarray(got["part"]).reshape(got["p1G"] * ks, 2)
     assert part[:, 0].sum() == pytest.approx(q, rel=1e-4)
     assert part[:, 1].sum() == pytest.approx(g, rel=1e-6, abs=1e-9)
+    assert got["t"] == pytest.approx(float(line_search_rule(part[:, 0].sum(), part[:, 1].sum(), P)), rel=1e-6)
+    t = np.float32(got["t"])
+    np.testing.assert_allclose(got["f"], f + t * d_f, rtol=1e-4, atol=3e-5)
+    G, rpt = got["G"], got["rpt"]
     if ks == 1:
         np.testing.assert_allclose(got["dfs"], d_f, rtol=1e-4, atol=2e-5)
-    assert got["t"] == pytest.approx(float(line_search_rule(part[:, 0].sum(), part[:, 1].sum(), P)), rel=1e-6)
-    assert got["t"] == pytest.approx(ref["t"], rel=1e-5)
-    np.testing.assert_allclose(got["f"], f + np.float32(got["t"]) * d_f, rtol=1e-4, atol=3e-5)
-    np.testing.assert_allclose(got["f"], ref["f"], rtol=1e-5, atol=2e-6)
-    np.testing.assert_allclose(got["alpha"], ref["alpha"], rtol=1e-5, atol=1e-6 * C)
-    G, rpt = got["G"], got["rpt"]
+        np.testing.assert_array_equal(got["f"], (f + (got["dfs"] if t == 1 else t * got["dfs"])).astype(np.float32))
+        assert rpt <= 4 and sum(nab) <= 192
+        one = K.ws_select(gram, f, a_new, y, np.zeros(n, np.float32), ch, coef, [sum(nab)], C, q_max=192)
+        np.testing.assert_array_equal(one["f"], (f + got["dfs"]).astype(np.float32))
+    assert not np.any(got["dalpha"])
     cand = np.asarray(got["cand"], dtype=np.uint64).reshape(G, 2, KC)
     np.testing.assert_array_equal(cand, candidates_model(got["f"], got["alpha"], y, C, G, rpt))
+
+
+@pytest.mark.parametrize("ks", [1, 3])
+def test_ws_select_wide_pass1_matches_model(K, ks):
+    """The pass 1 of every multi-block round (ws_pass1_v4_kernel: 1024-column
+    groups, four columns per thread, 16-B row loads, ks list slices); n not a
+    multiple of 1024 (the last group is partial)."""
+    check_wide_pass1(K, 3000, 3000, [40] * 4, ks, seed=70 + ks)
+
+
+@pytest.mark.parametrize("n,ldg,nab,ks", [
+    (1027, 1028, [40] * 4, 1),       # two column groups, the last 3 columns wide; n % 4 == 3
+    (5, 8, [2, 2], 1),               # one partial 16-byte load
+    (3000, 3000, [40, 0, 40, 2], 1),  # an empty segment inside the offset scan and its binary search
+    (3000, 3000, [1, 1, 1], 3),      # an odd block count; fewer rows than partitions x slices: empty slices
+], ids=["n1027", "n5", "empty-segment", "three-rows-ks3"])
+def test_ws_select_wide_pass1_edge_shapes_match_model(K, n, ldg, nab, ks):
+    check_wide_pass1(K, n, ldg, nab, ks, seed=80 + n % 7 + len(nab))
+
+
+def test_ws_select_two_pass_refuses_unaligned_gram(K):
+    """Pass 1 loads 16 bytes at every fourth column: ldg = n = 1027 (not a
+    multiple of 4) must raise, not load misaligned."""
+    n = 1027
+    z = np.zeros(n, np.float32)
+    with pytest.raises(RuntimeError, match="multiple of 4"):
+        K.ws_select(np.zeros((4, n), np.float32), z, z, np.ones(n, np.float32), z, [0, 1], [0.1, 0.1], [1, 1], 2.0,
+                    q_max=96)

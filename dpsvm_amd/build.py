@@ -67,6 +67,7 @@ LIB_SOURCES = [
     "kernels/ws_recompute.hip",
     "kernels/platt.hip",
     "kernels/gram_wsum.hip",
+    "kernels/gram_dot.hip",
 ]
 # the quarantined engines (solver/gpu_engines_pairq.hip registers them): a plugin
 # library for the Python module, linked into the CLIs (svmTrain --engines all)

@@ -168,6 +168,12 @@ struct SolverParams {
   // ceil(nu n) rows (gram_rows_wsum, docs/DESIGN.md §18).  b is rho.  Box clipping, one rank, no resume, no
   // per-row C; the device solver: one-block working-set rounds on the resident Gram.
   float one_class_nu = 0.f;
+  // the kernel: 0 RBF (gamma; the solvers compute the Gram from X), 1 precomputed — the caller hands over the
+  // n x n Gram of any kernel (GpuSolver::setup_gram, solve_cpu_gram) and never X; gamma, gram_precision and
+  // gram_adapt are ignored.  Combines with all three problems.  One rank, box clipping, the one-block working-set
+  // rounds on the resident Gram with the general-diagonal sub-problem kernels (problem.hpp: check_kernel;
+  // docs/DESIGN.md §20)
+  int kernel = 0;
 };
 
 
@@ -385,6 +391,64 @@ DPSVM_HD PairUpdate pair_update_w(float a_hi_old, float a_lo_old, float y_hi, fl
   u.c_hi = (a_hi_new - a_hi_old) * y_hi;
   u.c_lo = (a_lo_new - a_lo_old) * y_lo;
   return u;
+}
+
+// General diagonal (precomputed Grams): eta = K(hi,hi) + K(lo,lo) - 2 K(hi,lo) from the pair's own diagonal
+// entries k_hh, k_ll.  The operands keep the order of (1 + 1) - 2 k_hl above, so a unit diagonal gives the bits of
+// the overloads without k_hh / k_ll; everything after eta is pair_update_w's, expression by expression.
+DPSVM_HD PairUpdate pair_update_w(float a_hi_old, float a_lo_old, float y_hi, float y_lo, float b_hi,
+                                  float b_lo, float k_hl, float k_hh, float k_ll, float C_hi, float C_lo, float tau,
+                                  int clip_mode, bool same) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float eta = (k_hh + k_ll) - 2.0f * k_hl;
+  if (!(eta >= tau)) eta = tau;
+  float s = y_lo * y_hi;
+  float a_lo_new = a_lo_old + (y_lo * (b_hi - b_lo) / eta);
+  float a_hi_new;
+  if (clip_mode == (int)ClipMode::Box && !same) {
+    float L, H;
+    float hi_at_L, hi_at_H;  // a_hi value implied when a_lo lands on L / H (-1: none)
+    if (y_hi != y_lo) {
+      const float dl = a_lo_old - a_hi_old;
+      L = dl > 0.f ? dl : 0.f;
+      hi_at_L = dl > 0.f ? 0.f : -1.f;
+      H = C_hi + dl < C_lo ? C_hi + dl : C_lo;
+      hi_at_H = C_hi + dl < C_lo ? C_hi : -1.f;
+    } else {
+      const float sm = a_lo_old + a_hi_old;
+      L = sm - C_hi > 0.f ? sm - C_hi : 0.f;
+      hi_at_L = sm - C_hi > 0.f ? C_hi : -1.f;
+      H = sm < C_lo ? sm : C_lo;
+      hi_at_H = sm < C_lo ? 0.f : -1.f;
+    }
+    if (a_lo_new <= L) {
+      a_lo_new = L;
+      a_hi_new = hi_at_L >= 0.f ? hi_at_L : a_hi_old + (s * (a_lo_old - a_lo_new));
+    } else if (a_lo_new >= H) {
+      a_lo_new = H;
+      a_hi_new = hi_at_H >= 0.f ? hi_at_H : a_hi_old + (s * (a_lo_old - a_lo_new));
+    } else {
+      a_hi_new = a_hi_old + (s * (a_lo_old - a_lo_new));
+    }
+    a_hi_new = clip01(a_hi_new, 0.0f, C_hi);  // guards fp round-off only
+  } else {
+    a_hi_new = a_hi_old + (s * (a_lo_old - a_lo_new));
+    a_lo_new = clip01(a_lo_new, 0.0f, C_lo);
+    a_hi_new = clip01(a_hi_new, 0.0f, C_hi);
+  }
+  PairUpdate u;
+  u.a_hi_new = a_hi_new;
+  u.a_lo_new = a_lo_new;
+  u.c_hi = (a_hi_new - a_hi_old) * y_hi;
+  u.c_lo = (a_lo_new - a_lo_old) * y_lo;
+  return u;
+}
+// one bound for both rows (pair_update_w with C_hi == C_lo is pair_update, bit for bit)
+DPSVM_HD PairUpdate pair_update(float a_hi_old, float a_lo_old, float y_hi, float y_lo, float b_hi, float b_lo,
+                                float k_hl, float k_hh, float k_ll, float C, float tau, int clip_mode, bool same) {
+  return pair_update_w(a_hi_old, a_lo_old, y_hi, y_lo, b_hi, b_lo, k_hl, k_hh, k_ll, C, C, tau, clip_mode, same);
 }
 
 // Stop test of the reference do/while tail (svmTrainMain.cpp:310).

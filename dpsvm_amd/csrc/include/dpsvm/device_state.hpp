@@ -430,6 +430,8 @@ struct WsArgs {
                        // fold = n_x while the state (f / alpha / y: n = nl = 2 fold) holds alpha_j at j and
                        // alpha*_j at j + fold, K~(a, b) = K(a mod fold, b mod fold); 0: off.  Read by the fold
                        // kernels of ws_select / ws_merge only
+  int32_t diag;        // 1: the Gram's diagonal is read, not assumed 1 (precomputed Grams; one block, box clipping):
+                       // the kDiag instantiations of ws_solve
 };
 // keys per side and list of the multi-block selection (ws_select pass 2, the peer exchange)
 constexpr int ws_ncand(int ncand) { return ncand > 0 && ncand < kWsCand ? ncand : kWsCand; }

@@ -59,6 +59,60 @@ inline void check_problem(ProblemKind kind, const SolverParams& p, const Problem
   };
   for (const auto& r : rows) DPSVM_CHECK(r.ok, std::string(problem_name(kind)) + r.text);
 }
+// The kernel, resolved beside the problem kind: RBF from X (the solvers compute the Gram), or a precomputed n x n
+// Gram of any kernel handed over by the caller (GpuSolver::setup_gram, solve_cpu_gram; docs/DESIGN.md §20).
+// Precomputed combines with all three problem kinds.
+enum class KernelKind { Rbf, Precomputed };
+constexpr const char* kKernelName[] = {"rbf", "precomputed"};
+constexpr const char* kPrecomputedNote = "precomputed Gram: general diagonal, one block";
+inline const char* kernel_name(KernelKind k) { return kKernelName[(int)k]; }
+// The only reader of SolverParams::kernel.
+inline KernelKind resolve_kernel(const SolverParams& p) {
+  DPSVM_CHECK(p.kernel == 0 || p.kernel == 1, "kernel must be 0 (rbf) or 1 (precomputed)");
+  return p.kernel == 1 ? KernelKind::Precomputed : KernelKind::Rbf;
+}
+// The one table of refusals of a precomputed kernel, for both solvers: it runs the one-block working-set rounds on
+// the resident Gram of one rank with the joint box (general-diagonal sub-problem kernels), and nothing else.  Per-row
+// C stays allowed for the classifier (check_problem refuses it for the other kinds).  s.n_x_rows: n (there is no X).
+// ws_blocks = 0 and ws_wss = 0 are resolved by the caller (1 block; second order: there is no X to sample).
+inline void check_kernel(KernelKind k, const SolverParams& p, const ProblemSite& s) {
+  if (k == KernelKind::Rbf) return;
+  const bool dev = s.device;
+  const struct { bool ok; const char* text; } rows[] = {
+      {p.clip == ClipMode::Box,
+       " runs with box clipping (clip=box): clip=independent is not implemented on the general-diagonal kernels"},
+      {s.world == 1 && (!dev || (!p.force_collectives && p.exchange != 2)),
+       ": multi-rank solves (comm), forced collectives (force_collectives) and the peer exchange (exchange=peer) are "
+       "not implemented"},
+      {!s.resume && p.checkpoint_every == 0 && p.checkpoint_path.empty(),
+       ": checkpoints (checkpoint_path / checkpoint_every) and resume are not implemented"},
+      {!dev || (p.solver != 1 && p.engines == 0),
+       ": not implemented on the pair-at-a-time engines (solver=smo, engines=all)"},
+      {!dev || p.ws_blocks <= 1, ": multi-block rounds are not implemented (ws_blocks must be 1)"},
+      {!dev || (!p.force_cache && p.cache_lines == 0 && p.host_cache_lines == 0 && p.ws_recompute != 1),
+       ": the kernel-row cache (force_cache / cache_lines / host_cache_lines) and recompute rounds (ws_recompute) are "
+       "not implemented: the Gram must be resident"},
+      {!dev || (p.x_mode != 2 && s.n_x_rows == s.n), ": partitioned X (x_mode) is not implemented: there is no X"},
+  };
+  for (const auto& r : rows) DPSVM_CHECK(r.ok, std::string("precomputed kernel") + r.text);
+}
+// setup_gram's symmetry check: a fixed pseudo-random sample of kGramSymPairs pairs (i, j) of [0, n) (an LCG from
+// a fixed seed: the same pairs for the same n, everywhere), flattened [i0, j0, i1, j1, ..]
+constexpr int kGramSymPairs = 1024;
+inline std::vector<int32_t> gram_sym_pairs(int64_t n) {
+  std::vector<int32_t> ij(2 * (size_t)kGramSymPairs);
+  uint64_t r = 0x9E3779B97F4A7C15ull;
+  for (auto& v : ij) {
+    r = r * 6364136223846793005ull + 1442695040888963407ull;
+    v = (int32_t)((r >> 33) % (uint64_t)n);
+  }
+  return ij;
+}
+// a call that reads X: not served on a precomputed kernel
+inline void require_x(KernelKind k, const char* call) {
+  DPSVM_CHECK(k == KernelKind::Rbf, std::string(call) + ": reads X, not implemented for a precomputed kernel (there "
+                                        "is no X: decisions come from K(test, train), gram_rows_dot)");
+}
 // a call that serves the classifier alone
 inline void require_classifier(ProblemKind kind, const char* call) {
   DPSVM_CHECK(kind == ProblemKind::Classify, std::string(call) + ": serves the classifier, not implemented for " +

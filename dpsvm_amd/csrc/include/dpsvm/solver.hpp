@@ -52,6 +52,17 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
                       const Checkpoint* resume = nullptr, const ProgressFn& progress = {},
                       const float* row_C = nullptr);
 
+// The same loop on a precomputed n x n Gram (SolverParams::kernel = 1; K: host, row stride ld >= n, symmetric):
+// kernel rows are copied from K, k_hl is read from K and eta takes the pair's own diagonal entries (pair_update's
+// general-diagonal overloads).  y: labels (classification), targets (epsilon-SVR) or ignored (one-class).  One rank,
+// box clipping; row_C for the classifier only.
+SolveResult solve_cpu_gram(const float* K, int64_t ld, int64_t n, const float* y, const SolverParams& p,
+                           const float* row_C = nullptr, const ProgressFn& progress = {});
+// Decisions from a rectangular Gram, accumulated in fp64 (the twin of launch::gram_rows_dot):
+//   out[i k + c] = float(sum_{j < n} double(Kt[i ld + j]) double(coef[c ldc + j]) - double(b[c])), i < nt, c < k
+std::vector<float> gram_decision_cpu(const float* Kt, int64_t nt, int64_t ld, int64_t n, const float* coef,
+                                     int64_t ldc, int k, const float* b, int threads = 0);
+
 // Decision values d(x) = sum_sv alpha y K(sv,x) - b  (svmTrain.cu:646-658)
 std::vector<float> decision_cpu(const Model& m, const float* x, int64_t n, int d, int threads = 0);
 // One-vs-rest decision values [n][k]: column c = sum_sv coef[sv][c] K(sv, x) - b[c] (k passes of decision_cpu)
@@ -97,6 +108,7 @@ struct GpuSetupInfo {
   std::string comm_kind;               // communicator backend: local | rccl | thread | callback
   int ws_blocks = 0, ws_q_max = 0;     // working-set rounds: blocks per round x rows per block (the union)
   std::string gram = "f32";           // Gram / kernel-row GEMM arithmetic: "f32" or "split-f16" (rbf_gemm_split.hip)
+  std::string kernel = "rbf";         // "rbf" | "precomputed" (setup_gram: gram reads "precomputed" too)
 };
 
 // true once the pair-cache plugin (libdpsvm_pairq.so, or the CLIs that link it)
@@ -113,6 +125,14 @@ class GpuSolver {
   GpuSolver& operator=(const GpuSolver&) = delete;
 
   GpuSetupInfo setup(const float* x, int64_t n_x_rows, int64_t n, int d, const float* y);
+  // Precomputed kernel (SolverParams::kernel = 1): the setup without X.  K: the n x n Gram, row stride ld >= n, on
+  // the host or (on_device) on this solver's device; copied into the solver's own lines by one 2-D copy on the
+  // solver's stream, ordered after `stream` (hipStream_t as void*; device input) — the caller keeps its buffer.
+  // K must be symmetric (checked bitwise on a fixed pseudo-random sample of 1,024 pairs) with a finite,
+  // non-negative diagonal.  The Gram is valid from here on: every solve reports t_gram = 0 and gram_reused; a
+  // solve that finds it invalidated (after a failed solve) asks for setup_gram again.  y as setup's.
+  GpuSetupInfo setup_gram(const float* K, int64_t ld, int64_t n, const float* y, bool on_device = false,
+                          void* stream = nullptr);
   SolveResult solve(const Checkpoint* resume = nullptr, const ProgressFn& progress = {});
   // After solve(): distributed training accuracy (each rank predicts its shard)
   double train_accuracy(const SolveResult& r);
@@ -320,7 +340,8 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
                             const std::vector<float>& y, const std::vector<int32_t>& qb, int q_max, int blocks,
                             int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
                             float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss = 1,
-                            const std::vector<float>& row_C = {});  // [P * q_max] per-row bounds (empty: scalar C)
+                            const std::vector<float>& row_C = {},  // [P * q_max] per-row bounds (empty: scalar C)
+                            bool diag = false);  // the general-diagonal kernels (one block, box clipping)
 // ws_select: the f update of a round's alpha changes (apply rows: lines into
 // gram [L][ldg], coefficients) and the per-workgroup candidates.  blocks == 1:
 // the one-pass kernel; blocks > 1: pass 1 (d_f, line-search partials) and pass 2
@@ -361,6 +382,19 @@ struct GramWsumProbe {
 GramWsumProbe gram_rows_wsum_probe(const std::vector<float>& gram, int64_t L, int64_t ldg, int64_t n,
                                    const std::vector<int32_t>& lines, const std::vector<float>& coef,
                                    const std::vector<float>& base, int reps = 0);
+// gram_rows_dot (gram_dot.hip): out[i][c] = float(sum_j double(Kt[i][j]) double(coef[c][j]) - b[c]) on Kt [nt][ld],
+// coef [k][ldc], b [k].  out is [pad | nt * k | pad] with pad = kGramDotProbePad floats filled with
+// kGramDotProbeFill before the launch: the pads must come back as they were.  reps > 0: event times (us) of reps
+// launches before the returned one.
+constexpr int kGramDotProbePad = 64;
+constexpr float kGramDotProbeFill = -12345.f;
+struct GramDotProbe {
+  std::vector<float> out;
+  std::vector<float> us;
+};
+GramDotProbe gram_rows_dot_probe(const std::vector<float>& Kt, int64_t nt, int64_t ld, int64_t n,
+                                 const std::vector<float>& coef, int64_t ldc, int k, const std::vector<float>& b,
+                                 int reps = 0);
 // The one-block merge (ws_merge.hpp) through the two round kernels that run it
 // in every workgroup, one launch each: round `outer` builds parity outer & 1
 // from cand = [G][2][kWsCand] lists (the merge reads the first kWsCand1 keys a

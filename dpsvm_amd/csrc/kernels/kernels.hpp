@@ -26,6 +26,15 @@ int gram_wsum_slices(int64_t n, int64_t m);
 int64_t gram_wsum_scratch_doubles(int64_t n);
 void gram_rows_wsum(const float* gram, int64_t L, int64_t ldg, int64_t n, const int32_t* lines, const float* coef,
                     int64_t m, const float* base, float* out, double* part, hipStream_t s);
+// Decisions from a rectangular Gram K(test, train), accumulated in fp64 and rounded once (gram_dot.hip,
+// docs/DESIGN.md §20):
+//   out[i ldo + c] = float(sum_{j < n} double(Kt[i ld + j]) double(coef[c ldc + j]) - double(b[c])), i < nt, c < k
+// Kt [nt][ld >= n], coef [k][ldc >= n], b [k], out [nt][ldo >= k], all on the device; columns >= n of Kt / coef are
+// never read.  16-B loads where Kt / coef are 16-B aligned with ld, ldc multiples of 4, else the same units by
+// elements.  Kt is read once per group of kDotGroup machines.  No atomics: the summation order follows from n alone.
+constexpr int kDotGroup = 8;
+void gram_rows_dot(const float* Kt, int64_t nt, int64_t ld, int64_t n, const float* coef, int64_t ldc, int k,
+                   const float* b, float* out, int64_t ldo, hipStream_t s);
 
 // One SMO iteration's kernels (see device_state.hpp)
 void smo_rows(const SmoArgs& a, hipStream_t s);

@@ -23,7 +23,8 @@ constexpr int kWsSolvePollBatch = 10;
 // the sub-Gram load of one launch per round; the loop: ws_solve.hpp
 // kRowC: per-row bounds (WsArgs::c_row): the rows' C_i into LDS beside s_a / s_y, straight from c_row[idx] on every
 // load path; separate instantiations, the scalar ones keep their code
-template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS = 3, bool kRowC = false>
+// kDiag: the general-diagonal pair loop (ws_solve.hpp; WsArgs::diag), separate instantiations again
+template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS = 3, bool kRowC = false, bool kDiag = false>
 __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float K[];  // q rows of the sub-Gram, stride q_max
   __shared__ float s_a[kWsMax + 128], s_y[kWsMax], s_f[kWsMax];  // s_a: + 2 x 64 scratch words
@@ -188,11 +189,11 @@ __global__ __launch_bounds__(kWsSolveThreads) void ws_solve_kernel(WsArgs a) {
   if (wave != 0) return;
 
   if constexpr (kRowC)
-    ws_solve_run<kBox, kFull, kMulti, kW2, NS, true>(a, c, K, s_a, s_y, s_f, s_idx, s_line, q, blk, ib, it0, b_hi,
-                                                     b_lo, xfail, s_c);
+    ws_solve_run<kBox, kFull, kMulti, kW2, NS, true, kDiag>(a, c, K, s_a, s_y, s_f, s_idx, s_line, q, blk, ib, it0,
+                                                            b_hi, b_lo, xfail, s_c);
   else
-    ws_solve_run<kBox, kFull, kMulti, kW2, NS>(a, c, K, s_a, s_y, s_f, s_idx, s_line, q, blk, ib, it0, b_hi, b_lo,
-                                               xfail);
+    ws_solve_run<kBox, kFull, kMulti, kW2, NS, false, kDiag>(a, c, K, s_a, s_y, s_f, s_idx, s_line, q, blk, ib, it0,
+                                                             b_hi, b_lo, xfail);
 }
 
 }  // namespace dev
@@ -229,12 +230,25 @@ void ws_solve(const WsArgs& a, hipStream_t s) {
   const int v = (rowc ? 16 : 0) + (w2 ? 8 : 0) + (multi ? 4 : 0) + (box ? 2 : 0) + (full ? 1 : 0);
   const int v2 = (rowc ? 8 : 0) + (w2 ? 4 : 0) + (multi ? 2 : 0) + (box ? 1 : 0);
   const bool one = a.q_max <= 64, two = !one && a.q_max <= 128;
-  const Fn fn = one ? fns1[v2] : two ? fns2[v2] : fns[v];
+  // general diagonal (a.diag, precomputed Grams): box clipping, one block; tables of their own
+#define WS_SOLVE_FNSD(NS_, FULL)                                                                                   \
+  dev::ws_solve_kernel<true, FULL, false, false, NS_, false, true>,                                                \
+      dev::ws_solve_kernel<true, FULL, false, true, NS_, false, true>,                                             \
+      dev::ws_solve_kernel<true, FULL, false, false, NS_, true, true>,                                             \
+      dev::ws_solve_kernel<true, FULL, false, true, NS_, true, true>
+  static const Fn fnsd[16] = {WS_SOLVE_FNSD(3, false), WS_SOLVE_FNSD(3, true), WS_SOLVE_FNSD(2, false),
+                              WS_SOLVE_FNSD(1, false)};
+#undef WS_SOLVE_FNSD
+  const bool diag = a.diag != 0;
+  DPSVM_CHECK(!diag || (box && !multi), "ws_solve: the general-diagonal kernels run one block with box clipping");
+  const int vd = (one ? 12 : two ? 8 : full ? 4 : 0) + (rowc ? 2 : 0) + (w2 ? 1 : 0);
+  const Fn fn = diag ? fnsd[vd] : one ? fns1[v2] : two ? fns2[v2] : fns[v];
   // dynamic LDS above 64 KiB needs the attribute (160 KiB on gfx950); the
   // largest size set so far per device and kernel (rank threads of one process
   // launch on different devices concurrently)
   static std::atomic<size_t> attr[kMaxDevices][64];
-  std::atomic<size_t>& at = attr[current_device()][one ? 48 + v2 : two ? 32 + v2 : v];
+  static std::atomic<size_t> attr_d[kMaxDevices][16];
+  std::atomic<size_t>& at = diag ? attr_d[current_device()][vd] : attr[current_device()][one ? 48 + v2 : two ? 32 + v2 : v];
   size_t cur = at.load(std::memory_order_relaxed);
   if (lds > 64 * 1024 && lds > cur) {
     HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -57,13 +57,16 @@ __device__ __forceinline__ void ws_place(int pos, float an, float yv, float fp, 
 // the alphas actually taken, so it stays consistent), and the IEEE division
 // sequence is the longest dependent chain of a step.  C_hi / C_lo: the two
 // rows' bounds (pair_update_w's geometry; the scalar path passes C twice and
-// compiles to pair_update's expressions).
-template <bool kBox>
+// compiles to pair_update's expressions).  kDiag (precomputed Grams, docs/DESIGN.md
+// §20): eta from the pair's own diagonal entries khh = K(hi, hi), kll = K(lo, lo)
+// instead of the RBF kernel's 1 + 1 — the same expression in the same order, so a
+// unit diagonal gives the same bits.
+template <bool kBox, bool kDiag = false>
 __device__ __forceinline__ PairUpdate ws_pair_step(float a_hi, float a_lo, float y_hi, float y_lo, float bh, float bl,
                                                    float khl, float C_hi, float C_lo, float tau, bool same,
-                                                   bool* clipped) {
+                                                   bool* clipped, float khh = 1.0f, float kll = 1.0f) {
 #pragma clang fp contract(off)
-  float eta = (1.0f + 1.0f) - 2.0f * khl;
+  float eta = kDiag ? (khh + kll) - 2.0f * khl : (1.0f + 1.0f) - 2.0f * khl;
   eta = eta >= tau ? eta : tau;
   float r = __builtin_amdgcn_rcpf(eta);
   r = r + r * __builtin_fmaf(-eta, r, 1.0f);  // one Newton step: ~0.5 ulp
@@ -146,17 +149,21 @@ __device__ __forceinline__ int ws_argpos(const float (&x)[2], float v) {
 // NS: 64-row slots per lane (3 for q_max <= 192, 2 for q_max <= 128 — the
 // multi-block rounds' 96-row blocks: a third less work per pair step — and 1
 // for blocks of <= 64 rows)
+// kDiag: the sub-Gram's diagonal is read, not assumed 1 (precomputed Grams): the
+// step's eta = K(hi,hi) + K(lo,lo) - 2 K(hi,lo) from the step's load batch, the
+// WSS2 gains' from each slot's own diagonal entry, held in NS registers
 // The sub-problem loop and the round's commit, on wave 0 once the q rows are in
 // LDS: K (q rows, stride a.q_max), s_a (+ 128 scratch words), s_y, s_f, s_idx,
 // s_line, and with kRowC (per-row C, WsArgs::c_row) the rows' bounds s_c.  blk / ib: the block and its first row (multi-block rounds); it0,
 // b_hi, b_lo: the round's pair count and global selection at entry; xfail: the
 // peer exchange gave up (no step, kCommFail kept).
-template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS, bool kRowC = false>
+template <bool kBox, bool kFull, bool kMulti, bool kW2, int NS, bool kRowC = false, bool kDiag = false>
 __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const float* K, float* s_a, const float* s_y,
                                              const float* s_f, const int32_t* s_idx, const int32_t* s_line, int q,
                                              int blk, int ib, int64_t it0, float b_hi, float b_lo, bool xfail,
                                              const float* s_c = nullptr) {
   static_assert(NS == 3 || ((NS == 2 || NS == 1) && !kFull), "slots");
+  static_assert(!kDiag || (kBox && !kMulti), "general diagonal: one block, box clipping");
   const int lane = threadIdx.x & 63;
   const int ldk = a.q_max;
   const float INF = __builtin_inff();
@@ -177,6 +184,14 @@ __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const f
     } else {
       fu[s] = v && in_up(a0[s], yr[s], C) ? fv : INF;
       fl[s] = v && in_low(a0[s], yr[s], C) ? -fv : INF;
+    }
+  }
+  float kd[NS];  // kDiag, WSS2: the slots' own diagonal entries K(p, p)
+  if constexpr (kDiag && kW2) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int p = lane + 64 * s;
+      kd[s] = p < q ? K[p * ldk + p] : 1.0f;
     }
   }
   int64_t room = a.max_iter - it0;
@@ -214,10 +229,14 @@ __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const f
 #pragma unroll
         for (int s = 0; s < NS; ++s) kh[s] = K[ph * ldk + (kFull ? lane + 64 * s : min(lane + 64 * s, q - 1))];
         float g[NS];
+        float kd_hi = 1.0f;
+        if constexpr (kDiag) kd_hi = K[ph * ldk + ph];
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           const float dv = -fl[s] - bh;
-          float eta = (1.0f + 1.0f) - 2.0f * kh[s];
+          float eta;
+          if constexpr (kDiag) eta = (kd_hi + kd[s]) - 2.0f * kh[s];
+          else eta = (1.0f + 1.0f) - 2.0f * kh[s];
           eta = eta >= a.tau ? eta : a.tau;
           // on every lane, then a select: hipcc made each slot's conditional
           // reciprocal an exec-masked branch (three per step)
@@ -257,8 +276,12 @@ __device__ __forceinline__ void ws_solve_run(const WsArgs& a, WsCtrl* c, const f
       C_lo = s_c[pl];
     }
     bool clipped = false;
-    const PairUpdate up =
-        ws_pair_step<kBox>(a_hi, a_lo, y_hi, y_lo, bh, bl, khl, C_hi, C_lo, a.tau, ph == pl, &clipped);
+    PairUpdate up;
+    if constexpr (kDiag)
+      up = ws_pair_step<kBox, true>(a_hi, a_lo, y_hi, y_lo, bh, bl, khl, C_hi, C_lo, a.tau, ph == pl, &clipped, khh,
+                                    kll);
+    else
+      up = ws_pair_step<kBox>(a_hi, a_lo, y_hi, y_lo, bh, bl, khl, C_hi, C_lo, a.tau, ph == pl, &clipped);
     if (kMulti && !kBox) clipped_any |= clipped;
     float f_lo_new, f_hi_new;
 #pragma unroll

@@ -178,6 +178,7 @@ py::dict setup_dict(const GpuSetupInfo& i) {
   d["ws_rounds"] = i.ws_rounds;
   d["ws_rows"] = i.ws_rows;
   d["gram"] = i.gram;
+  d["kernel"] = i.kernel;
   d["xch_selftest"] = i.xch_selftest;
   d["comm_kind"] = i.comm_kind;
   d["ws_blocks"] = i.ws_blocks;
@@ -227,6 +228,7 @@ PYBIND11_MODULE(_C, m) {
       .def(py::init<>())
       .def_readwrite("C", &SolverParams::C)
       .def_readwrite("gamma", &SolverParams::gamma)
+      .def_readwrite("kernel", &SolverParams::kernel)
       .def_readwrite("eps", &SolverParams::eps)
       .def_readwrite("max_iter", &SolverParams::max_iter)
       .def_readwrite("clip", &SolverParams::clip)
@@ -540,6 +542,45 @@ PYBIND11_MODULE(_C, m) {
      py::arg("progress") = py::none(), py::arg("row_C") = py::none());
 
   m.def("problem_note", [](const SolverParams& p) { return std::string(problem_note(resolve_problem(p))); });
+  m.def("precomputed_note", []() { return std::string(kPrecomputedNote); });
+  m.def("gram_sym_pairs", [](int64_t n) {
+    const std::vector<int32_t> ij = gram_sym_pairs(n);
+    py::array_t<int32_t> a({(py::ssize_t)kGramSymPairs, (py::ssize_t)2});
+    memcpy(a.mutable_data(), ij.data(), ij.size() * 4);
+    return a;
+  }, py::arg("n"), "the fixed sample of pairs (i, j) setup_gram tests for K[i][j] == K[j][i]");
+  // the CPU solver on a precomputed Gram K (n, n) (SolverParams.kernel = 1); y: labels / targets / ignored
+  m.def("solve_cpu_gram", [](F32 K, F32 y, const SolverParams& p, py::object progress, py::object row_C) {
+    if (K.ndim() != 2 || K.shape(0) != K.shape(1)) throw py::value_error("K must be square (n, n)");
+    const int64_t n = K.shape(0);
+    if (y.ndim() != 1 || y.shape(0) != n) throw py::value_error("y must be 1-D with len(y) == K.shape[0]");
+    std::vector<float> rc;
+    if (!row_C.is_none()) {
+      const F32 c = row_C.cast<F32>();
+      if (c.ndim() != 1 || c.shape(0) != n) throw py::value_error("row_C must have n entries");
+      rc = from_np(c);
+    }
+    auto prog = wrap_progress(progress);
+    SolveResult r;
+    {
+      py::gil_scoped_release rel;
+      r = solve_cpu_gram(K.data(), n, n, y.data(), p, rc.empty() ? nullptr : rc.data(), prog);
+    }
+    return py::make_tuple(to_np(r.alpha), result_dict(r));
+  }, py::arg("K"), py::arg("y"), py::arg("params"), py::arg("progress") = py::none(), py::arg("row_C") = py::none());
+  // decisions from K(test, train) (nt, n), coef (k, n), b (k,) in fp64: (nt, k)
+  m.def("gram_decision_cpu", [](F32 Kt, F32 coef, F32 b, int threads) {
+    if (Kt.ndim() != 2 || coef.ndim() != 2 || b.ndim() != 1 || coef.shape(1) != Kt.shape(1) ||
+        b.shape(0) != coef.shape(0))
+      throw py::value_error("Kt must be (nt, n), coef (k, n), b (k,)");
+    std::vector<float> out;
+    {
+      py::gil_scoped_release rel;
+      out = gram_decision_cpu(Kt.data(), Kt.shape(0), Kt.shape(1), Kt.shape(1), coef.data(), coef.shape(1),
+                              (int)coef.shape(0), b.data(), threads);
+    }
+    return to_np2(out, Kt.shape(0), (int)coef.shape(0));
+  }, py::arg("Kt"), py::arg("coef"), py::arg("b"), py::arg("threads") = 0);
   m.def("solve_shrinking", [](F32 x, F32 y, const SolverParams& p, int device, const Checkpoint* resume,
                               py::object progress, std::shared_ptr<Communicator> comm) {
     int64_t n = 0;
@@ -578,6 +619,32 @@ PYBIND11_MODULE(_C, m) {
         }
         return setup_dict(i);
       })
+      .def("setup_gram", [](GpuSolver& s, py::object K, F32 y, int64_t n, int64_t ld, uintptr_t stream) {
+        // K: a numpy array (n, n), or a device pointer (int) to n rows of ld floats with the stream that wrote them
+        GpuSetupInfo i;
+        try {
+          if (py::isinstance<py::int_>(K)) {
+            if (n < 2 || ld < n) throw py::value_error("a device pointer needs n >= 2 and ld >= n");
+            if (y.ndim() != 1 || y.shape(0) != n) throw py::value_error("y must have n entries");
+            const float* kp = (const float*)K.cast<uintptr_t>();
+            py::gil_scoped_release r;
+            i = s.setup_gram(kp, ld, n, y.data(), true, (void*)stream);
+          } else {
+            const F32 a = K.cast<F32>();
+            if (a.ndim() != 2 || a.shape(0) != a.shape(1)) throw py::value_error("K must be square (n, n)");
+            if (y.ndim() != 1 || y.shape(0) != a.shape(0)) throw py::value_error("y must have n entries");
+            py::gil_scoped_release r;
+            i = s.setup_gram(a.data(), a.shape(1), a.shape(0), y.data(), false, nullptr);
+          }
+        } catch (const Error& e) {
+          // what the caller's matrix fails (diagonal, symmetry) is a value error; the rest stays NativeError
+          if (std::string(e.what()).find("invalid Gram") != std::string::npos) throw py::value_error(e.what());
+          throw;
+        }
+        return setup_dict(i);
+      }, py::arg("K"), py::arg("y"), py::arg("n") = 0, py::arg("ld") = 0, py::arg("stream") = 0,
+           "precomputed kernel: the setup without X; K is copied into the solver's own lines (it must be symmetric, "
+           "with a finite diagonal >= 0)")
       .def("solve", [](GpuSolver& s, const Checkpoint* resume, py::object progress) {
         auto prog = wrap_progress(progress);
         SolveResult r;
@@ -845,11 +912,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("k_ws_solve", [vi](const F32& K, const F32& f, const F32& alpha, const F32& y, const I32& qb, int q_max,
                            int blocks, int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
                            float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss,
-                           py::object row_C) {
+                           py::object row_C, bool diag) {
     const auto r = kernels::ws_solve_probe(from_np(K), from_np(f), from_np(alpha), from_np(y), vi(qb), q_max, blocks,
                                            p_round, C, clip, eps, rel, eps_floor, tau, b_hi, b_lo, inner_max, iter0,
                                            max_iter, wss,
-                                           row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()));
+                                           row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()), diag);
     py::dict d;
     d["alpha"] = to_np(r.alpha);
     d["steps"] = r.steps;
@@ -865,7 +932,29 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("K"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("qb"), py::arg("q_max"), py::arg("blocks"),
         py::arg("p_round"), py::arg("C"), py::arg("clip"), py::arg("eps"), py::arg("rel"), py::arg("eps_floor"),
         py::arg("tau"), py::arg("b_hi"), py::arg("b_lo"), py::arg("inner_max"), py::arg("iter0"), py::arg("max_iter"),
-        py::arg("wss"), py::arg("row_C") = py::none());
+        py::arg("wss"), py::arg("row_C") = py::none(), py::arg("diag") = false);
+  m.def("k_gram_rows_dot", [](const F32& Kt, int64_t nt, int64_t ld, int64_t n, const F32& coef, int64_t ldc, int k,
+                              const F32& b, int reps) {
+    kernels::GramDotProbe r;
+    {
+      const std::vector<float> kt = from_np(Kt), cf = from_np(coef), bb = from_np(b);
+      py::gil_scoped_release rel;
+      r = kernels::gram_rows_dot_probe(kt, nt, ld, n, cf, ldc, k, bb, reps);
+    }
+    py::dict d;
+    d["out"] = to_np(r.out);
+    d["us"] = r.us;
+    d["pad"] = kernels::kGramDotProbePad;
+    d["fill"] = kernels::kGramDotProbeFill;
+    return d;
+  }, py::arg("Kt"), py::arg("nt"), py::arg("ld"), py::arg("n"), py::arg("coef"), py::arg("ldc"), py::arg("k"),
+        py::arg("b"), py::arg("reps") = 0);
+  // the launch itself on device pointers (a GPU tensor's K(test, train) without a host copy)
+  m.def("k_gram_rows_dot_device", [](uintptr_t Kt, int64_t nt, int64_t ld, int64_t n, uintptr_t coef, int64_t ldc,
+                                     int k, uintptr_t b, uintptr_t out, int64_t ldo, uintptr_t stream) {
+    launch::gram_rows_dot((const float*)Kt, nt, ld, n, (const float*)coef, ldc, k, (const float*)b, (float*)out, ldo,
+                          (hipStream_t)stream);
+  });
   m.def("k_ws_select", [vi](const F32& gram, int64_t L, int64_t ldg, const F32& f, const F32& alpha, const F32& y,
                             const F32& dalpha, const I32& lines, const F32& coef, const I32& nab, int blocks,
                             int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps,
@@ -994,6 +1083,10 @@ PYBIND11_MODULE(_C, m) {
                                       std::vector<double>(B.data(), B.data() + B.size())),
                   dec.shape(0), (int)dec.shape(1));
   }, py::arg("dec"), py::arg("A"), py::arg("B"));
+  // proba_rows in place on device pointers (dec [n][k] float32, A / B k float64; stream: hipStream_t)
+  m.def("k_proba_rows_device", [](uintptr_t dec, int64_t n, int k, uintptr_t A, uintptr_t B, uintptr_t stream) {
+    launch::proba_rows((float*)dec, n, k, (const double*)A, (const double*)B, (hipStream_t)stream);
+  });
   m.attr("kWsProbeKey") = kernels::kWsProbeKey;
   m.attr("kWsProbeApply") = kernels::kWsProbeApply;
   m.def("production_line_cap", &production_line_cap, py::arg("cache_lines"), py::arg("ws_size"),
@@ -1008,6 +1101,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("pair_update_w", [](float a_hi, float a_lo, float y_hi, float y_lo, float b_hi, float b_lo, float k_hl,
                             float C_hi, float C_lo, float tau, int clip, bool same) {
     const PairUpdate u = pair_update_w(a_hi, a_lo, y_hi, y_lo, b_hi, b_lo, k_hl, C_hi, C_lo, tau, clip, same);
+    return py::make_tuple(u.a_hi_new, u.a_lo_new, u.c_hi, u.c_lo);
+  });
+  // their general-diagonal overloads (precomputed Grams): eta from the pair's own k_hh, k_ll
+  m.def("pair_update_diag", [](float a_hi, float a_lo, float y_hi, float y_lo, float b_hi, float b_lo, float k_hl,
+                               float k_hh, float k_ll, float C, float tau, int clip, bool same) {
+    const PairUpdate u = pair_update(a_hi, a_lo, y_hi, y_lo, b_hi, b_lo, k_hl, k_hh, k_ll, C, tau, clip, same);
+    return py::make_tuple(u.a_hi_new, u.a_lo_new, u.c_hi, u.c_lo);
+  });
+  m.def("pair_update_w_diag", [](float a_hi, float a_lo, float y_hi, float y_lo, float b_hi, float b_lo, float k_hl,
+                                 float k_hh, float k_ll, float C_hi, float C_lo, float tau, int clip, bool same) {
+    const PairUpdate u =
+        pair_update_w(a_hi, a_lo, y_hi, y_lo, b_hi, b_lo, k_hl, k_hh, k_ll, C_hi, C_lo, tau, clip, same);
     return py::make_tuple(u.a_hi_new, u.a_lo_new, u.c_hi, u.c_lo);
   });
   m.def("make_key", [](float f, uint32_t idx) { return make_key(f, idx); });

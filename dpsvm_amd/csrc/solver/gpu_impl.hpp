@@ -131,6 +131,12 @@ struct GpuSolver::Impl {
   float gamma = 0.f;
   int64_t n = 0, nl = 0, off = 0, x_rows = 0, G = 0, ldl = 0, L = 0;
   ProblemKind problem = ProblemKind::Classify;  // resolved once by setup (check_and_choose_policy)
+  // the kernel, resolved beside it.  Precomputed (setup_gram): X is an n x 1 zero matrix nothing reads, the lines
+  // hold the caller's Gram from setup on (gram_valid), every solve reuses it and wsa.diag selects the
+  // general-diagonal sub-problem kernels (docs/DESIGN.md §20)
+  KernelKind kernel = KernelKind::Rbf;
+  bool precomputed() const { return kernel == KernelKind::Precomputed; }
+  bool in_setup_gram = false;  // setup() reached through setup_gram
   // state rows: the length of alpha / y / f and of SolveResult::alpha.  n, except epsilon-SVR (one
   // rank, ws-dense, one block) where the folded dual has 2n of them while X, |x|^2, the split operands, the
   // Gram and every shard / geometry quantity above stay n-sized (wsa.fold = n); z: the targets (device, host)

@@ -169,6 +169,7 @@ void gpu_local_decision(GpuSolver::Impl& m, const std::vector<float>& alpha, flo
 double GpuSolver::train_accuracy(const SolveResult& r) {
   auto& m = *impl_;
   require_classifier(m.problem, "train_accuracy");
+  require_x(m.kernel, "train_accuracy");
   HIP_CHECK(hipSetDevice(m.device));
   DeviceSvs s;
   build_svs(m, r.alpha, s);
@@ -259,6 +260,7 @@ PlattFit GpuSolver::platt_fit(int slot) {
 std::vector<float> GpuSolver::decision(const SolveResult& r, const float* xh, int64_t nt, int d) {
   auto& m = *impl_;
   if (m.svr()) require_classifier(m.problem, "decision");  // (one-class: the same decision, served)
+  require_x(m.kernel, "decision");
   DPSVM_CHECK(d == m.d, "feature count mismatch");
   HIP_CHECK(hipSetDevice(m.device));
   DeviceSvs s;

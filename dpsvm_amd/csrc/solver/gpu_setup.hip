@@ -208,6 +208,8 @@ void GpuSolver::set_row_C(const float* c) {
 
 void GpuSolver::release_cache() {
   auto& m = *impl_;
+  DPSVM_CHECK(!m.precomputed(), "release_cache: not implemented for a precomputed kernel (the lines hold the "
+                                "caller's Gram, which no solve can rebuild)");
   if (!m.lines) return;
   HIP_CHECK(hipSetDevice(m.device));
   HIP_CHECK(hipStreamSynchronize(m.stream));
@@ -372,7 +374,12 @@ void check_and_choose_policy(GpuSolver::Impl& m, SetupState& s, int64_t n, int d
               "rows_per_group must be a multiple of 256");
   // epsilon-SVR, one-class: whatever they do not run is refused here, before any device state exists
   m.problem = resolve_problem(m.p);
+  m.kernel = resolve_kernel(m.p);
+  DPSVM_CHECK(m.precomputed() == m.in_setup_gram,
+              m.precomputed() ? "setup: a precomputed kernel takes its Gram through setup_gram (there is no X)"
+                              : "setup_gram: the solver's kernel must be precomputed (SolverParams::kernel = 1)");
   check_problem(m.problem, m.p, {n, m.outer_world, false, false, s.n_x_rows, s.yh, true});
+  check_kernel(m.kernel, m.p, {n, m.outer_world, false, false, s.n_x_rows, s.yh, true});
   m.n = n;
   m.ns = state_rows(m.problem, n);
   m.d = d;
@@ -747,7 +754,8 @@ void plan_rounds_and_exchange(GpuSolver::Impl& m, SetupState& s) {
   // the coupling of a row sample (mean off-diagonal K, host, outside the timed
   // region; read by the plan and by the pair choice): MNIST-shape at gamma
   // 0.25: 1.7e-9; the structured mnist-parity: 4.3e-3; covtype-shape 0.85
-  s.coupling = (s.ws_cand || s.wsc_cand) ? mean_offdiag_kernel(s.xh, s.n_x_rows, m.d, m.gamma) : 1.0;
+  // (precomputed kernel: there is no X to sample; the rounds are one block and the pair choice is resolved)
+  s.coupling = (s.ws_cand || s.wsc_cand) && !m.precomputed() ? mean_offdiag_kernel(s.xh, s.n_x_rows, m.d, m.gamma) : 1.0;
   WsPlanFacts& f = s.facts;
   f.uncoupled = m.all_agree(s.coupling < kWsUncoupled, m.comm, m.world);
   f.n = m.n;
@@ -828,6 +836,9 @@ void pick_engine(GpuSolver::Impl& m, const SetupState& s) {
               std::string(problem_name(m.problem)) +
                   ": the Gram must be resident (ws-dense); the kernel-row cache (ws-cache), recompute rounds and "
                   "the pair-at-a-time engines are not implemented");
+  DPSVM_CHECK(!m.precomputed() || m.kind == EngineKind::WsDense,
+              "precomputed kernel: the solver's copy of the Gram must fit the device (ws-dense); the kernel-row cache "
+              "cannot recompute a row it dropped");
   if (m.persistent() && !m.census(m.kind)) {
     DPSVM_CHECK(m.p.persist != 2, "persistent engine requested (persist=on) but its grid is not co-resident (" +
                                       m.info.engine_note + ")");
@@ -911,6 +922,12 @@ void fill_ws_args(GpuSolver::Impl& m, const SetupState& s) {
     DPSVM_CHECK(shape.blocks == 1 && !m.xch && m.world == 1 && m.nl == m.n && m.off == 0,
                 std::string(problem_name(m.problem)) + ": one-block rounds on one rank only");
     m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + problem_note(m.problem);
+  }
+  if (m.precomputed()) {
+    DPSVM_CHECK(shape.blocks == 1 && !m.xch && m.world == 1 && m.nl == m.n && m.off == 0,
+                "precomputed kernel: one-block rounds on one rank only");
+    w.diag = 1;
+    m.info.engine_note += std::string(m.info.engine_note.empty() ? "" : "; ") + kPrecomputedNote;
   }
   if (m.svr()) {
     // the folded dual: 2n state rows on the n x n Gram; the selection geometry (s.ws_G, s.ws_rpt) is that of
@@ -1053,9 +1070,91 @@ void finish_info(GpuSolver::Impl& m) {
   m.info.groups = m.working_set() ? m.wsa.G : m.fused() ? m.Gf : m.G;
   m.info.poll_batch = m.xch && !m.working_set() ? launch::poll_batch(m.args) : 0;
   m.info.bytes_device = m.bytes;
+  m.info.kernel = kernel_name(m.kernel);
+  if (m.precomputed()) m.info.gram = "precomputed";
+}
+
+// setup_gram's checks on the solver's copy of the Gram (row i at g + i ldg): the diagonal, and both entries of a
+// fixed sample of pairs
+__global__ void gram_diag_kernel(const float* g, int64_t ldg, int64_t n, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = g[i * ldg + i];
+}
+__global__ void gram_pairs_kernel(const float* g, int64_t ldg, const int32_t* ij, int pairs, float* out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= pairs) return;
+  const int64_t i = ij[2 * k], j = ij[2 * k + 1];
+  out[2 * k] = g[i * ldg + j];
+  out[2 * k + 1] = g[j * ldg + i];
 }
 
 }  // namespace
+
+GpuSetupInfo GpuSolver::setup_gram(const float* K, int64_t ld, int64_t n, const float* yh, bool on_device,
+                                   void* stream) {
+  auto& m = *impl_;
+  DPSVM_CHECK(K != nullptr && ld >= n && n >= 2, "setup_gram: K must be n x n with row stride ld >= n, n >= 2");
+  // what a precomputed solve resolves before the table of refusals reads the rest: the one-block working-set
+  // rounds, LIBSVM's second-order pair choice (no X to sample a coupling from); no X means no split operands and
+  // no adaptive Gram (gram_precision, gram_adapt and gamma are ignored)
+  if (m.p.solver == 0) m.p.solver = 2;
+  if (m.p.ws_blocks == 0) m.p.ws_blocks = 1;
+  if (m.p.ws_wss == 0) m.p.ws_wss = 2;
+  if (m.p.ws_recompute == 0) m.p.ws_recompute = 2;
+  m.p.gram_precision = 1;
+  m.p.gram_adapt = 2;
+  m.p.gamma = 0.f;
+  // the ordinary setup on an n x 1 zero matrix: vectors, geometry, engine, round buffers and the lines
+  m.in_setup_gram = true;
+  struct Leave {
+    bool& v;
+    ~Leave() { v = false; }
+  } leave{m.in_setup_gram};
+  {
+    const std::vector<float> x0((size_t)n, 0.f);
+    setup(x0.data(), n, n, 1, yh);
+  }
+  // the caller's Gram into the solver's own lines: one 2-D copy on the solver's stream, after the caller's work
+  HIP_CHECK(hipSetDevice(m.device));
+  if (on_device) {
+    hipEvent_t e = nullptr;
+    HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(e, (hipStream_t)stream));
+    HIP_CHECK(hipStreamWaitEvent(m.stream, e, 0));
+    (void)hipEventDestroy(e);
+  }
+  HIP_CHECK(hipMemcpy2DAsync(m.lines, (size_t)m.ldl * 4, K, (size_t)ld * 4, (size_t)n * 4, (size_t)n,
+                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m.stream));
+  // the line padding pass 1 and gram_rows_wsum read (16-B loads: columns [n, round_up(n, 4))), and the rest of it
+  if (m.ldl > n)
+    HIP_CHECK(hipMemset2DAsync(m.lines + n, (size_t)m.ldl * 4, 0, (size_t)(m.ldl - n) * 4, (size_t)n, m.stream));
+  // the diagonal (finite, >= 0) and bitwise symmetry on a fixed pseudo-random sample of pairs: the round kernels
+  // read K(i, j) from either triangle
+  const std::vector<int32_t> ij = gram_sym_pairs(n);
+  size_t tb = 0;
+  int32_t* dij = dmalloc<int32_t>(ij.size(), &tb);
+  float* dout = dmalloc<float>((size_t)n + ij.size(), &tb);
+  std::vector<float> h((size_t)n + ij.size());
+  HIP_CHECK(hipMemcpyAsync(dij, ij.data(), ij.size() * 4, hipMemcpyHostToDevice, m.stream));
+  gram_diag_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, m.stream>>>(m.lines, m.ldl, n, dout);
+  gram_pairs_kernel<<<dim3((kGramSymPairs + 255) / 256), 256, 0, m.stream>>>(m.lines, m.ldl, dij, kGramSymPairs,
+                                                                           dout + n);
+  post_launch("setup_gram checks", m.stream);
+  HIP_CHECK(hipMemcpyAsync(h.data(), dout, h.size() * 4, hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));  // the caller's K is free again
+  (void)hipFree(dij);
+  (void)hipFree(dout);
+  for (int64_t i = 0; i < n; ++i)
+    DPSVM_CHECK(std::isfinite(h[i]) && h[i] >= 0.f,
+                "setup_gram: invalid Gram: diagonal entry " + std::to_string(i) + " is not finite and >= 0");
+  for (int k = 0; k < kGramSymPairs; ++k)
+    DPSVM_CHECK(f32_bits(h[n + 2 * k]) == f32_bits(h[n + 2 * k + 1]),
+                "setup_gram: invalid Gram: not symmetric, K[" + std::to_string(ij[2 * k]) + "][" +
+                    std::to_string(ij[2 * k + 1]) + "] != K[" + std::to_string(ij[2 * k + 1]) + "][" +
+                    std::to_string(ij[2 * k]) + "] (bitwise)");
+  m.gram_valid = true;
+  return m.info;
+}
 
 GpuSetupInfo GpuSolver::setup(const float* xh, int64_t n_x_rows, int64_t n, int d, const float* yh) {
   auto& m = *impl_;

@@ -104,6 +104,11 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
     DPSVM_CHECK(pos && neg, "per-row C (set_row_C): each label needs at least one row with C_i > 0");
   }
 
+  if (m.precomputed()) {
+    DPSVM_CHECK(!resume, "precomputed kernel: resume is not implemented");
+    DPSVM_CHECK(m.lines && m.gram_valid && m.dense,
+                "precomputed kernel: the solver's Gram was invalidated (a failed solve): call setup_gram again");
+  }
   if (!m.lines) {  // released (release_cache): the same L lines again, empty
     m.lines = gpu::dmalloc<float>((size_t)m.L * m.ldl, &m.bytes);
     m.info.bytes_device = m.bytes;
@@ -112,7 +117,8 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   }
   // the resident Gram is kept only on request (set_labels / set_row_C) and only a completed one; it is not
   // valid again before this solve has ended well
-  m.reuse_gram = m.problem_swapped && m.gram_valid && m.dense;
+  // (a precomputed Gram is the caller's: every solve reuses it)
+  m.reuse_gram = (m.problem_swapped || m.precomputed()) && m.gram_valid && m.dense;
   m.problem_swapped = m.gram_valid = false;
   // ---- state init (alpha = 0, f = -y, empty cache) or resume ----
   int64_t iter0 = 0;
@@ -288,7 +294,8 @@ SolveResult GpuSolver::solve(const Checkpoint* resume, const ProgressFn& progres
   }
   // ================= end of timed region =================
 
-  if (trace::verify_enabled() && !m.svr()) {  // (regression: skipped — the predict GEMM takes n-row alphas)
+  // (regression: skipped — the predict GEMM takes n-row alphas; a precomputed kernel: it has no X)
+  if (trace::verify_enabled() && !m.svr() && !m.precomputed()) {
     // invariants: alpha in [0, C]; f consistent with alpha, i.e. the
     // incrementally updated f_j equals sum_i alpha_i y_i K(i, j) - y_j recomputed
     // from scratch (MFMA predict GEMM); float drift over 10^5 updates stays ~1e-5.

@@ -106,6 +106,7 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   const ProblemKind kind = resolve_problem(p);
   const bool oc = kind == ProblemKind::OneClass, svr = kind == ProblemKind::Svr;
   check_problem(kind, p, {n, world, Cr != nullptr, resume != nullptr, n, ds.y.data(), false});
+  require_x(resolve_kernel(p), "solve_cpu");  // a precomputed Gram goes through solve_cpu_gram
   const int64_t ns = state_rows(kind, n);
   const float* Z = ds.y.data();
   std::vector<float> labels;
@@ -396,6 +397,154 @@ SolveResult solve_cpu(const Dataset& ds, const SolverParams& p, Communicator* co
   res.alpha = std::move(alpha);
   if (oc) res.f = std::move(f);  // f - b: the training decisions
   return res;
+}
+
+// The same loop on a precomputed Gram (SolverParams::kernel = 1, docs/DESIGN.md §20): one rank, the kernel row of
+// state row g is K's row g mod n (no cache: the rows are there), k_hl is read from K, and eta takes the pair's own
+// diagonal entries through pair_update's general-diagonal overloads.  Selection, update order, f update, stop test
+// and b are solve_cpu's, statement by statement.
+SolveResult solve_cpu_gram(const float* K, int64_t ld, int64_t n, const float* y, const SolverParams& p,
+                           const float* row_C, const ProgressFn& progress) {
+  auto t_setup0 = Clock::now();
+  DPSVM_CHECK(K != nullptr && n >= 2 && ld >= n, "solve_cpu_gram: K must be n x n with row stride ld >= n, n >= 2");
+  DPSVM_CHECK(p.C > 0.f, "C must be > 0");
+  const KernelKind kernel = resolve_kernel(p);
+  DPSVM_CHECK(kernel == KernelKind::Precomputed, "solve_cpu_gram: the kernel must be precomputed (kernel = 1)");
+  const ProblemKind kind = resolve_problem(p);
+  const bool oc = kind == ProblemKind::OneClass, svr = kind == ProblemKind::Svr;
+  const float* Cr = row_C;
+  const ProblemSite site{n, 1, Cr != nullptr, false, n, y, false};
+  check_problem(kind, p, site);
+  check_kernel(kernel, p, site);
+  for (int64_t i = 0; i < n; ++i)
+    DPSVM_CHECK(std::isfinite(K[i * ld + i]) && K[i * ld + i] >= 0.f,
+                "solve_cpu_gram: invalid Gram: diagonal entry " + std::to_string(i) + " is not finite and >= 0");
+  const float C = p.C;
+  const int64_t ns = state_rows(kind, n);
+  std::vector<float> labels;
+  problem_labels(kind, y, n, labels);
+  const float* Y = labels.data();
+  if (Cr) {
+    bool pos = false, neg = false;
+    for (int64_t i = 0; i < n; ++i) {
+      DPSVM_CHECK(std::isfinite(Cr[i]) && Cr[i] >= 0.f, "row_C: every C_i must be finite and >= 0");
+      if (Cr[i] > 0.f) (Y[i] > 0.f ? pos : neg) = true;
+    }
+    DPSVM_CHECK(pos && neg, "row_C: each label needs at least one row with C_i > 0");
+  }
+  struct FpGuard {
+    unsigned old;
+    ~FpGuard() { set_fp_control(old); }
+  } fp_guard{flush_denormals()};
+  auto row_of = [&](int64_t g) { return K + (size_t)(g >= n ? g - n : g) * ld; };  // state row -> Gram row
+
+  std::vector<float> alpha((size_t)ns, 0.f), f((size_t)ns);
+  if (svr) {
+    for (int64_t j = 0; j < n; ++j) {
+      f[j] = p.svr_epsilon - y[j];
+      f[j + n] = -p.svr_epsilon - y[j];
+    }
+  } else {
+    for (int64_t j = 0; j < n; ++j) f[j] = -Y[j];
+  }
+  SolveResult res;
+  res.world = 1;
+  res.cache_lines = n;
+  res.gram_reused = true;
+  if (oc) {
+    const OneClassStart st = one_class_start(p.one_class_nu, n);
+    for (int64_t i = 0; i < st.full; ++i) alpha[i] = 1.f;
+    if (st.full < n) alpha[st.full] = st.rest;
+    std::vector<double> acc((size_t)n, 0.0);
+    for (int64_t r = 0; r < st.start_rows; ++r) {
+      const double a = alpha[r];
+      const float* row = row_of(r);
+      for (int64_t j = 0; j < n; ++j) acc[j] += a * (double)row[j];
+    }
+    for (int64_t j = 0; j < n; ++j) f[j] = (float)acc[j];
+  }
+  res.t_setup = secs_since(t_setup0);
+
+  auto t0 = Clock::now();
+  int64_t iter = 0;
+  int status = 0;
+  float b_hi = 0.f, b_lo = 0.f;
+  while (true) {
+    uint64_t kh = kKeyNone, kl = kKeyNone;
+    for (int64_t g = 0; g < ns; ++g) {
+      const float a = alpha[g], yj = Y[g], fj = f[g];
+      const bool up = Cr ? in_up_w(a, yj, Cr[g]) : in_up(a, yj, C);
+      const bool low = Cr ? in_low_w(a, yj, Cr[g]) : in_low(a, yj, C);
+      if (up) kh = std::min(kh, make_key(fj, (uint32_t)g));
+      if (low) kl = std::min(kl, make_key(-fj, (uint32_t)g));
+    }
+    if (kh == kKeyNone || kl == kKeyNone) {
+      status = 3;
+      break;
+    }
+    const int64_t i_hi = key_index(kh), i_lo = key_index(kl);
+    b_hi = key_value(kh);
+    b_lo = -key_value(kl);
+    if (!std::isfinite(b_hi) || !std::isfinite(b_lo)) {
+      status = 4;
+      break;
+    }
+    const float* khi = row_of(i_hi);
+    const float* klo = row_of(i_lo);
+    const int64_t r_hi = i_hi >= n ? i_hi - n : i_hi, r_lo = i_lo >= n ? i_lo - n : i_lo;
+    const float k_hl = khi[r_lo], k_hh = khi[r_hi], k_ll = klo[r_lo];
+    const float a_hi_old = alpha[i_hi], a_lo_old = alpha[i_lo];
+    const PairUpdate u = Cr ? pair_update_w(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, k_hh, k_ll,
+                                            Cr[i_hi], Cr[i_lo], p.tau, (int)p.clip, i_hi == i_lo)
+                            : pair_update(a_hi_old, a_lo_old, Y[i_hi], Y[i_lo], b_hi, b_lo, k_hl, k_hh, k_ll, C, p.tau,
+                                          (int)p.clip, i_hi == i_lo);
+    alpha[i_lo] = u.a_lo_new;
+    alpha[i_hi] = u.a_hi_new;  // hi written last: wins if i_hi == i_lo
+    const float ch = u.c_hi, cl = u.c_lo;
+    if (ch != 0.f || cl != 0.f) {
+      for (int64_t j = 0; j < n; ++j) {
+        float delta;
+        if (ch != 0.f && cl != 0.f) delta = (ch * khi[j]) + (cl * klo[j]);
+        else if (ch != 0.f) delta = ch * khi[j];
+        else delta = cl * klo[j];
+        f[j] += delta;
+        if (svr) f[j + n] += delta;
+      }
+    }
+    ++iter;
+    const bool open = gap_open(b_hi, b_lo, p.eps);
+    if (progress && p.log_every > 0 && iter % p.log_every == 0)
+      progress(Progress{iter, b_hi, b_lo, secs_since(t0), 0, 0});
+    if (!open) { status = 1; break; }
+    if (iter >= p.max_iter) { status = 2; break; }
+  }
+  res.t_solve = secs_since(t0);
+  res.iters = iter;
+  res.status = status;
+  res.b_hi = b_hi;
+  res.b_lo = b_lo;
+  res.b = (b_lo + b_hi) / 2.0f;
+  res.alpha = std::move(alpha);
+  res.f = std::move(f);  // the final gradient: f + y - b (classification), f - b (one-class) are the training decisions
+  return res;
+}
+
+std::vector<float> gram_decision_cpu(const float* Kt, int64_t nt, int64_t ld, int64_t n, const float* coef,
+                                     int64_t ldc, int k, const float* b, int threads) {
+  DPSVM_CHECK(nt >= 0 && n >= 0 && k >= 0 && ld >= n && ldc >= n, "gram_decision_cpu: ld >= n, ldc >= n");
+  std::vector<float> out((size_t)nt * k);
+  parallel_for(nt, threads, [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const float* row = Kt + (size_t)i * ld;
+      for (int c = 0; c < k; ++c) {
+        const float* cf = coef + (size_t)c * ldc;
+        double acc = 0.0;
+        for (int64_t j = 0; j < n; ++j) acc += (double)row[j] * (double)cf[j];
+        out[(size_t)i * k + c] = (float)(acc - (double)b[c]);
+      }
+    }
+  });
+  return out;
 }
 
 // ---------------------------------------------------------------------------

@@ -122,6 +122,42 @@ GramWsumProbe gram_rows_wsum_probe(const std::vector<float>& gram, int64_t L, in
   return r;
 }
 
+GramDotProbe gram_rows_dot_probe(const std::vector<float>& Kt, int64_t nt, int64_t ld, int64_t n,
+                                 const std::vector<float>& coef, int64_t ldc, int k, const std::vector<float>& b,
+                                 int reps) {
+  DPSVM_CHECK(nt >= 1 && n >= 1 && k >= 1 && ld >= n && ldc >= n, "gram_rows_dot_probe: nt, n, k >= 1, ld, ldc >= n");
+  DPSVM_CHECK((int64_t)Kt.size() == nt * ld && (int64_t)coef.size() == (int64_t)k * ldc && (int64_t)b.size() == k,
+              "gram_rows_dot_probe: Kt [nt][ld], coef [k][ldc], b [k]");
+  DPSVM_CHECK(reps >= 0, "gram_rows_dot_probe: reps >= 0");
+  Stream st;
+  const float* dk = st.up(Kt, Kt.size());
+  const float* dc = st.up(coef, coef.size());
+  const float* db = st.up(b, b.size());
+  const size_t n_out = (size_t)nt * k + 2 * kGramDotProbePad;
+  float* dout = st.up(std::vector<float>(n_out, kGramDotProbeFill), n_out);
+  HIP_CHECK(hipStreamSynchronize(st.s));  // the fill vector leaves scope
+  GramDotProbe r;
+  if (reps > 0) {
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    for (int i = 0; i < reps; ++i) {
+      HIP_CHECK(hipEventRecord(e0, st.s));
+      launch::gram_rows_dot(dk, nt, ld, n, dc, ldc, k, db, dout + kGramDotProbePad, k, st.s);
+      HIP_CHECK(hipEventRecord(e1, st.s));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      r.us.push_back(1e3f * ms);
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  launch::gram_rows_dot(dk, nt, ld, n, dc, ldc, k, db, dout + kGramDotProbePad, k, st.s);
+  r.out = download(dout, n_out, st.s);
+  return r;
+}
+
 WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int blocks, int p_act, int q_max,
                                   int n_new, float eps, const std::vector<int32_t>& prev_union, int64_t iter,
                                   int64_t max_iter) {
@@ -172,7 +208,9 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
                             const std::vector<float>& y, const std::vector<int32_t>& qb, int q_max, int blocks,
                             int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
                             float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss,
-                            const std::vector<float>& row_C) {
+                            const std::vector<float>& row_C, bool diag) {
+  DPSVM_CHECK(!diag || (blocks == 1 && clip == (int)ClipMode::Box),
+              "ws_solve_probe: diag runs one block with box clipping");
   DPSVM_CHECK(blocks >= 1 && blocks <= kWsMaxBlocks && (int)qb.size() == blocks && q_max >= 2 && q_max <= kWsMax,
               "ws_solve_probe: 1 <= blocks <= 128, qb per block, q_max <= 192");
   const size_t nq = (size_t)blocks * q_max;
@@ -226,6 +264,7 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
   a.max_iter = max_iter;
   a.wss = wss;
   if (!row_C.empty()) a.c_row = st.up(row_C, nq);  // row a of block p is global row p q_max + a
+  a.diag = diag ? 1 : 0;
   a.clip_fallback = 1;
   a.t_halve = 0.9f;
   a.world = 1;

@@ -55,12 +55,190 @@ def _pick(table: dict, value: str, name: str) -> int:
     return table[value]
 
 
+_KERNEL = {"rbf": 0, "precomputed": 1}  # SolverParams.kernel
+
+# what kernel="precomputed" refuses, for every estimator: (the test on the config, what the message names).  The
+# native table is check_kernel (csrc/include/dpsvm/problem.hpp); this one raises before any native state exists.
+_PRECOMPUTED_REFUSED = (
+    (lambda c: c.clip != "box", "clip={c.clip!r} (the general-diagonal kernels run the joint box)"),
+    (lambda c: c.solver == "smo", "solver='smo' (the pair-at-a-time engines)"),
+    (lambda c: c.engines != "production", "engines='all' (the pair-at-a-time engines)"),
+    (lambda c: c.ws_blocks not in (0, 1), "ws_blocks={c.ws_blocks} (multi-block rounds)"),
+    (lambda c: c.force_cache or c.cache_lines or c.host_cache_lines,
+     "the kernel-row cache (force_cache / cache_lines / host_cache_lines)"),
+    (lambda c: c.ws_recompute == "on", "ws_recompute='on' (recompute rounds)"),
+    (lambda c: c.shrink_mode() == "on", "shrink='on'"),
+    (lambda c: c.x_mode == "partitioned", "x_mode='partitioned' (partitioned X)"),
+    (lambda c: c.dp != "auto", "dp={c.dp!r} (a data-parallel policy: multi-rank solves)"),
+    (lambda c: c.exchange == "peer", "exchange='peer' (the peer exchange)"),
+    (lambda c: c.force_collectives, "force_collectives (forced collectives)"),
+    (lambda c: c.checkpoint_path or c.checkpoint_every, "checkpoints (checkpoint_path / checkpoint_every)"),
+)
+
+
+def _refuse_precomputed(cfg, **fit_args) -> None:
+    """kernel="precomputed": raise NotImplementedError for a refused setting or fit argument (comm, resume,
+    rank_rows), naming it"""
+    why = "a precomputed kernel runs one-block working-set rounds on the resident Gram of one rank, with box clipping"
+    for refused, what in _PRECOMPUTED_REFUSED:
+        if refused(cfg):
+            raise NotImplementedError(f"kernel='precomputed': {what.format(c=cfg)} is not implemented ({why})")
+    for name, val in fit_args.items():
+        if val is not None:
+            raise NotImplementedError(f"kernel='precomputed': {name} is not implemented ({why})")
+
+
+def _is_gpu_tensor(a) -> bool:
+    try:
+        import torch
+    except ImportError:
+        return False
+    return isinstance(a, torch.Tensor) and a.is_cuda
+
+
+class _Gram:
+    """The training Gram of a kernel="precomputed" fit: (n, n), symmetric (a precondition: the round kernels read
+    K(i, j) from either triangle; setup checks the diagonal and a fixed sample of 1,024 pairs bitwise).  A torch
+    tensor on the GPU stays there and is handed over by pointer (it must be float32 with unit column stride; a row
+    stride is accepted) on the current torch stream; a numpy array or CPU tensor is uploaded.  The solver copies
+    it into its own lines either way."""
+
+    def __init__(self, K, want_gpu: bool):
+        self.dev = None
+        if _is_gpu_tensor(K) and want_gpu:
+            import torch
+
+            K = K.detach()
+            if K.dtype != torch.float32:
+                raise ValueError(f"a GPU Gram must be float32, got {K.dtype}")
+            if K.dim() != 2 or K.shape[0] != K.shape[1]:
+                raise ValueError(f"K must be square (n, n), got shape {tuple(K.shape)}")
+            if K.stride(1) != 1 or K.stride(0) < K.shape[1]:
+                K = K.contiguous()
+            self.dev = K
+            self.host_ = None
+        else:
+            self.host_ = _as_f32_2d(K)
+            if self.host_.shape[0] != self.host_.shape[1]:
+                raise ValueError(f"K must be square (n, n), got shape {self.host_.shape}")
+        self.n = int((self.dev if self.dev is not None else self.host_).shape[0])
+        if self.n < 2:
+            raise ValueError("K needs at least 2 rows")
+        self.shape = (self.n, self.n)
+
+    def host(self) -> np.ndarray:
+        if self.host_ is None:
+            self.host_ = np.ascontiguousarray(self.dev.cpu().numpy())
+        return self.host_
+
+    def check_host(self) -> None:
+        """the native setup's checks, for the CPU solver: a finite diagonal >= 0, symmetry (here on all pairs)"""
+        K = self.host()
+        dg = np.diagonal(K)
+        if not (np.all(np.isfinite(dg)) and np.all(dg >= 0)):
+            raise ValueError("invalid Gram: the diagonal must be finite and >= 0")
+        if not np.array_equal(K.view(np.uint32), K.T.view(np.uint32)):
+            raise ValueError("invalid Gram: not symmetric (K[i][j] != K[j][i] bitwise)")
+
+    def setup(self, solver, y: np.ndarray) -> dict:
+        """GpuSolver.setup_gram on this Gram"""
+        if self.dev is None:
+            return solver.setup_gram(self.host_, y)
+        import torch
+
+        with torch.cuda.device(self.dev.device):
+            stream = torch.cuda.current_stream().cuda_stream
+        return solver.setup_gram(int(self.dev.data_ptr()), y, self.n, int(self.dev.stride(0)), int(stream))
+
+
+_DOT_CHUNK_BYTES = 256 << 20  # rows of a host K(test, train) uploaded per gram_rows_dot launch
+
+
+def _gram_decision(Kt, coef: np.ndarray, b: np.ndarray, device: tuple, proba=None) -> np.ndarray:
+    """Decisions of a precomputed-kernel model from Kt = K(test, train) (n_test, n_train): (n_test, k) float32,
+    column c = sum_j Kt[i, j] coef[c, j] - b[c] accumulated in fp64 (gram_rows_dot, docs/DESIGN.md §20).  On the
+    GPU a torch tensor there runs straight from its memory, anything else is chunked through the device; on the
+    CPU gram_decision_cpu.  ``proba`` = (A, B): the machines' sigmoids applied before the download (proba_rows)."""
+    C = load()
+    coef = np.ascontiguousarray(coef, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    k, n = coef.shape
+    if not hasattr(Kt, "shape"):
+        Kt = np.asarray(Kt, dtype=np.float32)
+    shape = tuple(Kt.shape)
+    if len(shape) != 2:
+        raise ValueError(f"K(test, train) must be 2-D (n_test, n_train), got shape {shape}")
+    if shape[1] != n:
+        raise ValueError(f"K(test, train) has {shape[1]} columns, the model was trained on {n} rows")
+    nt = shape[0]
+    kind, dev = device
+    if kind != "cuda":
+        out = np.asarray(C.gram_decision_cpu(_as_f32_2d(Kt), coef, b, 0), dtype=np.float32).reshape(nt, k)
+        if proba is not None:
+            out = np.asarray(C.proba_cpu(out, proba[0], proba[1]), dtype=np.float32)
+        return out
+    import torch
+
+    tdev = torch.device("cuda", dev)
+    with torch.cuda.device(tdev):
+        stream = torch.cuda.current_stream().cuda_stream
+        # coef rows padded to a multiple of 4 floats: 16-B loads in the kernel
+        ldc = (n + 3) // 4 * 4
+        cpad = np.zeros((k, ldc), dtype=np.float32)
+        cpad[:, :n] = coef
+        dcoef = torch.from_numpy(cpad).to(tdev)
+        db = torch.from_numpy(b).to(tdev)
+        dA = dB = None
+        if proba is not None:
+            dA = torch.from_numpy(np.ascontiguousarray(proba[0], dtype=np.float64)).to(tdev)
+            dB = torch.from_numpy(np.ascontiguousarray(proba[1], dtype=np.float64)).to(tdev)
+        out = np.empty((nt, k), dtype=np.float32)
+
+        def run(t, row0):
+            m = t.shape[0]
+            dout = torch.empty((m, k), dtype=torch.float32, device=tdev)
+            C.k_gram_rows_dot_device(int(t.data_ptr()), m, int(t.stride(0)), n, int(dcoef.data_ptr()), ldc, k,
+                                     int(db.data_ptr()), int(dout.data_ptr()), k, int(stream))
+            if dA is not None:
+                C.k_proba_rows_device(int(dout.data_ptr()), m, k, int(dA.data_ptr()), int(dB.data_ptr()), int(stream))
+            out[row0:row0 + m] = dout.cpu().numpy()
+
+        if _is_gpu_tensor(Kt) and Kt.device == tdev and Kt.dtype == torch.float32:
+            t = Kt.detach()
+            if nt and (t.stride(1) != 1 or t.stride(0) < n):
+                t = t.contiguous()
+            if nt:
+                run(t, 0)
+        else:
+            Kh = _as_f32_2d(Kt)
+            rows = max(1, _DOT_CHUNK_BYTES // (4 * max(n, 1)))
+            for r0 in range(0, nt, rows):
+                run(torch.from_numpy(Kh[r0:r0 + rows]).to(tdev), r0)
+    return out
+
+
 class _Predicts:
     """The predictor holder of every estimator and loaded model: a device string, the GpuPredictor built on
     first use, one decision path.  A user provides ``_device()`` and ``_native_model()``."""
 
     _gpu = None
     _multi = False  # k one-vs-rest machines: (n, k) decisions
+
+    def _precomputed(self) -> bool:
+        return getattr(getattr(self, "config", None), "kernel", "rbf") == "precomputed"
+
+    def _gram_coef(self):
+        """kernel="precomputed": the dense coefficients (k, n_train) and thresholds (k,) of the fitted machines"""
+        coef = getattr(self, "_coef", None)
+        if coef is None:
+            raise RuntimeError("decision_function needs a fitted estimator")
+        return np.atleast_2d(coef), np.atleast_1d(np.asarray(self.b_, dtype=np.float32))
+
+    def _decision_gram(self, Kt, proba=None) -> np.ndarray:
+        """kernel="precomputed": decisions (or probabilities) from K(test, train): (n,), or (n, k) for k machines"""
+        coef, b = self._gram_coef()
+        out = _gram_decision(Kt, coef, b, _parse_device(self._device()), proba)
+        return out if (self._multi or proba is not None) else out[:, 0]
 
     def _device(self) -> str:
         return self.config.device
@@ -81,7 +259,10 @@ class _Predicts:
         return self._gpu
 
     def _decision(self, X) -> np.ndarray:
-        """sum_sv coef K(sv, x) - b, float32: (n,), or (n, k) for k machines"""
+        """sum_sv coef K(sv, x) - b, float32: (n,), or (n, k) for k machines (kernel="precomputed": X is
+        K(test, train), (n_test, n_train))"""
+        if self._precomputed():
+            return self._decision_gram(X)
         X = _as_f32_2d(X)
         d = getattr(self, "n_features_in_", None)
         if d is not None and X.shape[1] != d:
@@ -160,6 +341,8 @@ class _OneBlockEstimator(_Predicts):
         cfg = self.config
         self._check_extra()
         _parse_device(cfg.device)
+        if cfg.kernel == "precomputed":  # its own table first: it names each setting
+            _refuse_precomputed(cfg)
         for refused, what in _REFUSED:
             if refused(cfg):
                 self._refuse(what.format(c=cfg, clip_why=self._CLIP_WHY))
@@ -174,13 +357,15 @@ class _OneBlockEstimator(_Predicts):
                 self._refuse(name)
 
     def _run(self, X: np.ndarray, y_native: np.ndarray, p, progress, want_gradient: bool):
-        """one solve on the configured device -> alpha, info, the gradient (or None), the setup info"""
+        """one solve on the configured device -> alpha, info, the gradient (or None), the setup info; X: the rows,
+        or the _Gram of a precomputed kernel"""
         C = load()
         kind, dev = self.config.device_kind()
         f = None
+        gram = isinstance(X, _Gram)
         if kind == "cuda":
             solver = C.GpuSolver(p, None, dev)  # dropped after the solve, with its resident Gram
-            setup = solver.setup(X, len(X), y_native)
+            setup = X.setup(solver, y_native) if gram else solver.setup(X, len(X), y_native)
             alpha, info = solver.solve(None, progress)
             if want_gradient:
                 f = solver.gradient()
@@ -188,10 +373,17 @@ class _OneBlockEstimator(_Predicts):
             info = dict(info)
         else:
             setup = {"iteration": "cpu", "engine_note": C.problem_note(p)}
-            alpha, info = C.solve_cpu(X, y_native, p, None, None, progress, None)
+            if gram:
+                X.check_host()
+                setup["kernel"] = "precomputed"
+                setup["engine_note"] = "; ".join(s for s in (C.precomputed_note(), setup["engine_note"]) if s)
+                alpha, info = C.solve_cpu_gram(X.host(), y_native, p, progress, None)
+            else:
+                alpha, info = C.solve_cpu(X, y_native, p, None, None, progress, None)
             info = dict(info)
-            if want_gradient:
-                f = info.pop("f")
+            f = info.pop("f", None)
+            if not want_gradient:
+                f = None
         self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
         return alpha, info, None if f is None else np.asarray(f, dtype=np.float32), setup
 
@@ -199,10 +391,15 @@ class _OneBlockEstimator(_Predicts):
         """the attributes of a fit whose model is sum_i coef_i K(x_i, x) - b; called by fit()"""
         self.setup_info_ = setup
         _publish_solves(self, [info])
-        self.gamma_ = gamma
+        gram = isinstance(X, _Gram)
+        self.gamma_ = None if gram else gamma  # a precomputed kernel has no gamma (and no rows to keep)
         self.n_features_in_ = X.shape[1]
         self.support_ = np.nonzero(coef != 0)[0]
-        self.support_vectors_ = X[self.support_]
+        if gram:
+            X = None
+            self.__dict__.pop("support_vectors_", None)
+        else:
+            self.support_vectors_ = X[self.support_]
         self.dual_coef_ = coef[self.support_].astype(np.float32)
         self.n_support_ = int(len(self.support_))
         self._X_train, self._coef = X, coef
@@ -214,6 +411,9 @@ class _OneBlockEstimator(_Predicts):
 
     def to_model(self):
         """the binary model of coef: alpha = |coef|, y = sign(coef) (rows with coef = 0 are no SVs)"""
+        if self._precomputed():
+            raise NotImplementedError(f"{self._NAME}: kernel='precomputed' has no model file (there are no rows to "
+                                      "write): keep support_, dual_coef_ and intercept_")
         if self._model is None:
             coef = getattr(self, "_coef", None)
             if coef is None:
@@ -228,5 +428,7 @@ class _OneBlockEstimator(_Predicts):
 
     def get_params(self, deep: bool = True) -> dict:
         out = dataclasses.asdict(self.config)
+        if self.config.kernel != "rbf":  # init-only (SVCConfig): reported when it is not the default
+            out["kernel"] = self.config.kernel
         out[self._EXTRA] = getattr(self, self._EXTRA)
         return out

@@ -23,7 +23,7 @@ from typing import Any, Callable, Optional, Sequence
 import numpy as np
 
 from .._native import load
-from ._base import _OneBlockEstimator, _as_f32_2d
+from ._base import _Gram, _OneBlockEstimator, _as_f32_2d
 from .svc import LoadedModel
 
 
@@ -94,7 +94,8 @@ class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
         """Train on the rows of ``X`` (``y`` is ignored).  One rank, from the nu start, unweighted."""
         self._refuse_fit_args(comm, resume, rank_rows, sample_weight)
         self._resolve()
-        X = _as_f32_2d(X)
+        # kernel="precomputed": X is the (n, n) Gram; decision_function() then takes K(test, train)
+        X = _Gram(X, self.config.device_kind()[0] == "cuda") if self._precomputed() else _as_f32_2d(X)
         n, d = X.shape
         p = self._params(d)
         t0 = time.perf_counter()
@@ -115,7 +116,8 @@ class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
         nus = [_check_nu(v) for v in nus]
         if not nus:
             raise ValueError("nu_path needs at least one nu")
-        X = _as_f32_2d(X)
+        gram = self._precomputed()
+        X = _Gram(X, self.config.device_kind()[0] == "cuda") if gram else _as_f32_2d(X)
         n, d = X.shape
         C = load()
         ones = np.ones(n, dtype=np.float32)
@@ -124,7 +126,9 @@ class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
         solver = None
         if kind == "cuda":
             solver = C.GpuSolver(self._params(d, nus[0]), None, dev)
-            self.path_setup_info_ = solver.setup(X, n, ones)
+            self.path_setup_info_ = X.setup(solver, ones) if gram else solver.setup(X, n, ones)
+        elif gram:
+            X.check_host()
         for i, nu in enumerate(nus):
             if solver is not None:
                 if i > 0:
@@ -133,7 +137,10 @@ class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
                 info = dict(info)
                 f = np.asarray(solver.gradient(), dtype=np.float64)
             else:
-                alpha, info = C.solve_cpu(X, ones, self._params(d, nu), None, None, progress, None)
+                if gram:
+                    alpha, info = C.solve_cpu_gram(X.host(), ones, self._params(d, nu), progress, None)
+                else:
+                    alpha, info = C.solve_cpu(X, ones, self._params(d, nu), None, None, progress, None)
                 info = dict(info)
                 f = np.asarray(info.pop("f"), dtype=np.float64)
             alpha = np.asarray(alpha, dtype=np.float32)

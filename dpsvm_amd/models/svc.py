@@ -21,7 +21,8 @@ from typing import Any, Callable, Optional
 import numpy as np
 
 from .._native import load, load_quarantine
-from ._base import _Predicts, _as_1d, _as_f32_2d, _parse_device, _pick, _publish_solves  # noqa: F401 (re-exported)
+from ._base import (_Gram, _KERNEL, _Predicts, _as_1d, _as_f32_2d, _parse_device, _pick,  # noqa: F401 (re-exported)
+                    _publish_solves, _refuse_precomputed)
 
 
 _CLIP = {"independent": 0, "box": 1}
@@ -186,6 +187,17 @@ class SVCConfig:
     # each machine's two sides) | {label: weight} (missing labels 1).  Multiplied by fit(sample_weight=).  Any
     # weights run the working-set engines on one rank (solver auto -> ws, shrink / ws_recompute auto -> off)
     class_weight: Any = None
+    # "rbf" (gamma; fit takes X) | "precomputed" (LIBSVM -t 4): fit takes the (n, n) Gram of any kernel and never X,
+    # decision_function K(test, train); gamma is ignored.  One-block working-set rounds on the resident Gram of one
+    # rank with box clipping (general-diagonal sub-problem kernels, docs/DESIGN.md §20); settings resolve as for a
+    # weighted fit plus ws_blocks=1, the rest is refused (README "Precomputed kernels").  Init-only: it is no
+    # solver knob but what fit() and decision_function() take, so it stays off dataclasses.fields(), the list of
+    # settings that map one to one onto SolverParams (get_params() reports it when it is not "rbf")
+    kernel: dataclasses.InitVar[str] = "rbf"
+
+    def __post_init__(self, kernel: str = "rbf"):
+        _pick(_KERNEL, kernel, "kernel")
+        self.kernel = kernel
 
     def shrink_mode(self) -> str:
         s = self.shrink
@@ -216,6 +228,10 @@ class SVCConfig:
         p.dp_policy = _pick(_DP, self.dp, "dp")
         p.gram_precision = _pick(_GRAM, self.gram, "gram")
         p.ws_clip_fallback = int(bool(self.ws_clip_fallback))
+        p.kernel = _pick(_KERNEL, self.kernel, "kernel")
+        if p.kernel:
+            _refuse_precomputed(self)
+            p.solver, p.ws_recompute, p.ws_blocks = 2, 2, 1
         return p
 
     def weighted_params(self, p, comm=None, resume=None, rank_rows=None) -> str:
@@ -278,7 +294,11 @@ class SVC(_Predicts):
 
     def __init__(self, C: float = 1.0, gamma: Optional[float] = None, eps: float = 1e-3,
                  max_iter: int = 150000, device: str = "auto", **kwargs: Any):
+        if kwargs.get("kernel", "rbf") == "precomputed":
+            kwargs.setdefault("clip", "box")
         self.config = SVCConfig(C=C, gamma=gamma, eps=eps, max_iter=max_iter, device=device, **kwargs)
+        if self.config.kernel == "precomputed":
+            _refuse_precomputed(self.config)
         self._model = None
         self._multi = False
         self.classes_ = np.array([-1.0, 1.0], dtype=np.float32)
@@ -391,7 +411,9 @@ class SVC(_Predicts):
         ck = C.read_checkpoint(resume) if isinstance(resume, str) else resume
         kind, dev = self.config.device_kind()
         alphas, infos, setup, solver = [], [], None, None
-        if kind == "cuda" and rank_rows is None and RC is None and self._use_shrink(p, n, X.shape[1], dev, comm):
+        gram = isinstance(X, _Gram)  # kernel="precomputed": no X, the solves run on the caller's Gram
+        if (kind == "cuda" and rank_rows is None and RC is None and not gram
+                and self._use_shrink(p, n, X.shape[1], dev, comm)):
             for c in range(m):  # ShrinkingSolver has no label swap: one per machine
                 shr = C.ShrinkingSolver(p, comm, dev)
                 s = shr.setup(X, Ys[c])  # the whole-problem phases' solver; iteration "ws+shrinking"
@@ -405,7 +427,7 @@ class SVC(_Predicts):
                 del shr
         elif kind == "cuda":
             solver = C.GpuSolver(p, comm, dev)
-            setup = solver.setup(X, n, Ys[0])
+            setup = X.setup(solver, Ys[0]) if gram else solver.setup(X, n, Ys[0])
             if note:
                 en = setup.get("engine_note", "")
                 setup["engine_note"] = (en + "; " if en else "") + note
@@ -422,10 +444,21 @@ class SVC(_Predicts):
         else:
             if rank_rows is not None:
                 raise ValueError("partitioned X needs the GPU solver")
+            if gram:
+                X.check_host()
+                setup = {"iteration": "cpu", "kernel": "precomputed", "engine_note": C.precomputed_note()}
             for c in range(m):
-                a, info = C.solve_cpu(X, Ys[lab[c]], p, comm, ck, progress, None if RC is None else RC[c])
+                rc = None if RC is None else RC[c]
+                if gram:
+                    a, info = C.solve_cpu_gram(X.host(), Ys[lab[c]], p, progress, rc)
+                else:
+                    a, info = C.solve_cpu(X, Ys[lab[c]], p, comm, ck, progress, rc)
+                info = dict(info)
+                if hook is not None and gram:
+                    hook(c, None, info)
+                info.pop("f", None)
                 alphas.append(a)
-                infos.append(dict(info))
+                infos.append(info)
         return alphas, infos, setup, solver if keep else None
 
     def _cv_solves(self, X: np.ndarray, Ys: np.ndarray, W: Optional[np.ndarray], p, cv: int, seed: int,
@@ -461,8 +494,14 @@ class SVC(_Predicts):
         platt = [None] * k
         on_device = []
 
+        sink = getattr(self, "_grad_sink", None)  # kernel="precomputed": the full-data solves' gradients
+
         def hook(i, solver, info):  # cold solves (alpha = 0, f = -y): the gradient is the whole decision
             c, j = role[i]
+            if j < 0 and sink is not None:
+                sink[c] = np.asarray(solver.gradient() if solver is not None else info["f"], dtype=np.float32)
+            if solver is None:  # (the CPU solver on a precomputed Gram: only the gradient sink)
+                return
             if j >= 0:
                 solver.holdout_decisions(rows[j], float(info["b"]), c)
             if i + 1 == len(role) or role[i + 1][0] != c:  # machine c's last solve: its labels are still current
@@ -475,7 +514,12 @@ class SVC(_Predicts):
                                                             keep=keep, lab=lab)
         if not on_device:
             for i, (c, j) in enumerate(role):
-                if j >= 0:
+                if j >= 0 and isinstance(X, _Gram):  # the held-out rows of K against the fold's coefficients
+                    coef = (np.asarray(alphas[i], dtype=np.float32) * Ys[c])[None, :]
+                    Kf = np.ascontiguousarray(X.host()[folds[j]])
+                    dec[c, folds[j]] = C.gram_decision_cpu(Kf, coef, np.array([infos[i]["b"]], dtype=np.float32),
+                                                           0)[:, 0]
+                elif j >= 0:
                     model = C.make_model(X, Ys[c], alphas[i], float(infos[i]["b"]), p.gamma)
                     dec[c, folds[j]] = C.decision_cpu(model, np.ascontiguousarray(X[folds[j]]), 0)
             if full is not None:
@@ -494,8 +538,13 @@ class SVC(_Predicts):
         probability results (None without)."""
         p, RC, note = self._problem(X.shape[1], y, Ys, sample_weight, comm, resume, rank_rows)
         if not probability:
+            sink = getattr(self, "_grad_sink", None)  # kernel="precomputed": machine c's gradient after its solve
+            hook = None
+            if sink is not None:
+                def hook(c, solver, info):  # noqa: E306
+                    sink[c] = np.asarray(solver.gradient() if solver is not None else info["f"], dtype=np.float32)
             alphas, infos, setup, solver = self._solve_machines(X, Ys, RC, p, note, comm, resume, progress,
-                                                                rank_rows, keep=keep)
+                                                                rank_rows, hook=hook, keep=keep)
             return p, RC, alphas, infos, setup, solver, None
         if RC is None:  # resolved as a weighted fit; the full-data solves keep the scalar C
             note = self.config.weighted_params(p, comm, resume, rank_rows)
@@ -542,6 +591,9 @@ class SVC(_Predicts):
         probability = int(probability)
         if probability != 0 and probability < 2:
             raise ValueError(f"probability is the number of folds: 0 (off) or >= 2, got {probability}")
+        if self.config.kernel == "precomputed":
+            return self._fit_gram(X, y, comm, resume, progress, rank_rows, sample_weight, probability,
+                                  probability_seed)
         if self.config.engines == "all" or self.config.host_cache_lines or self.config.cache_engine == "chain":
             load_quarantine()  # the quarantined pair-at-a-time cache engines (plugin)
         X = _as_f32_2d(X)
@@ -583,6 +635,63 @@ class SVC(_Predicts):
             self.support_vectors_ = X[self.support_]
             self.dual_coef_ = (alpha[self.support_] * ys[self.support_]).astype(np.float32)
             self.n_support_ = int(len(self.support_))
+        return self
+
+    def _fit_gram(self, K, y, comm, resume, progress, rank_rows, sample_weight, probability: int,
+                  probability_seed: int) -> "SVC":
+        """kernel="precomputed": fit on the (n, n) Gram K of any kernel (symmetric; a GPU torch tensor is passed by
+        pointer, anything else uploaded).  Binary and one-vs-rest fits, weights and probability folds all run on
+        one GpuSolver and its one copy of K (``setup_gram``, then k solves with ``set_labels`` / ``set_row_C``).
+        There are no rows to keep: ``support_``, ``dual_coef_``, ``alpha_``, ``b_`` / ``intercept_`` and
+        ``probA_`` / ``probB_`` are the model, ``gamma_`` is None, and prediction takes K(test, train)."""
+        _refuse_precomputed(self.config, comm=comm, resume=resume, rank_rows=rank_rows)
+        G = _Gram(K, self.config.device_kind()[0] == "cuda")
+        y1 = _as_1d(y)
+        n = G.n
+        if y1.shape[0] != n:
+            raise ValueError("len(y) != K.shape[0]")
+        classes = np.unique(y1)
+        multi = len(classes) > 2
+        if multi:
+            Ys = np.stack([np.where(y1 == c, 1.0, -1.0).astype(np.float32) for c in classes])
+        else:
+            Ys = self._encode(y)[None, :]
+        self._grad_sink = [None] * len(Ys)
+        t0 = time.perf_counter()
+        try:
+            p, RC, alphas, infos, setup, _, proba = self._fit_solves(
+                G, y1, Ys, sample_weight, probability, probability_seed, None, None, progress, None, keep=False)
+            grads = self._grad_sink
+        finally:
+            self._grad_sink = None
+        self._solver = None  # dropped with its copy of the Gram: every later call reads K(test, train)
+        self._publish(p, n, time.perf_counter() - t0, setup)
+        self.gamma_ = None
+        self._multi = multi
+        self._publish_proba(proba)
+        if multi:
+            self.classes_ = classes
+        A = np.stack(alphas).astype(np.float32)
+        _publish_solves(self, infos, multi=multi)
+        self.alpha_ = A if multi else A[0]
+        self.row_C_ = RC if (multi or RC is None) else RC[0]
+        bound = RC if RC is not None else np.float32(self.config.C)
+        self.n_bounded_ = int(np.sum((A == bound) & (A > 0)))
+        if any(i["status"] == 2 for i in infos):
+            import warnings
+
+            warnings.warn("stopped at max_iter before the gap closed: raise max_iter to converge", RuntimeWarning,
+                          stacklevel=3)
+        self._X_train, self._y_train, self._Ys = None, (y1 if multi else Ys[0]), Ys
+        self._coef = (A * Ys).astype(np.float32)  # (k, n): the dense coefficients gram_rows_dot reads
+        self.support_ = np.nonzero((A > 0).any(axis=0))[0]
+        self.__dict__.pop("support_vectors_", None)
+        self.dual_coef_ = self._coef[:, self.support_] if multi else self._coef[0, self.support_]
+        self.n_support_ = int(len(self.support_))
+        # the training decisions f + y - b from the solver's gradient (no predict pass): train_accuracy()
+        b = np.atleast_1d(np.asarray(self.b_, dtype=np.float64))
+        self._train_dec = np.stack([(grads[c].astype(np.float64) + Ys[c] - b[c]).astype(np.float32)
+                                    for c in range(len(Ys))])
         return self
 
     def _publish(self, p, d: int, wall: float, setup) -> None:
@@ -649,8 +758,9 @@ class SVC(_Predicts):
         entry f_i = sum_j alpha_j y_j K_ij - y_i is kept by every round's f update, so its decision value is
         f_i + y_i - b, read from the solver's gradient — no sub-Gram, no second upload, no predict pass.
         Folds: ``cv_folds(n, cv, seed)``.  ``class_weight='balanced'`` is computed on all n rows.  Settings
-        resolve as for a weighted fit.  ``cv_stats_``: the per-fold solve dicts."""
-        X = _as_f32_2d(X)
+        resolve as for a weighted fit.  ``cv_stats_``: the per-fold solve dicts.  kernel="precomputed": X is the
+        (n, n) Gram, uploaded once for the ``cv`` solves."""
+        X = _Gram(X, self.config.device_kind()[0] == "cuda") if self._precomputed() else _as_f32_2d(X)
         y1 = _as_1d(y)
         if len(np.unique(y1)) != 2:
             raise ValueError("cross_val_decision is binary: y needs two classes")
@@ -679,6 +789,9 @@ class SVC(_Predicts):
     # ------------------------------------------------------------------ model
     def to_model(self):
         C = load()
+        if self._precomputed():
+            raise NotImplementedError("kernel='precomputed' has no model file (there are no rows to write): keep "
+                                      "support_, dual_coef_, intercept_ and probA_ / probB_")
         if self._model is None and self._multi:
             try:
                 cls = np.asarray(self.classes_, dtype=np.float32)
@@ -727,6 +840,12 @@ class SVC(_Predicts):
         value; two classes: [1 - p, p] with p = P(classes_[-1]); more: the k values divided by their sum (a row
         whose sum is 0: 1 / k each).  On the GPU the sigmoids run on the decision GEMM's output before its
         download.  ``predict`` stays the sign / the argmax of the decision values."""
+        if self._precomputed():  # X is K(test, train): the sigmoids on gram_rows_dot's output before the download
+            if getattr(self, "probA_", None) is None:
+                raise RuntimeError("predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
+            p = self._decision_gram(X, (np.atleast_1d(np.asarray(self.probA_, dtype=np.float64)),
+                                        np.atleast_1d(np.asarray(self.probB_, dtype=np.float64))))
+            return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
         X = _as_f32_2d(X)
         if X.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X.shape[1]} features, model has {self.n_features_in_}")
@@ -739,7 +858,13 @@ class SVC(_Predicts):
         return float(np.mean(self.predict(X) == yy))
 
     def train_accuracy(self) -> float:
-        """Training accuracy computed on device (distributed across ranks)."""
+        """Training accuracy computed on device (distributed across ranks); kernel="precomputed": from the
+        solver's gradient, sign(f + y - b) per machine."""
+        if self._precomputed():
+            dec = self._train_dec
+            if self._multi:
+                return float(np.mean(self.classes_[np.argmax(dec, axis=0)] == self._y_train))
+            return float(np.mean(np.where(dec[0] < 0, -1.0, 1.0) == self._y_train))
         if self._multi:
             return self.score(self._X_train, self._y_train)  # the multi-output predictor
         if getattr(self, "_solver", None) is not None:
@@ -747,7 +872,10 @@ class SVC(_Predicts):
         return self.score(self._X_train, self._y_train)
 
     def get_params(self, deep: bool = True) -> dict:
-        return dataclasses.asdict(self.config)
+        out = dataclasses.asdict(self.config)
+        if self.config.kernel != "rbf":  # init-only (SVCConfig): reported when it is not the default
+            out["kernel"] = self.config.kernel
+        return out
 
 
 class _Loaded(_Predicts):

@@ -22,7 +22,7 @@ from typing import Any, Callable, Optional
 import numpy as np
 
 from .._native import load
-from ._base import _OneBlockEstimator, _as_1d, _as_f32_2d
+from ._base import _Gram, _OneBlockEstimator, _as_1d, _as_f32_2d
 from .svc import LoadedModel
 
 
@@ -73,7 +73,8 @@ class SVR(_OneBlockEstimator):
         """Train on real-valued targets ``z``.  One rank, from a cold start, unweighted."""
         self._refuse_fit_args(comm, resume, rank_rows, sample_weight)
         self._resolve()
-        X = _as_f32_2d(X)
+        # kernel="precomputed": X is the (n, n) Gram; predict() then takes K(test, train)
+        X = _Gram(X, self.config.device_kind()[0] == "cuda") if self._precomputed() else _as_f32_2d(X)
         z = np.ascontiguousarray(_as_1d(z), dtype=np.float32)
         n, d = X.shape
         if z.shape[0] != n:

@@ -249,14 +249,15 @@ def ws_merge_multi(cand, blocks: int, q_max: int, n_new: int, eps: float, prev_u
 def ws_solve(K, f, alpha, y, qb, q_max: int, C_: float, clip: str = "independent", eps: float = 1e-3,
              rel: float = 0.3, eps_floor: float = 3e-4, tau: float = 1e-12, b_hi: float = 0.0, b_lo: float = 0.0,
              inner_max: int = 768, p_round: int | None = None, iteration: int = 0, max_iter: int = 1 << 40,
-             wss: int = 1, row_C=None) -> dict:
+             wss: int = 1, row_C=None, diag: bool = False) -> dict:
     """One launch of the sub-problem solver (ws_solve_kernel): P = len(qb)
     blocks, block p with qb[p] rows, sub-Gram K[p] ([q_max][q_max]) and f /
     alpha / y [p][q_max]; b_hi / b_lo = the round's global selection (the local
     tolerance is max(eps_floor, rel (b_lo - b_hi) / 2)).  P > 1 runs the
     multi-block kernel (p_round active blocks share max_iter).  wss: 1 the
     reference's first-order pair choice, 2 second order (WSS2).  row_C: per-row
-    bounds C_i [p][q_max] (None: the scalar C_; the kRowC instantiations)."""
+    bounds C_i [p][q_max] (None: the scalar C_; the kRowC instantiations).  diag: the general-diagonal kernels
+    (kDiag: eta = K(hi,hi) + K(lo,lo) - 2 K(hi,lo) from the sub-Gram's own diagonal; one block, box clipping)."""
     import numpy as np
 
     P = len(qb)
@@ -265,7 +266,28 @@ def ws_solve(K, f, alpha, y, qb, q_max: int, C_: float, clip: str = "independent
                              P if p_round is None else p_round, float(C_), 1 if clip == "box" else 0, float(eps),
                              float(rel), float(eps_floor), float(tau), float(b_hi), float(b_lo), int(inner_max),
                              int(iteration), int(max_iter), int(wss),
-                             row_C=None if row_C is None else f32(row_C))
+                             row_C=None if row_C is None else f32(row_C), diag=bool(diag))
+
+
+def gram_rows_dot(Kt, n: int, coef, b, reps: int = 0) -> dict:
+    """Decisions from a rectangular Gram accumulated in fp64 and rounded once (gram_dot.hip):
+    out[i, c] = float(sum_{j < n} Kt[i, j] coef[c, j] - b[c]) on ``Kt`` [nt][ld >= n] and ``coef`` [k][ldc >= n]
+    (the columns from n on are padding the kernel must not read).  Returns ``out`` (nt, k), ``pad`` (the
+    sentinel-filled floats in front of and behind out on the device, as they came back), ``fill`` (what they held
+    before the launch) and, for reps > 0, ``us``: the event times of reps launches before the returned one."""
+    import numpy as np
+
+    kt = np.ascontiguousarray(np.asarray(Kt, dtype=np.float32))
+    cf = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
+    bb = np.ascontiguousarray(np.asarray(b, dtype=np.float32)).reshape(-1)
+    if kt.ndim != 2 or cf.ndim != 2 or cf.shape[0] != bb.shape[0]:
+        raise ValueError("Kt must be (nt, ld), coef (k, ldc), b (k,)")
+    nt, k = kt.shape[0], cf.shape[0]
+    r = load().k_gram_rows_dot(kt.reshape(-1), nt, kt.shape[1], int(n), cf.reshape(-1), cf.shape[1], k, bb,
+                               reps=int(reps))
+    raw, pad = np.asarray(r["out"]), int(r["pad"])
+    return {"out": raw[pad:pad + nt * k].reshape(nt, k).copy(),
+            "pad": np.concatenate([raw[:pad], raw[pad + nt * k:]]), "fill": float(r["fill"]), "us": list(r["us"])}
 
 
 def ws_select(gram, f, alpha, y, dalpha, apply_lines, apply_coef, nab, C_: float, q_max: int = 192,

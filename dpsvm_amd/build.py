@@ -68,6 +68,8 @@ LIB_SOURCES = [
     "kernels/platt.hip",
     "kernels/gram_wsum.hip",
     "kernels/gram_dot.hip",
+    "kernels/dot_gemm_split.hip",
+    "solver/dot_kernel_cpu.cpp",
 ]
 # the quarantined engines (solver/gpu_engines_pairq.hip registers them): a plugin
 # library for the Python module, linked into the CLIs (svmTrain --engines all)

@@ -58,6 +58,9 @@ int main(int argc, char** argv) {
                                    : make_synthetic(synth_from_name(synthetic), num_ex, num_att, seed);
     std::cout << "Populated test data\n";
     Model m = read_model(model, legacy);
+    if (m.kernel != "rbf")
+      fail("model " + model + " has the '" + m.kernel + "' kernel: svmTest predicts RBF models (load it with the "
+           "Python package's load_model)");
     if (m.nsv() > 0 && m.d != num_att)
       fail("model has " + std::to_string(m.d) + " features, -a says " + std::to_string(num_att));
     m.d = num_att;

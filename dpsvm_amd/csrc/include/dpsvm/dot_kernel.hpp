@@ -1,0 +1,52 @@
+// The named kernels that are functions of the dot product alone (LIBSVM -t 0 / 1 / 3), docs/DESIGN.md §21:
+//   linear   K = a.b
+//   poly     K = (gamma a.b + coef0)^degree
+//   sigmoid  K = tanh(gamma a.b + coef0)
+// ONE scalar formula in fp32 for the device Gram builder (kernels/dot_gemm_split.hip) and the CPU one
+// (solver/dot_kernel_cpu.cpp): the two differ through the rounding of the dot product they are handed (and, for the
+// sigmoid, through the two tanhf implementations), never through the formula.  The value is a function of the
+// BITS of `dot`, so a builder whose dot products are symmetric bit for bit stores a bitwise symmetric Gram.
+#pragma once
+
+#include <cmath>
+
+#include "dpsvm/common.hpp"
+
+namespace dpsvm {
+
+enum class DotKind : int { Linear = 0, Poly = 1, Sigmoid = 2 };
+constexpr int kDotMaxDegree = 32;
+
+struct DotKernelSpec {
+  DotKind kind = DotKind::Linear;
+  int degree = 1;      // poly only, 1 .. kDotMaxDegree
+  float coef0 = 0.f;   // poly and sigmoid
+};
+
+inline const char* dot_kind_name(DotKind k) {
+  return k == DotKind::Linear ? "linear" : k == DotKind::Poly ? "poly" : "sigmoid";
+}
+
+// u^degree by square-and-multiply in fp32: LIBSVM's powi, its multiplications in its order
+DPSVM_HD float dot_powi(float u, int degree) {
+  float tmp = u, ret = 1.f;
+  for (int t = degree; t > 0; t /= 2) {
+    if (t % 2 == 1) ret *= tmp;
+    tmp = tmp * tmp;
+  }
+  return ret;
+}
+
+// K from the fp32 dot product.  KF: the DotKind as an int (a template argument of the device kernel)
+template <int KF>
+DPSVM_HD float dot_kernel_value(float dot, float gamma, float coef0, int degree) {
+  if constexpr (KF == (int)DotKind::Linear) {
+    return dot;
+  } else {
+    const float u = __builtin_fmaf(gamma, dot, coef0);
+    if constexpr (KF == (int)DotKind::Sigmoid) return tanhf(u);
+    else return dot_powi(u, degree);
+  }
+}
+
+}  // namespace dpsvm

@@ -32,7 +32,14 @@ void write_csv(const std::string& path, const Dataset& ds);
 // Sparse LIBSVM text ("+1 3:1 11:1 ...") -> dense, feature k (1-based) -> column k-1.
 Dataset read_libsvm(const std::string& path, int d, int64_t n = 0);
 
+// kernel / degree / coef0 of Model and MultiModel: "rbf" (gamma; degree and coef0 unused), or a dot-product kernel
+// (dpsvm/dot_kernel.hpp) "linear" | "poly" | "sigmoid" on the same gamma.  The model files carry one leading line
+// "dpsvm-kernel <name> <degree> <coef0>" for a kernel other than "rbf" and nothing for "rbf" (those files are
+// unchanged); a reader fails on a name it does not know.
 struct Model {
+  std::string kernel = "rbf";
+  int degree = 0;
+  float coef0 = 0.f;
   float gamma = 0.f;
   float b = 0.f;
   int d = 0;
@@ -54,6 +61,9 @@ Model read_model(const std::string& path, bool force_legacy = false);
 // rest) with one gamma on the union of their support vectors.
 //   decision[i][c] = sum_s coef[s][c] K(x_s, x_i) - b[c]
 struct MultiModel {
+  std::string kernel = "rbf";  // as Model's
+  int degree = 0;
+  float coef0 = 0.f;
   float gamma = 0.f;
   int d = 0;
   std::vector<float> classes;  // k class labels
@@ -71,7 +81,7 @@ MultiModel make_multi_model(const Dataset& ds, const std::vector<float>& classes
 // coefficients and d features; numbers comma-separated, `precision` as write_model.
 void write_multi_model(const std::string& path, const MultiModel& m, int precision = 9);
 MultiModel read_multi_model(const std::string& path);
-// true when the file starts with the multi-class header
+// true when the file starts with the multi-class header (after a "dpsvm-kernel" line, if any)
 bool is_multi_model(const std::string& path);
 
 // Deterministic synthetic generators (identical on every rank; row-seeded so a

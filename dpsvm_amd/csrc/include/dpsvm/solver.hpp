@@ -12,6 +12,7 @@
 
 #include "dpsvm/comm.hpp"
 #include "dpsvm/common.hpp"
+#include "dpsvm/dot_kernel.hpp"
 #include "dpsvm/io.hpp"
 
 namespace dpsvm {
@@ -63,6 +64,12 @@ SolveResult solve_cpu_gram(const float* K, int64_t ld, int64_t n, const float* y
 std::vector<float> gram_decision_cpu(const float* Kt, int64_t nt, int64_t ld, int64_t n, const float* coef,
                                      int64_t ldc, int k, const float* b, int threads = 0);
 
+// The Gram of a dot-product kernel on the host (dot_kernel_cpu.cpp): out[i n + j] = k(X_i . Y_j), X [m][d],
+// Y [n][d]; the dot in fp64 rounded once to fp32, then dot_kernel_value.  Y == nullptr: the symmetric m x m Gram of
+// X (j >= i computed and mirrored: bitwise symmetric).  threads <= 0: default_threads().
+std::vector<float> kernel_gram_cpu(const float* X, int64_t m, const float* Y, int64_t n, int d,
+                                   const DotKernelSpec& spec, float gamma, int threads = 0);
+
 // Decision values d(x) = sum_sv alpha y K(sv,x) - b  (svmTrain.cu:646-658)
 std::vector<float> decision_cpu(const Model& m, const float* x, int64_t n, int d, int threads = 0);
 // One-vs-rest decision values [n][k]: column c = sum_sv coef[sv][c] K(sv, x) - b[c] (k passes of decision_cpu)
@@ -109,6 +116,7 @@ struct GpuSetupInfo {
   int ws_blocks = 0, ws_q_max = 0;     // working-set rounds: blocks per round x rows per block (the union)
   std::string gram = "f32";           // Gram / kernel-row GEMM arithmetic: "f32" or "split-f16" (rbf_gemm_split.hip)
   std::string kernel = "rbf";         // "rbf" | "precomputed" (setup_gram: gram reads "precomputed" too)
+  double t_gram_build = 0.0;          // setup_rows_gram: seconds of the Gram build on the device (event-timed)
 };
 
 // true once the pair-cache plugin (libdpsvm_pairq.so, or the CLIs that link it)
@@ -133,6 +141,14 @@ class GpuSolver {
   // solve that finds it invalidated (after a failed solve) asks for setup_gram again.  y as setup's.
   GpuSetupInfo setup_gram(const float* K, int64_t ld, int64_t n, const float* y, bool on_device = false,
                           void* stream = nullptr);
+  // A dot-product kernel (linear, poly, sigmoid) on the rows x [n][ldx >= d] (host, or on_device as setup_gram's
+  // K): setup_gram with the 2-D copy replaced by the Gram builder — X is uploaded to a temporary, split
+  // (split_rows_f16) and multiplied by the symmetric dot GEMM (dot_gemm_split.hip) straight into the solver's
+  // lines; the temporaries are freed before it returns, so the peak is one Gram plus X and its split rows.  gamma
+  // is read from the solver's params before they resolve as a precomputed kernel's.  Everything after it is a
+  // precomputed solve (same resolutions, refusals, checks and messages); info.t_gram_build holds the build time.
+  GpuSetupInfo setup_rows_gram(const float* x, int64_t n, int d, const float* y, const DotKernelSpec& spec,
+                               bool on_device = false, void* stream = nullptr, int64_t ldx = 0);
   SolveResult solve(const Checkpoint* resume = nullptr, const ProgressFn& progress = {});
   // After solve(): distributed training accuracy (each rank predicts its shard)
   double train_accuracy(const SolveResult& r);
@@ -184,6 +200,9 @@ class GpuSolver {
   struct Impl;
 
  private:
+  // what setup_gram and setup_rows_gram share before and after the Gram reaches the lines
+  void gram_setup_begin(int64_t n, const float* y, bool on_device, void* stream);
+  void gram_setup_finish(int64_t n);
   std::unique_ptr<Impl> impl_;
 };
 
@@ -289,6 +308,12 @@ std::vector<float> rbf_rows_indexed_split_bench(const float* x, const float* xsq
 void rbf_gram_split(const float* a, const float* asq, int64_t m, const float* b, const float* bsq, int64_t n, int ld,
                     float gamma, float* out, int64_t out_ld, bool symmetric, void* stream,
                     float cold_tau = 0.f);
+// the Gram of a dot-product kernel (dot_gemm_split.hip) from f32 device rows a [m][lda >= d], b [n][ldb >= d] (split
+// here, into stream-ordered temporaries); symmetric: b unused, n = m, out_ld % 4 == 0.  Columns >= n of out are not
+// written.  reps > 0: the event times (us) of reps launches of the GEMM before the returned one.
+std::vector<float> dot_gram_split(const float* a, int64_t m, const float* b, int64_t n, int d, int lda, int ldb,
+                                  const DotKernelSpec& spec, float gamma, float* out, int64_t out_ld, bool symmetric,
+                                  void* stream, int reps = 0);
 // the adaptive Gram of the calling thread's last rbf_gram_split / solve: (one-product tiles, hot tiles) or (-1, -1)
 std::pair<int64_t, int64_t> gram_adapt_last();
 void xpass_rows(const float* x, const float* xsq, int64_t n, int ld, const int* keys, int nq, float gamma,

@@ -15,6 +15,38 @@
 
 namespace dpsvm {
 
+namespace {
+const char* const kKernelMagic = "dpsvm-kernel";
+
+// the leading "dpsvm-kernel <name> <degree> <coef0>" line of a model whose kernel is not "rbf"
+void write_kernel_line(FILE* fp, const std::string& kernel, int degree, float coef0) {
+  if (kernel == "rbf") return;
+  if (kernel != "linear" && kernel != "poly" && kernel != "sigmoid")
+    fail("model: unknown kernel '" + kernel + "' (rbf, linear, poly or sigmoid)");
+  fprintf(fp, "%s %s %d %.9g\n", kKernelMagic, kernel.c_str(), degree, (double)coef0);
+}
+
+// `line`: the file's first line.  A kernel line is parsed into kernel / degree / coef0 and replaced by the line
+// after it; any other line is left alone (an RBF model)
+void read_kernel_line(std::ifstream& in, std::string& line, const std::string& path, std::string& kernel,
+                      int& degree, float& coef0) {
+  if (line.rfind(kKernelMagic, 0) != 0) return;
+  std::istringstream hs(line.substr(std::string(kKernelMagic).size()));
+  std::string name;
+  long long deg = 0;
+  double c0 = 0.0;
+  if (!(hs >> name >> deg >> c0)) fail("model file " + path + ": bad kernel line: " + line.substr(0, 80));
+  if (name != "rbf" && name != "linear" && name != "poly" && name != "sigmoid")
+    fail("model file " + path + ": unknown kernel '" + name + "' (this build reads rbf, linear, poly and sigmoid)");
+  if (name == "poly" && (deg < 1 || deg > 32)) fail("model file " + path + ": poly degree must be in [1, 32]");
+  if (!std::isfinite(c0)) fail("model file " + path + ": coef0 must be finite");
+  kernel = name;
+  degree = (int)deg;
+  coef0 = (float)c0;
+  if (!std::getline(in, line)) fail("model file " + path + " ends after its kernel line");
+}
+}  // namespace
+
 Model make_model(const Dataset& ds, const std::vector<float>& alpha, float b, float gamma) {
   DPSVM_CHECK((int64_t)alpha.size() == ds.n, "alpha length != n");
   Model m;
@@ -38,6 +70,8 @@ void write_model(const std::string& path, const Model& m, int precision, bool le
   setvbuf(fp, buf.data(), _IOFBF, buf.size());
   char fmt[16];
   snprintf(fmt, sizeof(fmt), "%%.%dg", precision);
+  if (legacy && m.kernel != "rbf") fail("the legacy model format holds an RBF machine");
+  write_kernel_line(fp, m.kernel, m.degree, m.coef0);
   fprintf(fp, fmt, (double)m.gamma);
   fputc('\n', fp);
   if (!legacy) {
@@ -92,6 +126,7 @@ Model read_model(const std::string& path, bool force_legacy) {
   std::string line;
   Model m;
   if (!std::getline(in, line)) fail("model file " + path + " is empty");
+  read_kernel_line(in, line, path, m.kernel, m.degree, m.coef0);
   if (line.rfind(kMultiMagic, 0) == 0)
     fail("model file " + path + " is a multi-class (one-vs-rest) model: read it with read_multi_model");
   m.gamma = split_floats(line).at(0);
@@ -169,6 +204,7 @@ void write_multi_model(const std::string& path, const MultiModel& m, int precisi
       else fprintf(fp, fmt, (double)v[i]);
     }
   };
+  write_kernel_line(fp, m.kernel, m.degree, m.coef0);
   fprintf(fp, "%s %d %lld %d\n", kMultiMagic, k, (long long)nsv, m.d);
   row(m.classes.data(), k, true);
   fputc('\n', fp);
@@ -188,7 +224,9 @@ bool is_multi_model(const std::string& path) {
   std::ifstream in(path);
   if (!in.is_open()) fail("Couldn't open model file " + path);
   std::string line;
-  return std::getline(in, line) && line.rfind(kMultiMagic, 0) == 0;
+  if (!std::getline(in, line)) return false;
+  if (line.rfind(kKernelMagic, 0) == 0 && !std::getline(in, line)) return false;
+  return line.rfind(kMultiMagic, 0) == 0;
 }
 
 MultiModel read_multi_model(const std::string& path) {
@@ -196,6 +234,8 @@ MultiModel read_multi_model(const std::string& path) {
   if (!in.is_open()) fail("Couldn't open model file " + path);
   std::string line;
   if (!std::getline(in, line)) fail("model file " + path + " is empty");
+  MultiModel m;
+  read_kernel_line(in, line, path, m.kernel, m.degree, m.coef0);
   if (line.rfind(kMultiMagic, 0) != 0)
     fail("read_multi_model: " + path + " is not a multi-class (one-vs-rest) model: read it with read_model");
   long long k = 0, nsv = 0, d = 0;
@@ -209,7 +249,6 @@ MultiModel read_multi_model(const std::string& path) {
     if (v.size() != count) fail(std::string("read_multi_model: wrong number of values in ") + what);
     return v;
   };
-  MultiModel m;
   m.d = (int)d;
   m.classes = next("the class line", (size_t)k);
   m.gamma = next("the gamma line", 1)[0];

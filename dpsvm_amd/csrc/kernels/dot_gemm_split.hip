@@ -1,0 +1,143 @@
+// Gram builder of the kernels that are functions of the dot product alone (linear, polynomial, sigmoid;
+// dpsvm/dot_kernel.hpp, docs/DESIGN.md §21): the split-operand fp16 MFMA GEMM of rbf_gemm_split.hip with another
+// epilogue.
+//
+// The dot products are those of the RBF Gram: every X row scaled by a power of two and split into two fp16 planes
+// (split_rows_f16), three accumulators H = sum h_a h_b, P = sum h_a l_b, Q = sum l_a h_b over the k blocks in
+// order, dot = 2^-(s_a + s_b) (H + (P + Q)).  Swapping the operands swaps P and Q bit for bit and leaves H
+// unchanged (the header of rbf_gemm_split.hip), so dot(i, j) == dot(j, i) bitwise in every tile, and any function
+// of the dot's bits alone — dot_kernel_value — is a bitwise symmetric Gram: above the diagonal by the mirrored
+// store, inside the diagonal tiles (which compute both (i, j) and (j, i)) by that argument.
+//
+// The kernel is rbf_gemm_split_glds_kernel with the |x|^2 row data and the RBF epilogue taken out: 128 x 128
+// tiles, 8 waves of 32 x 64, four 32-k LDS-DMA buffers with three blocks in flight, counted vmcnt, one raw
+// barrier a k block, w32_kblock and w32_store_tile (split_mma.hpp), 64-bit indexing, the XCD tile order, and in
+// symmetric mode the tiles below the diagonal return at once (the tiles above write them through the mirror).
+// The wide-wave and persistent paths of the RBF Gram are not built for these kernels.
+#include <hip/hip_runtime.h>
+
+#include "dpsvm/common.hpp"
+#include "dpsvm/dot_kernel.hpp"
+#include "device_util.hpp"
+#include "kernels.hpp"
+#include "split_mma.hpp"
+#include "../runtime/hip_check.hpp"
+
+namespace dpsvm {
+namespace dev {
+
+// K from the three accumulators and the two rows' shifts.  Everything after `dot` reads dot alone.
+template <int KF>
+__device__ __forceinline__ float dot_value(float h, float p, float q, int ash, int bsh, float gamma, float coef0,
+                                           int degree) {
+  const float sum = h + (p + q);
+  const float dot = ldexpf(sum, -(ash + bsh));
+  return dot_kernel_value<KF>(dot, gamma, coef0, degree);
+}
+
+constexpr int kDotGldsThreads = 512;
+// A, B: split rows (split_rows_f16) of at least round_up(M, 128) / round_up(N, 128) rows of nkb blocks (the rows
+// past M / N are read, never stored); Ash / Bsh: their shifts [M] / [N].  out: M rows of ldo floats; columns >= N
+// are not written.  sym: B == A, N == M, ldo % 4 == 0 and out 16-B aligned (the mirrored 16-B stores).
+template <int KF>
+__global__ __launch_bounds__(kDotGldsThreads, 1) void dot_gemm_split_glds_kernel(
+    const u4* __restrict__ A, const int32_t* __restrict__ Ash, int64_t M, const u4* __restrict__ B,
+    const int32_t* __restrict__ Bsh, int64_t N, int nkb, float gamma, float coef0, int degree,
+    float* __restrict__ out, int64_t ldo, int sym) {
+  constexpr int WN = 2, TM = 128, TN = 128, ROWS = TM + TN, CPR = 8, BUF = ROWS * CPR, NB = 4;
+  int64_t tx, ty;
+  xcd_tile(tx, ty);
+  if (sym && ty < tx) return;
+  __shared__ u4 lds[NB * BUF + ROWS / 4];  // 4 operand buffers, then the shifts [ROWS] (one array: see the RBF kernel)
+  int32_t* s_sh = (int32_t*)(lds + NB * BUF);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
+  const int64_t m0 = tx * TM, n0 = ty * TN;
+  const int64_t rstride = (int64_t)nkb * 8;  // u4 per split row
+
+  if (tid < ROWS) {
+    const int64_t ri = tid < TM ? min(m0 + tid, M - 1) : min(n0 + (tid - TM), N - 1);
+    s_sh[tid] = tid < TM ? Ash[ri] : Bsh[ri];
+  }
+  // DMA sources: wave w fills rows 32 w + 8 i + (lane >> 3), i = 0..3 (waves 0-3: A rows,
+  // 4-7: B rows); lane position p = lane & 7 takes global chunk p ^ ((row >> 1) & 7)
+  const u4* src[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = 32 * wave + 8 * i + (lane >> 3);
+    const int c = (lane & 7) ^ ((r >> 1) & 7);
+    src[i] = r < TM ? A + (m0 + r) * rstride + c : B + (n0 + (r - TM)) * rstride + c;
+  }
+  auto dma = [&](int kb) {
+    u4* dst = lds + (kb & (NB - 1)) * BUF + 32 * wave * CPR;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      lds_dma16(src[i] + (int64_t)kb * 8, dst + 8 * i * CPR);
+  };
+  __syncthreads();  // shifts written (no DMA in flight yet)
+  dma(0);
+  if (nkb > 1) dma(1);
+  if (nkb > 2) dma(2);
+
+  f16v H[2], P[2], Q[2];
+  zero_acc(H, P, Q);
+  const int sw = ((lane & 31) >> 1) & 7;
+  const int ra = (wm * 32 + (lane & 31)) * CPR;
+  const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR, rb1 = rb0 + 32 * CPR;
+  for (int kb = 0; kb < nkb; ++kb) {
+    // retire block kb's DMA: the blocks after it (up to 2) may stay in flight
+    const int ahead = min(2, nkb - 1 - kb);
+    if (ahead == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ring_barrier();
+    if (kb + 3 < nkb) dma(kb + 3);  // into the buffer of block kb - 1 (every wave is past it)
+    const u4* buf = lds + (kb & (NB - 1)) * BUF;
+    w32_kblock(H, P, Q, buf, buf, ra, rb0, rb1, hl, sw);
+  }
+
+  // ---- epilogue: value r of MFMA tile j belongs to row wm 32 + 4 hl + mfma32_row(r), column cb ----
+  const int32_t* ash = s_sh + wm * 32 + 4 * hl;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int bsh = s_sh[TM + wn * 64 + 32 * j + (lane & 31)];
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      H[j][r] = dot_value<KF>(H[j][r], P[j][r], Q[j][r], ash[mfma32_row(r)], bsh, gamma, coef0, degree);
+  }
+  w32_store_tile(H, out, ldo, m0 + wm * 32, n0 + wn * 64, hl, lane, M, N, m0 + TM <= M && n0 + TN <= N,
+                 sym && ty != tx);
+}
+
+}  // namespace dev
+
+namespace launch {
+
+void dot_gram_split(const void* A, const int32_t* Ash, int64_t M, const void* B, const int32_t* Bsh, int64_t N,
+                    int dp, const DotKernelSpec& spec, float gamma, float* out, int64_t ldo, bool sym,
+                    hipStream_t s) {
+  if (M <= 0 || N <= 0) return;
+  DPSVM_CHECK(dp > 0 && ldo >= N, "dot_gram_split: dp > 0 and ldo >= N");
+  DPSVM_CHECK(!sym || (A == B && Ash == Bsh && M == N && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0),
+              "dot_gram_split: symmetric mode needs B == A, N == M, ldo a multiple of 4 and out 16-B aligned");
+  DPSVM_CHECK(spec.kind != DotKind::Poly || (spec.degree >= 1 && spec.degree <= kDotMaxDegree),
+              "dot_gram_split: poly degree must be in [1, 32]");
+  const int64_t tm = (M + 127) / 128, tn = (N + 127) / 128;
+  DPSVM_CHECK(tn < 65536, "dot_gram_split: N too large for grid.y");
+  const int nkb = (dp + 31) / 32;
+  const dim3 grid((unsigned)tm, (unsigned)tn);
+#define DPSVM_DOT_LAUNCH(KF)                                                                                       \
+  dev::dot_gemm_split_glds_kernel<KF><<<grid, dev::kDotGldsThreads, 0, s>>>(                                       \
+      (const dev::u4*)A, Ash, M, (const dev::u4*)B, Bsh, N, nkb, gamma, spec.coef0, spec.degree, out, ldo, sym ? 1 : 0)
+  switch (spec.kind) {
+    case DotKind::Linear: DPSVM_DOT_LAUNCH(0); break;
+    case DotKind::Poly: DPSVM_DOT_LAUNCH(1); break;
+    case DotKind::Sigmoid: DPSVM_DOT_LAUNCH(2); break;
+  }
+#undef DPSVM_DOT_LAUNCH
+  post_launch("dot_gemm_split_glds", s);
+}
+
+}  // namespace launch
+}  // namespace dpsvm

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "dpsvm/device_state.hpp"
+#include "dpsvm/dot_kernel.hpp"
 
 namespace dpsvm {
 namespace launch {
@@ -146,6 +147,14 @@ void rbf_rows_indexed(const float* X, const float* Xsq, const int32_t* a_rows, c
 int64_t split_row_u4(int dp);
 int64_t split_pad_rows(int64_t rows);
 void split_rows_f16(const float* x, int64_t rows, int dp, int ldx, void* out, int32_t* shift, hipStream_t s);
+// The Gram of a dot-product kernel (dpsvm/dot_kernel.hpp: linear, poly, sigmoid) from split rows
+// (dot_gemm_split.hip): out[i ldo + j] = k(A_i . B_j), i < M, j < N; columns >= N are not written.  A / B hold
+// split_pad_rows(M) / split_pad_rows(N) rows of split_row_u4(dp) units (the kernel reads whole 128-row tiles), Ash /
+// Bsh their shifts.  sym: B == A, N == M, ldo % 4 == 0, out 16-B aligned — the upper tiles computed, the lower
+// written by their mirrors, the result bitwise symmetric.  gamma is unused by the linear kernel.
+void dot_gram_split(const void* A, const int32_t* Ash, int64_t M, const void* B, const int32_t* Bsh, int64_t N,
+                    int dp, const DotKernelSpec& spec, float gamma, float* out, int64_t ldo, bool sym,
+                    hipStream_t s);
 // the persistent split kernels' grid limit: one workgroup per CU of the current device
 int persistent_grid_limit();
 // The split STORE GEMM's launch plan (host only: no HIP call, no environment, no state).

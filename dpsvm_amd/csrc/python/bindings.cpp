@@ -179,11 +179,27 @@ py::dict setup_dict(const GpuSetupInfo& i) {
   d["ws_rows"] = i.ws_rows;
   d["gram"] = i.gram;
   d["kernel"] = i.kernel;
+  d["t_gram_build"] = i.t_gram_build;
   d["xch_selftest"] = i.xch_selftest;
   d["comm_kind"] = i.comm_kind;
   d["ws_blocks"] = i.ws_blocks;
   d["ws_q_max"] = i.ws_q_max;
   return d;
+}
+
+// a dot-product kernel from Python: kind 0 linear, 1 poly, 2 sigmoid (models/_base.py: the spec objects)
+DotKernelSpec dot_spec(int kind, int degree, float coef0) {
+  if (kind < 0 || kind > 2) throw py::value_error("kernel kind must be 0 (linear), 1 (poly) or 2 (sigmoid)");
+  if (kind == 1 && (degree < 1 || degree > kDotMaxDegree)) throw py::value_error("poly degree must be in [1, 32]");
+  if (!std::isfinite(coef0)) throw py::value_error("coef0 must be finite");
+  return DotKernelSpec{(DotKind)kind, degree, coef0};
+}
+
+// the predictors and the CPU decision functions evaluate the RBF kernel
+void need_rbf(const std::string& kernel, const char* who) {
+  if (kernel != "rbf")
+    throw py::value_error(std::string(who) + ": the model's kernel is '" + kernel +
+                          "'; this path evaluates RBF models (a dot-product kernel's decisions run on K(test, SV))");
 }
 
 py::dict platt_dict(const PlattFit& r) {
@@ -446,6 +462,9 @@ PYBIND11_MODULE(_C, m) {
   py::class_<Model>(m, "Model")
       .def(py::init<>())
       .def_readwrite("gamma", &Model::gamma)
+      .def_readwrite("kernel", &Model::kernel)
+      .def_readwrite("degree", &Model::degree)
+      .def_readwrite("coef0", &Model::coef0)
       .def_readwrite("b", &Model::b)
       .def_readwrite("d", &Model::d)
       .def_readwrite("has_b", &Model::has_b)
@@ -468,6 +487,9 @@ PYBIND11_MODULE(_C, m) {
   py::class_<MultiModel>(m, "MultiModel")
       .def(py::init<>())
       .def_readwrite("gamma", &MultiModel::gamma)
+      .def_readwrite("kernel", &MultiModel::kernel)
+      .def_readwrite("degree", &MultiModel::degree)
+      .def_readwrite("coef0", &MultiModel::coef0)
       .def_readwrite("d", &MultiModel::d)
       .def_property_readonly("k", &MultiModel::k)
       .def_property_readonly("nsv", &MultiModel::nsv)
@@ -494,10 +516,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("read_multi_model", &read_multi_model, py::arg("path"));
   m.def("is_multi_model", &is_multi_model, py::arg("path"));
   m.def("decision_multi_cpu", [](const MultiModel& md, F32 x, int threads) {
+    need_rbf(md.kernel, "decision_multi_cpu");
     return decide(x, md.k(),
                   [&](const float* xd, int64_t n, int d) { return decision_multi_cpu(md, xd, n, d, threads); });
   }, py::arg("model"), py::arg("x"), py::arg("threads") = 0);
   m.def("decision_cpu", [](const Model& md, F32 x, int threads) {
+    need_rbf(md.kernel, "decision_cpu");
     return decide(x, 0, [&](const float* xd, int64_t n, int d) { return decision_cpu(md, xd, n, d, threads); });
   }, py::arg("model"), py::arg("x"), py::arg("threads") = 0);
   m.def("platt_fit_cpu", [](F32 dec, F32 y) {
@@ -581,6 +605,30 @@ PYBIND11_MODULE(_C, m) {
     }
     return to_np2(out, Kt.shape(0), (int)coef.shape(0));
   }, py::arg("Kt"), py::arg("coef"), py::arg("b"), py::arg("threads") = 0);
+  // the Gram of a dot-product kernel on the host: (m, n), or the symmetric (m, m) one for Y = None
+  m.def("kernel_gram_cpu", [](F32 X, py::object Y, int kind, int degree, float coef0, float gamma, int threads) {
+    const DotKernelSpec spec = dot_spec(kind, degree, coef0);
+    if (X.ndim() != 2 || X.shape(1) < 1) throw py::value_error("X must be 2-D (m, d), d >= 1");
+    const int64_t mm = X.shape(0);
+    const int d = (int)X.shape(1);
+    F32 Yb;
+    int64_t n = mm;
+    if (!Y.is_none()) {
+      Yb = Y.cast<F32>();
+      if (Yb.ndim() != 2 || Yb.shape(1) != d) throw py::value_error("Y must be 2-D (n, d) with X's d");
+      n = Yb.shape(0);
+    }
+    std::vector<float> out;
+    {
+      const float* yp = Y.is_none() ? nullptr : Yb.data();
+      py::gil_scoped_release rel;
+      out = kernel_gram_cpu(X.data(), mm, yp, n, d, spec, gamma, threads);
+    }
+    py::array_t<float> a({(py::ssize_t)mm, (py::ssize_t)n});
+    if (!out.empty()) memcpy(a.mutable_data(), out.data(), out.size() * 4);
+    return a;
+  }, py::arg("X"), py::arg("Y"), py::arg("kind"), py::arg("degree"), py::arg("coef0"), py::arg("gamma"),
+     py::arg("threads") = 0);
   m.def("solve_shrinking", [](F32 x, F32 y, const SolverParams& p, int device, const Checkpoint* resume,
                               py::object progress, std::shared_ptr<Communicator> comm) {
     int64_t n = 0;
@@ -645,6 +693,34 @@ PYBIND11_MODULE(_C, m) {
       }, py::arg("K"), py::arg("y"), py::arg("n") = 0, py::arg("ld") = 0, py::arg("stream") = 0,
            "precomputed kernel: the setup without X; K is copied into the solver's own lines (it must be symmetric, "
            "with a finite diagonal >= 0)")
+      .def("setup_rows_gram", [](GpuSolver& s, py::object X, F32 y, int kind, int degree, float coef0, int64_t n,
+                                 int d, int64_t ldx, uintptr_t stream) {
+        // X: a numpy array (n, d), or a device pointer (int) to n rows of ldx floats with the stream that wrote them
+        const DotKernelSpec spec = dot_spec(kind, degree, coef0);
+        GpuSetupInfo i;
+        try {
+          if (py::isinstance<py::int_>(X)) {
+            if (n < 2 || d < 1 || ldx < d) throw py::value_error("a device pointer needs n >= 2, d >= 1 and ldx >= d");
+            if (y.ndim() != 1 || y.shape(0) != n) throw py::value_error("y must have n entries");
+            const float* xp = (const float*)X.cast<uintptr_t>();
+            py::gil_scoped_release r;
+            i = s.setup_rows_gram(xp, n, d, y.data(), spec, true, (void*)stream, ldx);
+          } else {
+            const F32 a = X.cast<F32>();
+            if (a.ndim() != 2 || a.shape(0) < 2 || a.shape(1) < 1) throw py::value_error("X must be (n >= 2, d >= 1)");
+            if (y.ndim() != 1 || y.shape(0) != a.shape(0)) throw py::value_error("y must have n entries");
+            py::gil_scoped_release r;
+            i = s.setup_rows_gram(a.data(), a.shape(0), (int)a.shape(1), y.data(), spec, false, nullptr, 0);
+          }
+        } catch (const Error& e) {
+          if (std::string(e.what()).find("invalid Gram") != std::string::npos) throw py::value_error(e.what());
+          throw;
+        }
+        return setup_dict(i);
+      }, py::arg("X"), py::arg("y"), py::arg("kind"), py::arg("degree"), py::arg("coef0"), py::arg("n") = 0,
+           py::arg("d") = 0, py::arg("ldx") = 0, py::arg("stream") = 0,
+           "a dot-product kernel (0 linear, 1 poly, 2 sigmoid; gamma from the params): the Gram of the rows X built "
+           "straight into the solver's lines, then everything as setup_gram")
       .def("solve", [](GpuSolver& s, const Checkpoint* resume, py::object progress) {
         auto prog = wrap_progress(progress);
         SolveResult r;
@@ -772,9 +848,14 @@ PYBIND11_MODULE(_C, m) {
       }, py::arg("resume") = nullptr, py::arg("progress") = py::none());
 
   py::class_<GpuPredictor, std::shared_ptr<GpuPredictor>>(m, "GpuPredictor")
-      .def(py::init<const Model&, int, int>(), py::arg("model"), py::arg("device") = 0, py::arg("precision") = 0)
-      .def(py::init<const MultiModel&, int, int>(), py::arg("model"), py::arg("device") = 0,
-           py::arg("precision") = 0)
+      .def(py::init([](const Model& md, int device, int precision) {
+             need_rbf(md.kernel, "GpuPredictor");
+             return std::make_shared<GpuPredictor>(md, device, precision);
+           }), py::arg("model"), py::arg("device") = 0, py::arg("precision") = 0)
+      .def(py::init([](const MultiModel& md, int device, int precision) {
+             need_rbf(md.kernel, "GpuPredictor");
+             return std::make_shared<GpuPredictor>(md, device, precision);
+           }), py::arg("model"), py::arg("device") = 0, py::arg("precision") = 0)
       .def("decision_multi", [](GpuPredictor& p, F32 x) {
         return decide(x, p.k(), [&](const float* xd, int64_t n, int d) { return p.decision_multi(xd, n, d); });
       }, py::arg("x"))
@@ -879,6 +960,16 @@ PYBIND11_MODULE(_C, m) {
                             (float*)out, out_ld, sym, (void*)stream, cold_tau);
   }, py::arg("a"), py::arg("asq"), py::arg("m"), py::arg("b"), py::arg("bsq"), py::arg("n"), py::arg("ld"),
      py::arg("gamma"), py::arg("out"), py::arg("out_ld"), py::arg("sym"), py::arg("stream"), py::arg("cold_tau") = 0.f);
+  m.def("k_dot_gram_split", [](uintptr_t a, int64_t m_, uintptr_t b, int64_t n, int d, int lda, int ldb, int kind,
+                               int degree, float coef0, float gamma, uintptr_t out, int64_t out_ld, bool sym,
+                               uintptr_t stream, int reps) {
+    return kernels::dot_gram_split((const float*)a, m_, (const float*)b, n, d, lda, ldb, dot_spec(kind, degree, coef0),
+                                   gamma, (float*)out, out_ld, sym, (void*)stream, reps);
+  }, py::arg("a"), py::arg("m"), py::arg("b"), py::arg("n"), py::arg("d"), py::arg("lda"), py::arg("ldb"),
+     py::arg("kind"), py::arg("degree"), py::arg("coef0"), py::arg("gamma"), py::arg("out"), py::arg("out_ld"),
+     py::arg("sym"), py::arg("stream"), py::arg("reps") = 0,
+     "the Gram of a dot-product kernel (dot_gemm_split.hip) from f32 device rows; returns the event times (us) of "
+     "reps launches before the returned one");
   m.def("split_cold_consts", [](float gamma, float tau) {
     float c0 = 0.f, c1 = 0.f;
     launch::split_cold_consts(gamma, tau, &c0, &c1);

@@ -1,0 +1,61 @@
+// The CPU Gram builder of the dot-product kernels (dpsvm/dot_kernel.hpp; docs/DESIGN.md §21): the twin of
+// kernels/dot_gemm_split.hip for device="cpu".  The dot product is accumulated in fp64 in column order and rounded
+// once to fp32, then the shared fp32 formula — so the CPU and the device Gram differ through the dot's rounding
+// (and the two tanhf implementations) alone.
+#include <cstdint>
+#include <vector>
+
+#include "dpsvm/common.hpp"
+#include "dpsvm/dot_kernel.hpp"
+#include "dpsvm/io.hpp"
+#include "dpsvm/solver.hpp"
+
+namespace dpsvm {
+
+namespace {
+inline float dot32(const float* a, const float* b, int d) {
+  double s = 0.0;
+  for (int k = 0; k < d; ++k) s += (double)a[k] * (double)b[k];
+  return (float)s;
+}
+
+template <int KF>
+void fill(const float* X, int64_t m, const float* Y, int64_t n, int d, float gamma, float coef0, int degree,
+          int threads, float* out) {
+  if (Y == nullptr) {  // symmetric: j >= i computed, mirrored (a dot product in this order is its own transpose)
+    parallel_for(m, threads, [&](int64_t i0, int64_t i1) {
+      for (int64_t i = i0; i < i1; ++i)
+        for (int64_t j = i; j < m; ++j) {
+          const float v = dot_kernel_value<KF>(dot32(X + i * d, X + j * d, d), gamma, coef0, degree);
+          out[i * m + j] = v;
+          out[j * m + i] = v;
+        }
+    });
+    return;
+  }
+  parallel_for(m, threads, [&](int64_t i0, int64_t i1) {
+    for (int64_t i = i0; i < i1; ++i)
+      for (int64_t j = 0; j < n; ++j)
+        out[i * n + j] = dot_kernel_value<KF>(dot32(X + i * d, Y + j * d, d), gamma, coef0, degree);
+  });
+}
+}  // namespace
+
+std::vector<float> kernel_gram_cpu(const float* X, int64_t m, const float* Y, int64_t n, int d,
+                                   const DotKernelSpec& spec, float gamma, int threads) {
+  DPSVM_CHECK(X != nullptr && m >= 0 && d >= 1, "kernel_gram_cpu: X must be m x d, d >= 1");
+  DPSVM_CHECK(spec.kind != DotKind::Poly || (spec.degree >= 1 && spec.degree <= kDotMaxDegree),
+              "kernel_gram_cpu: poly degree must be in [1, 32]");
+  if (Y == nullptr) n = m;
+  std::vector<float> out((size_t)(m * n));
+  if (m == 0 || n == 0) return out;
+  if (threads <= 0) threads = default_threads();
+  switch (spec.kind) {
+    case DotKind::Linear: fill<0>(X, m, Y, n, d, gamma, spec.coef0, spec.degree, threads, out.data()); break;
+    case DotKind::Poly: fill<1>(X, m, Y, n, d, gamma, spec.coef0, spec.degree, threads, out.data()); break;
+    case DotKind::Sigmoid: fill<2>(X, m, Y, n, d, gamma, spec.coef0, spec.degree, threads, out.data()); break;
+  }
+  return out;
+}
+
+}  // namespace dpsvm

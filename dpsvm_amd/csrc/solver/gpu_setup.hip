@@ -1090,10 +1090,10 @@ __global__ void gram_pairs_kernel(const float* g, int64_t ldg, const int32_t* ij
 
 }  // namespace
 
-GpuSetupInfo GpuSolver::setup_gram(const float* K, int64_t ld, int64_t n, const float* yh, bool on_device,
-                                   void* stream) {
+// What setup_gram and setup_rows_gram share in front of the Gram's arrival: the resolutions of a precomputed solve
+// and the ordinary setup on an n x 1 zero matrix; the solver's stream then waits for the caller's (device input).
+void GpuSolver::gram_setup_begin(int64_t n, const float* yh, bool on_device, void* stream) {
   auto& m = *impl_;
-  DPSVM_CHECK(K != nullptr && ld >= n && n >= 2, "setup_gram: K must be n x n with row stride ld >= n, n >= 2");
   // what a precomputed solve resolves before the table of refusals reads the rest: the one-block working-set
   // rounds, LIBSVM's second-order pair choice (no X to sample a coupling from); no X means no split operands and
   // no adaptive Gram (gram_precision, gram_adapt and gamma are ignored)
@@ -1114,7 +1114,7 @@ GpuSetupInfo GpuSolver::setup_gram(const float* K, int64_t ld, int64_t n, const 
     const std::vector<float> x0((size_t)n, 0.f);
     setup(x0.data(), n, n, 1, yh);
   }
-  // the caller's Gram into the solver's own lines: one 2-D copy on the solver's stream, after the caller's work
+  // what fills the lines runs on the solver's stream, after the caller's work
   HIP_CHECK(hipSetDevice(m.device));
   if (on_device) {
     hipEvent_t e = nullptr;
@@ -1123,8 +1123,11 @@ GpuSetupInfo GpuSolver::setup_gram(const float* K, int64_t ld, int64_t n, const 
     HIP_CHECK(hipStreamWaitEvent(m.stream, e, 0));
     (void)hipEventDestroy(e);
   }
-  HIP_CHECK(hipMemcpy2DAsync(m.lines, (size_t)m.ldl * 4, K, (size_t)ld * 4, (size_t)n * 4, (size_t)n,
-                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m.stream));
+}
+
+// ... and behind it: the line padding zeroed, the diagonal and symmetry checks on the solver's own copy, gram_valid
+void GpuSolver::gram_setup_finish(int64_t n) {
+  auto& m = *impl_;
   // the line padding pass 1 and gram_rows_wsum read (16-B loads: columns [n, round_up(n, 4))), and the rest of it
   if (m.ldl > n)
     HIP_CHECK(hipMemset2DAsync(m.lines + n, (size_t)m.ldl * 4, 0, (size_t)(m.ldl - n) * 4, (size_t)n, m.stream));
@@ -1153,6 +1156,72 @@ GpuSetupInfo GpuSolver::setup_gram(const float* K, int64_t ld, int64_t n, const 
                     std::to_string(ij[2 * k + 1]) + "] != K[" + std::to_string(ij[2 * k + 1]) + "][" +
                     std::to_string(ij[2 * k]) + "] (bitwise)");
   m.gram_valid = true;
+}
+
+GpuSetupInfo GpuSolver::setup_gram(const float* K, int64_t ld, int64_t n, const float* yh, bool on_device,
+                                   void* stream) {
+  auto& m = *impl_;
+  DPSVM_CHECK(K != nullptr && ld >= n && n >= 2, "setup_gram: K must be n x n with row stride ld >= n, n >= 2");
+  gram_setup_begin(n, yh, on_device, stream);
+  // the caller's Gram into the solver's own lines: one 2-D copy on the solver's stream, after the caller's work
+  HIP_CHECK(hipMemcpy2DAsync(m.lines, (size_t)m.ldl * 4, K, (size_t)ld * 4, (size_t)n * 4, (size_t)n,
+                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m.stream));
+  gram_setup_finish(n);
+  return m.info;
+}
+
+// A dot-product kernel's Gram built into the lines (docs/DESIGN.md §21).  Temporaries: X [n][d], its split rows
+// (split_pad_rows(n) rows, pad zeroed) and shifts; all freed before the checks' download returns.
+GpuSetupInfo GpuSolver::setup_rows_gram(const float* x, int64_t n, int d, const float* yh, const DotKernelSpec& spec,
+                                        bool on_device, void* stream, int64_t ldx) {
+  auto& m = *impl_;
+  if (ldx == 0) ldx = d;
+  DPSVM_CHECK(x != nullptr && n >= 2 && d >= 1 && ldx >= d && ldx < (1ll << 31),
+              "setup_rows_gram: x must be n x d with row stride ldx >= d, n >= 2, d >= 1");
+  DPSVM_CHECK(spec.kind != DotKind::Poly || (spec.degree >= 1 && spec.degree <= kDotMaxDegree),
+              "setup_rows_gram: poly degree must be in [1, 32]");
+  DPSVM_CHECK(std::isfinite(spec.coef0), "setup_rows_gram: coef0 must be finite");
+  const float gamma = m.p.gamma;  // the precomputed resolutions zero it
+  gram_setup_begin(n, yh, on_device, stream);
+  const int64_t pad = launch::split_pad_rows(n), ru4 = launch::split_row_u4(d);
+  const size_t xb = (size_t)n * (size_t)ldx * 4, pb = (size_t)pad * (size_t)ru4 * 16, sb = (size_t)pad * 4;
+  float* dx = nullptr;
+  void* planes = nullptr;
+  int32_t* shift = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct Free {
+    float*& dx;
+    void*& planes;
+    int32_t*& shift;
+    hipEvent_t &e0, &e1;
+    ~Free() {
+      if (dx) (void)hipFree(dx);
+      if (planes) (void)hipFree(planes);
+      if (shift) (void)hipFree(shift);
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+    }
+  } free_all{dx, planes, shift, e0, e1};
+  const float* xs = x;
+  if (!on_device) {
+    HIP_CHECK(hipMalloc((void**)&dx, xb));
+    HIP_CHECK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, m.stream));
+    xs = dx;
+  }
+  HIP_CHECK(hipMalloc(&planes, pb));
+  HIP_CHECK(hipMalloc((void**)&shift, sb));
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventRecord(e0, m.stream));
+  HIP_CHECK(hipMemsetAsync(planes, 0, pb, m.stream));
+  HIP_CHECK(hipMemsetAsync(shift, 0, sb, m.stream));
+  launch::split_rows_f16(xs, n, d, (int)ldx, planes, shift, m.stream);
+  launch::dot_gram_split(planes, shift, n, planes, shift, n, d, spec, gamma, m.lines, m.ldl, true, m.stream);
+  HIP_CHECK(hipEventRecord(e1, m.stream));
+  gram_setup_finish(n);  // synchronizes the stream: the caller's x is free again
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  m.info.t_gram_build = (double)ms * 1e-3;
   return m.info;
 }
 

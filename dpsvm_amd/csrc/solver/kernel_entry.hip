@@ -184,6 +184,62 @@ void rbf_gram_split(const float* a, const float* asq, int64_t m, const float* b,
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
+std::vector<float> dot_gram_split(const float* a, int64_t m, const float* b, int64_t n, int d, int lda, int ldb,
+                                  const DotKernelSpec& spec, float gamma, float* out, int64_t out_ld, bool symmetric,
+                                  void* stream, int reps) {
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<float> us;
+  if (m <= 0 || n <= 0) return us;
+  DPSVM_CHECK(d >= 1 && lda >= d && (symmetric || ldb >= d), "dot_gram_split: rows of d >= 1 floats at stride >= d");
+  const auto split = [&](const float* x, int64_t rows, int ldx, void** planes, int32_t** shift) {
+    const int64_t pr = launch::split_pad_rows(rows);
+    const size_t bytes = (size_t)pr * launch::split_row_u4(d) * 16;
+    size_t tb = 0;
+    *planes = dmalloc<uint8_t>(bytes, &tb);
+    *shift = dmalloc<int32_t>((size_t)pr, &tb);
+    HIP_CHECK(hipMemsetAsync(*planes, 0, bytes, s));
+    HIP_CHECK(hipMemsetAsync(*shift, 0, (size_t)pr * 4, s));
+    launch::split_rows_f16(x, rows, d, ldx, *planes, *shift, s);
+  };
+  void *pa = nullptr, *pb = nullptr;
+  int32_t *sa = nullptr, *sb = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct Free {
+    void *&pa, *&pb;
+    int32_t *&sa, *&sb;
+    hipEvent_t &e0, &e1;
+    ~Free() {
+      (void)hipFree(pa);
+      (void)hipFree(pb);
+      (void)hipFree(sa);
+      (void)hipFree(sb);
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+    }
+  } free_all{pa, pb, sa, sb, e0, e1};
+  split(a, m, lda, &pa, &sa);
+  if (!symmetric) split(b, n, ldb, &pb, &sb);
+  const void* B = symmetric ? pa : pb;
+  const int32_t* Bsh = symmetric ? sa : sb;
+  if (reps > 0) {
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+  }
+  for (int r = 0; r <= reps; ++r) {  // reps timed launches, then the returned one
+    if (r < reps) HIP_CHECK(hipEventRecord(e0, s));
+    launch::dot_gram_split(pa, sa, m, B, Bsh, n, d, spec, gamma, out, out_ld, symmetric, s);
+    if (r < reps) {
+      HIP_CHECK(hipEventRecord(e1, s));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      us.push_back(ms * 1e3f);
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  return us;
+}
+
 std::pair<int64_t, int64_t> gram_adapt_last() {
   int64_t t = -1, h = -1;
   launch::gram_adapt_last(&t, &h);

@@ -5,8 +5,10 @@ rounds on the resident Gram (SVR, OneClassSVM; the native side of it: csrc/inclu
 from __future__ import annotations
 
 import dataclasses
+import math
+import operator
 import warnings
-from typing import Any
+from typing import Any, Optional
 
 import numpy as np
 
@@ -57,6 +59,99 @@ def _pick(table: dict, value: str, name: str) -> int:
 
 _KERNEL = {"rbf": 0, "precomputed": 1}  # SolverParams.kernel
 
+_DOT_KIND = {"linear": 0, "poly": 1, "sigmoid": 2}  # DotKind (csrc/include/dpsvm/dot_kernel.hpp)
+_MAX_DEGREE = 32
+
+
+@dataclasses.dataclass(frozen=True)
+class KernelSpec:
+    """A named kernel that is a function of the dot product alone, passed as ``kernel=`` in place of a string
+    (the strings stay "rbf" and "precomputed"): ``Linear()``, ``Poly(degree, coef0)``, ``Sigmoid(coef0)``.  The
+    estimator's ``gamma`` (default 1 / d) is the kernel's gamma.  ``fit`` takes the rows X; the Gram is built on
+    the device straight into the solver's lines and everything after it is a precomputed-kernel solve
+    (docs/DESIGN.md §21)."""
+
+    name: str
+    degree: int = 1
+    coef0: float = 0.0
+
+    def __post_init__(self):
+        if self.name not in _DOT_KIND:
+            raise ValueError(f"kernel spec name must be one of {list(_DOT_KIND)}, got {self.name!r}")
+        deg = self.degree
+        try:
+            if isinstance(deg, bool):
+                raise TypeError
+            deg = operator.index(deg)
+        except TypeError:
+            raise ValueError(f"degree must be an integer in [1, {_MAX_DEGREE}], got {self.degree!r}") from None
+        if not 1 <= deg <= _MAX_DEGREE:
+            raise ValueError(f"degree must be an integer in [1, {_MAX_DEGREE}], got {self.degree!r}")
+        try:
+            c0 = float(self.coef0)
+        except (TypeError, ValueError):
+            raise ValueError(f"coef0 must be a finite number, got {self.coef0!r}") from None
+        if not math.isfinite(c0) or abs(c0) > 3.4028234e38:
+            raise ValueError(f"coef0 must be finite (in float32), got {self.coef0!r}")
+        object.__setattr__(self, "degree", int(deg))
+        object.__setattr__(self, "coef0", c0)
+
+    @property
+    def kind(self) -> int:
+        return _DOT_KIND[self.name]
+
+    def native(self) -> tuple:
+        """(kind, degree, coef0) as the native calls take them"""
+        return self.kind, self.degree, self.coef0
+
+
+class Linear(KernelSpec):
+    """K(x, y) = x.y (LIBSVM -t 0); gamma is unused"""
+
+    def __init__(self):
+        super().__init__("linear")
+
+
+class Poly(KernelSpec):
+    """K(x, y) = (gamma x.y + coef0)^degree (LIBSVM -t 1), degree an integer in [1, 32]; the power by
+    square-and-multiply in float32 (LIBSVM's powi)"""
+
+    def __init__(self, degree: int = 3, coef0: float = 0.0):
+        super().__init__("poly", degree, coef0)
+
+
+class Sigmoid(KernelSpec):
+    """K(x, y) = tanh(gamma x.y + coef0) (LIBSVM -t 3).  Not positive semi-definite in general; a Gram with a
+    negative diagonal entry (coef0 < 0) is refused at setup"""
+
+    def __init__(self, coef0: float = 0.0):
+        super().__init__("sigmoid", 1, coef0)
+
+
+def _spec_of(name: str, degree: int, coef0: float) -> KernelSpec:
+    """the spec of a model file's kernel line"""
+    return {"linear": lambda: Linear(), "poly": lambda: Poly(degree, coef0), "sigmoid": lambda: Sigmoid(coef0)}[name]()
+
+
+def _kernel_code(kernel) -> int:
+    """SolverParams.kernel of the init-only ``kernel`` argument: a string of _KERNEL, or a KernelSpec (its Gram is
+    built at setup and the solve is a precomputed one).  Anything else is a ValueError naming the strings."""
+    if isinstance(kernel, KernelSpec):
+        return 1
+    if not isinstance(kernel, str):
+        raise ValueError(f"kernel must be one of {list(_KERNEL)} or a kernel spec (Linear(), Poly(...), "
+                         f"Sigmoid(...)), got {kernel!r}")
+    return _pick(_KERNEL, kernel, "kernel")
+
+
+def _kernel_name(kernel) -> str:
+    return kernel.name if isinstance(kernel, KernelSpec) else kernel
+
+
+def _on_gram(kernel) -> bool:
+    """the solve runs on a resident Gram handed over (precomputed) or built from the rows (a spec)"""
+    return kernel == "precomputed" or isinstance(kernel, KernelSpec)
+
 # what kernel="precomputed" refuses, for every estimator: (the test on the config, what the message names).  The
 # native table is check_kernel (csrc/include/dpsvm/problem.hpp); this one raises before any native state exists.
 _PRECOMPUTED_REFUSED = (
@@ -77,15 +172,18 @@ _PRECOMPUTED_REFUSED = (
 
 
 def _refuse_precomputed(cfg, **fit_args) -> None:
-    """kernel="precomputed": raise NotImplementedError for a refused setting or fit argument (comm, resume,
-    rank_rows), naming it"""
+    """kernel="precomputed" or a kernel spec: raise NotImplementedError for a refused setting or fit argument
+    (comm, resume, rank_rows), naming it"""
     why = "a precomputed kernel runs one-block working-set rounds on the resident Gram of one rank, with box clipping"
+    kname = _kernel_name(cfg.kernel)
+    if kname != "precomputed":
+        why = f"the {kname} kernel's Gram is built at setup and the solve is a precomputed one: {why}"
     for refused, what in _PRECOMPUTED_REFUSED:
         if refused(cfg):
-            raise NotImplementedError(f"kernel='precomputed': {what.format(c=cfg)} is not implemented ({why})")
+            raise NotImplementedError(f"kernel={kname!r}: {what.format(c=cfg)} is not implemented ({why})")
     for name, val in fit_args.items():
         if val is not None:
-            raise NotImplementedError(f"kernel='precomputed': {name} is not implemented ({why})")
+            raise NotImplementedError(f"kernel={kname!r}: {name} is not implemented ({why})")
 
 
 def _is_gpu_tensor(a) -> bool:
@@ -149,6 +247,92 @@ class _Gram:
         with torch.cuda.device(self.dev.device):
             stream = torch.cuda.current_stream().cuda_stream
         return solver.setup_gram(int(self.dev.data_ptr()), y, self.n, int(self.dev.stride(0)), int(stream))
+
+
+class _RowsGram(_Gram):
+    """The training Gram of a kernel-spec fit: the rows X (n, d) and the spec.  On the GPU the solver builds the
+    Gram from the rows straight into its lines (GpuSolver.setup_rows_gram: X is uploaded, or read in place when it
+    is a float32 torch tensor on that device); on the CPU ``host()`` is kernel_gram_cpu(X).  ``shape`` is X's."""
+
+    def __init__(self, X, spec: KernelSpec, gamma: Optional[float], want_gpu: bool):
+        self.spec = spec
+        self.dev = None
+        self.host_ = None  # the (n, n) Gram, built on first use (CPU solves)
+        self.rows_ = None
+        if _is_gpu_tensor(X) and want_gpu:
+            import torch
+
+            X = X.detach()
+            if X.dim() != 2:
+                raise ValueError(f"X must be 2-D (n_samples, n_features), got shape {tuple(X.shape)}")
+            if X.dtype != torch.float32 or X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+                X = X.to(torch.float32).contiguous()
+            self.dev = X
+        else:
+            self.rows_ = _as_f32_2d(X)
+        self.n, self.d = (int(v) for v in (self.dev if self.dev is not None else self.rows_).shape)
+        if self.n < 2 or self.d < 1:
+            raise ValueError("X needs at least 2 rows and 1 column")
+        self.shape = (self.n, self.d)
+        self.gamma = float(gamma) if gamma is not None and gamma >= 0 else 1.0 / float(self.d)
+
+    def rows(self) -> np.ndarray:
+        if self.rows_ is None:
+            self.rows_ = np.ascontiguousarray(self.dev.cpu().numpy())
+        return self.rows_
+
+    def host(self) -> np.ndarray:
+        if self.host_ is None:
+            self.host_ = np.asarray(load().kernel_gram_cpu(self.rows(), None, *self.spec.native(), self.gamma, 0),
+                                    dtype=np.float32)
+        return self.host_
+
+    def setup(self, solver, y: np.ndarray) -> dict:
+        """GpuSolver.setup_rows_gram on these rows (gamma: the solver's params)"""
+        if self.dev is None:
+            info = solver.setup_rows_gram(self.rows_, y, *self.spec.native())
+        else:
+            import torch
+
+            with torch.cuda.device(self.dev.device):
+                stream = torch.cuda.current_stream().cuda_stream
+            info = solver.setup_rows_gram(int(self.dev.data_ptr()), y, *self.spec.native(), self.n, self.d,
+                                          int(self.dev.stride(0)), int(stream))
+        info["kernel"] = self.spec.name
+        return info
+
+
+def _train_input(cfg, X):
+    """what fit() trains on: the rows (RBF), the caller's Gram (precomputed) or the rows under a kernel spec"""
+    want_gpu = cfg.device_kind()[0] == "cuda"
+    if isinstance(cfg.kernel, KernelSpec):
+        return _RowsGram(X, cfg.kernel, cfg.gamma, want_gpu)
+    if cfg.kernel == "precomputed":
+        return _Gram(X, want_gpu)
+    return _as_f32_2d(X)
+
+
+def _stamp_kernel(model, spec: Optional[KernelSpec]):
+    """a native Model / MultiModel of a kernel-spec fit: its kernel line's fields"""
+    if spec is not None:
+        model.kernel, model.degree, model.coef0 = spec.name, spec.degree, spec.coef0
+    return model
+
+
+_SCRATCH_BYTES = 1 << 30  # K(test, SV) of one prediction chunk at most (predict_chunk_rows=None)
+
+
+def _chunk_rows(nsv: int, chunk_rows) -> int:
+    """test rows per prediction chunk of a kernel-spec model: the caller's, or as many as keep K(chunk, SV) — rows
+    of round_up(nsv, 128) floats — within _SCRATCH_BYTES (whole 128-row tiles where that is more than one)"""
+    if chunk_rows is not None:
+        rows = operator.index(chunk_rows)
+        if rows < 1:
+            raise ValueError(f"predict_chunk_rows must be >= 1, got {chunk_rows!r}")
+        return rows
+    ld = max(128, (nsv + 127) // 128 * 128)
+    rows = max(1, _SCRATCH_BYTES // (4 * ld))
+    return rows // 128 * 128 if rows >= 128 else rows
 
 
 _DOT_CHUNK_BYTES = 256 << 20  # rows of a host K(test, train) uploaded per gram_rows_dot launch
@@ -227,6 +411,77 @@ class _Predicts:
     def _precomputed(self) -> bool:
         return getattr(getattr(self, "config", None), "kernel", "rbf") == "precomputed"
 
+    def _kernel_spec(self) -> Optional[KernelSpec]:
+        """the kernel spec of an estimator, or of a loaded model whose file names a dot-product kernel; else None"""
+        k = getattr(getattr(self, "config", None), "kernel", None)
+        if isinstance(k, KernelSpec):
+            return k
+        m = getattr(self, "model", None)
+        if m is not None and m.kernel != "rbf":
+            return _spec_of(m.kernel, m.degree, m.coef0)
+        return None
+
+    def _rows_model(self):
+        """a kernel-spec model as (SV rows (nsv, d), coefficients (k, nsv), thresholds (k,), gamma)"""
+        cached = getattr(self, "_rows_cache", None)
+        if cached is not None:
+            return cached
+        m = getattr(self, "model", None)
+        if m is not None:  # a loaded model
+            sv = np.ascontiguousarray(np.asarray(m.x, dtype=np.float32)).reshape(m.nsv, m.d)
+            if self._multi:
+                coef = np.ascontiguousarray(np.asarray(m.coef, dtype=np.float32).reshape(m.nsv, m.k).T)
+                b = np.asarray(m.b, dtype=np.float32)
+            else:
+                coef = (np.asarray(m.alpha, dtype=np.float32) * np.asarray(m.y, dtype=np.float32))[None, :]
+                b = np.array([m.b], dtype=np.float32)
+            gamma = float(m.gamma)
+        else:
+            coef, b = self._gram_coef()
+            sup = self.support_
+            sv = np.ascontiguousarray(self._X_train[sup])
+            coef = np.ascontiguousarray(coef[:, sup])
+            gamma = float(self._kgamma)
+        self._rows_cache = (sv, coef, b, gamma)
+        return self._rows_cache
+
+    def _decision_rows(self, X, proba=None, chunk_rows=None) -> np.ndarray:
+        """A kernel-spec model's decisions (or probabilities) of the rows X: the test rows in chunks of
+        ``chunk_rows`` (_chunk_rows), per chunk K(chunk, SV) built by the kernel's Gram builder (on the device
+        ops.kernel_gram, on the CPU kernel_gram_cpu), then the precomputed decision path (_gram_decision: fp64
+        accumulation).  A row's value does not depend on the chunking."""
+        spec = self._kernel_spec()
+        sv, coef, b, gamma = self._rows_model()
+        X = _as_f32_2d(X)
+        if X.shape[1] != sv.shape[1]:
+            raise ValueError(f"X has {X.shape[1]} features, model has {sv.shape[1]}")
+        device = _parse_device(self._device())
+        nt, k, nsv = X.shape[0], coef.shape[0], sv.shape[0]
+        rows = _chunk_rows(nsv, chunk_rows)
+        out = np.empty((nt, k), dtype=np.float32)
+        if nsv == 0:  # no support vector: every decision is -b
+            out[:] = -np.asarray(b, dtype=np.float32)[None, :]
+            if proba is not None:
+                out = np.asarray(load().proba_cpu(out, proba[0], proba[1]), dtype=np.float32)
+        elif device[0] == "cuda":
+            import torch
+
+            from ..ops.kernels import kernel_gram
+
+            tdev = torch.device("cuda", device[1])
+            with torch.cuda.device(tdev):
+                dsv = torch.tensor(sv, device=tdev)
+                for r0 in range(0, nt, rows):
+                    chunk = torch.tensor(X[r0:r0 + rows], device=tdev)  # (a copy: the caller's X may be read-only)
+                    Kt = kernel_gram(chunk, dsv, kernel=spec, gamma=gamma)
+                    out[r0:r0 + rows] = _gram_decision(Kt, coef, b, device, proba)
+        else:
+            C = load()
+            for r0 in range(0, nt, rows):
+                Kt = C.kernel_gram_cpu(np.ascontiguousarray(X[r0:r0 + rows]), sv, *spec.native(), gamma, 0)
+                out[r0:r0 + rows] = _gram_decision(Kt, coef, b, device, proba)
+        return out if (self._multi or proba is not None) else out[:, 0]
+
     def _gram_coef(self):
         """kernel="precomputed": the dense coefficients (k, n_train) and thresholds (k,) of the fitted machines"""
         coef = getattr(self, "_coef", None)
@@ -253,16 +508,22 @@ class _Predicts:
 
     def _predictor(self):
         """the device predictor, None on the CPU"""
+        if self._kernel_spec() is not None:
+            raise RuntimeError("the device predictor evaluates RBF models; a kernel-spec model predicts through "
+                               "K(test, SV) (decision_function)")
         kind, dev = _parse_device(self._device())
         if kind == "cuda" and self._gpu is None:
             self._gpu = load().GpuPredictor(self._native_model(), dev)
         return self._gpu
 
-    def _decision(self, X) -> np.ndarray:
+    def _decision(self, X, predict_chunk_rows=None) -> np.ndarray:
         """sum_sv coef K(sv, x) - b, float32: (n,), or (n, k) for k machines (kernel="precomputed": X is
-        K(test, train), (n_test, n_train))"""
+        K(test, train), (n_test, n_train)).  ``predict_chunk_rows``: a kernel-spec model's test rows per chunk
+        (_decision_rows); the other kernels ignore it."""
         if self._precomputed():
             return self._decision_gram(X)
+        if self._kernel_spec() is not None:
+            return self._decision_rows(X, None, predict_chunk_rows)
         X = _as_f32_2d(X)
         d = getattr(self, "n_features_in_", None)
         if d is not None and X.shape[1] != d:
@@ -341,7 +602,7 @@ class _OneBlockEstimator(_Predicts):
         cfg = self.config
         self._check_extra()
         _parse_device(cfg.device)
-        if cfg.kernel == "precomputed":  # its own table first: it names each setting
+        if _on_gram(cfg.kernel):  # its own table first: it names each setting
             _refuse_precomputed(cfg)
         for refused, what in _REFUSED:
             if refused(cfg):
@@ -375,7 +636,7 @@ class _OneBlockEstimator(_Predicts):
             setup = {"iteration": "cpu", "engine_note": C.problem_note(p)}
             if gram:
                 X.check_host()
-                setup["kernel"] = "precomputed"
+                setup["kernel"] = _kernel_name(self.config.kernel)
                 setup["engine_note"] = "; ".join(s for s in (C.precomputed_note(), setup["engine_note"]) if s)
                 alpha, info = C.solve_cpu_gram(X.host(), y_native, p, progress, None)
             else:
@@ -392,10 +653,14 @@ class _OneBlockEstimator(_Predicts):
         self.setup_info_ = setup
         _publish_solves(self, [info])
         gram = isinstance(X, _Gram)
-        self.gamma_ = None if gram else gamma  # a precomputed kernel has no gamma (and no rows to keep)
+        rows = isinstance(X, _RowsGram)  # a kernel spec: the model keeps its rows; gamma is the kernel's (linear: none)
+        self._kgamma = X.gamma if rows else gamma
+        self.gamma_ = None if (gram and not rows) or isinstance(self.config.kernel, Linear) else self._kgamma
         self.n_features_in_ = X.shape[1]
         self.support_ = np.nonzero(coef != 0)[0]
-        if gram:
+        if rows:
+            X = X.rows()
+        if gram and not rows:  # a precomputed kernel has no gamma (and no rows to keep)
             X = None
             self.__dict__.pop("support_vectors_", None)
         else:
@@ -405,6 +670,7 @@ class _OneBlockEstimator(_Predicts):
         self._X_train, self._coef = X, coef
         self._model = None
         self._gpu = None
+        self._rows_cache = None
         if self.status_ == 2:
             warnings.warn(f"stopped at max_iter with gap {info['b_lo'] - info['b_hi']:.3g} > 2 eps: raise max_iter "
                           "to converge", RuntimeWarning, stacklevel=3)
@@ -419,7 +685,10 @@ class _OneBlockEstimator(_Predicts):
             if coef is None:
                 raise RuntimeError(f"to_model() needs a fitted {self._NAME}")
             y = np.where(coef < 0, -1.0, 1.0).astype(np.float32)
-            self._model = load().make_model(self._X_train, y, np.abs(coef).astype(np.float32), self.b_, self.gamma_)
+            spec = self._kernel_spec()
+            gamma = self.gamma_ if self.gamma_ is not None else 0.0  # (the linear kernel has none)
+            self._model = _stamp_kernel(load().make_model(self._X_train, y, np.abs(coef).astype(np.float32), self.b_,
+                                                          gamma), spec)
         return self._model
 
     def save(self, path: str, precision: int = 9) -> None:
@@ -429,6 +698,6 @@ class _OneBlockEstimator(_Predicts):
     def get_params(self, deep: bool = True) -> dict:
         out = dataclasses.asdict(self.config)
         if self.config.kernel != "rbf":  # init-only (SVCConfig): reported when it is not the default
-            out["kernel"] = self.config.kernel
+            out["kernel"] = _kernel_name(self.config.kernel)
         out[self._EXTRA] = getattr(self, self._EXTRA)
         return out

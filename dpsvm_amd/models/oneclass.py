@@ -23,7 +23,7 @@ from typing import Any, Callable, Optional, Sequence
 import numpy as np
 
 from .._native import load
-from ._base import _Gram, _OneBlockEstimator, _as_f32_2d
+from ._base import _Gram, _OneBlockEstimator, _train_input
 from .svc import LoadedModel
 
 
@@ -37,17 +37,17 @@ def _check_nu(nu: float) -> float:
 class _OneClassDecisions:
     """what the estimator and the loaded model derive from the decision sum_sv alpha K(sv, x) - rho"""
 
-    def decision_function(self, X) -> np.ndarray:
-        """float32: >= 0 inside the estimated support"""
-        return self._decision(X)
+    def decision_function(self, X, predict_chunk_rows=None) -> np.ndarray:
+        """float32: >= 0 inside the estimated support (``predict_chunk_rows``: a kernel spec's test rows per chunk)"""
+        return self._decision(X, predict_chunk_rows)
 
-    def score_samples(self, X) -> np.ndarray:
+    def score_samples(self, X, predict_chunk_rows=None) -> np.ndarray:
         """the decision without the offset: sum_sv alpha K(sv, x)"""
-        return (self.decision_function(X) + np.float32(self._rho())).astype(np.float32)
+        return (self.decision_function(X, predict_chunk_rows) + np.float32(self._rho())).astype(np.float32)
 
-    def predict(self, X) -> np.ndarray:
+    def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
         """+1 where the decision is >= 0 (inlier), else -1"""
-        return np.where(self.decision_function(X) >= 0, 1, -1).astype(np.int32)
+        return np.where(self.decision_function(X, predict_chunk_rows) >= 0, 1, -1).astype(np.int32)
 
 
 class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
@@ -94,8 +94,9 @@ class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
         """Train on the rows of ``X`` (``y`` is ignored).  One rank, from the nu start, unweighted."""
         self._refuse_fit_args(comm, resume, rank_rows, sample_weight)
         self._resolve()
-        # kernel="precomputed": X is the (n, n) Gram; decision_function() then takes K(test, train)
-        X = _Gram(X, self.config.device_kind()[0] == "cuda") if self._precomputed() else _as_f32_2d(X)
+        # kernel="precomputed": X is the (n, n) Gram; decision_function() then takes K(test, train).  A kernel spec:
+        # the rows
+        X = _train_input(self.config, X)
         n, d = X.shape
         p = self._params(d)
         t0 = time.perf_counter()
@@ -116,8 +117,8 @@ class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
         nus = [_check_nu(v) for v in nus]
         if not nus:
             raise ValueError("nu_path needs at least one nu")
-        gram = self._precomputed()
-        X = _Gram(X, self.config.device_kind()[0] == "cuda") if gram else _as_f32_2d(X)
+        X = _train_input(self.config, X)
+        gram = isinstance(X, _Gram)  # precomputed, or the rows under a kernel spec
         n, d = X.shape
         C = load()
         ones = np.ones(n, dtype=np.float32)

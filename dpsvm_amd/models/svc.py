@@ -21,8 +21,9 @@ from typing import Any, Callable, Optional
 import numpy as np
 
 from .._native import load, load_quarantine
-from ._base import (_Gram, _KERNEL, _Predicts, _as_1d, _as_f32_2d, _parse_device, _pick,  # noqa: F401 (re-exported)
-                    _publish_solves, _refuse_precomputed)
+from ._base import (Linear, _Gram, _KERNEL, _Predicts, _RowsGram, _as_1d, _as_f32_2d,  # noqa: F401 (re-exported)
+                    _kernel_code, _kernel_name, _on_gram, _parse_device, _pick, _publish_solves, _refuse_precomputed,
+                    _stamp_kernel, _train_input)
 
 
 _CLIP = {"independent": 0, "box": 1}
@@ -192,11 +193,15 @@ class SVCConfig:
     # rank with box clipping (general-diagonal sub-problem kernels, docs/DESIGN.md §20); settings resolve as for a
     # weighted fit plus ws_blocks=1, the rest is refused (README "Precomputed kernels").  Init-only: it is no
     # solver knob but what fit() and decision_function() take, so it stays off dataclasses.fields(), the list of
-    # settings that map one to one onto SolverParams (get_params() reports it when it is not "rbf")
-    kernel: dataclasses.InitVar[str] = "rbf"
+    # settings that map one to one onto SolverParams (get_params() reports it when it is not "rbf").
+    # Or a kernel spec — Linear(), Poly(degree, coef0), Sigmoid(coef0) — in place of a string: fit takes X, the
+    # Gram of (gamma x.y + coef0)^degree etc. is built on the device straight into the solver's lines and solved
+    # as a precomputed one (same resolutions and refusals); the model keeps its rows and predicts from X
+    # (docs/DESIGN.md §21).  gamma stays this config's field (default 1 / d)
+    kernel: dataclasses.InitVar[Any] = "rbf"
 
-    def __post_init__(self, kernel: str = "rbf"):
-        _pick(_KERNEL, kernel, "kernel")
+    def __post_init__(self, kernel: Any = "rbf"):
+        _kernel_code(kernel)
         self.kernel = kernel
 
     def shrink_mode(self) -> str:
@@ -228,7 +233,7 @@ class SVCConfig:
         p.dp_policy = _pick(_DP, self.dp, "dp")
         p.gram_precision = _pick(_GRAM, self.gram, "gram")
         p.ws_clip_fallback = int(bool(self.ws_clip_fallback))
-        p.kernel = _pick(_KERNEL, self.kernel, "kernel")
+        p.kernel = _kernel_code(self.kernel)
         if p.kernel:
             _refuse_precomputed(self)
             p.solver, p.ws_recompute, p.ws_blocks = 2, 2, 1
@@ -294,10 +299,10 @@ class SVC(_Predicts):
 
     def __init__(self, C: float = 1.0, gamma: Optional[float] = None, eps: float = 1e-3,
                  max_iter: int = 150000, device: str = "auto", **kwargs: Any):
-        if kwargs.get("kernel", "rbf") == "precomputed":
+        if _on_gram(kwargs.get("kernel", "rbf")):
             kwargs.setdefault("clip", "box")
         self.config = SVCConfig(C=C, gamma=gamma, eps=eps, max_iter=max_iter, device=device, **kwargs)
-        if self.config.kernel == "precomputed":
+        if _on_gram(self.config.kernel):
             _refuse_precomputed(self.config)
         self._model = None
         self._multi = False
@@ -446,7 +451,8 @@ class SVC(_Predicts):
                 raise ValueError("partitioned X needs the GPU solver")
             if gram:
                 X.check_host()
-                setup = {"iteration": "cpu", "kernel": "precomputed", "engine_note": C.precomputed_note()}
+                setup = {"iteration": "cpu", "kernel": _kernel_name(self.config.kernel),
+                         "engine_note": C.precomputed_note()}
             for c in range(m):
                 rc = None if RC is None else RC[c]
                 if gram:
@@ -591,7 +597,7 @@ class SVC(_Predicts):
         probability = int(probability)
         if probability != 0 and probability < 2:
             raise ValueError(f"probability is the number of folds: 0 (off) or >= 2, got {probability}")
-        if self.config.kernel == "precomputed":
+        if _on_gram(self.config.kernel):
             return self._fit_gram(X, y, comm, resume, progress, rank_rows, sample_weight, probability,
                                   probability_seed)
         if self.config.engines == "all" or self.config.host_cache_lines or self.config.cache_engine == "chain":
@@ -643,13 +649,17 @@ class SVC(_Predicts):
         pointer, anything else uploaded).  Binary and one-vs-rest fits, weights and probability folds all run on
         one GpuSolver and its one copy of K (``setup_gram``, then k solves with ``set_labels`` / ``set_row_C``).
         There are no rows to keep: ``support_``, ``dual_coef_``, ``alpha_``, ``b_`` / ``intercept_`` and
-        ``probA_`` / ``probB_`` are the model, ``gamma_`` is None, and prediction takes K(test, train)."""
+        ``probA_`` / ``probB_`` are the model, ``gamma_`` is None, and prediction takes K(test, train).
+        A kernel spec (Linear / Poly / Sigmoid): K is X; the solver builds the Gram from the rows into its lines
+        (``setup_rows_gram``), everything else as above, and the model keeps its rows (``support_vectors_``,
+        ``save``; prediction takes test rows)."""
         _refuse_precomputed(self.config, comm=comm, resume=resume, rank_rows=rank_rows)
-        G = _Gram(K, self.config.device_kind()[0] == "cuda")
+        G = _train_input(self.config, K)
+        rows = isinstance(G, _RowsGram)  # a kernel spec: K is X, the model keeps its rows
         y1 = _as_1d(y)
         n = G.n
         if y1.shape[0] != n:
-            raise ValueError("len(y) != K.shape[0]")
+            raise ValueError("len(y) != X.shape[0]" if rows else "len(y) != K.shape[0]")
         classes = np.unique(y1)
         multi = len(classes) > 2
         if multi:
@@ -665,8 +675,10 @@ class SVC(_Predicts):
         finally:
             self._grad_sink = None
         self._solver = None  # dropped with its copy of the Gram: every later call reads K(test, train)
-        self._publish(p, n, time.perf_counter() - t0, setup)
-        self.gamma_ = None
+        self._publish(p, G.shape[1], time.perf_counter() - t0, setup)
+        self._kgamma = p.gamma  # a spec's gamma as the solver built the Gram with it
+        self.gamma_ = p.gamma if rows and not isinstance(self.config.kernel, Linear) else None
+        self._rows_cache = None
         self._multi = multi
         self._publish_proba(proba)
         if multi:
@@ -682,10 +694,13 @@ class SVC(_Predicts):
 
             warnings.warn("stopped at max_iter before the gap closed: raise max_iter to converge", RuntimeWarning,
                           stacklevel=3)
-        self._X_train, self._y_train, self._Ys = None, (y1 if multi else Ys[0]), Ys
+        self._X_train, self._y_train, self._Ys = (G.rows() if rows else None), (y1 if multi else Ys[0]), Ys
         self._coef = (A * Ys).astype(np.float32)  # (k, n): the dense coefficients gram_rows_dot reads
         self.support_ = np.nonzero((A > 0).any(axis=0))[0]
-        self.__dict__.pop("support_vectors_", None)
+        if rows:
+            self.support_vectors_ = self._X_train[self.support_]
+        else:
+            self.__dict__.pop("support_vectors_", None)
         self.dual_coef_ = self._coef[:, self.support_] if multi else self._coef[0, self.support_]
         self.n_support_ = int(len(self.support_))
         # the training decisions f + y - b from the solver's gradient (no predict pass): train_accuracy()
@@ -760,7 +775,7 @@ class SVC(_Predicts):
         Folds: ``cv_folds(n, cv, seed)``.  ``class_weight='balanced'`` is computed on all n rows.  Settings
         resolve as for a weighted fit.  ``cv_stats_``: the per-fold solve dicts.  kernel="precomputed": X is the
         (n, n) Gram, uploaded once for the ``cv`` solves."""
-        X = _Gram(X, self.config.device_kind()[0] == "cuda") if self._precomputed() else _as_f32_2d(X)
+        X = _train_input(self.config, X)
         y1 = _as_1d(y)
         if len(np.unique(y1)) != 2:
             raise ValueError("cross_val_decision is binary: y needs two classes")
@@ -800,17 +815,24 @@ class SVC(_Predicts):
                 self._file_classes = False
             if not self._file_classes:  # the predictors need only the columns' order
                 cls = np.arange(len(self.classes_), dtype=np.float32)
-            self._model = C.make_multi_model(self._X_train, cls, self.alpha_, self._Ys, self.b_, self.gamma_)
+            self._model = _stamp_kernel(C.make_multi_model(self._X_train, cls, self.alpha_, self._Ys, self.b_,
+                                                           self._model_gamma()), self._kernel_spec())
         if self._model is None:
             if self._X_train is None:
                 raise RuntimeError("to_model() needs the full training set on this rank")
-            self._model = C.make_model(self._X_train, self._y_train, self.alpha_, self.b_, self.gamma_)
+            self._model = _stamp_kernel(C.make_model(self._X_train, self._y_train, self.alpha_, self.b_,
+                                                     self._model_gamma()), self._kernel_spec())
         return self._model
+
+    def _model_gamma(self) -> float:
+        return self.gamma_ if self.gamma_ is not None else 0.0  # (the linear kernel has none)
 
     def save(self, path: str, precision: int = 9, legacy: bool = False) -> None:
         """Write the reference text model (gamma, b, then alpha,y,x... per SV);
         after a multi-class fit the one-vs-rest format ("dpsvm-ovr k nsv d",
         classes, gamma, b_0..b_k-1, then the k coefficients and x per SV)."""
+        if legacy and self._kernel_spec() is not None:
+            raise ValueError("the legacy format holds an RBF machine")
         if self._multi:
             if legacy:
                 raise ValueError("the legacy format holds one binary machine")
@@ -824,17 +846,19 @@ class SVC(_Predicts):
         _write_platt(path, getattr(self, "probA_", None), getattr(self, "probB_", None))
 
     # ------------------------------------------------------------------ predict
-    def decision_function(self, X) -> np.ndarray:
-        """sum_sv alpha y K(sv, x) - b  (svmTrain.cu:646-652)."""
-        return self._decision(X)
+    def decision_function(self, X, predict_chunk_rows=None) -> np.ndarray:
+        """sum_sv alpha y K(sv, x) - b  (svmTrain.cu:646-652).  ``predict_chunk_rows`` (here and in predict,
+        predict_proba, score): a kernel-spec model's test rows per chunk of K(test, SV); default: as many as keep
+        that scratch within 1 GiB.  The other kernels ignore it."""
+        return self._decision(X, predict_chunk_rows)
 
-    def predict(self, X) -> np.ndarray:
-        dec = self.decision_function(X)
+    def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
+        dec = self.decision_function(X, predict_chunk_rows)
         if self._multi:
             return self.classes_[np.argmax(dec, axis=1)]  # ties: the lowest class index
         return self._decode(np.where(dec < 0, -1.0, 1.0))  # d >= 0 -> +1 (svmTrain.cu:654-657)
 
-    def predict_proba(self, X) -> np.ndarray:
+    def predict_proba(self, X, predict_chunk_rows=None) -> np.ndarray:
         """(n, k) float32 class probabilities, columns in the order of ``classes_``, after
         ``fit(probability=cv)``: machine c's Platt sigmoid p = 1 / (1 + exp(probA_ d + probB_)) of its decision
         value; two classes: [1 - p, p] with p = P(classes_[-1]); more: the k values divided by their sum (a row
@@ -846,6 +870,12 @@ class SVC(_Predicts):
             p = self._decision_gram(X, (np.atleast_1d(np.asarray(self.probA_, dtype=np.float64)),
                                         np.atleast_1d(np.asarray(self.probB_, dtype=np.float64))))
             return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
+        if self._kernel_spec() is not None:  # the sigmoids on each chunk's gram_rows_dot output
+            if getattr(self, "probA_", None) is None:
+                raise RuntimeError("predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
+            p = self._decision_rows(X, (np.atleast_1d(np.asarray(self.probA_, dtype=np.float64)),
+                                        np.atleast_1d(np.asarray(self.probB_, dtype=np.float64))), predict_chunk_rows)
+            return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
         X = _as_f32_2d(X)
         if X.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X.shape[1]} features, model has {self.n_features_in_}")
@@ -853,14 +883,14 @@ class SVC(_Predicts):
             raise RuntimeError("predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
         return _predict_proba(self._predictor(), self.to_model, self._multi, X, self.probA_, self.probB_)
 
-    def score(self, X, y) -> float:
+    def score(self, X, y, predict_chunk_rows=None) -> float:
         yy = _as_1d(y)
-        return float(np.mean(self.predict(X) == yy))
+        return float(np.mean(self.predict(X, predict_chunk_rows) == yy))
 
     def train_accuracy(self) -> float:
         """Training accuracy computed on device (distributed across ranks); kernel="precomputed": from the
         solver's gradient, sign(f + y - b) per machine."""
-        if self._precomputed():
+        if _on_gram(self.config.kernel):
             dec = self._train_dec
             if self._multi:
                 return float(np.mean(self.classes_[np.argmax(dec, axis=0)] == self._y_train))
@@ -874,7 +904,7 @@ class SVC(_Predicts):
     def get_params(self, deep: bool = True) -> dict:
         out = dataclasses.asdict(self.config)
         if self.config.kernel != "rbf":  # init-only (SVCConfig): reported when it is not the default
-            out["kernel"] = self.config.kernel
+            out["kernel"] = _kernel_name(self.config.kernel)
         return out
 
 
@@ -887,11 +917,15 @@ class _Loaded(_Predicts):
         self._check_device()
         self.probA_, self.probB_ = platt if platt is not None else (None, None)  # the sidecar's sigmoids
 
-    def predict_proba(self, X) -> np.ndarray:
+    def predict_proba(self, X, predict_chunk_rows=None) -> np.ndarray:
         """SVC.predict_proba on the sigmoids read from the model file's ``.platt`` sidecar"""
         if self.probA_ is None:
             raise RuntimeError("predict_proba needs the model file's .platt sidecar (a model saved after "
                                "fit(probability=cv))")
+        if self._kernel_spec() is not None:
+            p = self._decision_rows(X, (np.atleast_1d(np.asarray(self.probA_, dtype=np.float64)),
+                                        np.atleast_1d(np.asarray(self.probB_, dtype=np.float64))), predict_chunk_rows)
+            return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
         return _predict_proba(self._predictor(), lambda: self.model, self._multi, _as_f32_2d(X), self.probA_,
                               self.probB_)
 
@@ -917,14 +951,14 @@ class _Loaded(_Predicts):
 class LoadedModel(_Loaded):
     """A model read from a reference-format file (svmTest path)."""
 
-    def decision_function(self, X) -> np.ndarray:
-        return self._decision(X)
+    def decision_function(self, X, predict_chunk_rows=None) -> np.ndarray:
+        return self._decision(X, predict_chunk_rows)
 
-    def predict(self, X) -> np.ndarray:
-        return np.where(self.decision_function(X) < 0, -1.0, 1.0).astype(np.float32)
+    def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
+        return np.where(self.decision_function(X, predict_chunk_rows) < 0, -1.0, 1.0).astype(np.float32)
 
-    def score(self, X, y) -> float:
-        return float(np.mean(self.predict(X) == np.where(_as_1d(y) > 0, 1.0, -1.0)))
+    def score(self, X, y, predict_chunk_rows=None) -> float:
+        return float(np.mean(self.predict(X, predict_chunk_rows) == np.where(_as_1d(y) > 0, 1.0, -1.0)))
 
 
 class LoadedMultiModel(_Loaded):
@@ -936,14 +970,14 @@ class LoadedMultiModel(_Loaded):
         super().__init__(model, device, platt)
         self.classes_ = np.asarray(model.classes)
 
-    def decision_function(self, X) -> np.ndarray:
-        return self._decision(X)
+    def decision_function(self, X, predict_chunk_rows=None) -> np.ndarray:
+        return self._decision(X, predict_chunk_rows)
 
-    def predict(self, X) -> np.ndarray:
-        return self.classes_[np.argmax(self.decision_function(X), axis=1)]
+    def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
+        return self.classes_[np.argmax(self.decision_function(X, predict_chunk_rows), axis=1)]
 
-    def score(self, X, y) -> float:
-        return float(np.mean(self.predict(X) == _as_1d(y)))
+    def score(self, X, y, predict_chunk_rows=None) -> float:
+        return float(np.mean(self.predict(X, predict_chunk_rows) == _as_1d(y)))
 
 
 def load_model(path: str, device: str = "auto", legacy: bool = False):

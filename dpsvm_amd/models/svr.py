@@ -22,7 +22,7 @@ from typing import Any, Callable, Optional
 import numpy as np
 
 from .._native import load
-from ._base import _Gram, _OneBlockEstimator, _as_1d, _as_f32_2d
+from ._base import _OneBlockEstimator, _as_1d, _train_input
 from .svc import LoadedModel
 
 
@@ -73,8 +73,8 @@ class SVR(_OneBlockEstimator):
         """Train on real-valued targets ``z``.  One rank, from a cold start, unweighted."""
         self._refuse_fit_args(comm, resume, rank_rows, sample_weight)
         self._resolve()
-        # kernel="precomputed": X is the (n, n) Gram; predict() then takes K(test, train)
-        X = _Gram(X, self.config.device_kind()[0] == "cuda") if self._precomputed() else _as_f32_2d(X)
+        # kernel="precomputed": X is the (n, n) Gram; predict() then takes K(test, train).  A kernel spec: the rows
+        X = _train_input(self.config, X)
         z = np.ascontiguousarray(_as_1d(z), dtype=np.float32)
         n, d = X.shape
         if z.shape[0] != n:
@@ -96,13 +96,13 @@ class SVR(_OneBlockEstimator):
         self._publish_fit(X, self.alpha_[0] - self.alpha_[1], info, p.gamma, setup)
         return self
 
-    def predict(self, X) -> np.ndarray:
-        """sum_sv beta K(sv, x) - b, float32"""
-        return self._decision(X)
+    def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
+        """sum_sv beta K(sv, x) - b, float32 (``predict_chunk_rows``: a kernel spec's test rows per chunk)"""
+        return self._decision(X, predict_chunk_rows)
 
-    def score(self, X, z) -> float:
+    def score(self, X, z, predict_chunk_rows=None) -> float:
         """R^2 of the predictions"""
-        return _r2(z, self.predict(X))
+        return _r2(z, self.predict(X, predict_chunk_rows))
 
 
 class LoadedSVR(LoadedModel):
@@ -110,8 +110,8 @@ class LoadedSVR(LoadedModel):
 
     predict = LoadedModel.decision_function
 
-    def score(self, X, z) -> float:
-        return _r2(z, self.predict(X))
+    def score(self, X, z, predict_chunk_rows=None) -> float:
+        return _r2(z, self.predict(X, predict_chunk_rows))
 
 
 def load_svr(path: str, device: str = "auto") -> LoadedSVR:

@@ -72,6 +72,35 @@ def rbf_gram(a: torch.Tensor, b: torch.Tensor | None = None, gamma: float = 1.0,
     return out[:, :n]
 
 
+def kernel_gram(a: torch.Tensor, b: torch.Tensor | None = None, kernel=None, gamma: float = 1.0, reps: int = 0):
+    """Gram block K[i, j] = k(a_i . b_j) of a dot-product kernel spec (``dpsvm_amd.Linear()``, ``Poly(degree,
+    coef0)``, ``Sigmoid(coef0)``; gamma unused by the linear kernel) with the split-operand fp16 MFMA GEMM of
+    dot_gemm_split.hip (fp32-accurate dot products, then the shared fp32 formula).  b=None: the symmetric Gram of
+    a — upper tiles plus their mirrored transposes, bitwise symmetric.  Padding as rbf_gram's: the result is a view
+    of an (m, round_up(n, 128)) tensor pre-filled with NaN whose columns >= n are never written.  reps > 0: returns
+    (K, us) with the event times of reps launches of the GEMM before the returned one."""
+    from ..models._base import KernelSpec
+
+    if not isinstance(kernel, KernelSpec):
+        raise ValueError(f"kernel must be a kernel spec (Linear(), Poly(...), Sigmoid(...)), got {kernel!r}")
+    C = load()
+    sym = b is None
+    if a.dim() != 2 or (not sym and (b.dim() != 2 or b.shape[1] != a.shape[1])) or a.shape[1] < 1:
+        raise ValueError("a must be (m, d) and b (n, d), d >= 1")
+    a32 = a.detach().to(torch.float32).contiguous()
+    b32 = a32 if sym else b.detach().to(device=a.device, dtype=torch.float32).contiguous()
+    m, d = a32.shape
+    n = b32.shape[0]
+    ld = (n + 127) // 128 * 128
+    out = torch.full((m, ld), float("nan"), device=a.device)
+    kind, degree, coef0 = kernel.native()
+    us = []
+    if m and n:
+        us = C.k_dot_gram_split(a32.data_ptr(), m, b32.data_ptr(), n, d, d, d, kind, degree, coef0, float(gamma),
+                                out.data_ptr(), ld, sym, _stream(a), int(reps))
+    return (out[:, :n], list(us)) if reps else out[:, :n]
+
+
 def split_gram_path(m: int, n: int, d: int, sym: bool = False, cold: bool = False) -> str:
     """The launch path rbf_gram(split=True) takes for an m x n Gram of d
     columns under the current variant (launch::split_gram_path: Tile, Glds,

@@ -1,13 +1,13 @@
-"""Where a tile of the one-product Gram pass (rbf_gemm_split_h1s_kernel) spends
-its time, on both kinds of wave: the stamped build of the kernel
-(C.k_set_gram_stamps, 16 words a tile) records, for a workgroup's first
-compute wave, s_memtime at the tile's start / stage 0 landed / k loop done /
-values done / stores issued, and for its first DMA wave the cycles spent at the
-barrier of the tile's stage 0 (waiting out the previous tile's epilogue), at
-the other stages' barriers, waiting for its own DMA to land, and in all.
+"""The adaptive Gram at the headline shape: event times of the whole call (both
+passes and the per-call operand prep) and a checksum of the stored bits, the
+figures profiles/gram_overlap/ and profiles/gram_tile256/ compare builds by.
 
-Also times the unstamped adaptive Gram (events, both passes and the per-call
-operand prep) and prints a checksum of the stored bits.
+No longer reported: the per-tile s_memtime stamps (compute wave: stage 0 landed
+/ k loop / values / store issue; DMA wave: barrier and landing waits).  They
+belonged to the stamped build of rbf_gemm_split_h1s_kernel, which went with
+that kernel: the 256 x 256 one-product kernel (rbf_gemm_split_h1_kernel) has
+no stamped build and no DMA waves.  profiles/gram_overlap/h1s_before.txt keeps
+the last stamps taken.
 
     python bench/gram_overlap_stamps.py [--n 60000] [--reps 5] [--out FILE]
 """
@@ -16,7 +16,6 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -62,37 +61,7 @@ def main():
     bits = out[:, :n].contiguous().view(torch.int32)
     checksum = int(bits.to(torch.int64).sum().item())
     nan = int(torch.isnan(out[:, :n]).sum().item())
-    stamps = torch.zeros(tiles * 16, dtype=torch.int64, device="cuda")
-    C.k_set_gram_stamps(stamps.data_ptr())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    gram()
-    e1.record()
-    torch.cuda.synchronize()
-    C.k_set_gram_stamps(0)
-    st = stamps.view(-1, 16).cpu().numpy().astype(np.int64)
-    cw = (np.diff(st[:, :5], axis=1) & 0xffffffff)  # low words: differences mod 2^32
-    first, loop, values, store = cw.T
-    tile_us = ((st[:, 6] - st[:, 5]) & 0xffffffff) / 100.0
-    clk = float(np.median((first + loop + values + store) / np.maximum(tile_us, 1e-9)))  # cycles per us
-    bar0, bar, land, total = st[:, 8], st[:, 9], st[:, 10], st[:, 11]
-    G = 256
-    later = np.arange(len(st)) >= G  # a workgroup's tiles after its first (whose stage-0 wait is the prologue)
-    med = lambda v: float(np.median(v))  # noqa: E731
-    res = {
-        "n": n, "tiles": tiles, "hot_tiles": hot,
-        "adaptive_gram_ms_unstamped": ms, "adaptive_gram_ms_stamped": round(e0.elapsed_time(e1), 3),
-        "checksum": checksum, "nan": nan, "memtime_cycles_per_us": round(clk, 1),
-        "compute_wave_cycles_median": {"stage0_wait": med(first[later]), "k_loop_rest": med(loop[later]),
-                                       "values": med(values[later]), "store_issue": med(store[later]),
-                                       "tile": med((first + loop + values + store)[later])},
-        "compute_wave_epilogue_share": round(med((values + store)[later]) /
-                                             med((first + loop + values + store)[later]), 3),
-        "dma_wave_cycles_median": {"barrier_stage0": med(bar0[later]), "barrier_other_stages": med(bar[later]),
-                                   "own_dma_landing": med(land[later]), "tile": med(total[later])},
-        "dma_wave_blocked_at_stage0_share": round(med(bar0[later]) / med(total[later]), 3),
-        "tile_us_median": med(tile_us[later]),
-    }
+    res = {"n": n, "tiles": tiles, "hot_tiles": hot, "adaptive_gram_ms": ms, "checksum": checksum, "nan": nan}
     print(json.dumps(res), flush=True)
     if a.out:
         with open(a.out, "a") as fh:

@@ -193,10 +193,11 @@ struct GramAdaptPrep {
   const void* A = nullptr;  // the split rows it was built from
   int64_t M = 0;
   int dp = 0;
-  void* planes = nullptr;   // h planes of the 256-row tiles' rows
+  void* planes = nullptr;   // stage-major h planes [k block][256-row tiles' rows][32 halfs]
   float* r = nullptr;       // log2 |x| [M]
-  uint32_t* hot = nullptr;  // [2 ntiles + 1]: per-tile reports, the hot list's length, its entries
-  int64_t ntiles = 0;
+  // per-half reports [2 x the one-product pass's 256 x 256 tiles], the hot list's length, its entries [ntiles]
+  uint32_t* hot = nullptr;
+  int64_t ntiles = 0;       // in 256 x 128 tiles, the hot-tile pass's unit
   size_t bytes = 0;
 };
 void gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, int64_t ldo, hipStream_t s,

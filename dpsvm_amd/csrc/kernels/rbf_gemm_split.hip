@@ -35,7 +35,7 @@
 //
 // Which kernel a Gram runs: launch::split_gram_path (kernels.hpp), first
 // eligible of
-//   Adaptive    h1s one-product pass + w64p over the hot tiles: cold_tau > 0,
+//   Adaptive    h1 one-product pass + w64p over the hot tiles: cold_tau > 0,
 //               >= 5 k blocks, ldo < 2^21, rows / tile tables in 32 bits (the
 //               solver's resident Gram and its slabs)
 //   W64Persist  w64p: the same without cold_tau, and M ldo, N ldo < 2^32
@@ -47,7 +47,7 @@
 // profiles/.
 //
 // This file: the operand prep (split rows, h planes, log2 norms), the STORE
-// GEMMs (tile, glds, w64, w64p, h1s) and their launch plan.  The working-set
+// GEMMs (tile, glds, w64, w64p, h1) and their launch plan.  The working-set
 // row GEMM is in rbf_rows_split.hip, the decision GEMM in
 // rbf_predict_split.hip; the k blocks and epilogues all of them share are in
 // split_mma.hpp.
@@ -65,6 +65,7 @@
 #include "dpsvm/common.hpp"
 #include "device_util.hpp"
 #include "kernels.hpp"
+#include "gram_tile_order.hpp"
 #include "split_mma.hpp"
 #include "../runtime/hip_check.hpp"
 
@@ -836,71 +837,66 @@ __global__ __launch_bounds__(kW64Threads, 1) void rbf_gemm_split_w64p_kernel(
 // those tiles with all three products.  The H accumulator's MFMA sequence is
 // the three-product kernels' (same k order), so K1 and the rule's inputs are
 // the same bits in both passes.
-// Tiles and the persistent LDS-DMA ring are the w64p kernel's; the operands are
-// h planes (split_hplane_kernel: a row's h halves back to back, zero-padded to an
-// even block count), so a ring stage is 64 k = one whole 128-B line a row; an
-// odd block count's last stage multiplies the zero pad (H + 0 is H).  64
-// accumulator registers instead of 192.  Measured and dropped on the way
-// (profiles/r6_gram_adapt/h1_ablation_kernels.txt): one workgroup whose waves
-// both feed the ring and store (each tile then waits on its own stores:
-// 6.32 ms), the split rows' h halves as operands (half of every fetched line
-// unused: 7.32 ms), deferring a tile's stores into the next tile's ring (spills,
-// 10.3 ms), two workgroups per CU of 128 x 64 waves over 32-k stages (8.5 ms),
-// staggered workgroup starts (no change).
-// tile_hot [ntiles] (zeroed): per-tile report counts; hot[0] (zeroed) the
-// list's length, hot[1 ..] the reported tiles' table entries.
+// The operands are h planes (split_hplane_kernel, stage-major); the tile is
+// 256 x 256, the pair of 256 x 128 tiles the hot-tile pass counts in: 832 KB of
+// operands through the CU per 256 KB of stores instead of 1,248 KB (the kernel
+// is bound by the bytes through the CU's one memory pipeline, not by MFMAs or
+// latency: profiles/gram_overlap/).  The kernel is described at its definition
+// below.  Measured and dropped on the way (256 x 128 tiles,
+// profiles/r6_gram_adapt/h1_ablation_kernels.txt, profiles/gram_overlap/): the
+// split rows' h halves as operands (half of every fetched line unused: 7.32
+// ms), deferring a tile's stores into the next tile's ring (spills, 10.3 ms),
+// two workgroups per CU of 128 x 64 waves over 32-k stages (8.5 ms),
+// staggered workgroup starts (no change); DMA waves apart from the compute
+// waves were worth 3.5% there (6.32 -> 6.10 ms) and have no room beside the
+// 16 compute waves of this tile.
 // ---------------------------------------------------------------------------
-// the one-product epilogue's math: H becomes K1 = exp2(t1) in place; returns
-// (wave-uniform) whether any of the wave's elements is hot
-__device__ __forceinline__ bool h1_values(f16v (&H)[2][2], const float* s_sq, const int32_t* s_sh, const float* s_r,
-                                          int lane, int wm, int wn, float gamma, float c0, float c1) {
+// the one-product epilogue's math for one 32 x 32 MFMA block (i, j) of a wave:
+// v becomes K1 = exp2(t1) in place; returns (per lane) whether one of the
+// lane's elements is hot.  One block at a time, each followed by its stores
+// (h1_store_block): the wave's first stores enter the memory pipeline after one
+// block's values, not after all four
+__device__ __forceinline__ bool h1_block_values(f16v& v, int i, int j, const float* s_sq, const int32_t* s_sh,
+                                                const float* s_r, int lane, int wm, int wn, float gamma, float c0,
+                                                float c1) {
   constexpr int TM = 256;
   const int hl = lane >> 5;
   const float ng = -gamma, l2e = 1.4426950408889634f;
   bool hot = false;
+  const int cl = wn * 64 + 32 * j + (lane & 31);
+  const float bsq = s_sq[TM + cl];
+  const int nbsh = -s_sh[TM + cl];
+  const float rb = s_r[TM + cl];
+  const int lr0 = wm * 64 + 32 * i + 4 * hl;
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int cl = wn * 64 + 32 * j + (lane & 31);
-    const float bsq = s_sq[TM + cl];
-    const int nbsh = -s_sh[TM + cl];
-    const float rb = s_r[TM + cl];
+  for (int g = 0; g < 4; ++g) {
+    const f4 asq = *(const f4*)(s_sq + lr0 + 8 * g);
+    const i4v ash = *(const i4v*)(s_sh + lr0 + 8 * g);
+    const f4 ar = *(const f4*)(s_r + lr0 + 8 * g);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      // one 32 x 32 block's row data at a time (the scheduler hoisting every
-      // block's LDS reads ahead made the specialised kernel spill)
-      __builtin_amdgcn_sched_barrier(0);
-      const int lr0 = wm * 64 + 32 * i + 4 * hl;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f4 asq = *(const f4*)(s_sq + lr0 + 8 * g);
-        const i4v ash = *(const i4v*)(s_sh + lr0 + 8 * g);
-        const f4 ar = *(const f4*)(s_r + lr0 + 8 * g);
-#pragma unroll
-        for (int e = 0; e < 4; e += 2) {
-          const int r = 4 * g + e;
-          f2 h, dot, sq, d2, t;
-          h.x = H[i][j][r];
-          h.y = H[i][j][r + 1];
-          {
+    for (int e = 0; e < 4; e += 2) {
+      const int r = 4 * g + e;
+      f2 h, dot, sq, d2, t;
+      h.x = v[r];
+      h.y = v[r + 1];
+      {
 #pragma clang fp contract(off)
-            dot.x = ldexpf(h.x, nbsh - ash[e]);
-            dot.y = ldexpf(h.y, nbsh - ash[e + 1]);
-            sq.x = asq[e];
-            sq.y = asq[e + 1];
-            d2 = (sq + bsq) - (dot + dot);
-            d2.x = d2.x > 0.f ? d2.x : 0.f;
-            d2.y = d2.y > 0.f ? d2.y : 0.f;
-            t = (ng * d2) * l2e;
-            hot |= !split_cold(t.x, ar[e] + rb, c0, c1);
-            hot |= !split_cold(t.y, ar[e + 1] + rb, c0, c1);
-          }
-          H[i][j][r] = __builtin_amdgcn_exp2f(t.x);
-          H[i][j][r + 1] = __builtin_amdgcn_exp2f(t.y);
-        }
+        dot.x = ldexpf(h.x, nbsh - ash[e]);
+        dot.y = ldexpf(h.y, nbsh - ash[e + 1]);
+        sq.x = asq[e];
+        sq.y = asq[e + 1];
+        d2 = (sq + bsq) - (dot + dot);
+        d2.x = d2.x > 0.f ? d2.x : 0.f;
+        d2.y = d2.y > 0.f ? d2.y : 0.f;
+        t = (ng * d2) * l2e;
+        hot |= !split_cold(t.x, ar[e] + rb, c0, c1);
+        hot |= !split_cold(t.y, ar[e + 1] + rb, c0, c1);
       }
+      v[r] = __builtin_amdgcn_exp2f(t.x);
+      v[r + 1] = __builtin_amdgcn_exp2f(t.y);
     }
   }
-  return __builtin_amdgcn_ballot_w64(hot) != 0;
+  return hot;
 }
 
 // the stores of one 32 x 32 MFMA block (i, j) of a wave's values v: 16 direct
@@ -910,7 +906,7 @@ __device__ __forceinline__ bool h1_values(f16v (&H)[2][2], const float* s_sq, co
 // stores as w64_epilogue_pe's (above), which keeps its own copy: see there.
 __device__ __forceinline__ void h1_store_block(const f16v& v, int i, int j, int lane, int wm, int wn, bool mirror,
                                                bool valid, float* out, int m0, int n0, int M, int N, int ldo) {
-  constexpr int TM = 256, TN = 128;
+  constexpr int TM = 256, TN = 256;
   constexpr uint32_t OOB = 0x80000000u;
   const int hl = lane >> 5;
   float* const ob = out + ((int64_t)m0 * ldo + n0);
@@ -957,160 +953,98 @@ __device__ __forceinline__ void h1_store_block(const f16v& v, int i, int j, int 
   }
 }
 
-__device__ __forceinline__ uint32_t clock_lo_v() {  // s_memtime's low word, in a vector register
-  uint32_t c = (uint32_t)__builtin_amdgcn_s_memtime();
-  asm volatile("" : "+v"(c));
-  return c;
+template <class T>
+__device__ __forceinline__ T pick(bool c, T a, T b) {  // c ? a : b of two values
+  return c ? a : b;
 }
 
-// the h1s kernel's DMA waves (a function of its own: its uniform addressing
-// does not share the compute waves' scalar registers).  ST (diagnostics):
-// per tile, stamps[16 L + 8 ..] = the first wave's cycles at the barrier of
-// the tile's stage 0 (where it waits out the previous tile's epilogue), at
-// the other stages' barriers, waiting for its own DMA to land, and in all
-template <bool ST>
-__device__ __noinline__ void h1s_dma(const u4* __restrict__ A, const int32_t* __restrict__ Ash,
-                                     const float* __restrict__ Asq, const float* __restrict__ Ar, int M,
-                                     const u4* __restrict__ B, const int32_t* __restrict__ Bsh,
-                                     const float* __restrict__ Bsq, const float* __restrict__ Br, int N, int nst,
-                                     const uint32_t* __restrict__ tiles, int ntiles, int L, int dwave, int lane,
-                                     u4* lds, uint32_t* s_rows, uint64_t* stamps) {
-  constexpr int TM = 256, TN = 128, ROWS = TM + TN, NB = 3, RD = 1536;
-  const int G = gridDim.x;
-  const uint32_t rs = (uint32_t)nst * 8;
-  uint32_t t = tiles[L];
-  int Ln = L + G;
-  uint32_t tn_next = Ln < ntiles ? tiles[Ln] : 0u;
-  uint32_t g = 0;
-  const int dw = __builtin_amdgcn_readfirstlane(dwave);
-    const int p = lane & 7;
-    uint32_t off_e = 16u * ((uint32_t)(lane >> 3) * rs + (uint32_t)(p ^ (lane >> 4)));
-    uint32_t off_o = 16u * ((uint32_t)(lane >> 3) * rs + (uint32_t)(p ^ ((lane >> 4) + 4)));
-    asm volatile("" : "+v"(off_e), "+v"(off_o));
-    auto stage = [&](int m0_, int n0_, int st, int buf) {
-      const uint32_t uA = (uint32_t)(m0_ + 64 * dw) * rs + (uint32_t)st * 8;
-      const uint32_t uB = (uint32_t)(n0_ + 32 * dw) * rs + (uint32_t)st * 8;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) w64p_piece(A, lds, uA, 8 * rs, 64 * dw * 8, off_e, off_o, buf, i);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w64p_piece(B, lds, uB, 8 * rs, (TM + 32 * dw) * 8, off_e, off_o, buf, i);
-    };
-    // row data: DMA wave dw = 0 / 1 / 2 loads |x|^2 / shifts / log2 |x| of the 384 rows (six chunks of 64:
-    // A rows for i < 4); wave 3 loads a valid word into the padding (every stage wait counts 6)
-    const uint32_t* const rd_a =
-        dw == 0 ? (const uint32_t*)Asq : dw == 1 ? (const uint32_t*)Ash : (const uint32_t*)Ar;
-    const uint32_t* const rd_b =
-        dw == 0 ? (const uint32_t*)Bsq : dw == 1 ? (const uint32_t*)Bsh : (const uint32_t*)Br;
-    auto rowdata = [&](int m0_, int n0_, int par_) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int r = 64 * i + lane;
-        const int ri = i < 4 ? min(m0_ + r, M - 1) : min(n0_ + (r - TM), N - 1);
-        const uint32_t* src = dw == 3 ? (const uint32_t*)Asq : (i < 4 ? rd_a : rd_b) + ri;
-        lds_dma4(src, s_rows + par_ * RD + 64 * (6 * dw + i));
-      }
-    };
-    {
-      const int m0 = (int)(t >> 16) * TM, n0 = (int)(t & 0xffffu) * TN;
-      stage(m0, n0, 0, 0);
-      stage(m0, n0, 1, 1);
-      rowdata(m0, n0, 0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    int par = 0;
-    while (true) {
-      const bool has_next = Ln < ntiles;  // uniform
-      const int m0 = (int)(t >> 16) * TM, n0 = (int)(t & 0xffffu) * TN;
-      const uint32_t tp = has_next ? tn_next : t;
-      const int nm0 = (int)(tp >> 16) * TM, nn0 = (int)(tp & 0xffffu) * TN;
-      uint32_t c_bar0 = 0, c_bar = 0, c_land = 0, c_t0 = 0;  // (the clock's low word)
-      if constexpr (ST) c_t0 = clock_lo_v();
-#pragma clang loop unroll(disable)
-      for (int s = 0; s < nst; ++s) {
-        uint32_t ca = 0, cb = 0;
-        if constexpr (ST) ca = clock_lo_v();
-        // stage s landed: younger are stage s + 1 (12 pieces) and, at s == 1, the next tile's row data (6)
-        if (s == 1) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        if constexpr (ST) cb = clock_lo_v();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if constexpr (ST) {
-          const uint32_t cc = clock_lo_v();
-          c_land += cb - ca;
-          if (s == 0) c_bar0 = cc - cb;
-          else c_bar += cc - cb;
-        }
-        const bool own = s + 2 < nst;
-        stage(own ? m0 : nm0, own ? n0 : nn0, own ? s + 2 : s + 2 - nst, (int)((g + 2) % NB));
-        // the next tile's row data (the last tile reloads its own into the unused parity: the count stays 6)
-        if (s == 0) rowdata(nm0, nn0, par ^ 1);
-        ++g;
-      }
-      if constexpr (ST) {
-        const uint32_t c_t1 = clock_lo_v();
-        if (dw == 0 && lane == 0) {
-          uint64_t* o = stamps + (size_t)L * 16 + 8;
-          o[0] = c_bar0;
-          o[1] = c_bar;
-          o[2] = c_land;
-          o[3] = c_t1 - c_t0;
-        }
-      }
-      if (!has_next) break;
-      L = Ln;
-      t = tn_next;
-      par ^= 1;
-      Ln = L + G;
-      if (Ln < ntiles) tn_next = tiles[Ln];
-    }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-constexpr int kH1sThreads = 768;  // 8 compute waves + 4 DMA waves
-// ST (diagnostics, set_gram_stamps): 16 words a tile — the first compute wave's s_memtime at the tile's start,
-// stage 0 landed, k loop done, values done, stores issued, s_memrealtime at start / end, the tile; then h1s_dma's
-template <bool ST>
-__global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
+constexpr int kH1Threads = 1024;  // 16 waves of 64 x 64: 4 x 4 over a 256 x 256 tile
+// The one-product pass: 256 x 256 tiles (the pair of 256 x 128 tiles (tx, 2 u), (tx, 2 u + 1) in one), one
+// persistent workgroup a CU.  Operands are the stage-major h planes (split_hplane_kernel): a ring stage is 32 k of
+// the tile's 256 A rows and 256 B rows, two contiguous 16-KiB blocks of whole lines; FOUR 32-KiB buffers, three
+// stages in flight (96 KiB), the ring running on across tiles as in the w64p kernel.  Every wave issues two of a
+// stage's 32 LDS-DMA pieces (waves 0-7: A rows 32 w + 16 i, waves 8-15: B rows), multiplies its 64 x 64 block
+// (two k16 steps a stage: the H accumulator's MFMA sequence of every other kernel) and stores it; every epilogue
+// ends with vmcnt(0), so the loop's one counted wait holds at the next tile's first stage.  LDS rows are 64 B:
+// chunk c of stage row r sits at position c ^ ((r >> 2) & 3), so the 16 rows of a ds_read_b128 lane group hit 16
+// distinct bank quads; the swizzle is in the lanes' source offsets, which are the same for every piece.
+// Epilogue: one 32 x 32 block at a time, its values then its stores (h1_block_values / h1_store_block).
+// Symmetric: tile (tx, u) is computed iff u >= tx; a tile right of the diagonal is also stored transposed, a
+// diagonal tile computes both triangles and stores directly only.  Hot reports are per 256 x 128 half, as the
+// hot-tile pass and gram_adapt_last count: half (tx, 2 u + h) is appended once iff one of its elements fails
+// split_cold (half_hot [2 ntiles], zeroed: the per-half report counts; hot[0] the list's length, hot[1 ..] its
+// entries).  tn: the Gram's count of 128-column tiles (an odd count: the last tile has a left half only — its
+// right half's stores fall to the buffer range check, its row data indices clamp, and it is never reported).
+// RA / RB: the rows of the A / B planes (multiples of 256).
+__global__ __launch_bounds__(kH1Threads, 1) void rbf_gemm_split_h1_kernel(
     const u4* __restrict__ A, const int32_t* __restrict__ Ash, const float* __restrict__ Asq,
-    const float* __restrict__ Ar, int M, const u4* __restrict__ B, const int32_t* __restrict__ Bsh,
-    const float* __restrict__ Bsq, const float* __restrict__ Br, int N, int nkb, float gamma, float c0, float c1,
-    float* __restrict__ out, int ldo, int sym, const uint32_t* __restrict__ tiles, int ntiles,
-    uint32_t* __restrict__ tile_hot, uint32_t* __restrict__ hot, uint64_t* __restrict__ stamps) {
-  constexpr int WN = 2, TM = 256, TN = 128, ROWS = TM + TN, CPR = 8, BUF = ROWS * CPR, NB = 3, RD = 1536;
-  __shared__ u4 lds[NB * BUF + 2 * RD / 4];  // 3 operand buffers, then row data [2][RD]
+    const float* __restrict__ Ar, int M, int RA, const u4* __restrict__ B, const int32_t* __restrict__ Bsh,
+    const float* __restrict__ Bsq, const float* __restrict__ Br, int N, int RB, int nst, float gamma, float c0,
+    float c1, float* __restrict__ out, int ldo, int sym, const uint32_t* __restrict__ tiles, int ntiles, int tn,
+    uint32_t* __restrict__ half_hot, uint32_t* __restrict__ hot) {
+  constexpr int WN = 4, TM = 256, TN = 256, ROWS = TM + TN, CPR = 4, BUF = ROWS * CPR, NB = 4, RD = 2048;
+  __shared__ u4 lds[NB * BUF + 2 * RD / 4];  // 4 operand buffers, then row data [2][RD]: |x|^2, shifts, log2 |x| [ROWS]
   uint32_t* const s_rows = (uint32_t*)(lds + NB * BUF);
   const int G = gridDim.x;
   int L = blockIdx.x;
-  if (L >= ntiles) return;  // uniform
+  if (L >= ntiles) return;  // uniform: no barrier reached
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nst = (nkb + 1) >> 1;  // ring stages a tile (launcher: nkb >= 5)
-  if (__builtin_amdgcn_readfirstlane(wave) >= 8) {
-    h1s_dma<ST>(A, Ash, Asq, Ar, M, B, Bsh, Bsq, Br, N, nst, tiles, ntiles, L, wave - 8, lane, lds, s_rows, stamps);
-    return;
-  }
-  // ---- compute waves: the h1 kernel's 64 x 64 waves; never a load, so their stores drain unwaited ----
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
+  // this wave's pieces of a stage: rows 32 wv + 16 i of the stage's 512 (A rows, then B rows)
+  const bool a_wave = wv < 8;  // uniform
+  const u4* const P = pick(a_wave, A, B);
+  const int64_t R = pick(a_wave, RA, RB);
+  const int prow = a_wave ? 32 * wv : 32 * (wv - 8);
+  uint32_t loff = 16u * (uint32_t)((lane >> 2) * 4 + ((lane & 3) ^ ((lane >> 4) & 3)));  // bytes within a piece
+  asm volatile("" : "+v"(loff));
+  auto stage_dma = [&](int m0_, int n0_, int st, int buf) {
+    const char* src = (const char*)(P + ((int64_t)st * R + pick(a_wave, m0_, n0_) + prow) * CPR);  // uniform
+    u4* dst = lds + buf * BUF + 32 * wv * CPR;
+    lds_dma16(src + loff, dst);
+    lds_dma16(src + 1024 + loff, dst + 16 * CPR);
+  };
+  // a tile's row data into parity par_: 32 instructions of 64 dwords, two a wave; q = wv + 16 i < 24: array q / 8
+  // (|x|^2, shifts, log2 |x|), rows 64 (q % 8) .. (A rows below 256); the rest load a valid word into the padding
+  auto rowdata = [&](int m0_, int n0_, int par_) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int q = wv + 16 * i, ch = q & 7;  // uniform
+      const bool a_rows = ch < 4, pad = q >= 24;
+      // (pick: by value — a conditional on two captured pointers is an lvalue, and its address select keeps
+      // the captures in scratch)
+      const float* const fa = pick(q < 8 || pad, Asq, Ar);
+      const float* const fb = pick(pad, Asq, pick(q < 8, Bsq, Br));
+      const uint32_t* base = pick(q >= 8 && q < 16, (const uint32_t*)pick(a_rows, Ash, Bsh),
+                                  (const uint32_t*)pick(a_rows, fa, fb));
+      const int r = 64 * (ch & 3) + lane;
+      const int ri = pad ? min(lane, M - 1) : a_rows ? min(m0_ + r, M - 1) : min(n0_ + r, N - 1);
+      lds_dma4(base + ri, s_rows + par_ * RD + 64 * q);
+    }
+  };
   uint32_t t = tiles[L];
   int Ln = L + G;
   uint32_t tn_next = Ln < ntiles ? tiles[Ln] : 0u;
-  uint32_t g = 0;
-  const int wm = wave / WN, wn = wave % WN, hl = lane >> 5;
-  const int sw = ((lane & 31) >> 1) & 7;
-  const int ra0 = (wm * 64 + (lane & 31)) * CPR;
-  const int rb0 = (TM + wn * 64 + (lane & 31)) * CPR;
+  uint32_t g = 0;  // stages started over all of this workgroup's tiles: ring buffer g % NB
+  {
+    const int m0 = (int)(t >> 16) * TM, n0 = (int)(t & 0xffffu) * TN;
+    rowdata(m0, n0, 0);
+    stage_dma(m0, n0, 0, 0);  // (launcher: nst >= 5)
+    stage_dma(m0, n0, 1, 1);
+    stage_dma(m0, n0, 2, 2);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the loop's first wait counts 4 younger: tile 0 starts landed
+  }
+  const int sw = (lane >> 2) & 3;
+  const uint32_t ra0 = (uint32_t)(wm * 64 + (lane & 31)) * 64u, rb0 = (uint32_t)(TM + wn * 64 + (lane & 31)) * 64u;
+  const uint32_t ck0 = 16u * (uint32_t)(hl ^ sw), ck1 = 16u * (uint32_t)((2 + hl) ^ sw);  // k16 steps 0 / 1
   int par = 0;
-  // (stamps: the clocks' low words, each stored as it is read — none stays live over the k loop)
-  auto stamp = [&](int i, uint32_t v) {
-    if (tid == 0) stamps[(size_t)L * 16 + i] = v;
-  };
   while (true) {
     const bool has_next = Ln < ntiles;  // uniform
-    const int tx = (int)(t >> 16), ty = (int)(t & 0xffffu);
-    const int m0 = tx * TM, n0 = ty * TN;
-    if constexpr (ST) {
-      stamp(0, (uint32_t)__builtin_amdgcn_s_memtime());
-      stamp(5, (uint32_t)__builtin_amdgcn_s_memrealtime());
-    }
+    const int tx = (int)(t >> 16), tu = (int)(t & 0xffffu);
+    const int m0 = tx * TM, n0 = tu * TN;
+    // (the last tile prefetches its own stages 0-2 into dead buffers: no branch in the loop)
+    const uint32_t tp = has_next ? tn_next : t;
+    const int nm0 = (int)(tp >> 16) * TM, nn0 = (int)(tp & 0xffffu) * TN;
     f16v H[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1118,70 +1052,70 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) H[i][j][r] = 0.f;
-    // FS: the tile's first stage (stamps)
-    auto stage = [&]<bool FS = false>() {
-      ring_barrier();
-      if constexpr (ST && FS) stamp(1, (uint32_t)__builtin_amdgcn_s_memtime());
-      const u4* buf = lds + (g % NB) * BUF;
-      const uint32_t abase = lds_addr(buf + ra0), bbase = lds_addr(buf + rb0);
-      auto rd = [&](int q, h8& a0, h8& a1, h8& b0, h8& b1) {
-        const uint32_t c = 16u * (uint32_t)((2 * q + hl) ^ sw);
-        const uint32_t pa = abase + c, pb = bbase + c;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(a0) : "v"(pa) : "memory");
-        asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(a1) : "v"(pa) : "memory");
-        asm volatile("ds_read_b128 %0, %1" : "=v"(b0) : "v"(pb) : "memory");
-        asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(b1) : "v"(pb) : "memory");
-      };
-      auto mma = [&](const h8& a0, const h8& a1, const h8& b0, const h8& b1) {
-        H[0][0] = mfma32_f16(a0, b0, H[0][0]);
-        H[0][1] = mfma32_f16(a0, b1, H[0][1]);
-        H[1][0] = mfma32_f16(a1, b0, H[1][0]);
-        H[1][1] = mfma32_f16(a1, b1, H[1][1]);
-      };
-      // (an odd block count's last stage multiplies the h plane's zero pad: H + 0 is H, bit for bit)
-      h8 x0, x1, x2, x3, y0, y1, y2, y3;
-      rd(0, x0, x1, x2, x3);
-      rd(1, y0, y1, y2, y3);
-      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
-      mma(x0, x1, x2, x3);
-      rd(2, x0, x1, x2, x3);
-      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3));
-      mma(y0, y1, y2, y3);
-      rd(3, y0, y1, y2, y3);
-      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
-      mma(x0, x1, x2, x3);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3));
-      mma(y0, y1, y2, y3);
-      ++g;
-    };
-    if constexpr (ST) stage.template operator()<true>();
 #pragma clang loop unroll(disable)
-    for (int s = ST ? 1 : 0; s < nst; ++s) stage();
-    if constexpr (ST) stamp(2, (uint32_t)__builtin_amdgcn_s_memtime());
+    for (int s = 0; s < nst; ++s) {
+      // retire stage s's DMA: stages s + 1 and s + 2 (two pieces a wave each) may stay in flight
+      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      ring_barrier();
+      // stage s + 3 of this tile, or stage s + 3 - nst of the next, into the buffer of stage g - 1
+      const bool own = s + 3 < nst;
+      stage_dma(own ? m0 : nm0, own ? n0 : nn0, own ? s + 3 : s + 3 - nst, (int)((g + 3) % NB));
+      const uint32_t bb = lds_addr(lds + (g % NB) * BUF);
+      const uint32_t pa = bb + ra0, pb = bb + rb0;
+      auto rd = [&](uint32_t c, h8& a0, h8& a1, h8& b0, h8& b1) {
+        const uint32_t qa = pa + c, qb = pb + c;
+        asm volatile("ds_read_b128 %0, %1" : "=v"(a0) : "v"(qa) : "memory");
+        asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(a1) : "v"(qa) : "memory");  // + 32 rows
+        asm volatile("ds_read_b128 %0, %1" : "=v"(b0) : "v"(qb) : "memory");
+        asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(b1) : "v"(qb) : "memory");
+      };
+      h8 x0, x1, x2, x3, y0, y1, y2, y3;
+      rd(ck0, x0, x1, x2, x3);
+      rd(ck1, y0, y1, y2, y3);
+      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
+      H[0][0] = mfma32_f16(x0, x2, H[0][0]);
+      H[0][1] = mfma32_f16(x0, x3, H[0][1]);
+      H[1][0] = mfma32_f16(x1, x2, H[1][0]);
+      H[1][1] = mfma32_f16(x1, x3, H[1][1]);
+      __builtin_amdgcn_sched_barrier(0);  // (the second wait would otherwise move above the first step's MFMAs)
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3));
+      H[0][0] = mfma32_f16(y0, y2, H[0][0]);
+      H[0][1] = mfma32_f16(y0, y3, H[0][1]);
+      H[1][0] = mfma32_f16(y1, y2, H[1][0]);
+      H[1][1] = mfma32_f16(y1, y3, H[1][1]);
+      ++g;
+    }
+    // the next tile's row data into the other parity (last read by the previous tile's epilogue)
+    if (has_next) rowdata(nm0, nn0, par ^ 1);
     int el = lane;
     asm volatile("" : "+v"(el));
     const float* rows = (const float*)(s_rows + par * RD);
-    const bool hotw = h1_values(H, rows, (const int32_t*)(rows + ROWS), rows + 2 * ROWS, el, wm, wn, gamma, c0, c1);
-    if constexpr (ST) stamp(3, (uint32_t)__builtin_amdgcn_s_memtime());
-    const bool mirror = sym && ty > 2 * tx + (wm >> 1);
+    const bool mirror = sym && tu > tx;
+    // one 32 x 32 block at a time: its values, then its stores, so the waves feed the memory pipeline after
+    // the first block's values.  The hot flag is reduced to a wave-uniform bit per block: one per-lane flag over
+    // the four blocks lets the compiler sink every block's split_cold to the tile's end, its inputs live
+    // across the stores
+    bool hotw = false;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
+      for (int i = 0; i < 2; ++i) {
+        __builtin_amdgcn_sched_barrier(0);
+        hotw |= __builtin_amdgcn_ballot_w64(h1_block_values(H[i][j], i, j, rows, (const int32_t*)(rows + ROWS),
+                                                            rows + 2 * ROWS, el, wm, wn, gamma, c0, c1)) != 0;
         __builtin_amdgcn_sched_barrier(0);
         h1_store_block(H[i][j], i, j, el, wm, wn, mirror, true, out, m0, n0, M, N, ldo);
       }
-    if (hotw && lane == 0) {  // the tile's first report appends it to the list
-      if (atomicAdd(tile_hot + L, 1u) == 0u) {
+    const int half = wn >> 1, ty = 2 * tu + half;  // the wave's 256 x 128 half
+    if (hotw && ty < tn && lane == 0) {  // the half's first report appends it to the list
+      if (atomicAdd(half_hot + 2 * L + half, 1u) == 0u) {
         const uint32_t k = atomicAdd(hot, 1u);
-        hot[1 + k] = t;
+        hot[1 + k] = ((uint32_t)tx << 16) | (uint32_t)ty;
       }
     }
-    if constexpr (ST) {
-      stamp(4, (uint32_t)__builtin_amdgcn_s_memtime());
-      stamp(6, (uint32_t)__builtin_amdgcn_s_memrealtime());
-      stamp(7, t);
-    }
+    // the stores, the next tile's stages 0-2 and its row data retired here: the loop's uniform vmcnt(4) then
+    // holds at the next tile's first stage (and no DMA is in flight when the kernel ends)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (!has_next) break;
     L = Ln;
     t = tn_next;
@@ -1189,19 +1123,17 @@ __global__ __launch_bounds__(kH1sThreads, 1) void rbf_gemm_split_h1s_kernel(
     Ln = L + G;
     if (Ln < ntiles) tn_next = tiles[Ln];
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// h planes of split rows (the one-product pass's operands): row r holds the h
-// halves of its nkb split blocks back to back, then zeros to an even count
+// h planes of split rows (the one-product pass's operands), stage-major: [k block][row][32 halfs] — a tile's
+// 256-row panel of one ring stage is one contiguous 16-KiB block of whole 128-B lines
 __global__ __launch_bounds__(256) void split_hplane_kernel(const u4* __restrict__ src, int64_t rows, int nkb,
                                                           u4* __restrict__ dst) {
-  const int nq = ((nkb + 1) >> 1) * 8;  // u4 per plane row
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= rows * nq) return;
-  const int64_t r = e / nq;
-  const int q = (int)(e - r * nq), b = q >> 2, c = q & 3;
-  dst[e] = b < nkb ? src[r * nkb * 8 + b * 8 + c] : u4{0u, 0u, 0u, 0u};
+  if (e >= rows * nkb * 4) return;
+  const int64_t b = e / (rows * 4), q = e - b * rows * 4, r = q >> 2;
+  const int c = (int)(q & 3);
+  dst[e] = src[r * nkb * 8 + b * 8 + c];
 }
 
 // R = log2 |x| = split_log2norm(|x|^2) of n rows (the adaptive Gram's rule input)
@@ -1311,26 +1243,22 @@ const TileTable& sym_tile_table(int64_t tm, int64_t tn, hipStream_t s, bool sym 
   // Three-product kernels: GM 4 / CH 32 (an XCD's chunk: 4 A panels x 8 B
   // panels), 9.34-9.45 ms vs 9.47-9.50 for GM 8 / CH 64
   // (profiles/r5_gram_tile_order_ab.txt; bit-identical output).  The one-product
-  // pass: 8 / 64, 6.73-6.93 vs 7.03-7.10 ms for 4 / 32
-  // (profiles/r6_gram_adapt/h1_tile_order_sweep.txt)
-  std::vector<uint32_t> order;
-  const int64_t GM = one_product ? 8 : 4, CH = one_product ? 64 : 32;
-  for (int64_t g0 = 0; g0 < tm; g0 += GM) {
-    const int64_t gm = std::min(GM, tm - g0);
-    for (int64_t ty = 0; ty < tn; ++ty)
-      for (int64_t tx = g0; tx < g0 + gm; ++tx)
-        if (!sym || ty >= 2 * tx) order.push_back((uint32_t)((tx << 16) | ty));
-  }
-  const int64_t total = (int64_t)order.size(), full = total / (8 * CH) * (8 * CH);
-  std::vector<uint32_t> tab((size_t)total);
-  for (int64_t L = 0; L < total; ++L) {  // workgroup L runs on XCD L % 8: XCD x takes chunks x, x + 8, ...
-    int64_t T = L;
-    if (L < full) {
-      const int64_t xcd = L % 8, local = L / 8;
-      T = ((local / CH) * 8 + xcd) * CH + local % CH;
+  // pass has its own table of 256 x 256 tiles (gram_tile_order.hpp)
+  std::vector<uint32_t> tab;
+  if (one_product) {
+    tab = gram_tile_order(tm, tn, sym);  // 256 x 256 tiles (gram_tile_order.hpp)
+  } else {
+    std::vector<uint32_t> order;
+    const int64_t GM = 4, CH = 32;
+    for (int64_t g0 = 0; g0 < tm; g0 += GM) {
+      const int64_t gm = std::min(GM, tm - g0);
+      for (int64_t ty = 0; ty < tn; ++ty)
+        for (int64_t tx = g0; tx < g0 + gm; ++tx)
+          if (!sym || ty >= 2 * tx) order.push_back((uint32_t)((tx << 16) | ty));
     }
-    tab[(size_t)L] = order[(size_t)T];
+    tab = xcd_deal(order, CH);
   }
+  const int64_t total = (int64_t)tab.size();
   TileTable t;
   t.count = total;
   HIP_CHECK(hipMalloc((void**)&t.dev, (size_t)total * sizeof(uint32_t)));
@@ -1369,14 +1297,15 @@ void gram_adapt_prep(const void* A, const float* Asq, int64_t M, int dp, int64_t
   const int nkb = (dp + 31) / 32;
   const int64_t tm2 = (M + 255) / 256, tn = (M + 127) / 128;
   const int64_t ntiles = sym_tile_table(tm2, tn, s, true).count;
-  const int64_t nq = (int64_t)((nkb + 1) / 2) * 8, ra = tm2 * 256;
-  const size_t pb = (size_t)ra * nq * 16, rb = (size_t)M * 4, hb = (size_t)(2 * ntiles + 1) * 4;
+  const int64_t nt256 = sym_tile_table(tm2, tn, s, true, true).count;
+  const int64_t ra = tm2 * 256, np = ra * nkb * 4;  // stage-major planes: [nkb][ra] rows of 4 u4
+  const size_t pb = (size_t)np * 16, rb = (size_t)M * 4, hb = (size_t)(2 * nt256 + 1 + ntiles) * 4;
   HIP_CHECK(hipMalloc(&prep->planes, pb));
   HIP_CHECK(hipMalloc((void**)&prep->r, rb));
   HIP_CHECK(hipMalloc((void**)&prep->hot, hb));
   prep->bytes = pb + rb + hb;
-  dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, s>>>((const dev::u4*)A, ra, nkb,
-                                                                                    (dev::u4*)prep->planes);
+  dev::split_hplane_kernel<<<dim3((unsigned)((np + 255) / 256)), 256, 0, s>>>((const dev::u4*)A, ra, nkb,
+                                                                             (dev::u4*)prep->planes);
   post_launch("split_hplane", s);
   dev::split_log2norm_kernel<<<dim3((unsigned)((M + 255) / 256)), 256, 0, s>>>(Asq, (int)M, prep->r);
   post_launch("split_log2norm", s);
@@ -1461,13 +1390,15 @@ void launch_gram_w64_persist(const GramArgs& g) {
 }
 
 // adaptive: pass 1 one-product over every tile, pass 2 three products over the reported ones.  Its kernels
-// (h1s, w64p with AD) index a tile's stores from 64-bit tile bases with 32-bit offsets and the operand rows
+// (h1, w64p with AD) index a tile's stores from 64-bit tile bases with 32-bit offsets and the operand rows
 // in 32 bits: they also take Grams of more than 2^32 elements (200k rows: 160 GB)
 void launch_gram_adaptive(const GramArgs& g, float cold_tau, const GramAdaptPrep* prep) {
   const int64_t tm2 = (g.M + 255) / 256, tn = (g.N + 127) / 128;
-  const int64_t ntiles = sym_tile_table(tm2, tn, g.s, g.symmetric).count;
-  const int64_t grid = std::min<int64_t>(ntiles, persistent_grid_limit());
-  const auto& t1 = sym_tile_table(tm2, tn, g.s, g.symmetric, true);  // the one-product pass's own tile order
+  const int64_t ntiles = sym_tile_table(tm2, tn, g.s, g.symmetric).count;  // in 256 x 128 units
+  const auto& t1 = sym_tile_table(tm2, tn, g.s, g.symmetric, true);       // the one-product pass's 256 x 256 tiles
+  const int64_t nt256 = t1.count;
+  const int64_t grid1 = std::min<int64_t>(nt256, persistent_grid_limit());
+  const int64_t grid2 = std::min<int64_t>(ntiles, persistent_grid_limit());
   float c0 = 0.f, c1 = 0.f;
   split_cold_consts(g.gamma, cold_tau, &c0, &c1);
   // a solver's prep of these very rows: the h planes and R are there, the hot buffer is re-zeroed
@@ -1475,12 +1406,14 @@ void launch_gram_adaptive(const GramArgs& g, float cold_tau, const GramAdaptPrep
                    prep->ntiles == ntiles;
   const int64_t nr = g.symmetric ? g.M : g.M + g.N;
   float* r = pre ? prep->r : nullptr;
-  uint32_t* hb = pre ? prep->hot : nullptr;  // [ntiles] per-tile reports, then the list's length and entries
+  // [2 nt256] per-half report counts, then the hot list: its length and its entries (at most ntiles)
+  uint32_t* hb = pre ? prep->hot : nullptr;
   if (!pre) {
     HIP_CHECK(hipMallocAsync((void**)&r, (size_t)nr * 4, g.s));
-    HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * ntiles + 1) * 4, g.s));
+    HIP_CHECK(hipMallocAsync((void**)&hb, (size_t)(2 * nt256 + 1 + ntiles) * 4, g.s));
   }
-  HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(ntiles + 1) * 4, g.s));
+  HIP_CHECK(hipMemsetAsync(hb, 0, (size_t)(2 * nt256 + 1) * 4, g.s));
+  uint32_t* const hot = hb + 2 * nt256;
   float* br = r;
   if (!pre) {
     dev::split_log2norm_kernel<<<dim3((unsigned)((g.M + 255) / 256)), 256, 0, g.s>>>(g.Asq, (int)g.M, r);
@@ -1490,36 +1423,36 @@ void launch_gram_adaptive(const GramArgs& g, float cold_tau, const GramAdaptPrep
     }
     post_launch("split_log2norm", g.s);
   }
-  const void *hA = g.A, *hB = g.B;
+  // the stage-major h planes of the rows the tiles read (whole 256-row panels of A and of B)
+  const int64_t ra = tm2 * 256, rb = g.symmetric ? ra : (g.N + 255) / 256 * 256;
+  const dev::u4 *hA = nullptr, *hB = nullptr;
   dev::u4* planes = nullptr;
   if (pre) {
-    hA = hB = prep->planes;
-  } else {  // the h planes of the rows the tiles read (whole 256 / 128-row tiles)
-    const int64_t nq = (int64_t)((g.nkb + 1) / 2) * 8, ra = tm2 * 256, rb = g.symmetric ? 0 : tn * 128;
-    HIP_CHECK(hipMallocAsync((void**)&planes, (size_t)(ra + rb) * nq * 16, g.s));
-    dev::split_hplane_kernel<<<dim3((unsigned)((ra * nq + 255) / 256)), 256, 0, g.s>>>((const dev::u4*)g.A, ra, g.nkb,
-                                                                                      planes);
+    hA = hB = (const dev::u4*)prep->planes;
+  } else {
+    const int64_t npa = ra * g.nkb * 4, npb = g.symmetric ? 0 : rb * g.nkb * 4;
+    HIP_CHECK(hipMallocAsync((void**)&planes, (size_t)(npa + npb) * 16, g.s));
+    dev::split_hplane_kernel<<<dim3((unsigned)((npa + 255) / 256)), 256, 0, g.s>>>((const dev::u4*)g.A, ra, g.nkb,
+                                                                                  planes);
     hA = hB = planes;
     if (!g.symmetric) {
-      dev::split_hplane_kernel<<<dim3((unsigned)((rb * nq + 255) / 256)), 256, 0, g.s>>>((const dev::u4*)g.B, rb, g.nkb,
-                                                                                        planes + ra * nq);
-      hB = planes + ra * nq;
+      dev::split_hplane_kernel<<<dim3((unsigned)((npb + 255) / 256)), 256, 0, g.s>>>((const dev::u4*)g.B, rb, g.nkb,
+                                                                                    planes + npa);
+      hB = planes + npa;
     }
     post_launch("split_hplane", g.s);
   }
-  // (stamps, set_gram_stamps: the one-product pass's 16 words a tile; pass 2 runs unstamped)
-  auto h1k = g_gram_stamps ? dev::rbf_gemm_split_h1s_kernel<true> : dev::rbf_gemm_split_h1s_kernel<false>;
-  h1k<<<dim3((unsigned)grid), dev::kH1sThreads, 0, g.s>>>(
-      (const dev::u4*)hA, g.Ash, g.Asq, r, (int)g.M, (const dev::u4*)hB, g.Bsh, g.Bsq, br, (int)g.N, g.nkb, g.gamma, c0,
-      c1, g.out, (int)g.ldo, g.symmetric ? 1 : 0, t1.dev, (int)ntiles, hb, hb + ntiles, g_gram_stamps);
+  dev::rbf_gemm_split_h1_kernel<<<dim3((unsigned)grid1), dev::kH1Threads, 0, g.s>>>(
+      hA, g.Ash, g.Asq, r, (int)g.M, (int)ra, hB, g.Bsh, g.Bsq, br, (int)g.N, (int)rb, g.nkb, g.gamma, c0, c1, g.out,
+      (int)g.ldo, g.symmetric ? 1 : 0, t1.dev, (int)nt256, (int)tn, hb, hot);
   if (planes) HIP_CHECK(hipFreeAsync(planes, g.s));
   post_launch("rbf_gemm_split_h1", g.s);
-  dev::rbf_gemm_split_w64p_kernel<false, true><<<dim3((unsigned)grid), dev::kW64Threads, 0, g.s>>>(
+  dev::rbf_gemm_split_w64p_kernel<false, true><<<dim3((unsigned)grid2), dev::kW64Threads, 0, g.s>>>(
       (const dev::u4*)g.A, g.Ash, g.Asq, (int)g.M, (const dev::u4*)g.B, g.Bsh, g.Bsq, (int)g.N, g.nkb, g.gamma, g.out,
-      (int)g.ldo, g.symmetric ? 1 : 0, hb + ntiles + 1, 0, (int)tm2, (int)tn, nullptr, r, br, c0, c1, hb + ntiles);
+      (int)g.ldo, g.symmetric ? 1 : 0, hot + 1, 0, (int)tm2, (int)tn, nullptr, r, br, c0, c1, hot);
   post_launch("rbf_gemm_split_w64p_hot", g.s);
   if (!t_adapt_hot) HIP_CHECK(hipHostMalloc((void**)&t_adapt_hot, 4, hipHostMallocDefault));
-  HIP_CHECK(hipMemcpyAsync(t_adapt_hot, hb + ntiles, 4, hipMemcpyDeviceToHost, g.s));
+  HIP_CHECK(hipMemcpyAsync(t_adapt_hot, hot, 4, hipMemcpyDeviceToHost, g.s));
   t_adapt_tiles = ntiles;
   if (!pre) {
     HIP_CHECK(hipFreeAsync(r, g.s));

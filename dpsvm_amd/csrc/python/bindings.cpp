@@ -17,6 +17,7 @@
 #include "dpsvm/params_io.hpp"
 #include "dpsvm/problem.hpp"
 #include "dpsvm/ws_plan.hpp"
+#include "../kernels/gram_tile_order.hpp"
 #include "../kernels/kernels.hpp"
 
 namespace py = pybind11;
@@ -977,6 +978,10 @@ PYBIND11_MODULE(_C, m) {
   }, "the adaptive Gram's element rule constants (c0, c1): cold iff R_i + R_j <= c1 and t1 <= c0 - (R_i + R_j)");
   m.def("k_gram_adapt_last", []() { return kernels::gram_adapt_last(); },
         "(one-product tiles, hot tiles) of the calling thread's last adaptive split Gram, or (-1, -1)");
+  m.def("gram_tile_order", [](int64_t tm, int64_t tn, bool sym) { return launch::gram_tile_order(tm, tn, sym); },
+        py::arg("tm"), py::arg("tn"), py::arg("sym"),
+        "the one-product Gram pass's table of 256 x 256 tiles, entries (tx << 16) | u, for tm 256-row tiles by tn "
+        "128-column tiles, in the order the persistent workgroups walk it (host only)");
   m.def("k_fused_select", [](uintptr_t f, uintptr_t alpha, uintptr_t y, int64_t n, float C, int rows, uintptr_t out,
                              uintptr_t stream) {
     kernels::fused_select((const float*)f, (const float*)alpha, (const float*)y, n, C, rows, (uint64_t*)out,

@@ -1,6 +1,8 @@
 """What the estimators and the loaded models share: input conversion, the device string, one predictor holder
 and decision path, the per-solve attributes, and the base of the estimators that run one-block working-set
-rounds on the resident Gram (SVR, OneClassSVM; the native side of it: csrc/include/dpsvm/problem.hpp).
+rounds on the resident Gram (SVR, OneClassSVM; the native side of it: csrc/include/dpsvm/problem.hpp).  The kernel
+families meet the rest of the model layer here and nowhere else: the kernel object a model asks (``_Kernel``) and
+the three training inputs of one interface that ``_train_input`` returns (docs/DESIGN.md §21, "The seam").
 """
 from __future__ import annotations
 
@@ -144,13 +146,21 @@ def _kernel_code(kernel) -> int:
     return _pick(_KERNEL, kernel, "kernel")
 
 
-def _kernel_name(kernel) -> str:
-    return kernel.name if isinstance(kernel, KernelSpec) else kernel
+class _Kernel:
+    """What a model asks about its kernel, so that nobody asks which family it is: ``name`` (get_params, messages),
+    ``spec`` (a model file's kernel line; None for the strings), ``on_gram`` (the solve runs on a resident Gram,
+    handed over or built from the rows: the general-diagonal rounds and their refusals), ``has_file`` (there are
+    rows to write), and ``family`` — rbf | gram | rows — which names the training input (_train_input) and the
+    decision path (_Predicts._decision) and is read by those two alone.  ``kernel``: an estimator's ``kernel=``
+    (validated by SVCConfig: anything unknown reads as RBF here), or a model file's kernel line as its spec."""
 
+    def __init__(self, kernel):
+        self.spec = kernel if isinstance(kernel, KernelSpec) else None
+        self.name = kernel.name if self.spec is not None else kernel
+        self.family = "rows" if self.spec is not None else "gram" if kernel == "precomputed" else "rbf"
+        self.on_gram = self.family != "rbf"
+        self.has_file = self.family != "gram"
 
-def _on_gram(kernel) -> bool:
-    """the solve runs on a resident Gram handed over (precomputed) or built from the rows (a spec)"""
-    return kernel == "precomputed" or isinstance(kernel, KernelSpec)
 
 # what kernel="precomputed" refuses, for every estimator: (the test on the config, what the message names).  The
 # native table is check_kernel (csrc/include/dpsvm/problem.hpp); this one raises before any native state exists.
@@ -175,7 +185,7 @@ def _refuse_precomputed(cfg, **fit_args) -> None:
     """kernel="precomputed" or a kernel spec: raise NotImplementedError for a refused setting or fit argument
     (comm, resume, rank_rows), naming it"""
     why = "a precomputed kernel runs one-block working-set rounds on the resident Gram of one rank, with box clipping"
-    kname = _kernel_name(cfg.kernel)
+    kname = _Kernel(cfg.kernel).name
     if kname != "precomputed":
         why = f"the {kname} kernel's Gram is built at setup and the solve is a precomputed one: {why}"
     for refused, what in _PRECOMPUTED_REFUSED:
@@ -194,12 +204,69 @@ def _is_gpu_tensor(a) -> bool:
     return isinstance(a, torch.Tensor) and a.is_cuda
 
 
-class _Gram:
+class _TrainInput:
+    """What fit() trains on, whatever the kernel family.  The three inputs answer:
+
+      n, shape           rows, and X's (or K's) shape; shape[1] is the feature count of the native params
+      what               the input's letter in messages ("X" / "K")
+      setup(solver, y)   the GpuSolver's setup call for this input -> its info dict
+      cpu_setup(p)       the setup info a CPU fit publishes (None: none)
+      solve_cpu(...)     one CPU solve -> (alpha, info); info["f"] is the gradient
+      holdout_cpu(...)   the decisions of the held-out rows of a CPU fold
+      kept_rows()        the rows the fitted model keeps (support_vectors_, the model file), or None
+      published_gamma(g) ``gamma_`` of a fit whose native params resolved gamma to g
+      may_shrink         the shrinking phases subset rows of X: RBF rows only
+      train_pass         the fitted model can predict its own training rows (else the training decisions come
+                         from the solves' gradients)
+      gamma              the gamma the input itself resolved (the rows under a spec), else None"""
+
+    may_shrink = train_pass = False
+    what = "X"
+    gamma = None
+
+    def cpu_setup(self, p) -> Optional[dict]:
+        return None
+
+    def published_gamma(self, g: float) -> Optional[float]:
+        return g
+
+
+class _RbfRows(_TrainInput):
+    """The training input of an RBF fit: the rows X (n, d), float32 on the host; the solvers compute kernel values
+    from them."""
+
+    may_shrink = train_pass = True
+
+    def __init__(self, X):
+        self.X = _as_f32_2d(X)
+        self.shape = self.X.shape
+        self.n = int(self.shape[0])
+
+    def setup(self, solver, y: np.ndarray) -> dict:
+        return solver.setup(self.X, len(y), y)  # (len(y): the global row count when X is this rank's part)
+
+    def solve_cpu(self, p, y, row_C=None, comm=None, ck=None, progress=None):
+        return load().solve_cpu(self.X, y, p, comm, ck, progress, row_C)
+
+    def holdout_cpu(self, p, y, alpha, b: float, fold) -> np.ndarray:
+        C = load()
+        model = C.make_model(self.X, y, alpha, float(b), p.gamma)
+        return C.decision_cpu(model, np.ascontiguousarray(self.X[fold]), 0)
+
+    def kept_rows(self) -> np.ndarray:
+        return self.X
+
+
+class _Gram(_TrainInput):
     """The training Gram of a kernel="precomputed" fit: (n, n), symmetric (a precondition: the round kernels read
     K(i, j) from either triangle; setup checks the diagonal and a fixed sample of 1,024 pairs bitwise).  A torch
     tensor on the GPU stays there and is handed over by pointer (it must be float32 with unit column stride; a row
     stride is accepted) on the current torch stream; a numpy array or CPU tensor is uploaded.  The solver copies
-    it into its own lines either way."""
+    it into its own lines either way.  There are no rows to keep and no gamma."""
+
+    what = "K"
+    name = "precomputed"
+    checked = False
 
     def __init__(self, K, want_gpu: bool):
         self.dev = None
@@ -230,13 +297,17 @@ class _Gram:
         return self.host_
 
     def check_host(self) -> None:
-        """the native setup's checks, for the CPU solver: a finite diagonal >= 0, symmetry (here on all pairs)"""
+        """the native setup's checks, for the CPU solver, once per input: a finite diagonal >= 0, symmetry (here
+        on all pairs)"""
+        if self.checked:
+            return
         K = self.host()
         dg = np.diagonal(K)
         if not (np.all(np.isfinite(dg)) and np.all(dg >= 0)):
             raise ValueError("invalid Gram: the diagonal must be finite and >= 0")
         if not np.array_equal(K.view(np.uint32), K.T.view(np.uint32)):
             raise ValueError("invalid Gram: not symmetric (K[i][j] != K[j][i] bitwise)")
+        self.checked = True
 
     def setup(self, solver, y: np.ndarray) -> dict:
         """GpuSolver.setup_gram on this Gram"""
@@ -248,14 +319,39 @@ class _Gram:
             stream = torch.cuda.current_stream().cuda_stream
         return solver.setup_gram(int(self.dev.data_ptr()), y, self.n, int(self.dev.stride(0)), int(stream))
 
+    def cpu_setup(self, p) -> dict:
+        C = load()
+        return {"iteration": "cpu", "kernel": self.name,
+                "engine_note": "; ".join(s for s in (C.precomputed_note(), C.problem_note(p)) if s)}
+
+    def solve_cpu(self, p, y, row_C=None, comm=None, ck=None, progress=None):
+        self.check_host()
+        return load().solve_cpu_gram(self.host(), y, p, progress, row_C)
+
+    def holdout_cpu(self, p, y, alpha, b: float, fold) -> np.ndarray:
+        """the held-out rows of K against the fold's coefficients"""
+        coef = (np.asarray(alpha, dtype=np.float32) * y)[None, :]
+        Kf = np.ascontiguousarray(self.host()[fold])
+        return load().gram_decision_cpu(Kf, coef, np.array([b], dtype=np.float32), 0)[:, 0]
+
+    def kept_rows(self) -> Optional[np.ndarray]:
+        return None
+
+    def published_gamma(self, g: float) -> Optional[float]:
+        return None
+
 
 class _RowsGram(_Gram):
     """The training Gram of a kernel-spec fit: the rows X (n, d) and the spec.  On the GPU the solver builds the
     Gram from the rows straight into its lines (GpuSolver.setup_rows_gram: X is uploaded, or read in place when it
-    is a float32 torch tensor on that device); on the CPU ``host()`` is kernel_gram_cpu(X).  ``shape`` is X's."""
+    is a float32 torch tensor on that device); on the CPU ``host()`` is kernel_gram_cpu(X).  ``shape`` is X's; the
+    model keeps the rows, and the kernel's gamma (the linear kernel has none)."""
+
+    what = "X"
 
     def __init__(self, X, spec: KernelSpec, gamma: Optional[float], want_gpu: bool):
         self.spec = spec
+        self.name = spec.name
         self.dev = None
         self.host_ = None  # the (n, n) Gram, built on first use (CPU solves)
         self.rows_ = None
@@ -276,14 +372,14 @@ class _RowsGram(_Gram):
         self.shape = (self.n, self.d)
         self.gamma = float(gamma) if gamma is not None and gamma >= 0 else 1.0 / float(self.d)
 
-    def rows(self) -> np.ndarray:
+    def kept_rows(self) -> np.ndarray:
         if self.rows_ is None:
             self.rows_ = np.ascontiguousarray(self.dev.cpu().numpy())
         return self.rows_
 
     def host(self) -> np.ndarray:
         if self.host_ is None:
-            self.host_ = np.asarray(load().kernel_gram_cpu(self.rows(), None, *self.spec.native(), self.gamma, 0),
+            self.host_ = np.asarray(load().kernel_gram_cpu(self.kept_rows(), None, *self.spec.native(), self.gamma, 0),
                                     dtype=np.float32)
         return self.host_
 
@@ -301,15 +397,19 @@ class _RowsGram(_Gram):
         info["kernel"] = self.spec.name
         return info
 
+    def published_gamma(self, g: float) -> Optional[float]:
+        return None if isinstance(self.spec, Linear) else g
+
 
 def _train_input(cfg, X):
     """what fit() trains on: the rows (RBF), the caller's Gram (precomputed) or the rows under a kernel spec"""
     want_gpu = cfg.device_kind()[0] == "cuda"
-    if isinstance(cfg.kernel, KernelSpec):
+    family = _Kernel(cfg.kernel).family
+    if family == "rows":
         return _RowsGram(X, cfg.kernel, cfg.gamma, want_gpu)
-    if cfg.kernel == "precomputed":
+    if family == "gram":
         return _Gram(X, want_gpu)
-    return _as_f32_2d(X)
+    return _RbfRows(X)
 
 
 def _stamp_kernel(model, spec: Optional[KernelSpec]):
@@ -408,18 +508,13 @@ class _Predicts:
     _gpu = None
     _multi = False  # k one-vs-rest machines: (n, k) decisions
 
-    def _precomputed(self) -> bool:
-        return getattr(getattr(self, "config", None), "kernel", "rbf") == "precomputed"
-
-    def _kernel_spec(self) -> Optional[KernelSpec]:
-        """the kernel spec of an estimator, or of a loaded model whose file names a dot-product kernel; else None"""
-        k = getattr(getattr(self, "config", None), "kernel", None)
-        if isinstance(k, KernelSpec):
-            return k
-        m = getattr(self, "model", None)
-        if m is not None and m.kernel != "rbf":
-            return _spec_of(m.kernel, m.degree, m.coef0)
-        return None
+    def _kernel(self) -> _Kernel:
+        """the kernel object: of an estimator's ``config.kernel``, of a loaded model's file"""
+        cfg = getattr(self, "config", None)
+        if cfg is not None:
+            return _Kernel(cfg.kernel)
+        m = self.model
+        return _Kernel("rbf" if m.kernel == "rbf" else _spec_of(m.kernel, m.degree, m.coef0))
 
     def _rows_model(self):
         """a kernel-spec model as (SV rows (nsv, d), coefficients (k, nsv), thresholds (k,), gamma)"""
@@ -450,7 +545,7 @@ class _Predicts:
         ``chunk_rows`` (_chunk_rows), per chunk K(chunk, SV) built by the kernel's Gram builder (on the device
         ops.kernel_gram, on the CPU kernel_gram_cpu), then the precomputed decision path (_gram_decision: fp64
         accumulation).  A row's value does not depend on the chunking."""
-        spec = self._kernel_spec()
+        spec = self._kernel().spec
         sv, coef, b, gamma = self._rows_model()
         X = _as_f32_2d(X)
         if X.shape[1] != sv.shape[1]:
@@ -508,7 +603,7 @@ class _Predicts:
 
     def _predictor(self):
         """the device predictor, None on the CPU"""
-        if self._kernel_spec() is not None:
+        if self._kernel().spec is not None:
             raise RuntimeError("the device predictor evaluates RBF models; a kernel-spec model predicts through "
                                "K(test, SV) (decision_function)")
         kind, dev = _parse_device(self._device())
@@ -516,24 +611,41 @@ class _Predicts:
             self._gpu = load().GpuPredictor(self._native_model(), dev)
         return self._gpu
 
-    def _decision(self, X, predict_chunk_rows=None) -> np.ndarray:
+    def _decision(self, X, proba=None, predict_chunk_rows=None) -> np.ndarray:
         """sum_sv coef K(sv, x) - b, float32: (n,), or (n, k) for k machines (kernel="precomputed": X is
-        K(test, train), (n_test, n_train)).  ``predict_chunk_rows``: a kernel-spec model's test rows per chunk
-        (_decision_rows); the other kernels ignore it."""
-        if self._precomputed():
-            return self._decision_gram(X)
-        if self._kernel_spec() is not None:
-            return self._decision_rows(X, None, predict_chunk_rows)
+        K(test, train), (n_test, n_train)) — the one place that picks the path, by the kernel's family.  ``proba`` =
+        (A, B): the machines' sigmoids on the decision values, on the device before the download: (n, k), k = 1
+        included.  ``predict_chunk_rows``: a kernel-spec model's test rows per chunk (_decision_rows); the other
+        kernels ignore it."""
+        family = self._kernel().family
+        if family == "gram":
+            return self._decision_gram(X, proba)
+        if family == "rows":
+            return self._decision_rows(X, proba, predict_chunk_rows)
         X = _as_f32_2d(X)
         d = getattr(self, "n_features_in_", None)
         if d is not None and X.shape[1] != d:
             raise ValueError(f"X has {X.shape[1]} features, model has {d}")
-        gp = self._predictor()
-        if self._multi:
-            out = gp.decision_multi(X) if gp is not None else load().decision_multi_cpu(self._native_model(), X, 0)
+        gp, C = self._predictor(), load()
+        if gp is not None:
+            out = gp.proba(X, *proba) if proba is not None else gp.decision_multi(X) if self._multi else gp.decision(X)
         else:
-            out = gp.decision(X) if gp is not None else load().decision_cpu(self._native_model(), X, 0)
+            out = (C.decision_multi_cpu if self._multi else C.decision_cpu)(self._native_model(), X, 0)
+            if proba is not None:
+                out = C.proba_cpu(out if self._multi else out.reshape(-1, 1), *proba)
         return np.asarray(out, dtype=np.float32)
+
+    def _predict_proba(self, X, predict_chunk_rows, needs: str) -> np.ndarray:
+        """predict_proba of SVC and the loaded models: the sigmoids (probA_, probB_) on the decision values; two
+        classes: [1 - p, p].  ``needs``: what a model without sigmoids is told"""
+        if getattr(self, "probA_", None) is None:
+            raise RuntimeError(needs)
+        sigmoids = tuple(np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (self.probA_, self.probB_))
+        p = self._decision(X, sigmoids, predict_chunk_rows)
+        return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
+
+    def _model_gamma(self) -> float:
+        return self.gamma_ if self.gamma_ is not None else 0.0  # (the linear kernel has none)
 
 
 def _publish_solves(est, infos: list, multi: bool = False) -> None:
@@ -554,6 +666,15 @@ def _publish_solves(est, infos: list, multi: bool = False) -> None:
     est.converged_ = bool(all(i["converged"] for i in infos))
     est.fit_time_ = float(sum(i["t_solve"] for i in infos))
     est.setup_time_ = float(infos[0]["t_setup"])
+
+
+def _config_params(est) -> dict:
+    """get_params() of an estimator: the config's fields, and its init-only kernel when it is not the default"""
+    out = dataclasses.asdict(est.config)
+    name = est._kernel().name
+    if name != "rbf":
+        out["kernel"] = name
+    return out
 
 
 # what the one-block estimators refuse: (the test on the config, what the message names)
@@ -602,7 +723,7 @@ class _OneBlockEstimator(_Predicts):
         cfg = self.config
         self._check_extra()
         _parse_device(cfg.device)
-        if _on_gram(cfg.kernel):  # its own table first: it names each setting
+        if self._kernel().on_gram:  # its own table first: it names each setting
             _refuse_precomputed(cfg)
         for refused, what in _REFUSED:
             if refused(cfg):
@@ -617,57 +738,54 @@ class _OneBlockEstimator(_Predicts):
             if val is not None:
                 self._refuse(name)
 
-    def _run(self, X: np.ndarray, y_native: np.ndarray, p, progress, want_gradient: bool):
-        """one solve on the configured device -> alpha, info, the gradient (or None), the setup info; X: the rows,
-        or the _Gram of a precomputed kernel"""
+    def _solves(self, X, y: np.ndarray, params: list, progress, want_gradient: bool, between=None):
+        """The solves of the input X on the configured device, one per entry of ``params``: on the GPU one solver
+        (of params[0]), one setup and one resident Gram, ``between(solver, i)`` before solve i > 0, the solver
+        dropped on return with its Gram; on the CPU a plain solve per entry.  Returns [(alpha, info, gradient)]
+        (the gradient from the solver, or from the CPU solve's info; None unless wanted) and the setup info."""
         C = load()
         kind, dev = self.config.device_kind()
-        f = None
-        gram = isinstance(X, _Gram)
+        out = []
         if kind == "cuda":
-            solver = C.GpuSolver(p, None, dev)  # dropped after the solve, with its resident Gram
-            setup = X.setup(solver, y_native) if gram else solver.setup(X, len(X), y_native)
-            alpha, info = solver.solve(None, progress)
-            if want_gradient:
-                f = solver.gradient()
-            del solver
-            info = dict(info)
+            solver = C.GpuSolver(params[0], None, dev)
+            setup = X.setup(solver, y)
+            for i in range(len(params)):
+                if i:
+                    between(solver, i)
+                alpha, info = solver.solve(None, progress)
+                out.append((alpha, dict(info), solver.gradient() if want_gradient else None))
         else:
-            setup = {"iteration": "cpu", "engine_note": C.problem_note(p)}
-            if gram:
-                X.check_host()
-                setup["kernel"] = _kernel_name(self.config.kernel)
-                setup["engine_note"] = "; ".join(s for s in (C.precomputed_note(), setup["engine_note"]) if s)
-                alpha, info = C.solve_cpu_gram(X.host(), y_native, p, progress, None)
-            else:
-                alpha, info = C.solve_cpu(X, y_native, p, None, None, progress, None)
-            info = dict(info)
-            f = info.pop("f", None)
-            if not want_gradient:
-                f = None
+            setup = X.cpu_setup(params[0]) or {"iteration": "cpu", "engine_note": C.problem_note(params[0])}
+            for p in params:
+                alpha, info = X.solve_cpu(p, y, progress=progress)
+                info = dict(info)
+                f = info.pop("f", None)
+                out.append((alpha, info, f if want_gradient else None))
+        return out, setup
+
+    def _run(self, X, y_native: np.ndarray, p, progress, want_gradient: bool):
+        """one solve of fit() -> alpha, info, the gradient (or None), the setup info"""
+        ((alpha, info, f),), setup = self._solves(X, y_native, [p], progress, want_gradient)
+        kind, dev = self.config.device_kind()
         self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
         return alpha, info, None if f is None else np.asarray(f, dtype=np.float32), setup
 
-    def _publish_fit(self, X: np.ndarray, coef: np.ndarray, info: dict, gamma: float, setup: dict) -> None:
-        """the attributes of a fit whose model is sum_i coef_i K(x_i, x) - b; called by fit()"""
+    def _publish_fit(self, X, coef: np.ndarray, info: dict, gamma: float, setup: dict) -> None:
+        """the attributes of a fit on the input X whose model is sum_i coef_i K(x_i, x) - b; called by fit()"""
         self.setup_info_ = setup
         _publish_solves(self, [info])
-        gram = isinstance(X, _Gram)
-        rows = isinstance(X, _RowsGram)  # a kernel spec: the model keeps its rows; gamma is the kernel's (linear: none)
-        self._kgamma = X.gamma if rows else gamma
-        self.gamma_ = None if (gram and not rows) or isinstance(self.config.kernel, Linear) else self._kgamma
+        self._kgamma = X.gamma if X.gamma is not None else gamma  # (a spec's rows resolved their own)
+        self.gamma_ = X.published_gamma(self._kgamma)
         self.n_features_in_ = X.shape[1]
         self.support_ = np.nonzero(coef != 0)[0]
-        if rows:
-            X = X.rows()
-        if gram and not rows:  # a precomputed kernel has no gamma (and no rows to keep)
-            X = None
+        rows = X.kept_rows()
+        if rows is None:
             self.__dict__.pop("support_vectors_", None)
         else:
-            self.support_vectors_ = X[self.support_]
+            self.support_vectors_ = rows[self.support_]
         self.dual_coef_ = coef[self.support_].astype(np.float32)
         self.n_support_ = int(len(self.support_))
-        self._X_train, self._coef = X, coef
+        self._X_train, self._coef = rows, coef
         self._model = None
         self._gpu = None
         self._rows_cache = None
@@ -677,7 +795,8 @@ class _OneBlockEstimator(_Predicts):
 
     def to_model(self):
         """the binary model of coef: alpha = |coef|, y = sign(coef) (rows with coef = 0 are no SVs)"""
-        if self._precomputed():
+        kern = self._kernel()
+        if not kern.has_file:
             raise NotImplementedError(f"{self._NAME}: kernel='precomputed' has no model file (there are no rows to "
                                       "write): keep support_, dual_coef_ and intercept_")
         if self._model is None:
@@ -685,10 +804,8 @@ class _OneBlockEstimator(_Predicts):
             if coef is None:
                 raise RuntimeError(f"to_model() needs a fitted {self._NAME}")
             y = np.where(coef < 0, -1.0, 1.0).astype(np.float32)
-            spec = self._kernel_spec()
-            gamma = self.gamma_ if self.gamma_ is not None else 0.0  # (the linear kernel has none)
             self._model = _stamp_kernel(load().make_model(self._X_train, y, np.abs(coef).astype(np.float32), self.b_,
-                                                          gamma), spec)
+                                                          self._model_gamma()), kern.spec)
         return self._model
 
     def save(self, path: str, precision: int = 9) -> None:
@@ -696,8 +813,6 @@ class _OneBlockEstimator(_Predicts):
         load().write_model(path, self.to_model(), precision, False)
 
     def get_params(self, deep: bool = True) -> dict:
-        out = dataclasses.asdict(self.config)
-        if self.config.kernel != "rbf":  # init-only (SVCConfig): reported when it is not the default
-            out["kernel"] = _kernel_name(self.config.kernel)
+        out = _config_params(self)
         out[self._EXTRA] = getattr(self, self._EXTRA)
         return out

@@ -23,7 +23,7 @@ from typing import Any, Callable, Optional, Sequence
 import numpy as np
 
 from .._native import load
-from ._base import _Gram, _OneBlockEstimator, _train_input
+from ._base import _OneBlockEstimator, _train_input
 from .svc import LoadedModel
 
 
@@ -39,7 +39,7 @@ class _OneClassDecisions:
 
     def decision_function(self, X, predict_chunk_rows=None) -> np.ndarray:
         """float32: >= 0 inside the estimated support (``predict_chunk_rows``: a kernel spec's test rows per chunk)"""
-        return self._decision(X, predict_chunk_rows)
+        return self._decision(X, predict_chunk_rows=predict_chunk_rows)
 
     def score_samples(self, X, predict_chunk_rows=None) -> np.ndarray:
         """the decision without the offset: sum_sv alpha K(sv, x)"""
@@ -118,39 +118,19 @@ class OneClassSVM(_OneClassDecisions, _OneBlockEstimator):
         if not nus:
             raise ValueError("nu_path needs at least one nu")
         X = _train_input(self.config, X)
-        gram = isinstance(X, _Gram)  # precomputed, or the rows under a kernel spec
         n, d = X.shape
-        C = load()
-        ones = np.ones(n, dtype=np.float32)
-        kind, dev = self.config.device_kind()
+        solves, setup = self._solves(X, np.ones(n, dtype=np.float32), [self._params(d, nu) for nu in nus], progress,
+                                     True, between=lambda solver, i: solver.set_nu(nus[i]))
+        if self.config.device_kind()[0] == "cuda":
+            self.path_setup_info_ = setup
         rho, nsv, out, stats, alphas = [], [], [], [], []
-        solver = None
-        if kind == "cuda":
-            solver = C.GpuSolver(self._params(d, nus[0]), None, dev)
-            self.path_setup_info_ = X.setup(solver, ones) if gram else solver.setup(X, n, ones)
-        elif gram:
-            X.check_host()
-        for i, nu in enumerate(nus):
-            if solver is not None:
-                if i > 0:
-                    solver.set_nu(nu)
-                alpha, info = solver.solve(None, progress)
-                info = dict(info)
-                f = np.asarray(solver.gradient(), dtype=np.float64)
-            else:
-                if gram:
-                    alpha, info = C.solve_cpu_gram(X.host(), ones, self._params(d, nu), progress, None)
-                else:
-                    alpha, info = C.solve_cpu(X, ones, self._params(d, nu), None, None, progress, None)
-                info = dict(info)
-                f = np.asarray(info.pop("f"), dtype=np.float64)
+        for alpha, info, f in solves:
             alpha = np.asarray(alpha, dtype=np.float32)
             rho.append(float(info["b"]))
             nsv.append(int(np.count_nonzero(alpha > 0)))
-            out.append(float(np.mean(f - float(info["b"]) < 0)))
+            out.append(float(np.mean(np.asarray(f, dtype=np.float64) - float(info["b"]) < 0)))
             stats.append(info)
             alphas.append(alpha)
-        del solver
         self.path_stats_ = stats
         self.path_alpha_ = np.stack(alphas)
         return {"nu": list(nus), "rho": rho, "n_support": nsv, "outlier_fraction": out}

@@ -15,15 +15,14 @@ from __future__ import annotations
 import dataclasses
 import math
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import Any, Callable, Optional
 
 import numpy as np
 
 from .._native import load, load_quarantine
-from ._base import (Linear, _Gram, _KERNEL, _Predicts, _RowsGram, _as_1d, _as_f32_2d,  # noqa: F401 (re-exported)
-                    _kernel_code, _kernel_name, _on_gram, _parse_device, _pick, _publish_solves, _refuse_precomputed,
-                    _stamp_kernel, _train_input)
+from ._base import (_Kernel, _Predicts, _as_1d, _config_params, _kernel_code, _parse_device, _pick, _publish_solves,
+                    _refuse_precomputed, _stamp_kernel, _train_input)
 
 
 _CLIP = {"independent": 0, "box": 1}
@@ -54,19 +53,9 @@ _PLAIN = {
 }
 
 
-def _predict_proba(gp, model, multi: bool, X: np.ndarray, A, B) -> np.ndarray:
-    """What SVC and the loaded models share: the machines' sigmoids (A, B) on the decision values of X — on the
-    device predictor ``gp`` before the download, else (gp None) on the host; ``model()``: the native model."""
-    C = load()
-    A = np.atleast_1d(np.asarray(A, dtype=np.float64))
-    B = np.atleast_1d(np.asarray(B, dtype=np.float64))
-    if gp is not None:
-        p = gp.proba(X, A, B)
-    elif multi:
-        p = C.proba_cpu(C.decision_multi_cpu(model(), X, 0), A, B)
-    else:
-        p = C.proba_cpu(C.decision_cpu(model(), X, 0).reshape(-1, 1), A, B)
-    return p if multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
+def _gradient(solver, info: dict) -> np.ndarray:
+    """the gradient f after a solve: the live GpuSolver's, or (solver None) the CPU solve's info["f"]"""
+    return np.asarray(solver.gradient() if solver is not None else info["f"], dtype=np.float32)
 
 
 def _write_platt(path: str, A, B) -> None:
@@ -299,10 +288,11 @@ class SVC(_Predicts):
 
     def __init__(self, C: float = 1.0, gamma: Optional[float] = None, eps: float = 1e-3,
                  max_iter: int = 150000, device: str = "auto", **kwargs: Any):
-        if _on_gram(kwargs.get("kernel", "rbf")):
+        on_gram = _Kernel(kwargs.get("kernel", "rbf")).on_gram
+        if on_gram:
             kwargs.setdefault("clip", "box")
         self.config = SVCConfig(C=C, gamma=gamma, eps=eps, max_iter=max_iter, device=device, **kwargs)
-        if _on_gram(self.config.kernel):
+        if on_gram:
             _refuse_precomputed(self.config)
         self._model = None
         self._multi = False
@@ -397,17 +387,18 @@ class SVC(_Predicts):
         return p, RC, self.config.weighted_params(p, comm, resume, rank_rows)
 
     # ------------------------------------------------------------------ fit
-    def _solve_machines(self, X: np.ndarray, Ys: np.ndarray, RC, p, note=None, comm=None,
+    def _solve_machines(self, X, Ys: np.ndarray, RC, p, note=None, comm=None,
                         resume=None, progress=None, rank_rows=None, hook=None, keep=False, lab=None):
-        """The solves of one fit on one X: machine c has the labels ``Ys[c]`` and the row bounds ``RC[c]`` (RC None:
-        the scalar C; an entry None: the scalar C for that solve); ``Ys`` (1, n) under more rows of RC is one set
-        of labels for all of them (the folds of a cross-validation); ``lab[c]``: the row of Ys that solve c uses
-        (the full-data solve and the folds of each machine of a probability fit).  On the GPU one solver: setup()
-        (X upload, norms, operand prep, engine choice) once, then per machine set_labels (after the first),
-        set_row_C (with RC) and solve; the resident Gram built by the first solve is kept by the swaps after it.
-        ``hook(c, solver, info)`` runs after solve c on the live GpuSolver.  Returns the alphas, the info dicts,
-        the setup info (None on the CPU) and, with ``keep``, the GpuSolver (else it is dropped here, with its
-        Gram)."""
+        """The solves of one fit on one training input X (_train_input): machine c has the labels ``Ys[c]`` and the
+        row bounds ``RC[c]`` (RC None: the scalar C; an entry None: the scalar C for that solve); ``Ys`` (1, n)
+        under more rows of RC is one set of labels for all of them (the folds of a cross-validation); ``lab[c]``:
+        the row of Ys that solve c uses (the full-data solve and the folds of each machine of a probability fit).
+        On the GPU one solver: the input's setup (upload, norms, operand prep, engine choice) once, then per
+        machine set_labels (after the first), set_row_C (with RC) and solve; the resident Gram built by the first
+        solve is kept by the swaps after it.  ``hook(c, solver, info)`` runs after solve c on the live GpuSolver
+        (on the CPU: solver None, info["f"] the gradient).  Returns the alphas, the info dicts, the setup info (on
+        the CPU the input's, None for RBF rows) and, with ``keep``, the GpuSolver (else it is dropped here, with
+        its Gram)."""
         C = load()
         k, n = Ys.shape
         m = k if RC is None else len(RC)
@@ -416,12 +407,11 @@ class SVC(_Predicts):
         ck = C.read_checkpoint(resume) if isinstance(resume, str) else resume
         kind, dev = self.config.device_kind()
         alphas, infos, setup, solver = [], [], None, None
-        gram = isinstance(X, _Gram)  # kernel="precomputed": no X, the solves run on the caller's Gram
-        if (kind == "cuda" and rank_rows is None and RC is None and not gram
+        if (kind == "cuda" and rank_rows is None and RC is None and X.may_shrink
                 and self._use_shrink(p, n, X.shape[1], dev, comm)):
             for c in range(m):  # ShrinkingSolver has no label swap: one per machine
                 shr = C.ShrinkingSolver(p, comm, dev)
-                s = shr.setup(X, Ys[c])  # the whole-problem phases' solver; iteration "ws+shrinking"
+                s = shr.setup(X.kept_rows(), Ys[c])  # the whole-problem phases' solver; iteration "ws+shrinking"
                 a, info = shr.solve(ck, progress)
                 if c == 0:
                     setup = s
@@ -432,7 +422,7 @@ class SVC(_Predicts):
                 del shr
         elif kind == "cuda":
             solver = C.GpuSolver(p, comm, dev)
-            setup = X.setup(solver, Ys[0]) if gram else solver.setup(X, n, Ys[0])
+            setup = X.setup(solver, Ys[0])
             if note:
                 en = setup.get("engine_note", "")
                 setup["engine_note"] = (en + "; " if en else "") + note
@@ -449,36 +439,30 @@ class SVC(_Predicts):
         else:
             if rank_rows is not None:
                 raise ValueError("partitioned X needs the GPU solver")
-            if gram:
-                X.check_host()
-                setup = {"iteration": "cpu", "kernel": _kernel_name(self.config.kernel),
-                         "engine_note": C.precomputed_note()}
+            setup = X.cpu_setup(p)
             for c in range(m):
-                rc = None if RC is None else RC[c]
-                if gram:
-                    a, info = C.solve_cpu_gram(X.host(), Ys[lab[c]], p, progress, rc)
-                else:
-                    a, info = C.solve_cpu(X, Ys[lab[c]], p, comm, ck, progress, rc)
+                a, info = X.solve_cpu(p, Ys[lab[c]], None if RC is None else RC[c], comm, ck, progress)
                 info = dict(info)
-                if hook is not None and gram:
+                if hook is not None:
                     hook(c, None, info)
                 info.pop("f", None)
                 alphas.append(a)
                 infos.append(info)
         return alphas, infos, setup, solver if keep else None
 
-    def _cv_solves(self, X: np.ndarray, Ys: np.ndarray, W: Optional[np.ndarray], p, cv: int, seed: int,
-                   full: Optional[list] = None, note=None, progress=None, keep=False):
+    def _cv_solves(self, X, Ys: np.ndarray, W: Optional[np.ndarray], p, cv: int, seed: int,
+                   full: Optional[list] = None, note=None, progress=None, keep=False, want_grads=False):
         """Per machine c (labels ``Ys[c]``, weights ``W[c]`` or ones): with ``full`` the full-data solve under the
         bounds ``full[c]`` (None: the scalar C), then the ``cv`` fold solves, each with the fold's weights zeroed
         (C_i = 0: alpha_i stays 0, the row is out of the problem) — all through _solve_machines, so on the GPU on
         one solver, one setup() and one resident Gram.  There a held-out row's decision value is f_i + y_i - b,
         its gradient entry as every round's f update kept it: written on the device into the solver's slot c
         (holdout_decision_kernel), downloaded once per machine, and with ``full`` fitted there by
-        platt_fit_kernel against the machine's labels.  On the CPU the decisions come from decision_cpu and the
-        fit from platt_fit_cpu.  Folds: ``cv_folds(n, cv, seed)``, the same for every machine.  Returns the
+        platt_fit_kernel against the machine's labels.  On the CPU the decisions come from the input's holdout_cpu
+        and the fit from platt_fit_cpu.  Folds: ``cv_folds(n, cv, seed)``, the same for every machine.  Returns the
         out-of-fold decisions (k, n), the folds, the Platt fits (k dicts; None without ``full``), the full-data
-        solves' alphas and dicts, the folds' dicts per machine, the setup info and the kept GpuSolver."""
+        solves' alphas and dicts, the folds' dicts per machine, the setup info, the kept GpuSolver and, with
+        ``want_grads``, the full-data solves' gradients (k arrays; else None)."""
         C = load()
         k, n = Ys.shape
         folds = self.cv_folds(n, cv, seed)
@@ -499,14 +483,13 @@ class SVC(_Predicts):
         dec = np.zeros((k, n), dtype=np.float32)
         platt = [None] * k
         on_device = []
-
-        sink = getattr(self, "_grad_sink", None)  # kernel="precomputed": the full-data solves' gradients
+        grads = [None] * k if want_grads else None
 
         def hook(i, solver, info):  # cold solves (alpha = 0, f = -y): the gradient is the whole decision
             c, j = role[i]
-            if j < 0 and sink is not None:
-                sink[c] = np.asarray(solver.gradient() if solver is not None else info["f"], dtype=np.float32)
-            if solver is None:  # (the CPU solver on a precomputed Gram: only the gradient sink)
+            if j < 0 and want_grads:
+                grads[c] = _gradient(solver, info)
+            if solver is None:  # (the CPU solver: only the gradients)
                 return
             if j >= 0:
                 solver.holdout_decisions(rows[j], float(info["b"]), c)
@@ -520,45 +503,40 @@ class SVC(_Predicts):
                                                             keep=keep, lab=lab)
         if not on_device:
             for i, (c, j) in enumerate(role):
-                if j >= 0 and isinstance(X, _Gram):  # the held-out rows of K against the fold's coefficients
-                    coef = (np.asarray(alphas[i], dtype=np.float32) * Ys[c])[None, :]
-                    Kf = np.ascontiguousarray(X.host()[folds[j]])
-                    dec[c, folds[j]] = C.gram_decision_cpu(Kf, coef, np.array([infos[i]["b"]], dtype=np.float32),
-                                                           0)[:, 0]
-                elif j >= 0:
-                    model = C.make_model(X, Ys[c], alphas[i], float(infos[i]["b"]), p.gamma)
-                    dec[c, folds[j]] = C.decision_cpu(model, np.ascontiguousarray(X[folds[j]]), 0)
+                if j >= 0:
+                    dec[c, folds[j]] = X.holdout_cpu(p, Ys[c], alphas[i], infos[i]["b"], folds[j])
             if full is not None:
                 platt = [dict(C.platt_fit_cpu(dec[c], Ys[c])) for c in range(k)]
         is_full = [j < 0 for _, j in role]
         f_alphas = [a for a, f in zip(alphas, is_full) if f]
         f_infos = [s for s, f in zip(infos, is_full) if f]
         cv_infos = [[s for s, (cc, j) in zip(infos, role) if cc == c and j >= 0] for c in range(k)]
-        return dec, folds, (platt if full is not None else None), f_alphas, f_infos, cv_infos, setup, solver
+        return dec, folds, (platt if full is not None else None), f_alphas, f_infos, cv_infos, setup, solver, grads
 
     def _fit_solves(self, X, y, Ys, sample_weight, probability: int, seed: int, comm, resume, progress, rank_rows,
-                    keep: bool):
+                    keep: bool, want_grads: bool):
         """The solves of fit(): the machines of Ys, or with ``probability`` folds each machine's full-data solve
         and fold solves on one Gram (_cv_solves) with the Platt fits.  Returns the native params, the machines'
-        row bounds, the alphas, the full-data solves' dicts, the setup info, the kept GpuSolver and the
-        probability results (None without)."""
+        row bounds, the alphas, the full-data solves' dicts, the setup info, the kept GpuSolver, the
+        probability results (None without) and, with ``want_grads``, the full-data solves' gradients (else None)."""
         p, RC, note = self._problem(X.shape[1], y, Ys, sample_weight, comm, resume, rank_rows)
         if not probability:
-            sink = getattr(self, "_grad_sink", None)  # kernel="precomputed": machine c's gradient after its solve
-            hook = None
-            if sink is not None:
-                def hook(c, solver, info):  # noqa: E306
-                    sink[c] = np.asarray(solver.gradient() if solver is not None else info["f"], dtype=np.float32)
+            grads = hook = None
+            if want_grads:
+                grads = [None] * len(Ys)
+
+                def hook(c, solver, info):  # machine c's gradient after its solve
+                    grads[c] = _gradient(solver, info)
             alphas, infos, setup, solver = self._solve_machines(X, Ys, RC, p, note, comm, resume, progress,
                                                                 rank_rows, hook=hook, keep=keep)
-            return p, RC, alphas, infos, setup, solver, None
+            return p, RC, alphas, infos, setup, solver, None, grads
         if RC is None:  # resolved as a weighted fit; the full-data solves keep the scalar C
             note = self.config.weighted_params(p, comm, resume, rank_rows)
         full = [None] * len(Ys) if RC is None else list(RC)
         W = self._weights(y, Ys, sample_weight)
-        dec, folds, platt, alphas, infos, cv_infos, setup, solver = self._cv_solves(
-            X, Ys, W, p, probability, seed, full, note, progress, keep)
-        return p, RC, alphas, infos, setup, solver, (dec, folds, platt, cv_infos)
+        dec, folds, platt, alphas, infos, cv_infos, setup, solver, grads = self._cv_solves(
+            X, Ys, W, p, probability, seed, full, note, progress, keep, want_grads)
+        return p, RC, alphas, infos, setup, solver, (dec, folds, platt, cv_infos), grads
 
     def _publish_proba(self, proba) -> None:
         """cv_decision_, cv_stats_, cv_folds_, probA_, probB_, platt_stats_ of a probability fit (else cleared)"""
@@ -593,169 +571,121 @@ class SVC(_Predicts):
         decisions fit each machine's Platt sigmoid for ``predict_proba`` (0: off;
         LIBSVM uses 5; folds ``cv_folds(n, probability, probability_seed)``).
         The settings then resolve as for a weighted fit, and the full-data solve
-        and the folds of every machine run on one resident Gram."""
+        and the folds of every machine run on one resident Gram.
+
+        More than two labels: one-vs-rest, k machines on one input, the GpuSolver
+        dropped (with its resident Gram) after the last.  kernel="precomputed":
+        X is the (n, n) Gram K of any kernel (symmetric; a GPU torch tensor is
+        passed by pointer, anything else uploaded); there are no rows to keep:
+        ``support_``, ``dual_coef_``, ``alpha_``, ``b_`` / ``intercept_`` and
+        ``probA_`` / ``probB_`` are the model, ``gamma_`` is None, and prediction
+        takes K(test, train).  A kernel spec (Linear / Poly / Sigmoid): X is the
+        rows; the solver builds the Gram from them into its lines, everything else
+        as for a precomputed kernel, and the model keeps its rows
+        (``support_vectors_``, ``save``; prediction takes test rows).  Every case
+        runs on one GpuSolver and one setup: k solves with ``set_labels`` /
+        ``set_row_C``.  Only two classes under the RBF kernel — the reference's
+        trainer — take ``comm``, ``resume`` and ``rank_rows``, keep the solver
+        (``train_accuracy`` on the device) and print ``log_every``'s lines."""
         probability = int(probability)
         if probability != 0 and probability < 2:
             raise ValueError(f"probability is the number of folds: 0 (off) or >= 2, got {probability}")
-        if _on_gram(self.config.kernel):
-            return self._fit_gram(X, y, comm, resume, progress, rank_rows, sample_weight, probability,
-                                  probability_seed)
-        if self.config.engines == "all" or self.config.host_cache_lines or self.config.cache_engine == "chain":
-            load_quarantine()  # the quarantined pair-at-a-time cache engines (plugin)
-        X = _as_f32_2d(X)
-        y1 = _as_1d(y)
-        if len(np.unique(y1)) > 2:
-            return self._fit_multi(X, y1, comm, resume, progress, rank_rows, sample_weight, probability,
-                                   probability_seed)
-        self._multi = False
-        ys = self._encode(y)
-        n, d = X.shape[0], X.shape[1]
-        if rank_rows is None and ys.shape[0] != n:
-            raise ValueError("len(y) != X.shape[0]")
         cfg = self.config
-        if cfg.log_every and progress is None:
-            def progress(it, bh, bl, el, hits, misses):  # noqa: E306
-                print(f"iter {it}  b_hi {bh:.6g}  b_lo {bl:.6g}  gap {bl - bh:.3g}  "
-                      f"{it / max(el, 1e-9):.0f} it/s  hits {hits} misses {misses}", flush=True)
-        t0 = time.perf_counter()
-        p, RC, (alpha,), (info,), setup, self._solver, proba = self._fit_solves(
-            X, y1, ys[None, :], sample_weight, probability, probability_seed, comm, resume, progress, rank_rows,
-            keep=True)
-        self._publish(p, d, time.perf_counter() - t0, setup)
-        self._publish_proba(proba)
-        self.alpha_ = alpha
-        _publish_solves(self, [info])
-        self.row_C_ = row_C = None if RC is None else RC[0]
-        bound = row_C if row_C is not None else np.float32(cfg.C)
-        self.n_bounded_ = int(np.sum((alpha == bound) & (alpha > 0))) if rank_rows is None else None
-        if self.status_ == 2 and self.n_rounds_ > 0:
-            import warnings
-
-            warnings.warn(f"stopped at max_iter with gap {info['b_lo'] - info['b_hi']:.3g} > 2 eps: an unconverged "
-                          "working-set model differs from the reference's pair-at-a-time iterate at the same cap; "
-                          "raise max_iter to converge, or solver='smo' for the reference's trajectory (engines='all' "
-                          "when the Gram is not resident)", RuntimeWarning, stacklevel=2)
-        self._X_train, self._y_train = (X, ys) if rank_rows is None else (None, None)
-        if rank_rows is None:
-            self.support_ = np.nonzero(alpha > 0)[0]
-            self.support_vectors_ = X[self.support_]
-            self.dual_coef_ = (alpha[self.support_] * ys[self.support_]).astype(np.float32)
-            self.n_support_ = int(len(self.support_))
-        return self
-
-    def _fit_gram(self, K, y, comm, resume, progress, rank_rows, sample_weight, probability: int,
-                  probability_seed: int) -> "SVC":
-        """kernel="precomputed": fit on the (n, n) Gram K of any kernel (symmetric; a GPU torch tensor is passed by
-        pointer, anything else uploaded).  Binary and one-vs-rest fits, weights and probability folds all run on
-        one GpuSolver and its one copy of K (``setup_gram``, then k solves with ``set_labels`` / ``set_row_C``).
-        There are no rows to keep: ``support_``, ``dual_coef_``, ``alpha_``, ``b_`` / ``intercept_`` and
-        ``probA_`` / ``probB_`` are the model, ``gamma_`` is None, and prediction takes K(test, train).
-        A kernel spec (Linear / Poly / Sigmoid): K is X; the solver builds the Gram from the rows into its lines
-        (``setup_rows_gram``), everything else as above, and the model keeps its rows (``support_vectors_``,
-        ``save``; prediction takes test rows)."""
-        _refuse_precomputed(self.config, comm=comm, resume=resume, rank_rows=rank_rows)
-        G = _train_input(self.config, K)
-        rows = isinstance(G, _RowsGram)  # a kernel spec: K is X, the model keeps its rows
+        kern = self._kernel()
+        rank_args = dict(comm=comm, resume=resume, rank_rows=rank_rows)
+        if kern.on_gram:
+            _refuse_precomputed(cfg, **rank_args)
+        elif cfg.engines == "all" or cfg.host_cache_lines or cfg.cache_engine == "chain":
+            load_quarantine()  # the quarantined pair-at-a-time cache engines (plugin)
+        inp = _train_input(cfg, X)
         y1 = _as_1d(y)
-        n = G.n
-        if y1.shape[0] != n:
-            raise ValueError("len(y) != X.shape[0]" if rows else "len(y) != K.shape[0]")
         classes = np.unique(y1)
         multi = len(classes) > 2
+        case = "gram" if kern.on_gram else "ovr" if multi else "binary"
+        if case == "ovr":
+            for name, val in rank_args.items():
+                if val is not None:
+                    raise NotImplementedError(f"multi-class (one-vs-rest) training runs on one rank from a cold "
+                                              f"start: {name} is only supported with two classes")
         if multi:
             Ys = np.stack([np.where(y1 == c, 1.0, -1.0).astype(np.float32) for c in classes])
         else:
             Ys = self._encode(y)[None, :]
-        self._grad_sink = [None] * len(Ys)
+        if rank_rows is None and Ys.shape[1] != inp.n:
+            raise ValueError(f"len(y) != {inp.what}.shape[0]")
+        if case == "binary" and cfg.log_every and progress is None:
+            def progress(it, bh, bl, el, hits, misses):  # noqa: E306
+                print(f"iter {it}  b_hi {bh:.6g}  b_lo {bl:.6g}  gap {bl - bh:.3g}  "
+                      f"{it / max(el, 1e-9):.0f} it/s  hits {hits} misses {misses}", flush=True)
         t0 = time.perf_counter()
-        try:
-            p, RC, alphas, infos, setup, _, proba = self._fit_solves(
-                G, y1, Ys, sample_weight, probability, probability_seed, None, None, progress, None, keep=False)
-            grads = self._grad_sink
-        finally:
-            self._grad_sink = None
-        self._solver = None  # dropped with its copy of the Gram: every later call reads K(test, train)
-        self._publish(p, G.shape[1], time.perf_counter() - t0, setup)
-        self._kgamma = p.gamma  # a spec's gamma as the solver built the Gram with it
-        self.gamma_ = p.gamma if rows and not isinstance(self.config.kernel, Linear) else None
-        self._rows_cache = None
-        self._multi = multi
+        # (the gradients: the training decisions of an input whose model has no predict pass for its own rows)
+        p, RC, alphas, infos, setup, self._solver, proba, grads = self._fit_solves(
+            inp, y1, Ys, sample_weight, probability, probability_seed, comm, resume, progress, rank_rows,
+            keep=case == "binary", want_grads=not inp.train_pass)
+        self.wall_time_ = time.perf_counter() - t0
+        self._publish(np.stack(alphas).astype(np.float32), Ys, RC, infos, inp, p, setup, grads, y1,
+                      partitioned=rank_rows is not None)
         self._publish_proba(proba)
+        self._warn_max_iter(case, infos)
+        return self
+
+    # the text of each case's max_iter warning; the working-set rounds alone leave the reference's trajectory, so
+    # the RBF cases warn only after rounds ran
+    _MAX_ITER = {
+        "binary": "stopped at max_iter with gap {gap:.3g} > 2 eps: an unconverged working-set model differs from the "
+                  "reference's pair-at-a-time iterate at the same cap; raise max_iter to converge, or solver='smo' "
+                  "for the reference's trajectory (engines='all' when the Gram is not resident)",
+        "ovr": "a one-vs-rest machine stopped at max_iter before its gap closed: raise max_iter to converge",
+        "gram": "stopped at max_iter before the gap closed: raise max_iter to converge",
+    }
+
+    def _warn_max_iter(self, case: str, infos: list) -> None:
+        """called by fit(): the warning points at fit's caller"""
+        if any(i["status"] == 2 and (case == "gram" or i.get("outer", 0) > 0) for i in infos):
+            import warnings
+
+            warnings.warn(self._MAX_ITER[case].format(gap=infos[0]["b_lo"] - infos[0]["b_hi"]), RuntimeWarning,
+                          stacklevel=3)
+
+    def _publish(self, A: np.ndarray, Ys: np.ndarray, RC, infos: list, inp, p, setup, grads, y: np.ndarray,
+                 partitioned: bool) -> None:
+        """The fitted attributes of the machines' alphas A (k, n) under the labels Ys (k, n) and the row bounds RC
+        ((k, n) or None), trained on the input ``inp`` with the caller's labels ``y``; k = 1: the scalar and 1-D
+        forms (and ``classes_`` as _encode set it).  ``grads``: the solves' gradients, of an input without a
+        predict pass for its own rows; ``partitioned``: this rank holds a part of X — no rows, no support set."""
+        multi = self._multi = len(Ys) > 1
+        kind, dev = self.config.device_kind()
+        self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
+        if setup is not None:
+            self.setup_info_ = setup
+        self._kgamma = p.gamma  # a spec's gamma as the solver built the Gram with it
+        self.gamma_ = inp.published_gamma(p.gamma)
+        self.n_features_in_ = inp.shape[1]
+        self._model = self._gpu = self._rows_cache = None
         if multi:
-            self.classes_ = classes
-        A = np.stack(alphas).astype(np.float32)
+            self.classes_ = np.unique(y)
         _publish_solves(self, infos, multi=multi)
         self.alpha_ = A if multi else A[0]
         self.row_C_ = RC if (multi or RC is None) else RC[0]
         bound = RC if RC is not None else np.float32(self.config.C)
-        self.n_bounded_ = int(np.sum((A == bound) & (A > 0)))
-        if any(i["status"] == 2 for i in infos):
-            import warnings
-
-            warnings.warn("stopped at max_iter before the gap closed: raise max_iter to converge", RuntimeWarning,
-                          stacklevel=3)
-        self._X_train, self._y_train, self._Ys = (G.rows() if rows else None), (y1 if multi else Ys[0]), Ys
+        self.n_bounded_ = None if partitioned else int(np.sum((A == bound) & (A > 0)))
+        self._Ys = Ys
+        # (_y_train: what train_accuracy compares with)
+        self._X_train, self._y_train = (None, None) if partitioned else (inp.kept_rows(), y if multi else Ys[0])
+        if partitioned:
+            return
         self._coef = (A * Ys).astype(np.float32)  # (k, n): the dense coefficients gram_rows_dot reads
         self.support_ = np.nonzero((A > 0).any(axis=0))[0]
-        if rows:
+        if self._X_train is not None:
             self.support_vectors_ = self._X_train[self.support_]
         else:
             self.__dict__.pop("support_vectors_", None)
         self.dual_coef_ = self._coef[:, self.support_] if multi else self._coef[0, self.support_]
         self.n_support_ = int(len(self.support_))
-        # the training decisions f + y - b from the solver's gradient (no predict pass): train_accuracy()
-        b = np.atleast_1d(np.asarray(self.b_, dtype=np.float64))
-        self._train_dec = np.stack([(grads[c].astype(np.float64) + Ys[c] - b[c]).astype(np.float32)
-                                    for c in range(len(Ys))])
-        return self
-
-    def _publish(self, p, d: int, wall: float, setup) -> None:
-        """the fitted attributes that do not depend on the number of machines"""
-        kind, dev = self.config.device_kind()
-        self.device_ = f"{kind}:{dev}" if kind == "cuda" else "cpu"
-        self.wall_time_ = wall
-        if setup is not None:
-            self.setup_info_ = setup
-        self.gamma_ = p.gamma
-        self.n_features_in_ = d
-        self._model = None
-        self._gpu = None
-
-    def _fit_multi(self, X: np.ndarray, y: np.ndarray, comm, resume, progress, rank_rows,
-                   sample_weight=None, probability: int = 0, probability_seed: int = 0) -> "SVC":
-        """One-vs-rest: k machines on one X, the GpuSolver dropped (with its resident Gram) after the last."""
-        for name, val in (("comm", comm), ("resume", resume), ("rank_rows", rank_rows)):
-            if val is not None:
-                raise NotImplementedError(f"multi-class (one-vs-rest) training runs on one rank from a cold start: "
-                                          f"{name} is only supported with two classes")
-        n, d = X.shape
-        if y.shape[0] != n:
-            raise ValueError("len(y) != X.shape[0]")
-        classes = np.unique(y)
-        Ys = np.stack([np.where(y == c, 1.0, -1.0).astype(np.float32) for c in classes])
-        t0 = time.perf_counter()
-        p, RC, alphas, infos, setup, self._solver, proba = self._fit_solves(
-            X, y, Ys, sample_weight, probability, probability_seed, None, None, progress, None, keep=False)
-        self._publish(p, d, time.perf_counter() - t0, setup)
-        self._multi = True
-        self._publish_proba(proba)
-        self.classes_ = classes
-        self.alpha_ = np.stack(alphas).astype(np.float32)
-        _publish_solves(self, infos, multi=True)
-        self.row_C_ = RC
-        bound = RC if RC is not None else np.float32(self.config.C)
-        self.n_bounded_ = int(np.sum((self.alpha_ == bound) & (self.alpha_ > 0)))
-        if any(i["status"] == 2 and i.get("outer", 0) > 0 for i in infos):
-            import warnings
-
-            warnings.warn("a one-vs-rest machine stopped at max_iter before its gap closed: raise max_iter to "
-                          "converge", RuntimeWarning, stacklevel=3)
-        self._X_train, self._y_train, self._Ys = X, y, Ys
-        self.support_ = np.nonzero((self.alpha_ > 0).any(axis=0))[0]
-        self.support_vectors_ = X[self.support_]
-        self.dual_coef_ = (self.alpha_[:, self.support_] * Ys[:, self.support_]).astype(np.float32)
-        self.n_support_ = int(len(self.support_))
-        return self
+        if grads is not None:  # the training decisions f + y - b (no predict pass): train_accuracy()
+            b = np.atleast_1d(np.asarray(self.b_, dtype=np.float64))
+            self._train_dec = np.stack([(grads[c].astype(np.float64) + Ys[c] - b[c]).astype(np.float32)
+                                        for c in range(len(Ys))])
 
     # ------------------------------------------------------------------ cross-validation
     @staticmethod
@@ -787,7 +717,7 @@ class SVC(_Predicts):
         W = self._weights(y1, ys[None, :], sample_weight)
         self.config.weighted_params(p)
         t0 = time.perf_counter()
-        dec, folds, _, _, _, stats, setup, _ = self._cv_solves(X, ys[None, :], W, p, cv, seed)
+        dec, folds, _, _, _, stats, setup, _, _ = self._cv_solves(X, ys[None, :], W, p, cv, seed)
         if setup is not None:
             self.cv_setup_info_ = setup
         self.cv_wall_time_ = time.perf_counter() - t0
@@ -804,7 +734,8 @@ class SVC(_Predicts):
     # ------------------------------------------------------------------ model
     def to_model(self):
         C = load()
-        if self._precomputed():
+        kern = self._kernel()
+        if not kern.has_file:
             raise NotImplementedError("kernel='precomputed' has no model file (there are no rows to write): keep "
                                       "support_, dual_coef_, intercept_ and probA_ / probB_")
         if self._model is None and self._multi:
@@ -816,22 +747,19 @@ class SVC(_Predicts):
             if not self._file_classes:  # the predictors need only the columns' order
                 cls = np.arange(len(self.classes_), dtype=np.float32)
             self._model = _stamp_kernel(C.make_multi_model(self._X_train, cls, self.alpha_, self._Ys, self.b_,
-                                                           self._model_gamma()), self._kernel_spec())
+                                                           self._model_gamma()), kern.spec)
         if self._model is None:
             if self._X_train is None:
                 raise RuntimeError("to_model() needs the full training set on this rank")
             self._model = _stamp_kernel(C.make_model(self._X_train, self._y_train, self.alpha_, self.b_,
-                                                     self._model_gamma()), self._kernel_spec())
+                                                     self._model_gamma()), kern.spec)
         return self._model
-
-    def _model_gamma(self) -> float:
-        return self.gamma_ if self.gamma_ is not None else 0.0  # (the linear kernel has none)
 
     def save(self, path: str, precision: int = 9, legacy: bool = False) -> None:
         """Write the reference text model (gamma, b, then alpha,y,x... per SV);
         after a multi-class fit the one-vs-rest format ("dpsvm-ovr k nsv d",
         classes, gamma, b_0..b_k-1, then the k coefficients and x per SV)."""
-        if legacy and self._kernel_spec() is not None:
+        if legacy and self._kernel().spec is not None:
             raise ValueError("the legacy format holds an RBF machine")
         if self._multi:
             if legacy:
@@ -850,7 +778,7 @@ class SVC(_Predicts):
         """sum_sv alpha y K(sv, x) - b  (svmTrain.cu:646-652).  ``predict_chunk_rows`` (here and in predict,
         predict_proba, score): a kernel-spec model's test rows per chunk of K(test, SV); default: as many as keep
         that scratch within 1 GiB.  The other kernels ignore it."""
-        return self._decision(X, predict_chunk_rows)
+        return self._decision(X, predict_chunk_rows=predict_chunk_rows)
 
     def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
         dec = self.decision_function(X, predict_chunk_rows)
@@ -864,24 +792,8 @@ class SVC(_Predicts):
         value; two classes: [1 - p, p] with p = P(classes_[-1]); more: the k values divided by their sum (a row
         whose sum is 0: 1 / k each).  On the GPU the sigmoids run on the decision GEMM's output before its
         download.  ``predict`` stays the sign / the argmax of the decision values."""
-        if self._precomputed():  # X is K(test, train): the sigmoids on gram_rows_dot's output before the download
-            if getattr(self, "probA_", None) is None:
-                raise RuntimeError("predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
-            p = self._decision_gram(X, (np.atleast_1d(np.asarray(self.probA_, dtype=np.float64)),
-                                        np.atleast_1d(np.asarray(self.probB_, dtype=np.float64))))
-            return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
-        if self._kernel_spec() is not None:  # the sigmoids on each chunk's gram_rows_dot output
-            if getattr(self, "probA_", None) is None:
-                raise RuntimeError("predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
-            p = self._decision_rows(X, (np.atleast_1d(np.asarray(self.probA_, dtype=np.float64)),
-                                        np.atleast_1d(np.asarray(self.probB_, dtype=np.float64))), predict_chunk_rows)
-            return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
-        X = _as_f32_2d(X)
-        if X.shape[1] != self.n_features_in_:
-            raise ValueError(f"X has {X.shape[1]} features, model has {self.n_features_in_}")
-        if getattr(self, "probA_", None) is None:
-            raise RuntimeError("predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
-        return _predict_proba(self._predictor(), self.to_model, self._multi, X, self.probA_, self.probB_)
+        return self._predict_proba(X, predict_chunk_rows,
+                                   "predict_proba needs fit(probability=cv): this model has no Platt sigmoids")
 
     def score(self, X, y, predict_chunk_rows=None) -> float:
         yy = _as_1d(y)
@@ -890,7 +802,7 @@ class SVC(_Predicts):
     def train_accuracy(self) -> float:
         """Training accuracy computed on device (distributed across ranks); kernel="precomputed": from the
         solver's gradient, sign(f + y - b) per machine."""
-        if _on_gram(self.config.kernel):
+        if self._kernel().on_gram:
             dec = self._train_dec
             if self._multi:
                 return float(np.mean(self.classes_[np.argmax(dec, axis=0)] == self._y_train))
@@ -902,10 +814,7 @@ class SVC(_Predicts):
         return self.score(self._X_train, self._y_train)
 
     def get_params(self, deep: bool = True) -> dict:
-        out = dataclasses.asdict(self.config)
-        if self.config.kernel != "rbf":  # init-only (SVCConfig): reported when it is not the default
-            out["kernel"] = _kernel_name(self.config.kernel)
-        return out
+        return _config_params(self)
 
 
 class _Loaded(_Predicts):
@@ -919,15 +828,8 @@ class _Loaded(_Predicts):
 
     def predict_proba(self, X, predict_chunk_rows=None) -> np.ndarray:
         """SVC.predict_proba on the sigmoids read from the model file's ``.platt`` sidecar"""
-        if self.probA_ is None:
-            raise RuntimeError("predict_proba needs the model file's .platt sidecar (a model saved after "
-                               "fit(probability=cv))")
-        if self._kernel_spec() is not None:
-            p = self._decision_rows(X, (np.atleast_1d(np.asarray(self.probA_, dtype=np.float64)),
-                                        np.atleast_1d(np.asarray(self.probB_, dtype=np.float64))), predict_chunk_rows)
-            return p if self._multi else np.concatenate([np.float32(1.0) - p, p], axis=1)
-        return _predict_proba(self._predictor(), lambda: self.model, self._multi, _as_f32_2d(X), self.probA_,
-                              self.probB_)
+        return self._predict_proba(X, predict_chunk_rows, "predict_proba needs the model file's .platt sidecar (a "
+                                   "model saved after fit(probability=cv))")
 
     @property
     def gamma(self) -> float:
@@ -952,7 +854,7 @@ class LoadedModel(_Loaded):
     """A model read from a reference-format file (svmTest path)."""
 
     def decision_function(self, X, predict_chunk_rows=None) -> np.ndarray:
-        return self._decision(X, predict_chunk_rows)
+        return self._decision(X, predict_chunk_rows=predict_chunk_rows)
 
     def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
         return np.where(self.decision_function(X, predict_chunk_rows) < 0, -1.0, 1.0).astype(np.float32)
@@ -971,7 +873,7 @@ class LoadedMultiModel(_Loaded):
         self.classes_ = np.asarray(model.classes)
 
     def decision_function(self, X, predict_chunk_rows=None) -> np.ndarray:
-        return self._decision(X, predict_chunk_rows)
+        return self._decision(X, predict_chunk_rows=predict_chunk_rows)
 
     def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
         return self.classes_[np.argmax(self.decision_function(X, predict_chunk_rows), axis=1)]

@@ -98,7 +98,7 @@ class SVR(_OneBlockEstimator):
 
     def predict(self, X, predict_chunk_rows=None) -> np.ndarray:
         """sum_sv beta K(sv, x) - b, float32 (``predict_chunk_rows``: a kernel spec's test rows per chunk)"""
-        return self._decision(X, predict_chunk_rows)
+        return self._decision(X, predict_chunk_rows=predict_chunk_rows)
 
     def score(self, X, z, predict_chunk_rows=None) -> float:
         """R^2 of the predictions"""

@@ -265,207 +265,6 @@ class GpuPredictor {
   std::unique_ptr<Impl> impl_;
 };
 
-// Low-level kernel entry points exposed for unit tests (device pointers; kernel_entry.hip).
-namespace kernels {
-void row_sqnorm(const float* x, int64_t n, int d, int ld, float* out, void* stream);
-// known-bytes 16-B streaming read (FETCH_SIZE probe, bench/fetch_probe.py)
-void stream_read(const void* x, int64_t bytes, float* out, int blocks, void* stream);
-// K[q][j] = exp(-gamma * max(|x_j|^2 + |w_q|^2 - 2 x_j.w_q, 0)) for q < nq <= 16
-void rbf_rows(const float* x, const float* xsq, int64_t n, int ld, const float* w, const float* wsq,
-              int nq, float gamma, float* out, int64_t out_ld, void* stream);
-// per-block selection partials over f/alpha/y (keys as in common.hpp)
-void select_partials(const float* f, const float* alpha, const float* y, int64_t n, int64_t offset,
-                     float C, uint64_t* partials, int* blocks_out, void* stream);
-void predict(const float* x, const float* xsq, int64_t n, int ld, const float* sv,
-             const float* svsq, const float* coef, int64_t nsv, int sv_ld, float gamma, float b,
-             float* dec, void* stream);
-// dec[i * k + c] = sum_j coef[j * k + c] K(x_i, sv_j) - b[c] (launch::rbf_predict_multi; b: device, k floats)
-void predict_multi(const float* x, const float* xsq, int64_t n, int ld, const float* sv, const float* svsq,
-                   const float* coef, int k, int64_t nsv, int sv_ld, float gamma, const float* b, float* dec,
-                   void* stream);
-// diagnostics (bench/predict_multi_probe.py): ms per repetition, event-timed, of the multi-output launch
-// (multi) or of k single-output rbf_predict launches, one per row of coef_cols [k][ldcc] (column c's
-// coefficients, zero-padded as predict's coef), into dec
-std::vector<float> predict_multi_bench(const float* x, const float* xsq, int64_t n, int ld, const float* sv,
-                                       const float* svsq, const float* coef, const float* coef_cols, int64_t ldcc,
-                                       int k, int64_t nsv, float gamma, const float* b, float* dec, bool multi,
-                                       int reps, void* stream);
-int64_t compact_nonzero(const float* alpha, int64_t n, int* idx_out, void* stream);
-// Gram block K[i][j] = K(a_i, b_j) (dense-mode GEMM; symmetric: b == a)
-void rbf_gram(const float* a, const float* asq, int64_t m, const float* b, const float* bsq, int64_t n, int ld,
-              float gamma, float* out, int64_t out_ld, bool symmetric, void* stream);
-// the cache engines' X pass: out[q][j] = K(x_keys[q], x_j), q < nq <= 16, j < n
-// (x: [rows >= G*rows_per_group][ld], xsq likewise; out rows >= G*rows_per_group)
-// the working-set cache engine's row GEMM: out[out_rows[i]][j] = K(x[rows[i]], x_j), i < m, j < n
-void rbf_rows_indexed(const float* x, const float* xsq, int64_t n, int ld, const int* rows, int m, float gamma,
-                      float* out, int64_t out_ld, const int* out_rows, void* stream, bool split = false);
-// diagnostics: the split row GEMM alone (operands split once), reps launches
-// event-timed; returns ms per launch (bench/rows_probe.py)
-std::vector<float> rbf_rows_indexed_split_bench(const float* x, const float* xsq, int64_t n, int ld, const int* rows,
-                                                int m, float gamma, float* out, int64_t out_ld, const int* out_rows,
-                                                int reps, void* stream);
-// the same two GEMMs on fp16 MFMA over split operands (rbf_gemm_split.hip)
-void rbf_gram_split(const float* a, const float* asq, int64_t m, const float* b, const float* bsq, int64_t n, int ld,
-                    float gamma, float* out, int64_t out_ld, bool symmetric, void* stream,
-                    float cold_tau = 0.f);
-// the Gram of a dot-product kernel (dot_gemm_split.hip) from f32 device rows a [m][lda >= d], b [n][ldb >= d] (split
-// here, into stream-ordered temporaries); symmetric: b unused, n = m, out_ld % 4 == 0.  Columns >= n of out are not
-// written.  reps > 0: the event times (us) of reps launches of the GEMM before the returned one.
-std::vector<float> dot_gram_split(const float* a, int64_t m, const float* b, int64_t n, int d, int lda, int ldb,
-                                  const DotKernelSpec& spec, float gamma, float* out, int64_t out_ld, bool symmetric,
-                                  void* stream, int reps = 0);
-// the adaptive Gram of the calling thread's last rbf_gram_split / solve: (one-product tiles, hot tiles) or (-1, -1)
-std::pair<int64_t, int64_t> gram_adapt_last();
-void xpass_rows(const float* x, const float* xsq, int64_t n, int ld, const int* keys, int nq, float gamma,
-                float* out, int64_t out_ld, int rows_per_group, void* stream);
-// the fused / persistent engines' selection: per workgroup of rows_per_group rows
-// the (up, low) keys of its rows -> keys_out[2 * groups]
-void fused_select(const float* f, const float* alpha, const float* y, int64_t n, float C, int rows_per_group,
-                  uint64_t* keys_out, void* stream);
-// probability estimates (platt.hip), host vectors in and out, one launch each.  holdout_decision: dec
-// [slots][n] with slot `slot`'s entries at `rows` (each in [0, n)) replaced by float(double(f) + y - b).
-// platt_fit: m machines (dec and y [m][n]) in one launch.  proba_rows: dec [n][k] -> probabilities [n][k].
-std::vector<float> holdout_decision(const std::vector<float>& f, const std::vector<float>& y,
-                                    const std::vector<int32_t>& rows, double b, std::vector<float> dec, int slot);
-std::vector<PlattFit> platt_fit(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n);
-std::vector<float> proba_rows(const std::vector<float>& dec, int64_t n, int k, const std::vector<double>& A,
-                              const std::vector<double>& B);
-// diagnostics (bench/platt_probe.py): ms per launch, event-timed, of platt_fit on device-resident inputs
-std::vector<float> platt_fit_bench(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n,
-                                   int reps);
-
-// ---- working-set kernels (ws_*.hip), one launch each on crafted state
-// (host vectors in and out; ws_kernel_entry.hip).  Reference counterparts:
-// the selection / update functors svmTrain.cu:41-137, the pair rule
-// svmTrainMain.cpp:255-299. ----
-// ws_merge_multi: cand = [G][2][kWsCand] per-list keys (up, low), the previous
-// union (newest first), the adaptive block count p_act of `blocks`
-struct WsMergeProbe {
-  std::vector<int32_t> uidx;  // the union, newest first
-  std::vector<int32_t> idx;   // [blocks][q_max] block layout (-1: unused)
-  std::vector<int32_t> qb;    // rows per block
-  float b_hi = 0.f, b_lo = 0.f;
-  int done = 0, p_round = 0;
-};
-WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int blocks, int p_act, int q_max,
-                                  int n_new, float eps, const std::vector<int32_t>& prev_union, int64_t iter,
-                                  int64_t max_iter);
-// ws_solve: P blocks; block p = qb[p] rows with sub-Gram K[p] ([q_max][q_max]),
-// f / alpha / y (row a of block p is global row p q_max + a)
-struct WsSolveProbe {
-  std::vector<float> alpha;       // [P * q_max] after the solve (untouched rows 0)
-  std::vector<int32_t> steps;     // pair steps per block
-  std::vector<int32_t> apply_idx; // changed rows per block segment (concatenated, block order)
-  std::vector<float> apply_coef;  // their (alpha_new - alpha_old) y
-  std::vector<int32_t> nab;       // changed rows per block
-  int64_t iter = 0, outer = 0, p1_round = 0;
-  int done = 0, p_act = 0;
-};
-WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float>& f, const std::vector<float>& alpha,
-                            const std::vector<float>& y, const std::vector<int32_t>& qb, int q_max, int blocks,
-                            int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
-                            float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss = 1,
-                            const std::vector<float>& row_C = {},  // [P * q_max] per-row bounds (empty: scalar C)
-                            bool diag = false);  // the general-diagonal kernels (one block, box clipping)
-// ws_select: the f update of a round's alpha changes (apply rows: lines into
-// gram [L][ldg], coefficients) and the per-workgroup candidates.  blocks == 1:
-// the one-pass kernel; blocks > 1: pass 1 (d_f, line-search partials) and pass 2
-// (t, f += t d_f, alpha fix-up, candidates) with p_round blocks this round;
-// pass 1 loads 16 bytes a thread, so blocks > 1 needs ldg % 4 == 0 and ldg >= round_up(n, 4).
-struct WsSelectProbe {
-  std::vector<float> f, alpha, dalpha, dfs;
-  std::vector<double> part;      // [p1G][ks][2] d'Qd, g'd partials (two-pass mode)
-  std::vector<uint64_t> cand;    // [G][2][kWsCand]
-  int G = 0, rpt = 0, p_act = 0, n_damped = 0, nonfinite = 0;
-  int p1G = 0;                   // pass-1 groups (blocks > 1: ceil(n / 1024), else G); part is [p1G][ks][2]
-  float t = 1.f;
-  int64_t p1_round = 0;
-  std::vector<float> pass1_us;  // reps > 0: event times of repeated pass-1 launches
-  std::vector<float> select_us; // one block, reps > 0: event times of repeated one-pass launches (plain or fold)
-};
-WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t ldg, const std::vector<float>& f,
-                              const std::vector<float>& alpha, const std::vector<float>& y,
-                              const std::vector<float>& dalpha, const std::vector<int32_t>& apply_line,
-                              const std::vector<float>& apply_coef, const std::vector<int32_t>& nab, int blocks,
-                              int p_round, int p_act, int q_max, float C, int64_t outer, int ks = 0,
-                              int reps = 0,
-                              const std::vector<float>& row_C = {},  // [n] per-row bounds (empty: scalar C)
-                              // fold > 0: the epsilon-SVR kernel — f / alpha / y of 2 fold state rows on gram
-                              // [L][ldg >= fold]; done: the run's state (DoneCode) the launch finds
-                              int64_t fold = 0, int done = 0);
-// gram_rows_wsum (gram_wsum.hip): out[j] = float(sum_r double(coef[r]) double(gram[line(r)][j]) + base[j]), j < n,
-// on gram [L][ldg].  lines empty: identity lines (row r), m = coef.size() <= L; base empty: none.  out is
-// round_up(n, 4) + kGramWsumProbePad floats filled with kGramWsumProbeFill before the launch: the entries from n
-// on must come back as they were.  reps > 0: event times (us) of reps launches before the returned one.
-constexpr int kGramWsumProbePad = 64;
-constexpr float kGramWsumProbeFill = -12345.f;
-struct GramWsumProbe {
-  std::vector<float> out;
-  int slices = 0;  // S = gram_wsum_slices(n, m)
-  std::vector<float> us;
-};
-GramWsumProbe gram_rows_wsum_probe(const std::vector<float>& gram, int64_t L, int64_t ldg, int64_t n,
-                                   const std::vector<int32_t>& lines, const std::vector<float>& coef,
-                                   const std::vector<float>& base, int reps = 0);
-// gram_rows_dot (gram_dot.hip): out[i][c] = float(sum_j double(Kt[i][j]) double(coef[c][j]) - b[c]) on Kt [nt][ld],
-// coef [k][ldc], b [k].  out is [pad | nt * k | pad] with pad = kGramDotProbePad floats filled with
-// kGramDotProbeFill before the launch: the pads must come back as they were.  reps > 0: event times (us) of reps
-// launches before the returned one.
-constexpr int kGramDotProbePad = 64;
-constexpr float kGramDotProbeFill = -12345.f;
-struct GramDotProbe {
-  std::vector<float> out;
-  std::vector<float> us;
-};
-GramDotProbe gram_rows_dot_probe(const std::vector<float>& Kt, int64_t nt, int64_t ld, int64_t n,
-                                 const std::vector<float>& coef, int64_t ldc, int k, const std::vector<float>& b,
-                                 int reps = 0);
-// The one-block merge (ws_merge.hpp) through the two round kernels that run it
-// in every workgroup, one launch each: round `outer` builds parity outer & 1
-// from cand = [G][2][kWsCand] lists (the merge reads the first kWsCand1 keys a
-// side) and the previous set (newest first, parity (outer & 1) ^ 1).  subg /
-// aux / idx are filled with a sentinel (NaN / -1) before the launch; n_apply
-// starts at kWsProbeApply, so a stop shows as 0.
-//   ws_gather_probe         dense: the sub-Gram rows from gram [n][ldg]
-//   ws_subgram_split_probe  recompute rounds: the sub-Gram tiles from x [n][d]
-//                           (padded to pad_features(d) <= 64 columns, |x|^2 by
-//                           row_sqnorm, operands by split_rows_f16: the solver's)
-constexpr int kWsProbeApply = 7;
-struct WsGatherProbe {
-  int done = 0, q = 0, n_apply = 0;
-  float b_hi = 0.f, b_lo = 0.f;
-  std::vector<int32_t> idx;  // [q] the set, newest first
-  std::vector<int32_t> line; // [q] the members' Gram lines as the round recorded them (WsCtrl::line)
-  std::vector<float> subg;   // [q_max][q_max]
-  std::vector<float> aux;    // [3][kWsMax] f / alpha / y of the set
-};
-WsGatherProbe ws_gather_probe(const std::vector<float>& gram, int64_t n, int64_t ldg, const std::vector<uint64_t>& cand,
-                              const std::vector<int32_t>& prev_set, const std::vector<float>& f,
-                              const std::vector<float>& alpha, const std::vector<float>& y, int q_max, int n_new,
-                              float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer,
-                              int64_t fold = 0);  // fold > 0: n = 2 fold state rows on gram [fold][ldg >= fold]
-WsGatherProbe ws_subgram_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<uint64_t>& cand,
-                                     const std::vector<int32_t>& prev_set, const std::vector<float>& f,
-                                     const std::vector<float>& alpha, const std::vector<float>& y, float gamma,
-                                     int q_max, int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite,
-                                     int64_t outer);
-// ws_fupdate_split: the recompute rounds' selection pass, one launch on x [n][d]
-// (operands as above) with the apply list of a round (rows, coefficients) and
-// the run's state `done`; cand is prefilled with kWsProbeKey (neither a key of
-// a row < 2^31 nor kKeyNone)
-constexpr uint64_t kWsProbeKey = 0xABCDABCDFFFFFFFFull;
-struct WsFupdateProbe {
-  std::vector<float> f;
-  std::vector<uint64_t> cand;  // [G][2][kWsCand]
-  int nonfinite = 0, G = 0, rpt = 0;
-  int64_t rows_computed = 0;
-};
-WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<float>& f,
-                                      const std::vector<float>& alpha, const std::vector<float>& y,
-                                      const std::vector<int32_t>& apply_idx, const std::vector<float>& apply_coef,
-                                      float gamma, float C, int done);
-}  // namespace kernels
-
 int device_count();
 std::string device_name(int dev);
 

@@ -13,6 +13,7 @@
 #include "dpsvm/common.hpp"
 #include "dpsvm/device_state.hpp"
 #include "dpsvm/io.hpp"
+#include "dpsvm/kernel_probes.hpp"
 #include "dpsvm/solver.hpp"
 #include "dpsvm/params_io.hpp"
 #include "dpsvm/problem.hpp"
@@ -25,7 +26,9 @@ using namespace dpsvm;
 
 namespace {
 
-using F32 = py::array_t<float, py::array::c_style | py::array::forcecast>;
+template <class T>
+using Arr = py::array_t<T, py::array::c_style | py::array::forcecast>;
+using F32 = Arr<float>;
 
 py::array_t<float> to_np(const std::vector<float>& v) {
   py::array_t<float> a((py::ssize_t)v.size());
@@ -48,7 +51,15 @@ py::array_t<float> decide(const F32& x, int cols, Fn&& fn) {
   }
   return cols ? to_np2(out, x.shape(0), cols) : to_np(out);
 }
-std::vector<float> from_np(const F32& a) { return std::vector<float>(a.data(), a.data() + a.size()); }
+template <class T>
+std::vector<T> from_np(const Arr<T>& a) {
+  return std::vector<T>(a.data(), a.data() + a.size());
+}
+// None: an empty vector
+template <class T>
+std::vector<T> from_np_or_none(const py::object& o) {
+  return o.is_none() ? std::vector<T>() : from_np(o.cast<Arr<T>>());
+}
 
 void check_xy(const F32& x, const F32& y, int64_t& n, int& d) {
   if (x.ndim() != 2) throw py::value_error("x must be 2-D (n, d)");
@@ -214,7 +225,7 @@ py::dict platt_dict(const PlattFit& r) {
   return d;
 }
 
-using F64 = py::array_t<double, py::array::c_style | py::array::forcecast>;
+using F64 = Arr<double>;
 // the k sigmoids (A, B) of decisions with `cols` columns
 void check_sigmoids(const F64& A, const F64& B, int64_t cols) {
   if (A.ndim() != 1 || B.ndim() != 1 || A.shape(0) != cols || B.shape(0) != cols)
@@ -988,13 +999,12 @@ PYBIND11_MODULE(_C, m) {
                           (void*)stream);
   });
   // working-set kernels on crafted state (ws_kernel_entry.hip)
-  using U64 = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>;
-  using I32 = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
-  auto vi = [](const I32& a) { return std::vector<int32_t>(a.data(), a.data() + a.size()); };
-  m.def("k_ws_merge_multi", [vi](const U64& cand, int G, int blocks, int p_act, int q_max, int n_new, float eps,
-                                 const I32& prev, int64_t iter, int64_t max_iter) {
-    const auto r = kernels::ws_merge_multi_probe(std::vector<uint64_t>(cand.data(), cand.data() + cand.size()), G,
-                                                 blocks, p_act, q_max, n_new, eps, vi(prev), iter, max_iter);
+  using U64 = Arr<uint64_t>;
+  using I32 = Arr<int32_t>;
+  m.def("k_ws_merge_multi", [](const U64& cand, int G, int blocks, int p_act, int q_max, int n_new, float eps,
+                               const I32& prev, int64_t iter, int64_t max_iter) {
+    const auto r = kernels::ws_merge_multi_probe(from_np(cand), G, blocks, p_act, q_max, n_new, eps, from_np(prev),
+                                                 iter, max_iter);
     py::dict d;
     d["uidx"] = r.uidx;
     d["idx"] = r.idx;
@@ -1005,14 +1015,13 @@ PYBIND11_MODULE(_C, m) {
     d["p_round"] = r.p_round;
     return d;
   });
-  m.def("k_ws_solve", [vi](const F32& K, const F32& f, const F32& alpha, const F32& y, const I32& qb, int q_max,
-                           int blocks, int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
-                           float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss,
-                           py::object row_C, bool diag) {
-    const auto r = kernels::ws_solve_probe(from_np(K), from_np(f), from_np(alpha), from_np(y), vi(qb), q_max, blocks,
-                                           p_round, C, clip, eps, rel, eps_floor, tau, b_hi, b_lo, inner_max, iter0,
-                                           max_iter, wss,
-                                           row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()), diag);
+  m.def("k_ws_solve", [](const F32& K, const F32& f, const F32& alpha, const F32& y, const I32& qb, int q_max,
+                         int blocks, int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
+                         float b_hi, float b_lo, int inner_max, int64_t iter0, int64_t max_iter, int wss,
+                         py::object row_C, bool diag) {
+    const auto r = kernels::ws_solve_probe(from_np(K), from_np(f), from_np(alpha), from_np(y), from_np(qb), q_max,
+                                           blocks, p_round, C, clip, eps, rel, eps_floor, tau, b_hi, b_lo, inner_max,
+                                           iter0, max_iter, wss, from_np_or_none<float>(row_C), diag);
     py::dict d;
     d["alpha"] = to_np(r.alpha);
     d["steps"] = r.steps;
@@ -1051,15 +1060,14 @@ PYBIND11_MODULE(_C, m) {
     launch::gram_rows_dot((const float*)Kt, nt, ld, n, (const float*)coef, ldc, k, (const float*)b, (float*)out, ldo,
                           (hipStream_t)stream);
   });
-  m.def("k_ws_select", [vi](const F32& gram, int64_t L, int64_t ldg, const F32& f, const F32& alpha, const F32& y,
-                            const F32& dalpha, const I32& lines, const F32& coef, const I32& nab, int blocks,
-                            int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps,
-                            py::object row_C, int64_t fold, int done) {
+  m.def("k_ws_select", [](const F32& gram, int64_t L, int64_t ldg, const F32& f, const F32& alpha, const F32& y,
+                          const F32& dalpha, const I32& lines, const F32& coef, const I32& nab, int blocks,
+                          int p_round, int p_act, int q_max, float C, int64_t outer, int ks, int reps,
+                          py::object row_C, int64_t fold, int done) {
     const auto r = kernels::ws_select_probe(from_np(gram), L, ldg, from_np(f), from_np(alpha), from_np(y),
-                                            from_np(dalpha), vi(lines), from_np(coef), vi(nab), blocks, p_round, p_act,
-                                            q_max, C, outer, ks, reps,
-                                            row_C.is_none() ? std::vector<float>() : from_np(row_C.cast<F32>()), fold,
-                                            done);
+                                            from_np(dalpha), from_np(lines), from_np(coef), from_np(nab), blocks,
+                                            p_round, p_act, q_max, C, outer, ks, reps, from_np_or_none<float>(row_C),
+                                            fold, done);
     py::dict d;
     d["f"] = to_np(r.f);
     d["alpha"] = to_np(r.alpha);
@@ -1084,11 +1092,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("row_C") = py::none(), py::arg("fold") = 0, py::arg("done") = 0);
   m.def("k_gram_wsum_slices", [](int64_t n, int64_t m) { return launch::gram_wsum_slices(n, m); }, py::arg("n"),
         py::arg("m"), "row slices S of gram_rows_wsum for n columns and m rows (a function of the shape alone)");
-  m.def("k_gram_rows_wsum", [vi](const F32& gram, int64_t L, int64_t ldg, int64_t n, py::object lines, const F32& coef,
-                                 py::object base, int reps) {
-    const auto r = kernels::gram_rows_wsum_probe(
-        from_np(gram), L, ldg, n, lines.is_none() ? std::vector<int32_t>() : vi(lines.cast<I32>()), from_np(coef),
-        base.is_none() ? std::vector<float>() : from_np(base.cast<F32>()), reps);
+  m.def("k_gram_rows_wsum", [](const F32& gram, int64_t L, int64_t ldg, int64_t n, py::object lines, const F32& coef,
+                               py::object base, int reps) {
+    const auto r = kernels::gram_rows_wsum_probe(from_np(gram), L, ldg, n, from_np_or_none<int32_t>(lines),
+                                                 from_np(coef), from_np_or_none<float>(base), reps);
     py::dict d;
     d["out"] = to_np(r.out);
     d["S"] = r.slices;
@@ -1097,7 +1104,6 @@ PYBIND11_MODULE(_C, m) {
     return d;
   }, py::arg("gram"), py::arg("L"), py::arg("ldg"), py::arg("n"), py::arg("lines"), py::arg("coef"),
         py::arg("base") = py::none(), py::arg("reps") = 0);
-  auto vu = [](const U64& a) { return std::vector<uint64_t>(a.data(), a.data() + a.size()); };
   auto gather_dict = [](const kernels::WsGatherProbe& r) {
     py::dict d;
     d["done"] = r.done;
@@ -1111,30 +1117,30 @@ PYBIND11_MODULE(_C, m) {
     d["aux"] = to_np(r.aux);
     return d;
   };
-  m.def("k_ws_gather", [vi, vu, gather_dict](const F32& gram, int64_t n, int64_t ldg, const U64& cand, const I32& prev,
-                                             const F32& f, const F32& alpha, const F32& y, int q_max, int n_new,
-                                             float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer,
-                                             int64_t fold) {
-    return gather_dict(kernels::ws_gather_probe(from_np(gram), n, ldg, vu(cand), vi(prev), from_np(f), from_np(alpha),
-                                                from_np(y), q_max, n_new, eps, iter, max_iter, nonfinite, outer,
-                                                fold));
+  m.def("k_ws_gather", [gather_dict](const F32& gram, int64_t n, int64_t ldg, const U64& cand, const I32& prev,
+                                     const F32& f, const F32& alpha, const F32& y, int q_max, int n_new,
+                                     float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer,
+                                     int64_t fold) {
+    return gather_dict(kernels::ws_gather_probe(from_np(gram), n, ldg, from_np(cand), from_np(prev), from_np(f),
+                                                from_np(alpha), from_np(y), q_max, n_new, eps, iter, max_iter,
+                                                nonfinite, outer, fold));
   }, py::arg("gram"), py::arg("n"), py::arg("ldg"), py::arg("cand"), py::arg("prev"), py::arg("f"), py::arg("alpha"),
         py::arg("y"), py::arg("q_max"), py::arg("n_new"), py::arg("eps"), py::arg("iter"), py::arg("max_iter"),
         py::arg("nonfinite"), py::arg("outer"), py::arg("fold") = 0);
-  m.def("k_ws_subgram_split", [vi, vu, gather_dict](const F32& x, int64_t n, int d, const U64& cand, const I32& prev,
-                                                    const F32& f, const F32& alpha, const F32& y, float gamma,
-                                                    int q_max, int n_new, float eps, int64_t iter, int64_t max_iter,
-                                                    int nonfinite, int64_t outer) {
-    return gather_dict(kernels::ws_subgram_split_probe(from_np(x), n, d, vu(cand), vi(prev), from_np(f),
+  m.def("k_ws_subgram_split", [gather_dict](const F32& x, int64_t n, int d, const U64& cand, const I32& prev,
+                                            const F32& f, const F32& alpha, const F32& y, float gamma,
+                                            int q_max, int n_new, float eps, int64_t iter, int64_t max_iter,
+                                            int nonfinite, int64_t outer) {
+    return gather_dict(kernels::ws_subgram_split_probe(from_np(x), n, d, from_np(cand), from_np(prev), from_np(f),
                                                        from_np(alpha), from_np(y), gamma, q_max, n_new, eps, iter,
                                                        max_iter, nonfinite, outer));
   }, py::arg("x"), py::arg("n"), py::arg("d"), py::arg("cand"), py::arg("prev"), py::arg("f"), py::arg("alpha"),
         py::arg("y"), py::arg("gamma"), py::arg("q_max"), py::arg("n_new"), py::arg("eps"), py::arg("iter"),
         py::arg("max_iter"), py::arg("nonfinite"), py::arg("outer"));
-  m.def("k_ws_fupdate_split", [vi](const F32& x, int64_t n, int d, const F32& f, const F32& alpha, const F32& y,
-                                   const I32& apply_idx, const F32& apply_coef, float gamma, float C, int done) {
+  m.def("k_ws_fupdate_split", [](const F32& x, int64_t n, int d, const F32& f, const F32& alpha, const F32& y,
+                                 const I32& apply_idx, const F32& apply_coef, float gamma, float C, int done) {
     const auto r = kernels::ws_fupdate_split_probe(from_np(x), n, d, from_np(f), from_np(alpha), from_np(y),
-                                                   vi(apply_idx), from_np(apply_coef), gamma, C, done);
+                                                   from_np(apply_idx), from_np(apply_coef), gamma, C, done);
     py::dict d_;
     d_["f"] = to_np(r.f);
     d_["cand"] = r.cand;
@@ -1146,13 +1152,13 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("x"), py::arg("n"), py::arg("d"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("apply_idx"),
         py::arg("apply_coef"), py::arg("gamma"), py::arg("C"), py::arg("done"));
   // probability estimates (platt.hip), one launch each on host arrays
-  m.def("k_holdout_decision", [vi](const F32& f, const F32& y, const I32& rows, double b, const F32& dec, int slot) {
+  m.def("k_holdout_decision", [](const F32& f, const F32& y, const I32& rows, double b, const F32& dec, int slot) {
     if (dec.ndim() != 2 || dec.shape(1) != f.size()) throw py::value_error("dec must be (slots, n)");
-    return to_np2(kernels::holdout_decision(from_np(f), from_np(y), vi(rows), b, from_np(dec), slot), dec.shape(0),
+    return to_np2(kernels::holdout_decision(from_np(f), from_np(y), from_np(rows), b, from_np(dec), slot), dec.shape(0),
                   (int)dec.shape(1));
   }, py::arg("f"), py::arg("y"), py::arg("rows"), py::arg("b"), py::arg("dec"), py::arg("slot"));
   m.def("k_platt_fit", [](const F32& dec, const F32& y) {
-    if (dec.ndim() != 2 || y.ndim() != 2 || dec.shape(0) != y.shape(0) || dec.shape(1) != y.shape(1))
+    if (dec.ndim() != 2 || y.ndim() != 2 || dec.shape(0) != y.shape(0))  // the row length: the probe's check
       throw py::value_error("dec and y must be (m, n)");
     std::vector<PlattFit> r;
     {
@@ -1167,16 +1173,13 @@ PYBIND11_MODULE(_C, m) {
     return out;
   }, py::arg("dec"), py::arg("y"));
   m.def("k_platt_fit_bench", [](const F32& dec, const F32& y, int reps) {
-    if (dec.ndim() != 2 || y.ndim() != 2 || dec.shape(0) != y.shape(0) || dec.shape(1) != y.shape(1))
+    if (dec.ndim() != 2 || y.ndim() != 2 || dec.shape(0) != y.shape(0))  // the row length: the probe's check
       throw py::value_error("dec and y must be (m, n)");
     return kernels::platt_fit_bench(from_np(dec), from_np(y), (int)dec.shape(0), dec.shape(1), reps);
   }, py::arg("dec"), py::arg("y"), py::arg("reps"), "diagnostics: ms per launch of the fit on resident decisions");
   m.def("k_proba_rows", [](const F32& dec, const F64& A, const F64& B) {
     if (dec.ndim() != 2) throw py::value_error("dec must be (n, k)");
-    check_sigmoids(A, B, dec.shape(1));
-    return to_np2(kernels::proba_rows(from_np(dec), dec.shape(0), (int)dec.shape(1),
-                                      std::vector<double>(A.data(), A.data() + A.size()),
-                                      std::vector<double>(B.data(), B.data() + B.size())),
+    return to_np2(kernels::proba_rows(from_np(dec), dec.shape(0), (int)dec.shape(1), from_np(A), from_np(B)),
                   dec.shape(0), (int)dec.shape(1));
   }, py::arg("dec"), py::arg("A"), py::arg("B"));
   // proba_rows in place on device pointers (dec [n][k] float32, A / B k float64; stream: hipStream_t)

@@ -4,13 +4,15 @@
 // pass, SV compaction.  The working-set kernels' are in ws_kernel_entry.hip.
 #include <hip/hip_runtime.h>
 
-#include "gpu_impl.hpp"
+#include "probe_util.hpp"
 
 namespace dpsvm {
-
-using gpu::dmalloc;
-
 namespace kernels {
+
+using probe::Arena;
+using probe::SplitRows;
+using probe::time_launches;
+using probe::to_f32;
 
 void row_sqnorm(const float* x, int64_t n, int d, int ld, float* out, void* stream) {
   launch::row_sqnorm(x, n, d, ld, out, (hipStream_t)stream);
@@ -24,10 +26,8 @@ void rbf_rows(const float* x, const float* xsq, int64_t n, int ld, const float* 
               float gamma, float* out, int64_t out_ld, void* stream) {
   DPSVM_CHECK(nq >= 1 && nq <= kNQ, "rbf_rows: 1 <= nq <= 16");
   DPSVM_CHECK(ld % 16 == 0, "rbf_rows: ld must be a multiple of 16");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<float> hsq((size_t)nq);
-  HIP_CHECK(hipMemcpyAsync(hsq.data(), wsq, nq * 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
+  Arena st(stream);
+  const std::vector<float> hsq = st.down(wsq, (size_t)nq);
   SmoCtrl c;
   memset(&c, 0, sizeof(c));
   c.nq = nq;
@@ -38,15 +38,12 @@ void rbf_rows(const float* x, const float* xsq, int64_t n, int ld, const float* 
     c.q_sq[q] = hsq[q];
     c.q_ptr[q] = w + (size_t)q * ld;
   }
-  size_t tb = 0;
-  SmoCtrl* dc = dmalloc<SmoCtrl>(1, &tb);
-  HIP_CHECK(hipMemcpyAsync(dc, &c, sizeof(c), hipMemcpyHostToDevice, s));
   SmoArgs a{};
   a.x = x;
   a.xsq = xsq;
   a.lines = out;
   a.ldl = out_ld;
-  a.ctrl = dc;
+  a.ctrl = st.up_one(c);
   a.n = n;
   a.nl = n;
   a.off = 0;
@@ -55,57 +52,48 @@ void rbf_rows(const float* x, const float* xsq, int64_t n, int ld, const float* 
   a.d = ld;
   a.G = (int32_t)((n + kStepRows - 1) / kStepRows);
   a.gamma = gamma;
-  gpu::need_quarantine("k_rbf_rows (smo_rows)").smo_rows(a, s);
-  HIP_CHECK(hipStreamSynchronize(s));
-  (void)hipFree(dc);
+  gpu::need_quarantine("k_rbf_rows (smo_rows)").smo_rows(a, st.s);
+  HIP_CHECK(hipStreamSynchronize(st.s));
 }
 
 void select_partials(const float* f, const float* alpha, const float* y, int64_t n, int64_t offset, float C,
                      uint64_t* partials, int* blocks_out, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
+  Arena st(stream);
   SmoCtrl c;
   memset(&c, 0, sizeof(c));
   c.line_hi = c.line_lo = -1;
-  size_t tb = 0;
-  SmoCtrl* dc = dmalloc<SmoCtrl>(1, &tb);
-  HIP_CHECK(hipMemcpyAsync(dc, &c, sizeof(c), hipMemcpyHostToDevice, s));
   SmoArgs a{};
   a.f = const_cast<float*>(f);
   a.alpha = const_cast<float*>(alpha);
   a.y = y;
-  a.ctrl = dc;
+  a.ctrl = st.up_one(c);
   a.partials = partials;
   a.nl = n;
   a.off = offset;
   a.C = C;
   a.G = (int32_t)((n + kStepRows - 1) / kStepRows);
-  gpu::need_quarantine("k_select_partials (smo_step)").smo_step(a, s);
-  HIP_CHECK(hipStreamSynchronize(s));
-  (void)hipFree(dc);
+  gpu::need_quarantine("k_select_partials (smo_step)").smo_step(a, st.s);
+  HIP_CHECK(hipStreamSynchronize(st.s));
   if (blocks_out) *blocks_out = a.G;
 }
 
 void predict(const float* x, const float* xsq, int64_t n, int ld, const float* sv, const float* svsq,
              const float* coef, int64_t nsv, int sv_ld, float gamma, float b, float* dec, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   DPSVM_CHECK(ld == sv_ld && ld % 16 == 0, "predict: ld == sv_ld, multiple of 16");
-  size_t tb = 0;
-  float* part = dmalloc<float>((size_t)launch::predict_scratch_floats(n, nsv), &tb);
-  launch::rbf_predict(x, xsq, n, ld, sv, svsq, coef, nsv, sv_ld, ld, gamma, b, part, dec, nullptr, nullptr, s);
-  HIP_CHECK(hipStreamSynchronize(s));
-  (void)hipFree(part);
+  Arena st(stream);
+  float* part = st.alloc<float>((size_t)launch::predict_scratch_floats(n, nsv));
+  launch::rbf_predict(x, xsq, n, ld, sv, svsq, coef, nsv, sv_ld, ld, gamma, b, part, dec, nullptr, nullptr, st.s);
+  HIP_CHECK(hipStreamSynchronize(st.s));
 }
 
 void predict_multi(const float* x, const float* xsq, int64_t n, int ld, const float* sv, const float* svsq,
                    const float* coef, int k, int64_t nsv, int sv_ld, float gamma, const float* b, float* dec,
                    void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   DPSVM_CHECK(ld == sv_ld && ld % 16 == 0 && k >= 1, "predict_multi: ld == sv_ld, multiple of 16; k >= 1");
-  size_t tb = 0;
-  float* scratch = dmalloc<float>((size_t)launch::predict_multi_scratch_floats(n, nsv, k), &tb);
-  launch::rbf_predict_multi(x, xsq, n, ld, sv, svsq, coef, k, k, nsv, sv_ld, ld, gamma, b, scratch, dec, k, s);
-  HIP_CHECK(hipStreamSynchronize(s));
-  (void)hipFree(scratch);
+  Arena st(stream);
+  float* scratch = st.alloc<float>((size_t)launch::predict_multi_scratch_floats(n, nsv, k));
+  launch::rbf_predict_multi(x, xsq, n, ld, sv, svsq, coef, k, k, nsv, sv_ld, ld, gamma, b, scratch, dec, k, st.s);
+  HIP_CHECK(hipStreamSynchronize(st.s));
 }
 
 std::vector<float> predict_multi_bench(const float* x, const float* xsq, int64_t n, int ld, const float* sv,
@@ -113,32 +101,18 @@ std::vector<float> predict_multi_bench(const float* x, const float* xsq, int64_t
                                        int k, int64_t nsv, float gamma, const float* b, float* dec, bool multi,
                                        int reps, void* stream) {
   DPSVM_CHECK(ld % 16 == 0 && k >= 1 && reps > 0, "predict_multi_bench: arguments");
-  hipStream_t s = (hipStream_t)stream;
-  size_t tb = 0;
-  float* scratch = dmalloc<float>((size_t)launch::predict_multi_scratch_floats(n, nsv, k), &tb);
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  std::vector<float> ms;
-  for (int r = 0; r < reps; ++r) {
-    HIP_CHECK(hipEventRecord(e0, s));
+  Arena st(stream);
+  float* scratch = st.alloc<float>((size_t)launch::predict_multi_scratch_floats(n, nsv, k));
+  const auto us = time_launches(st.s, reps, [&] {
     if (multi) {
-      launch::rbf_predict_multi(x, xsq, n, ld, sv, svsq, coef, k, k, nsv, ld, ld, gamma, b, scratch, dec, k, s);
+      launch::rbf_predict_multi(x, xsq, n, ld, sv, svsq, coef, k, k, nsv, ld, ld, gamma, b, scratch, dec, k, st.s);
     } else {
       for (int c = 0; c < k; ++c)
         launch::rbf_predict(x, xsq, n, ld, sv, svsq, coef_cols + (size_t)c * ldcc, nsv, ld, ld, gamma, 0.f, scratch,
-                            dec, nullptr, nullptr, s);
+                            dec, nullptr, nullptr, st.s);
     }
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float t = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-    ms.push_back(t);
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(scratch);
-  return ms;
+  });
+  return to_f32(us, 1e-3);
 }
 
 void rbf_gram(const float* a, const float* asq, int64_t m, const float* b, const float* bsq, int64_t n, int ld,
@@ -146,98 +120,37 @@ void rbf_gram(const float* a, const float* asq, int64_t m, const float* b, const
   launch::rbf_gemm_store(a, asq, m, ld, b, bsq, n, ld, ld, gamma, out, out_ld, (hipStream_t)stream, symmetric);
 }
 
-namespace {
-// split rows (rbf_gemm_split.hip) of `rows` fp32 rows of x, in a fresh buffer
-struct SplitRows {
-  void* planes = nullptr;
-  int32_t* shift = nullptr;
-  SplitRows(const float* x, int64_t rows, int ld, hipStream_t s) {
-    const int64_t pr = launch::split_pad_rows(rows);
-    const size_t bytes = (size_t)pr * launch::split_row_u4(ld) * 16;
-    size_t tb = 0;
-    planes = dmalloc<uint8_t>(bytes, &tb);
-    shift = dmalloc<int32_t>((size_t)pr, &tb);
-    HIP_CHECK(hipMemsetAsync(planes, 0, bytes, s));
-    HIP_CHECK(hipMemsetAsync(shift, 0, (size_t)pr * 4, s));
-    launch::split_rows_f16(x, rows, ld, ld, planes, shift, s);
-  }
-  ~SplitRows() {
-    (void)hipFree(planes);
-    (void)hipFree(shift);
-  }
-};
-}  // namespace
-
 void rbf_gram_split(const float* a, const float* asq, int64_t m, const float* b, const float* bsq, int64_t n, int ld,
                     float gamma, float* out, int64_t out_ld, bool symmetric, void* stream, float cold_tau) {
-  hipStream_t s = (hipStream_t)stream;
-  SplitRows sa(a, m, ld, s);
+  Arena st(stream);
+  const SplitRows sa(st, a, m, ld, ld);
   if (symmetric) {
-    launch::rbf_gemm_store_split(sa.planes, sa.shift, asq, m, sa.planes, sa.shift, asq, n, ld, gamma, out, out_ld, s,
-                                 true, cold_tau);
-    HIP_CHECK(hipStreamSynchronize(s));
-    return;
+    launch::rbf_gemm_store_split(sa.planes, sa.shift, asq, m, sa.planes, sa.shift, asq, n, ld, gamma, out, out_ld,
+                                 st.s, true, cold_tau);
+  } else {
+    const SplitRows sb(st, b, n, ld, ld);
+    launch::rbf_gemm_store_split(sa.planes, sa.shift, asq, m, sb.planes, sb.shift, bsq, n, ld, gamma, out, out_ld,
+                                 st.s, false, cold_tau);
   }
-  SplitRows sb(b, n, ld, s);
-  launch::rbf_gemm_store_split(sa.planes, sa.shift, asq, m, sb.planes, sb.shift, bsq, n, ld, gamma, out, out_ld, s,
-                               false, cold_tau);
-  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipStreamSynchronize(st.s));
 }
 
 std::vector<float> dot_gram_split(const float* a, int64_t m, const float* b, int64_t n, int d, int lda, int ldb,
                                   const DotKernelSpec& spec, float gamma, float* out, int64_t out_ld, bool symmetric,
                                   void* stream, int reps) {
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<float> us;
-  if (m <= 0 || n <= 0) return us;
+  if (m <= 0 || n <= 0) return {};
   DPSVM_CHECK(d >= 1 && lda >= d && (symmetric || ldb >= d), "dot_gram_split: rows of d >= 1 floats at stride >= d");
-  const auto split = [&](const float* x, int64_t rows, int ldx, void** planes, int32_t** shift) {
-    const int64_t pr = launch::split_pad_rows(rows);
-    const size_t bytes = (size_t)pr * launch::split_row_u4(d) * 16;
-    size_t tb = 0;
-    *planes = dmalloc<uint8_t>(bytes, &tb);
-    *shift = dmalloc<int32_t>((size_t)pr, &tb);
-    HIP_CHECK(hipMemsetAsync(*planes, 0, bytes, s));
-    HIP_CHECK(hipMemsetAsync(*shift, 0, (size_t)pr * 4, s));
-    launch::split_rows_f16(x, rows, d, ldx, *planes, *shift, s);
+  Arena st(stream);
+  const SplitRows sa(st, a, m, d, lda);
+  const SplitRows sb = symmetric ? sa : SplitRows(st, b, n, d, ldb);
+  const auto gemm = [&] {
+    launch::dot_gram_split(sa.planes, sa.shift, m, sb.planes, sb.shift, n, d, spec, gamma, out, out_ld, symmetric,
+                           st.s);
   };
-  void *pa = nullptr, *pb = nullptr;
-  int32_t *sa = nullptr, *sb = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct Free {
-    void *&pa, *&pb;
-    int32_t *&sa, *&sb;
-    hipEvent_t &e0, &e1;
-    ~Free() {
-      (void)hipFree(pa);
-      (void)hipFree(pb);
-      (void)hipFree(sa);
-      (void)hipFree(sb);
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-    }
-  } free_all{pa, pb, sa, sb, e0, e1};
-  split(a, m, lda, &pa, &sa);
-  if (!symmetric) split(b, n, ldb, &pb, &sb);
-  const void* B = symmetric ? pa : pb;
-  const int32_t* Bsh = symmetric ? sa : sb;
-  if (reps > 0) {
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-  }
-  for (int r = 0; r <= reps; ++r) {  // reps timed launches, then the returned one
-    if (r < reps) HIP_CHECK(hipEventRecord(e0, s));
-    launch::dot_gram_split(pa, sa, m, B, Bsh, n, d, spec, gamma, out, out_ld, symmetric, s);
-    if (r < reps) {
-      HIP_CHECK(hipEventRecord(e1, s));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      us.push_back(ms * 1e3f);
-    }
-  }
-  HIP_CHECK(hipStreamSynchronize(s));
-  return us;
+  const auto us = time_launches(st.s, reps, gemm);  // reps timed launches, then the returned one
+  gemm();
+  HIP_CHECK(hipStreamSynchronize(st.s));
+  return to_f32(us);
 }
 
 std::pair<int64_t, int64_t> gram_adapt_last() {
@@ -249,49 +162,30 @@ std::pair<int64_t, int64_t> gram_adapt_last() {
 void rbf_rows_indexed(const float* x, const float* xsq, int64_t n, int ld, const int* rows, int m, float gamma,
                       float* out, int64_t out_ld, const int* out_rows, void* stream, bool split) {
   DPSVM_CHECK(ld % 16 == 0 && m >= 0 && m <= 4096, "rbf_rows_indexed: ld multiple of 16, m <= 4096");
-  hipStream_t s = (hipStream_t)stream;
-  size_t tb = 0;
-  int32_t* md = dmalloc<int32_t>(1, &tb);
-  HIP_CHECK(hipMemcpyAsync(md, &m, 4, hipMemcpyHostToDevice, s));
+  Arena st(stream);
+  const int32_t* md = st.up_one<int32_t>(m);
   if (split) {
-    SplitRows sx(x, n, ld, s);
+    const SplitRows sx(st, x, n, ld, ld);
     launch::rbf_rows_indexed_split(sx.planes, sx.shift, xsq, rows, md, m, sx.planes, sx.shift, xsq, n, ld, gamma, out,
-                                   out_rows, out_ld, s);
-    HIP_CHECK(hipStreamSynchronize(s));
+                                   out_rows, out_ld, st.s);
   } else {
-    launch::rbf_rows_indexed(x, xsq, rows, md, m, x, xsq, n, ld, gamma, out, out_rows, out_ld, s);
-    HIP_CHECK(hipStreamSynchronize(s));
+    launch::rbf_rows_indexed(x, xsq, rows, md, m, x, xsq, n, ld, gamma, out, out_rows, out_ld, st.s);
   }
-  (void)hipFree(md);
+  HIP_CHECK(hipStreamSynchronize(st.s));
 }
 
 std::vector<float> rbf_rows_indexed_split_bench(const float* x, const float* xsq, int64_t n, int ld, const int* rows,
                                                 int m, float gamma, float* out, int64_t out_ld, const int* out_rows,
                                                 int reps, void* stream) {
   DPSVM_CHECK(ld % 16 == 0 && m >= 0 && m <= 4096 && reps > 0, "rbf_rows_indexed_split_bench: arguments");
-  hipStream_t s = (hipStream_t)stream;
-  size_t tb = 0;
-  int32_t* md = dmalloc<int32_t>(1, &tb);
-  HIP_CHECK(hipMemcpyAsync(md, &m, 4, hipMemcpyHostToDevice, s));
-  SplitRows sx(x, n, ld, s);
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  std::vector<float> ms;
-  for (int r = 0; r < reps; ++r) {
-    HIP_CHECK(hipEventRecord(e0, s));
+  Arena st(stream);
+  const int32_t* md = st.up_one<int32_t>(m);
+  const SplitRows sx(st, x, n, ld, ld);
+  const auto us = time_launches(st.s, reps, [&] {
     launch::rbf_rows_indexed_split(sx.planes, sx.shift, xsq, rows, md, m, sx.planes, sx.shift, xsq, n, ld, gamma, out,
-                                   out_rows, out_ld, s);
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float t = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-    ms.push_back(t);
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(md);
-  return ms;
+                                   out_rows, out_ld, st.s);
+  });
+  return to_f32(us, 1e-3);
 }
 
 void xpass_rows(const float* x, const float* xsq, int64_t n, int ld, const int* keys, int nq, float gamma,
@@ -339,43 +233,14 @@ void fused_select(const float* f, const float* alpha, const float* y, int64_t n,
 }
 
 int64_t compact_nonzero(const float* alpha, int64_t n, int* idx_out, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  size_t tb = 0;
-  int32_t* cnt = dmalloc<int32_t>(1, &tb);
-  int32_t* scratch = dmalloc<int32_t>((size_t)launch::compact_scratch_ints(n), &tb);
-  launch::compact_positive(alpha, n, idx_out, cnt, scratch, s);
-  int32_t h = 0;
-  HIP_CHECK(hipMemcpyAsync(&h, cnt, 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  (void)hipFree(cnt);
-  (void)hipFree(scratch);
-  return h;
+  Arena st(stream);
+  int32_t* cnt = st.alloc<int32_t>(1);
+  int32_t* scratch = st.alloc<int32_t>((size_t)launch::compact_scratch_ints(n));
+  launch::compact_positive(alpha, n, idx_out, cnt, scratch, st.s);
+  return st.down(cnt, 1)[0];
 }
 
 // ---- probability estimates (platt.hip): host vectors in and out on the null stream ----
-namespace {
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t count;
-  explicit DevBuf(size_t c) : count(std::max<size_t>(c, 1)) {
-    size_t tb = 0;
-    p = dmalloc<T>(count, &tb);
-    HIP_CHECK(hipMemset(p, 0, count * sizeof(T)));
-  }
-  explicit DevBuf(const std::vector<T>& h) : DevBuf(h.size()) {
-    if (!h.empty()) HIP_CHECK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  }
-  DevBuf(const DevBuf&) = delete;
-  ~DevBuf() { (void)hipFree(p); }
-  std::vector<T> down(size_t c) const {
-    std::vector<T> h(c);
-    if (c) HIP_CHECK(hipMemcpy(h.data(), p, c * sizeof(T), hipMemcpyDeviceToHost));
-    return h;
-  }
-};
-}  // namespace
-
 std::vector<float> holdout_decision(const std::vector<float>& f, const std::vector<float>& y,
                                     const std::vector<int32_t>& rows, double b, std::vector<float> dec, int slot) {
   const int64_t n = (int64_t)f.size();
@@ -383,56 +248,41 @@ std::vector<float> holdout_decision(const std::vector<float>& f, const std::vect
   DPSVM_CHECK(slot >= 0 && (int64_t)dec.size() % n == 0 && (int64_t)slot < (int64_t)dec.size() / n,
               "holdout_decision: dec [slots][n] with slot < slots");
   for (int32_t r : rows) DPSVM_CHECK(r >= 0 && r < n, "holdout_decision: a row outside [0, n)");
-  DevBuf<float> df(f), dy(y), dd(dec);
-  DevBuf<int32_t> dr(rows);
-  launch::holdout_decision(df.p, dy.p, dr.p, (int64_t)rows.size(), b, dd.p + (size_t)slot * n, nullptr);
-  HIP_CHECK(hipStreamSynchronize(nullptr));
-  return dd.down(dec.size());
+  Arena st(nullptr);
+  float* dd = st.up(dec, dec.size());
+  launch::holdout_decision(st.up(f, f.size()), st.up(y, y.size()), st.up(rows, rows.size()), (int64_t)rows.size(), b,
+                           dd + (size_t)slot * n, st.s);
+  return st.down(dd, dec.size());
 }
 
 std::vector<PlattFit> platt_fit(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n) {
   DPSVM_CHECK(m >= 1 && n >= 1 && (int64_t)dec.size() == m * n && (int64_t)y.size() == m * n,
               "platt_fit: dec and y [m][n], m, n >= 1");
-  DevBuf<float> dd(dec), dy(y);
-  DevBuf<PlattFit> out((size_t)m);
-  launch::platt_fit(dd.p, n, dy.p, n, n, m, out.p, nullptr);
-  HIP_CHECK(hipStreamSynchronize(nullptr));
-  return out.down((size_t)m);
+  Arena st(nullptr);
+  PlattFit* out = st.alloc<PlattFit>((size_t)m);
+  launch::platt_fit(st.up(dec, dec.size()), n, st.up(y, y.size()), n, n, m, out, st.s);
+  return st.down(out, (size_t)m);
 }
 
 std::vector<float> platt_fit_bench(const std::vector<float>& dec, const std::vector<float>& y, int m, int64_t n,
                                    int reps) {
   DPSVM_CHECK(m >= 1 && n >= 1 && reps > 0 && (int64_t)dec.size() == m * n && (int64_t)y.size() == m * n,
               "platt_fit_bench: dec and y [m][n], m, n >= 1, reps > 0");
-  DevBuf<float> dd(dec), dy(y);
-  DevBuf<PlattFit> out((size_t)m);
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  std::vector<float> ms;
-  for (int r = 0; r < reps; ++r) {
-    HIP_CHECK(hipEventRecord(e0, nullptr));
-    launch::platt_fit(dd.p, n, dy.p, n, n, m, out.p, nullptr);
-    HIP_CHECK(hipEventRecord(e1, nullptr));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float t = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-    ms.push_back(t);
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return ms;
+  Arena st(nullptr);
+  const float* dd = st.up(dec, dec.size());
+  const float* dy = st.up(y, y.size());
+  PlattFit* out = st.alloc<PlattFit>((size_t)m);
+  return to_f32(time_launches(st.s, reps, [&] { launch::platt_fit(dd, n, dy, n, n, m, out, st.s); }), 1e-3);
 }
 
 std::vector<float> proba_rows(const std::vector<float>& dec, int64_t n, int k, const std::vector<double>& A,
                               const std::vector<double>& B) {
   DPSVM_CHECK(n >= 1 && k >= 1 && (int64_t)dec.size() == n * k && (int)A.size() == k && (int)B.size() == k,
               "proba_rows: dec [n][k], A and B of k values");
-  DevBuf<float> dd(dec);
-  DevBuf<double> dA(A), dB(B);
-  launch::proba_rows(dd.p, n, k, dA.p, dB.p, nullptr);
-  HIP_CHECK(hipStreamSynchronize(nullptr));
-  return dd.down(dec.size());
+  Arena st(nullptr);
+  float* dd = st.up(dec, dec.size());
+  launch::proba_rows(dd, n, k, st.up(A, A.size()), st.up(B, B.size()), st.s);
+  return st.down(dd, dec.size());
 }
 
 }  // namespace kernels

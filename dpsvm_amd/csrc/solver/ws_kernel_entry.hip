@@ -29,55 +29,17 @@
 #include <cstring>
 #include <limits>
 
-#include "gpu_impl.hpp"
+#include "probe_util.hpp"
 
 namespace dpsvm {
 namespace kernels {
 
-namespace {
-
-template <class T>
-T* upload(const std::vector<T>& h, size_t count, hipStream_t s, size_t* tb) {
-  T* d = gpu::dmalloc<T>(std::max<size_t>(count, 1), tb);
-  HIP_CHECK(hipMemsetAsync(d, 0, std::max<size_t>(count, 1) * sizeof(T), s));
-  if (!h.empty()) HIP_CHECK(hipMemcpyAsync(d, h.data(), std::min(h.size(), count) * sizeof(T), hipMemcpyHostToDevice, s));
-  return d;
-}
-
-template <class T>
-std::vector<T> download(const T* d, size_t count, hipStream_t s) {
-  std::vector<T> h(count);
-  if (count) HIP_CHECK(hipMemcpyAsync(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  return h;
-}
-
-struct Stream {
-  hipStream_t s = nullptr;
-  std::vector<void*> bufs;
-  Stream() { HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-  ~Stream() {
-    (void)hipStreamSynchronize(s);
-    for (void* p : bufs) (void)hipFree(p);
-    (void)hipStreamDestroy(s);
-  }
-  template <class T>
-  T* up(const std::vector<T>& h, size_t count) {
-    size_t tb = 0;
-    T* d = upload(h, count, s, &tb);
-    bufs.push_back(d);
-    return d;
-  }
-};
-
-std::unique_ptr<WsCtrl> blank_ctrl() {
-  auto c = std::make_unique<WsCtrl>();
-  memset(c.get(), 0, sizeof(WsCtrl));
-  c->done = kRunning;
-  return c;
-}
-
-}  // namespace
+using probe::Arena;
+using probe::blank_ctrl;
+using probe::EventTimer;
+using probe::single_rank_args;
+using probe::time_launches;
+using probe::to_f32;
 
 GramWsumProbe gram_rows_wsum_probe(const std::vector<float>& gram, int64_t L, int64_t ldg, int64_t n,
                                    const std::vector<int32_t>& lines, const std::vector<float>& coef,
@@ -90,35 +52,20 @@ GramWsumProbe gram_rows_wsum_probe(const std::vector<float>& gram, int64_t L, in
   DPSVM_CHECK(!lines.empty() || m <= L, "gram_rows_wsum_probe: identity lines need m <= L");
   for (int32_t l : lines) DPSVM_CHECK(l >= 0 && l < L, "gram_rows_wsum_probe: line out of range");
   DPSVM_CHECK(reps >= 0, "gram_rows_wsum_probe: reps >= 0");
-  Stream st;
+  Arena st;
   const float* dg = st.up(gram, gram.size());
   const int32_t* dl = lines.empty() ? nullptr : st.up(lines, lines.size());
   const float* dc = st.up(coef, coef.size());
   const float* db = base.empty() ? nullptr : st.up(base, base.size());
   const size_t n_out = (size_t)((n + 3) / 4 * 4) + kGramWsumProbePad;
-  const std::vector<float> fill(n_out, kGramWsumProbeFill);
-  float* dout = st.up(fill, n_out);
-  double* part = st.up(std::vector<double>(), (size_t)launch::gram_wsum_scratch_doubles(n));
+  float* dout = st.up(std::vector<float>(n_out, kGramWsumProbeFill), n_out);
+  double* part = st.alloc<double>((size_t)launch::gram_wsum_scratch_doubles(n));
+  const auto wsum = [&] { launch::gram_rows_wsum(dg, L, ldg, n, dl, dc, m, db, dout, part, st.s); };
   GramWsumProbe r;
   r.slices = launch::gram_wsum_slices(n, m);
-  if (reps > 0) {
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    for (int i = 0; i < reps; ++i) {
-      HIP_CHECK(hipEventRecord(e0, st.s));
-      launch::gram_rows_wsum(dg, L, ldg, n, dl, dc, m, db, dout, part, st.s);
-      HIP_CHECK(hipEventRecord(e1, st.s));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      r.us.push_back(1e3f * ms);
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
-  launch::gram_rows_wsum(dg, L, ldg, n, dl, dc, m, db, dout, part, st.s);
-  r.out = download(dout, n_out, st.s);
+  r.us = to_f32(time_launches(st.s, reps, wsum));
+  wsum();
+  r.out = st.down(dout, n_out);
   return r;
 }
 
@@ -129,32 +76,17 @@ GramDotProbe gram_rows_dot_probe(const std::vector<float>& Kt, int64_t nt, int64
   DPSVM_CHECK((int64_t)Kt.size() == nt * ld && (int64_t)coef.size() == (int64_t)k * ldc && (int64_t)b.size() == k,
               "gram_rows_dot_probe: Kt [nt][ld], coef [k][ldc], b [k]");
   DPSVM_CHECK(reps >= 0, "gram_rows_dot_probe: reps >= 0");
-  Stream st;
+  Arena st;
   const float* dk = st.up(Kt, Kt.size());
   const float* dc = st.up(coef, coef.size());
   const float* db = st.up(b, b.size());
   const size_t n_out = (size_t)nt * k + 2 * kGramDotProbePad;
   float* dout = st.up(std::vector<float>(n_out, kGramDotProbeFill), n_out);
-  HIP_CHECK(hipStreamSynchronize(st.s));  // the fill vector leaves scope
+  const auto dot = [&] { launch::gram_rows_dot(dk, nt, ld, n, dc, ldc, k, db, dout + kGramDotProbePad, k, st.s); };
   GramDotProbe r;
-  if (reps > 0) {
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    for (int i = 0; i < reps; ++i) {
-      HIP_CHECK(hipEventRecord(e0, st.s));
-      launch::gram_rows_dot(dk, nt, ld, n, dc, ldc, k, db, dout + kGramDotProbePad, k, st.s);
-      HIP_CHECK(hipEventRecord(e1, st.s));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      r.us.push_back(1e3f * ms);
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
-  launch::gram_rows_dot(dk, nt, ld, n, dc, ldc, k, db, dout + kGramDotProbePad, k, st.s);
-  r.out = download(dout, n_out, st.s);
+  r.us = to_f32(time_launches(st.s, reps, dot));
+  dot();
+  r.out = st.down(dout, n_out);
   return r;
 }
 
@@ -166,7 +98,7 @@ WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int 
   DPSVM_CHECK(blocks >= 2 && blocks <= kWsMaxBlocks && q_max >= 2 && q_max <= kWsMax && q_max % 2 == 0,
               "ws_merge_multi_probe: 2 <= blocks <= 128, blocks x q_max <= 6144, even q_max <= 192");
   DPSVM_CHECK((int64_t)prev_union.size() <= (int64_t)blocks * q_max, "ws_merge_multi_probe: previous union too long");
-  Stream st;
+  Arena st;
   auto c = blank_ctrl();
   c->outer = 1;  // this round builds parity 1; the previous union sits in parity 0
   c->iter = iter;
@@ -174,22 +106,19 @@ WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int 
   for (size_t i = 0; i < prev_union.size(); ++i) c->uidx[0][i] = prev_union[i];
   c->p_act = p_act;
   for (int i = 0; i < kWsMaxAll; ++i) c->idx[1][i] = -1;
-  std::vector<WsCtrl> hc(1);
-  memcpy(&hc[0], c.get(), sizeof(WsCtrl));
-  WsCtrl* dc = st.up(hc, 1);
-  WsArgs a{};
+  WsCtrl* dc = st.up_one(*c);
+  WsArgs a = single_rank_args();
   a.cand = a.cand_out = st.up(cand, cand.size());
   a.G = a.G_all = G;
-  a.world = 1;
   a.blocks = blocks;
   a.q_max = q_max;
   a.n_new = n_new;
   a.eps = eps;
   a.max_iter = max_iter;
   a.ctrl = dc;
-  a.sorted = st.up(std::vector<uint64_t>(), (size_t)2 * kWsMaxGroups * kWsCand);
+  a.sorted = st.alloc<uint64_t>((size_t)2 * kWsMaxGroups * kWsCand);
   launch::ws_merge_multi(a, st.s);
-  const WsCtrl o = download(dc, 1, st.s)[0];
+  const WsCtrl o = st.down(dc, 1)[0];
   WsMergeProbe r;
   r.done = o.done;
   r.b_hi = o.b_hi;
@@ -219,7 +148,7 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
   for (int p = 0; p < blocks; ++p) DPSVM_CHECK(qb[p] >= 0 && qb[p] <= q_max, "ws_solve_probe: qb[p] <= q_max");
   DPSVM_CHECK(blocks > 1 || p_round == 1, "ws_solve_probe: one block means p_round 1");
   DPSVM_CHECK(row_C.empty() || row_C.size() == nq, "ws_solve_probe: row_C [P][q_max] or empty");
-  Stream st;
+  Arena st;
   const int stride = blocks * kWsMax;
   std::vector<float> sub(nq * q_max + 3 * (size_t)stride, 0.f);
   std::copy(K.begin(), K.end(), sub.begin());
@@ -242,16 +171,14 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
     c->qb[0][p] = qb[p];
     for (int a = 0; a < q_max; ++a) c->idx[0][p * q_max + a] = c->line[0][p * q_max + a] = p * q_max + a;
   }
-  std::vector<WsCtrl> hc(1);
-  memcpy(&hc[0], c.get(), sizeof(WsCtrl));
-  WsCtrl* dc = st.up(hc, 1);
+  WsCtrl* dc = st.up_one(*c);
   float* dsub = st.up(sub, sub.size());
-  WsArgs a{};
+  WsArgs a = single_rank_args();
   a.subg = dsub;
   a.aux = dsub + nq * q_max;
   a.aux_stride = stride;
   a.alpha = st.up(alpha, nq);
-  a.dalpha = st.up(std::vector<float>(nq, 0.f), nq);
+  a.dalpha = st.alloc<float>(nq);
   a.blocks = blocks;
   a.q_max = q_max;
   a.inner_max = inner_max;
@@ -265,14 +192,11 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
   a.wss = wss;
   if (!row_C.empty()) a.c_row = st.up(row_C, nq);  // row a of block p is global row p q_max + a
   a.diag = diag ? 1 : 0;
-  a.clip_fallback = 1;
-  a.t_halve = 0.9f;
-  a.world = 1;
   a.ctrl = dc;
   launch::ws_solve(a, st.s);
-  const WsCtrl o = download(dc, 1, st.s)[0];
+  const WsCtrl o = st.down(dc, 1)[0];
   WsSolveProbe r;
-  r.alpha = download(a.alpha, nq, st.s);
+  r.alpha = st.down(a.alpha, nq);
   r.iter = o.iter;
   r.outer = o.outer;
   r.done = o.done;
@@ -325,7 +249,7 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   int32_t G = 0, rpt = 0;
   launch::ws_geometry(ncol, 1, &G, &rpt);
   DPSVM_CHECK(rpt <= kWsMaxRPT, "ws_select_probe: too many rows");
-  Stream st;
+  Arena st;
   auto c = blank_ctrl();
   c->outer = outer;
   c->done = done;
@@ -342,10 +266,8 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
       c->apply_idx[base + k] = apply_line[at];
     }
   }
-  std::vector<WsCtrl> hc(1);
-  memcpy(&hc[0], c.get(), sizeof(WsCtrl));
-  WsArgs a{};
-  a.ctrl = st.up(hc, 1);
+  WsArgs a = single_rank_args(n);
+  a.ctrl = st.up_one(*c);
   a.gram = st.up(gram, gram.size());
   a.ldg = ldg;
   a.f = st.up(f, (size_t)n);
@@ -354,40 +276,19 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
   a.dalpha = st.up(dalpha, (size_t)n);
   a.ks = std::max(1, ks);
   a.p1G = blocks > 1 ? ws_pass1_v4_groups(n) : G;
-  a.dfs = st.up(std::vector<float>(), (size_t)n * a.ks);
-  a.part = st.up(std::vector<double>(), (size_t)2 * a.p1G * a.ks);
-  a.cand = a.cand_out = st.up(std::vector<uint64_t>(), (size_t)G * 2 * kWsCand);
-  a.n = a.nl = n;
-  a.off = 0;
+  a.dfs = st.alloc<float>((size_t)n * a.ks);
+  a.part = st.alloc<double>((size_t)2 * a.p1G * a.ks);
+  a.cand = a.cand_out = st.alloc<uint64_t>((size_t)G * 2 * kWsCand);
   a.G = a.G_all = G;
   a.rpt = rpt;
-  a.world = 1;
-  a.rank = 0;
   a.q_max = q_max;
   a.C = C;
   if (!row_C.empty()) a.c_row = st.up(row_C, (size_t)n);
   a.blocks = blocks;
   a.fold = fold;
-  a.t_halve = 0.9f;
-  a.clip_fallback = 1;
   WsSelectProbe r;
-  if (blocks > 1 && reps > 0) {
-    // timing (bench/pass1_probe.py): pass 1 only reads the state, so it can repeat
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    for (int i = 0; i < reps; ++i) {
-      HIP_CHECK(hipEventRecord(e0, st.s));
-      launch::ws_select_pass(a, 1, st.s);
-      HIP_CHECK(hipEventRecord(e1, st.s));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      r.pass1_us.push_back(1e3 * ms);
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  // timing (bench/pass1_probe.py): pass 1 only reads the state, so it can repeat
+  if (blocks > 1) r.pass1_us = to_f32(time_launches(st.s, reps, [&] { launch::ws_select_pass(a, 1, st.s); }));
   if (blocks == 1 && reps > 0) {
     // timing (bench/svr_probe.py): the one-pass kernel (plain or fold) repeated, rep i on the lines
     // apply_line[k] + (i mod (L / na)) na — a Gram of many times the list's lines keeps the rows out of the
@@ -395,37 +296,26 @@ WsSelectProbe ws_select_probe(const std::vector<float>& gram, int64_t L, int64_t
     const int64_t groups = std::max<int64_t>(1, tot > 0 ? L / tot : 1);
     int32_t* dline = (int32_t*)((char*)a.ctrl + offsetof(WsCtrl, apply_line));
     std::vector<int32_t> hl((size_t)tot);
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
+    EventTimer timer(st.s);
     for (int i = 0; i <= reps; ++i) {  // the last pass restores the caller's lines
       const int64_t shift = i < reps ? (i % groups) * tot : 0;
       for (int64_t k = 0; k < tot; ++k) hl[k] = (int32_t)((apply_line[k] + shift) % L);
       if (tot > 0) HIP_CHECK(hipMemcpyAsync(dline, hl.data(), tot * 4, hipMemcpyHostToDevice, st.s));
       HIP_CHECK(hipStreamSynchronize(st.s));
-      if (i == reps) break;
-      HIP_CHECK(hipEventRecord(e0, st.s));
-      launch::ws_select(a, st.s);
-      HIP_CHECK(hipEventRecord(e1, st.s));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      r.select_us.push_back(1e3 * ms);
+      if (i < reps) r.select_us.push_back((float)timer.us([&] { launch::ws_select(a, st.s); }));
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
   }
   launch::ws_select(a, st.s);  // blocks > 1: pass 1 then pass 2
-  const WsCtrl o = download(a.ctrl, 1, st.s)[0];
+  const WsCtrl o = st.down(a.ctrl, 1)[0];
   r.G = G;
   r.rpt = rpt;
-  r.f = download(a.f, (size_t)n, st.s);
-  r.alpha = download(a.alpha, (size_t)n, st.s);
-  r.dalpha = download(a.dalpha, (size_t)n, st.s);
-  r.dfs = download(a.dfs, (size_t)n, st.s);  // slice 0 (all of it at ks = 1)
-  r.part = download(a.part, (size_t)2 * a.p1G * a.ks, st.s);
+  r.f = st.down(a.f, (size_t)n);
+  r.alpha = st.down(a.alpha, (size_t)n);
+  r.dalpha = st.down(a.dalpha, (size_t)n);
+  r.dfs = st.down(a.dfs, (size_t)n);  // slice 0 (all of it at ks = 1)
+  r.part = st.down(a.part, (size_t)2 * a.p1G * a.ks);
   r.p1G = a.p1G;
-  r.cand = download(a.cand_out, (size_t)G * 2 * kWsCand, st.s);
+  r.cand = st.down(a.cand_out, (size_t)G * 2 * kWsCand);
   r.t = o.t_last;
   r.p_act = o.p_act;
   r.n_damped = o.n_damped;
@@ -443,18 +333,17 @@ struct SplitX {
   float* xsq = nullptr;
   void* xs = nullptr;
   int32_t* xsh = nullptr;
-  SplitX(Stream& st, const std::vector<float>& x, int64_t n, int d) {
+  SplitX(Arena& st, const std::vector<float>& x, int64_t n, int d) {
     dp = pad_features(d);
     const int64_t pr = launch::split_pad_rows(n);
     std::vector<float> xp((size_t)n * dp, 0.f);
     for (int64_t i = 0; i < n; ++i) std::copy(x.begin() + i * d, x.begin() + (i + 1) * d, xp.begin() + i * dp);
     const float* xd = st.up(xp, (size_t)pr * dp);
-    HIP_CHECK(hipStreamSynchronize(st.s));  // xp leaves scope
-    xsq = st.up(std::vector<float>(), (size_t)pr);
-    xs = st.up(std::vector<uint8_t>(), (size_t)pr * launch::split_row_u4(dp) * 16);
-    xsh = st.up(std::vector<int32_t>(), (size_t)pr);
+    xsq = st.alloc<float>((size_t)pr);
     launch::row_sqnorm(xd, n, dp, dp, xsq, st.s);
-    launch::split_rows_f16(xd, n, dp, dp, xs, xsh, st.s);
+    const probe::SplitRows sr(st, xd, n, dp, dp);
+    xs = sr.planes;
+    xsh = sr.shift;
   }
 };
 
@@ -489,7 +378,7 @@ void check_merge_state(int64_t n, const std::vector<uint64_t>& cand, const std::
 struct MergeRound {
   WsCtrl* dc = nullptr;
   WsArgs a{};
-  MergeRound(Stream& st, int64_t n, const std::vector<uint64_t>& cand, const std::vector<int32_t>& prev_set,
+  MergeRound(Arena& st, int64_t n, const std::vector<uint64_t>& cand, const std::vector<int32_t>& prev_set,
              const std::vector<float>& f, const std::vector<float>& alpha, const std::vector<float>& y, int q_max,
              int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer) {
     auto c = blank_ctrl();
@@ -501,12 +390,10 @@ struct MergeRound {
     c->q[par ^ 1] = (int32_t)prev_set.size();
     for (size_t i = 0; i < prev_set.size(); ++i) c->idx[par ^ 1][i] = prev_set[i];
     for (int i = 0; i < kWsMaxAll; ++i) c->idx[par][i] = -1;
-    std::vector<WsCtrl> hc(1);
-    memcpy(&hc[0], c.get(), sizeof(WsCtrl));
-    dc = st.up(hc, 1);
-    HIP_CHECK(hipStreamSynchronize(st.s));  // hc leaves scope
+    dc = st.up_one(*c);
     const float nan = std::numeric_limits<float>::quiet_NaN();
     float* sub = st.up(std::vector<float>((size_t)q_max * q_max + 3 * kWsMax, nan), (size_t)q_max * q_max + 3 * kWsMax);
+    a = single_rank_args(n);
     a.ctrl = dc;
     a.cand = a.cand_out = st.up(cand, cand.size());
     a.G = a.G_all = (int32_t)(cand.size() / (2 * kWsCand));
@@ -514,9 +401,6 @@ struct MergeRound {
     a.f = st.up(f, (size_t)n);
     a.alpha = st.up(alpha, (size_t)n);
     a.y = st.up(y, (size_t)n);
-    a.n = a.nl = n;
-    a.off = 0;
-    a.world = 1;
     a.blocks = 1;
     a.q_max = q_max;
     a.n_new = n_new;
@@ -526,8 +410,8 @@ struct MergeRound {
     a.aux = sub + (size_t)q_max * q_max;
     a.aux_stride = kWsMax;
   }
-  WsGatherProbe result(Stream& st, int64_t outer) const {
-    const WsCtrl o = download(dc, 1, st.s)[0];
+  WsGatherProbe result(Arena& st, int64_t outer) const {
+    const WsCtrl o = st.down(dc, 1)[0];
     const int par = (int)(outer & 1);
     WsGatherProbe r;
     r.done = o.done;
@@ -537,8 +421,8 @@ struct MergeRound {
     r.q = o.q[par];
     r.idx.assign(o.idx[par], o.idx[par] + std::max(0, std::min(r.q, (int)kWsMax)));
     r.line.assign(o.line[par], o.line[par] + std::max(0, std::min(r.q, (int)kWsMax)));
-    r.subg = download(a.subg, (size_t)a.q_max * a.q_max, st.s);
-    r.aux = download(a.aux, (size_t)3 * kWsMax, st.s);
+    r.subg = st.down(a.subg, (size_t)a.q_max * a.q_max);
+    r.aux = st.down(a.aux, (size_t)3 * kWsMax);
     return r;
   }
 };
@@ -554,7 +438,7 @@ WsGatherProbe ws_gather_probe(const std::vector<float>& gram, int64_t n, int64_t
   DPSVM_CHECK(fold == 0 || n == 2 * fold, "ws_gather_probe: fold needs n = 2 fold state rows");
   const int64_t ng = fold > 0 ? fold : n;
   DPSVM_CHECK(ldg >= ng && (int64_t)gram.size() == ng * ldg && outer >= 0, "ws_gather_probe: gram [n][ldg >= n]");
-  Stream st;
+  Arena st;
   MergeRound m(st, n, cand, prev_set, f, alpha, y, q_max, n_new, eps, iter, max_iter, nonfinite, outer);
   m.a.gram = st.up(gram, gram.size());
   m.a.ldg = ldg;
@@ -571,7 +455,7 @@ WsGatherProbe ws_subgram_split_probe(const std::vector<float>& x, int64_t n, int
   check_split_x(x, n, d);
   check_merge_state(n, cand, prev_set, f, alpha, y, q_max, n_new, nonfinite);
   DPSVM_CHECK(outer >= 0, "ws_subgram_split_probe: outer >= 0");
-  Stream st;
+  Arena st;
   SplitX sx(st, x, n, d);
   MergeRound m(st, n, cand, prev_set, f, alpha, y, q_max, n_new, eps, iter, max_iter, nonfinite, outer);
   DPSVM_CHECK(launch::ws_recompute_supported(m.a, sx.dp), "ws_subgram_split_probe: shape not supported");
@@ -593,7 +477,7 @@ WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, in
   int32_t G = 0, rpt = 0;
   launch::ws_geometry(n, 1, &G, &rpt);
   DPSVM_CHECK(rpt <= kWsMaxRPT, "ws_fupdate_split_probe: too many rows");
-  Stream st;
+  Arena st;
   SplitX sx(st, x, n, d);
   auto c = blank_ctrl();
   c->outer = 1;
@@ -606,29 +490,24 @@ WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, in
     c->apply_idx[k] = c->apply_line[k] = apply_idx[k];
     c->apply_coef[k] = apply_coef[k];
   }
-  std::vector<WsCtrl> hc(1);
-  memcpy(&hc[0], c.get(), sizeof(WsCtrl));
-  WsArgs a{};
-  a.ctrl = st.up(hc, 1);
+  WsArgs a = single_rank_args(n);
+  a.ctrl = st.up_one(*c);
   a.f = st.up(f, (size_t)n);
   a.alpha = st.up(alpha, (size_t)n);
   a.y = st.up(y, (size_t)n);
   const size_t nc = (size_t)G * 2 * kWsCand;
   a.cand = a.cand_out = st.up(std::vector<uint64_t>(nc, kWsProbeKey), nc);
-  a.n = a.nl = n;
-  a.off = 0;
   a.G = a.G_all = G;
   a.rpt = rpt;
-  a.world = 1;
   a.blocks = 1;
   a.q_max = kWsMax;
   a.C = C;
   DPSVM_CHECK(launch::ws_recompute_supported(a, sx.dp), "ws_fupdate_split_probe: shape not supported");
   launch::ws_fupdate_split(a, sx.xs, sx.xsh, sx.xsq, sx.dp, gamma, st.s);
-  const WsCtrl o = download(a.ctrl, 1, st.s)[0];
+  const WsCtrl o = st.down(a.ctrl, 1)[0];
   WsFupdateProbe r;
-  r.f = download(a.f, (size_t)n, st.s);
-  r.cand = download(a.cand_out, nc, st.s);
+  r.f = st.down(a.f, (size_t)n);
+  r.cand = st.down(a.cand_out, nc);
   r.nonfinite = o.nonfinite;
   r.rows_computed = o.rows_computed;
   r.G = G;

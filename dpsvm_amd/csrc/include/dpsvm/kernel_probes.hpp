@@ -47,6 +47,14 @@ void rbf_gram(const float* a, const float* asq, int64_t m, const float* b, const
 // (split: on fp16 MFMA over split operands, rbf_rows_split.hip; x is split here)
 void rbf_rows_indexed(const float* x, const float* xsq, int64_t n, int ld, const int* rows, int m, float gamma,
                       float* out, int64_t out_ld, const int* out_rows, void* stream, bool split = false);
+// the same row GEMM in the calling shape of a ws-cache round (gpu_engines.hip miss_rows): the launch is sized by
+// m_max >= m while the device count is m = rows.size() (0: nothing is written), and the column operand is the
+// shard x[off, off + nl) with xsq + off, so out[out_lines[i]][j] = K(x[rows[i]], x[off + j]), j < nl.  x: x_rows
+// >= max(n, off + round_up(nl, 256)) device rows of ld floats (the f32 kernel reads whole 256-column tiles), xsq
+// their norms; rows / out_lines: host, checked (rows < n, distinct lines < n_lines) before anything is launched.
+void rbf_rows_miss(const float* x, const float* xsq, int64_t x_rows, int64_t n, int ld, int64_t off, int64_t nl,
+                   const std::vector<int32_t>& rows, int64_t m_max, float gamma, float* out, int64_t n_lines,
+                   int64_t out_ld, const std::vector<int32_t>& out_lines, void* stream, bool split);
 // diagnostics: the split row GEMM alone (operands split once), reps launches
 // event-timed; returns ms per launch (bench/rows_probe.py)
 std::vector<float> rbf_rows_indexed_split_bench(const float* x, const float* xsq, int64_t n, int ld, const int* rows,
@@ -200,6 +208,62 @@ WsGatherProbe ws_subgram_split_probe(const std::vector<float>& x, int64_t n, int
                                      const std::vector<float>& alpha, const std::vector<float>& y, float gamma,
                                      int q_max, int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite,
                                      int64_t outer);
+// The cache-mode rounds (ws-cache): the merges with the line plan of the kernel-row cache, the gathers that read
+// WsCtrl::line, the misses' X-row pack.  The cache is the pair of maps slot_of [n] (a row's line or -1) and key_of
+// [L] (a line's row or -1), which must be mutual inverses with every entry in range, and the CLOCK hand in [0, L):
+// a probe refuses anything else before it launches.  Before the launch n_miss holds kWsProbeMiss, miss_row /
+// miss_line -1, the counters kWsProbeRowsComputed / kWsProbeRowHits.
+constexpr int32_t kWsProbeMiss = -3;
+constexpr int64_t kWsProbeRowsComputed = 1000003, kWsProbeRowHits = 2000003;
+struct WsCacheState {
+  int32_t n_miss = 0, hand = 0;
+  int64_t rows_computed = 0, row_hits = 0;
+  std::vector<int32_t> miss_row, miss_line;  // [kWsMaxAll] each, whole
+  std::vector<int32_t> slot_of, key_of;      // [n], [L] after the launch
+};
+// ws_merge_cache_probe: launch::ws_merge once (ws_merge_kernel: the one-block merge, then the line plan) on the
+// state of ws_gather_probe plus the run's state `done` and the cache.  lines != nullptr: a device array [L][ldl >=
+// n] of kernel rows; launch::ws_gather then runs once on it (cache, one block: ws_gather_lines_kernel) into the
+// NaN-filled subg / aux.
+struct WsMergeCacheProbe {
+  WsGatherProbe round;
+  WsCacheState cache;
+};
+WsMergeCacheProbe ws_merge_cache_probe(const std::vector<uint64_t>& cand, const std::vector<int32_t>& prev_set,
+                                       const std::vector<float>& f, const std::vector<float>& alpha,
+                                       const std::vector<float>& y, int q_max, int n_new, float eps, int64_t iter,
+                                       int64_t max_iter, int nonfinite, int64_t outer, int done, int64_t L, int hand,
+                                       const std::vector<int32_t>& slot_of, const std::vector<int32_t>& key_of,
+                                       const float* lines, int64_t ldl);
+// ws_merge_multi_cache_probe: launch::ws_merge_multi with WsArgs::cache = 1 on the arguments of
+// ws_merge_multi_probe plus the cache over n = slot_of.size() rows (every candidate and previous-union row must
+// be below n; the previous union holds no row twice).  Refuses what the launch refuses (L below
+// ws_cache_multi_min_lines, more than 4,096 union rows).  lines != nullptr ([L][ldl >= n], with f / alpha / y of
+// n rows): launch::ws_gather then runs once (ws_gather_multi_kernel) into NaN-filled subg [blocks][q_max][q_max]
+// and aux [3][blocks][kWsMax].
+struct WsMergeMultiCacheProbe {
+  WsMergeProbe merge;
+  std::vector<int32_t> line;  // [blocks][q_max] the members' lines at idx's positions (-1: unused)
+  WsCacheState cache;
+  std::vector<float> subg, aux;  // empty without lines
+};
+WsMergeMultiCacheProbe ws_merge_multi_cache_probe(const std::vector<uint64_t>& cand, int G, int blocks, int p_act,
+                                                  int q_max, int n_new, float eps,
+                                                  const std::vector<int32_t>& prev_union, int64_t iter,
+                                                  int64_t max_iter, int64_t L, int hand,
+                                                  const std::vector<int32_t>& slot_of,
+                                                  const std::vector<int32_t>& key_of, const std::vector<float>& f,
+                                                  const std::vector<float>& alpha, const std::vector<float>& y,
+                                                  const float* lines, int64_t ldl);
+// ws_pack_rows: one launch on the shard x [nl][dp] of rows [off, off + nl) of an n-row problem (xsq [n] global)
+// with miss_row placed in a control record (its first n_miss entries are the round's misses, each < n; what
+// follows them is what an earlier round left).  out [q_max][dp] and out_sq [q_max] are filled with NaN before.
+struct WsPackRowsProbe {
+  std::vector<float> out, out_sq;
+};
+WsPackRowsProbe ws_pack_rows_probe(const std::vector<float>& x, int64_t nl, int dp, int64_t off,
+                                   const std::vector<float>& xsq, const std::vector<int32_t>& miss_row, int n_miss,
+                                   int q_max);
 // ws_fupdate_split: the recompute rounds' selection pass, one launch on x [n][d]
 // (operands as above) with the apply list of a round (rows, coefficients) and
 // the run's state `done`; cand is prefilled with kWsProbeKey (neither a key of

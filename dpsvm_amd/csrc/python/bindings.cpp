@@ -1151,6 +1151,75 @@ PYBIND11_MODULE(_C, m) {
     return d_;
   }, py::arg("x"), py::arg("n"), py::arg("d"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("apply_idx"),
         py::arg("apply_coef"), py::arg("gamma"), py::arg("C"), py::arg("done"));
+  // the cache-mode rounds (lines: the device address of a float array [L][ldl], 0: no gather)
+  auto cache_dict = [](py::dict d, const kernels::WsCacheState& c) {
+    d["n_miss"] = c.n_miss;
+    d["hand"] = c.hand;
+    d["rows_computed"] = c.rows_computed;
+    d["row_hits"] = c.row_hits;
+    d["miss_row"] = c.miss_row;
+    d["miss_line"] = c.miss_line;
+    d["slot_of"] = c.slot_of;
+    d["key_of"] = c.key_of;
+    return d;
+  };
+  m.def("k_ws_merge_cache", [gather_dict, cache_dict](const U64& cand, const I32& prev, const F32& f, const F32& alpha,
+                                                      const F32& y, int q_max, int n_new, float eps, int64_t iter,
+                                                      int64_t max_iter, int nonfinite, int64_t outer, int done,
+                                                      int64_t L, int hand, const I32& slot_of, const I32& key_of,
+                                                      uintptr_t lines, int64_t ldl) {
+    const auto r = kernels::ws_merge_cache_probe(from_np(cand), from_np(prev), from_np(f), from_np(alpha), from_np(y),
+                                                 q_max, n_new, eps, iter, max_iter, nonfinite, outer, done, L, hand,
+                                                 from_np(slot_of), from_np(key_of), (const float*)lines, ldl);
+    return cache_dict(gather_dict(r.round), r.cache);
+  }, py::arg("cand"), py::arg("prev"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("q_max"),
+        py::arg("n_new"), py::arg("eps"), py::arg("iter"), py::arg("max_iter"), py::arg("nonfinite"), py::arg("outer"),
+        py::arg("done"), py::arg("L"), py::arg("hand"), py::arg("slot_of"), py::arg("key_of"), py::arg("lines") = 0,
+        py::arg("ldl") = 0);
+  m.def("k_ws_merge_multi_cache", [cache_dict](const U64& cand, int G, int blocks, int p_act, int q_max, int n_new,
+                                               float eps, const I32& prev, int64_t iter, int64_t max_iter, int64_t L,
+                                               int hand, const I32& slot_of, const I32& key_of, py::object f,
+                                               py::object alpha, py::object y, uintptr_t lines, int64_t ldl) {
+    const auto r = kernels::ws_merge_multi_cache_probe(
+        from_np(cand), G, blocks, p_act, q_max, n_new, eps, from_np(prev), iter, max_iter, L, hand, from_np(slot_of),
+        from_np(key_of), from_np_or_none<float>(f), from_np_or_none<float>(alpha), from_np_or_none<float>(y),
+        (const float*)lines, ldl);
+    py::dict d;
+    d["uidx"] = r.merge.uidx;
+    d["idx"] = r.merge.idx;
+    d["qb"] = r.merge.qb;
+    d["b_hi"] = r.merge.b_hi;
+    d["b_lo"] = r.merge.b_lo;
+    d["done"] = r.merge.done;
+    d["p_round"] = r.merge.p_round;
+    d["line"] = r.line;
+    d["subg"] = to_np(r.subg);
+    d["aux"] = to_np(r.aux);
+    return cache_dict(d, r.cache);
+  }, py::arg("cand"), py::arg("G"), py::arg("blocks"), py::arg("p_act"), py::arg("q_max"), py::arg("n_new"),
+        py::arg("eps"), py::arg("prev"), py::arg("iter"), py::arg("max_iter"), py::arg("L"), py::arg("hand"),
+        py::arg("slot_of"), py::arg("key_of"), py::arg("f") = py::none(), py::arg("alpha") = py::none(),
+        py::arg("y") = py::none(), py::arg("lines") = 0, py::arg("ldl") = 0);
+  m.def("k_ws_pack_rows", [](const F32& x, int64_t nl, int dp, int64_t off, const F32& xsq, const I32& miss_row,
+                             int n_miss, int q_max) {
+    const auto r = kernels::ws_pack_rows_probe(from_np(x), nl, dp, off, from_np(xsq), from_np(miss_row), n_miss, q_max);
+    py::dict d;
+    d["out"] = to_np(r.out);
+    d["out_sq"] = to_np(r.out_sq);
+    return d;
+  }, py::arg("x"), py::arg("nl"), py::arg("dp"), py::arg("off"), py::arg("xsq"), py::arg("miss_row"),
+        py::arg("n_miss"), py::arg("q_max"));
+  m.def("k_rbf_rows_miss", [](uintptr_t x, uintptr_t xsq, int64_t x_rows, int64_t n, int ld, int64_t off, int64_t nl,
+                              const I32& rows, int64_t m_max, float gamma, uintptr_t out, int64_t n_lines,
+                              int64_t out_ld, const I32& out_lines, uintptr_t stream, bool split) {
+    kernels::rbf_rows_miss((const float*)x, (const float*)xsq, x_rows, n, ld, off, nl, from_np(rows), m_max, gamma,
+                           (float*)out, n_lines, out_ld, from_np(out_lines), (void*)stream, split);
+  }, py::arg("x"), py::arg("xsq"), py::arg("x_rows"), py::arg("n"), py::arg("ld"), py::arg("off"), py::arg("nl"),
+        py::arg("rows"), py::arg("m_max"), py::arg("gamma"), py::arg("out"), py::arg("n_lines"), py::arg("out_ld"),
+        py::arg("out_lines"), py::arg("stream"), py::arg("split") = false);
+  m.attr("kWsProbeMiss") = kernels::kWsProbeMiss;
+  m.attr("kWsProbeRowsComputed") = kernels::kWsProbeRowsComputed;
+  m.attr("kWsProbeRowHits") = kernels::kWsProbeRowHits;
   // probability estimates (platt.hip), one launch each on host arrays
   m.def("k_holdout_decision", [](const F32& f, const F32& y, const I32& rows, double b, const F32& dec, int slot) {
     if (dec.ndim() != 2 || dec.shape(1) != f.size()) throw py::value_error("dec must be (slots, n)");

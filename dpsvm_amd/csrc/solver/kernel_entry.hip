@@ -174,6 +174,41 @@ void rbf_rows_indexed(const float* x, const float* xsq, int64_t n, int ld, const
   HIP_CHECK(hipStreamSynchronize(st.s));
 }
 
+void rbf_rows_miss(const float* x, const float* xsq, int64_t x_rows, int64_t n, int ld, int64_t off, int64_t nl,
+                   const std::vector<int32_t>& rows, int64_t m_max, float gamma, float* out, int64_t n_lines,
+                   int64_t out_ld, const std::vector<int32_t>& out_lines, void* stream, bool split) {
+  const int64_t m = (int64_t)rows.size();
+  DPSVM_CHECK(ld >= 16 && ld % 16 == 0 && n >= 1 && off >= 0 && nl >= 1 && off + nl <= n,
+              "rbf_rows_miss: ld a multiple of 16, the shard [off, off + nl) inside the n rows");
+  DPSVM_CHECK(x_rows >= n && x_rows >= off + (nl + 255) / 256 * 256,
+              "rbf_rows_miss: x must hold max(n, off + round_up(nl, 256)) rows (whole column tiles are read)");
+  DPSVM_CHECK(m <= m_max && m_max >= 1 && m_max <= kWsMaxAll && (int64_t)out_lines.size() == m,
+              "rbf_rows_miss: m <= m_max <= 6144 rows, a line each");
+  DPSVM_CHECK(n_lines >= 1 && out_ld >= nl, "rbf_rows_miss: out must be [n_lines][out_ld >= nl]");
+  std::vector<char> taken((size_t)n_lines, 0);
+  for (int64_t i = 0; i < m; ++i) {
+    DPSVM_CHECK(rows[i] >= 0 && rows[i] < n, "rbf_rows_miss: row out of range");
+    DPSVM_CHECK(out_lines[i] >= 0 && out_lines[i] < n_lines && !taken[out_lines[i]],
+                "rbf_rows_miss: lines must be distinct and below n_lines");
+    taken[out_lines[i]] = 1;
+  }
+  Arena st(stream);
+  const int32_t* md = st.up_one<int32_t>((int32_t)m);
+  const int32_t* rd = st.up(rows, (size_t)m);
+  const int32_t* od = st.up(out_lines, (size_t)m);
+  if (split) {
+    // split_pad_rows(n) zero-padded split rows: the widest column tile (192 rows) past off + nl stays inside
+    const SplitRows sx(st, x, n, ld, ld);
+    const uint8_t* Bs = (const uint8_t*)sx.planes + (size_t)off * launch::split_row_u4(ld) * 16;
+    launch::rbf_rows_indexed_split(sx.planes, sx.shift, xsq, rd, md, m_max, Bs, sx.shift + off, xsq + off, nl, ld,
+                                   gamma, out, od, out_ld, st.s);
+  } else {
+    launch::rbf_rows_indexed(x, xsq, rd, md, m_max, x + (size_t)off * ld, xsq + off, nl, ld, gamma, out, od, out_ld,
+                             st.s);
+  }
+  HIP_CHECK(hipStreamSynchronize(st.s));
+}
+
 std::vector<float> rbf_rows_indexed_split_bench(const float* x, const float* xsq, int64_t n, int ld, const int* rows,
                                                 int m, float gamma, float* out, int64_t out_ld, const int* out_rows,
                                                 int reps, void* stream) {

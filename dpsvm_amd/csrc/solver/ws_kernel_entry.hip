@@ -17,7 +17,15 @@
 //                           rows — the resident split Gram's bits, zeros in the columns past q
 //   ws_fupdate_split_probe  ws_fupdate_split: the recompute rounds' selection pass — f in the documented
 //                           summation order over the split Gram's bits, the candidate lists, the stop states
-// (tests/test_ws_kernels_gpu.py the first three, tests/test_ws_recompute_kernels_gpu.py the last three.)  A
+//   ws_merge_cache_probe    ws_merge: the same merge through its third kernel, then the cache-mode line plan
+//                           (hits keep their line, misses take victims after the CLOCK hand, pinned lines are
+//                           skipped, the evicted rows lose their line, the hand moves); with lines,
+//                           ws_gather_lines on the planned lines
+//   ws_merge_multi_cache_probe  ws_rank_merge with WsArgs::cache: the multi-block merge and the line plan of its
+//                           union; with lines, ws_gather_multi reading WsCtrl::line
+//   ws_pack_rows_probe      ws_pack_rows: the misses' X rows packed for a partitioned X
+// (tests/test_ws_kernels_gpu.py the first three, tests/test_ws_recompute_kernels_gpu.py the next three,
+// tests/test_ws_cache_kernels_gpu.py the last three and kernel_entry.hip's rbf_rows_miss.)  A
 // probe checks its arguments before it launches: a malformed call raises.
 //
 // Reference rules: the I-set classification and selection functors
@@ -27,6 +35,7 @@
 
 #include <cstddef>
 #include <cstring>
+#include <functional>
 #include <limits>
 
 #include "probe_util.hpp"
@@ -90,46 +99,198 @@ GramDotProbe gram_rows_dot_probe(const std::vector<float>& Kt, int64_t nt, int64
   return r;
 }
 
-WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int blocks, int p_act, int q_max,
-                                  int n_new, float eps, const std::vector<int32_t>& prev_union, int64_t iter,
-                                  int64_t max_iter) {
+namespace {
+
+// the cache-mode state a probe uploads: maps that are mutual inverses, every entry and the hand in range
+void check_cache_maps(int64_t n, int64_t L, int hand, const std::vector<int32_t>& slot_of,
+                      const std::vector<int32_t>& key_of) {
+  DPSVM_CHECK(n >= 1 && n < ((int64_t)1 << 31) && L >= 1 && L < ((int64_t)1 << 31) && (int64_t)slot_of.size() == n &&
+                  (int64_t)key_of.size() == L,
+              "ws cache probe: slot_of of n rows, key_of of L lines");
+  DPSVM_CHECK(hand >= 0 && hand < L, "ws cache probe: the hand must be a line");
+  for (int64_t r = 0; r < n; ++r) {
+    const int64_t l = slot_of[r];
+    DPSVM_CHECK(l >= -1 && l < L, "ws cache probe: slot_of entry out of range");
+    DPSVM_CHECK(l < 0 || key_of[l] == r, "ws cache probe: slot_of / key_of are not inverses");
+  }
+  for (int64_t l = 0; l < L; ++l) {
+    const int64_t r = key_of[l];
+    DPSVM_CHECK(r >= -1 && r < n, "ws cache probe: key_of entry out of range");
+    DPSVM_CHECK(r < 0 || slot_of[r] == l, "ws cache probe: slot_of / key_of are not inverses");
+  }
+}
+
+// the cache fields of a control record before the launch (kernel_probes.hpp)
+void blank_cache_ctrl(WsCtrl& c, int hand) {
+  c.hand = hand;
+  c.n_miss = kWsProbeMiss;
+  c.rows_computed = kWsProbeRowsComputed;
+  c.row_hits = kWsProbeRowHits;
+  for (int i = 0; i < kWsMaxAll; ++i) c.miss_row[i] = c.miss_line[i] = -1;
+}
+
+WsCacheState cache_state(Arena& st, const WsCtrl& o, const WsArgs& a, int64_t n) {
+  WsCacheState r;
+  r.n_miss = o.n_miss;
+  r.hand = o.hand;
+  r.rows_computed = o.rows_computed;
+  r.row_hits = o.row_hits;
+  r.miss_row.assign(o.miss_row, o.miss_row + kWsMaxAll);
+  r.miss_line.assign(o.miss_line, o.miss_line + kWsMaxAll);
+  r.slot_of = st.down(a.slot_of, (size_t)n);
+  r.key_of = st.down(a.key_of, (size_t)a.L);
+  return r;
+}
+
+void check_merge_multi(const std::vector<uint64_t>& cand, int G, int blocks, int q_max,
+                       const std::vector<int32_t>& prev_union) {
   DPSVM_CHECK(G >= 1 && G <= kWsMaxGroups && (int64_t)cand.size() == (int64_t)G * 2 * kWsCand,
               "ws_merge_multi_probe: cand must be [G][2][kWsCand = 16] with G <= 256");
   DPSVM_CHECK(blocks >= 2 && blocks <= kWsMaxBlocks && q_max >= 2 && q_max <= kWsMax && q_max % 2 == 0,
               "ws_merge_multi_probe: 2 <= blocks <= 128, blocks x q_max <= 6144, even q_max <= 192");
   DPSVM_CHECK((int64_t)prev_union.size() <= (int64_t)blocks * q_max, "ws_merge_multi_probe: previous union too long");
+}
+
+// control record (round 1: it builds parity 1, the previous union sits in parity 0) and arguments of one
+// multi-block merge
+struct MergeMultiRound {
+  std::unique_ptr<WsCtrl> c = blank_ctrl();
+  WsArgs a = single_rank_args();
+  MergeMultiRound(Arena& st, const std::vector<uint64_t>& cand, int G, int blocks, int p_act, int q_max, int n_new,
+                  float eps, const std::vector<int32_t>& prev_union, int64_t iter, int64_t max_iter) {
+    c->outer = 1;
+    c->iter = iter;
+    c->uq[0] = (int32_t)prev_union.size();
+    for (size_t i = 0; i < prev_union.size(); ++i) c->uidx[0][i] = prev_union[i];
+    c->p_act = p_act;
+    for (int i = 0; i < kWsMaxAll; ++i) c->idx[1][i] = c->line[1][i] = -1;
+    a.cand = a.cand_out = st.up(cand, cand.size());
+    a.G = a.G_all = G;
+    a.blocks = blocks;
+    a.q_max = q_max;
+    a.n_new = n_new;
+    a.eps = eps;
+    a.max_iter = max_iter;
+    a.sorted = st.alloc<uint64_t>((size_t)2 * kWsMaxGroups * kWsCand);
+  }
+  static WsMergeProbe result(const WsCtrl& o, int blocks, int q_max) {
+    WsMergeProbe r;
+    r.done = o.done;
+    r.b_hi = o.b_hi;
+    r.b_lo = o.b_lo;
+    r.p_round = o.p_round;
+    if (o.done != kRunning) return r;
+    r.uidx.assign(o.uidx[1], o.uidx[1] + o.uq[1]);
+    r.qb.assign(o.qb[1], o.qb[1] + blocks);
+    r.idx.assign((size_t)blocks * q_max, -1);
+    for (int p = 0; p < blocks; ++p)
+      for (int la = 0; la < o.qb[1][p]; ++la) r.idx[(size_t)p * q_max + la] = o.idx[1][p * q_max + la];
+    return r;
+  }
+};
+
+}  // namespace
+
+WsMergeProbe ws_merge_multi_probe(const std::vector<uint64_t>& cand, int G, int blocks, int p_act, int q_max,
+                                  int n_new, float eps, const std::vector<int32_t>& prev_union, int64_t iter,
+                                  int64_t max_iter) {
+  check_merge_multi(cand, G, blocks, q_max, prev_union);
+  Arena st;
+  MergeMultiRound m(st, cand, G, blocks, p_act, q_max, n_new, eps, prev_union, iter, max_iter);
+  m.a.ctrl = st.up_one(*m.c);
+  launch::ws_merge_multi(m.a, st.s);
+  return MergeMultiRound::result(st.down(m.a.ctrl, 1)[0], blocks, q_max);
+}
+
+WsMergeMultiCacheProbe ws_merge_multi_cache_probe(const std::vector<uint64_t>& cand, int G, int blocks, int p_act,
+                                                  int q_max, int n_new, float eps,
+                                                  const std::vector<int32_t>& prev_union, int64_t iter,
+                                                  int64_t max_iter, int64_t L, int hand,
+                                                  const std::vector<int32_t>& slot_of,
+                                                  const std::vector<int32_t>& key_of, const std::vector<float>& f,
+                                                  const std::vector<float>& alpha, const std::vector<float>& y,
+                                                  const float* lines, int64_t ldl) {
+  check_merge_multi(cand, G, blocks, q_max, prev_union);
+  const int64_t n = (int64_t)slot_of.size();
+  check_cache_maps(n, L, hand, slot_of, key_of);
+  DPSVM_CHECK(launch::ws_cache_multi_supported(L, blocks, q_max) && blocks * q_max <= kWsWindowMulti / 2,
+              "ws_merge_multi_cache_probe: cache mode takes <= 4096 union rows and L >= 2 blocks q_max + 8192 lines");
+  // the merge reads slot_of at every row it picks: any key of either side, any previous row
+  for (uint64_t k : cand)
+    DPSVM_CHECK(k == kKeyNone || (int64_t)key_index(k) < n, "ws_merge_multi_cache_probe: candidate row out of range");
+  std::vector<char> seen((size_t)n, 0);
+  for (int32_t r : prev_union) {
+    DPSVM_CHECK(r >= 0 && r < n && !seen[r], "ws_merge_multi_cache_probe: previous-union rows: distinct, below n");
+    seen[r] = 1;
+  }
+  DPSVM_CHECK(lines == nullptr || (ldl >= n && (int64_t)f.size() == n && (int64_t)alpha.size() == n &&
+                                   (int64_t)y.size() == n),
+              "ws_merge_multi_cache_probe: lines [L][ldl >= n] need f / alpha / y of n rows");
+  Arena st;
+  MergeMultiRound m(st, cand, G, blocks, p_act, q_max, n_new, eps, prev_union, iter, max_iter);
+  blank_cache_ctrl(*m.c, hand);
+  WsArgs& a = m.a;
+  a.ctrl = st.up_one(*m.c);
+  a.n = a.nl = n;
+  a.cache = 1;
+  a.L = (int32_t)L;
+  a.slot_of = st.up(slot_of, (size_t)n);
+  a.key_of = st.up(key_of, (size_t)L);
+  launch::ws_merge_multi(a, st.s);
+  const size_t nsub = (size_t)blocks * q_max * q_max, naux = (size_t)3 * blocks * kWsMax;
+  if (lines != nullptr) {
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    float* sub = st.up(std::vector<float>(nsub + naux, nan), nsub + naux);
+    a.subg = sub;
+    a.aux = sub + nsub;
+    a.aux_stride = blocks * kWsMax;
+    a.gram = lines;
+    a.ldg = ldl;
+    a.f = st.up(f, (size_t)n);
+    a.alpha = st.up(alpha, (size_t)n);
+    a.y = st.up(y, (size_t)n);
+    launch::ws_gather(a, st.s);  // blocks > 1: ws_gather_multi_kernel, lines from WsCtrl::line
+  }
+  const WsCtrl o = st.down(a.ctrl, 1)[0];
+  WsMergeMultiCacheProbe r;
+  r.merge = MergeMultiRound::result(o, blocks, q_max);
+  r.cache = cache_state(st, o, a, n);
+  if (lines != nullptr) {
+    r.subg = st.down(a.subg, nsub);
+    r.aux = st.down(a.aux, naux);
+  }
+  if (o.done != kRunning) return r;
+  r.line.assign((size_t)blocks * q_max, -1);
+  for (int p = 0; p < blocks; ++p)
+    for (int la = 0; la < o.qb[1][p]; ++la) r.line[(size_t)p * q_max + la] = o.line[1][p * q_max + la];
+  return r;
+}
+
+WsPackRowsProbe ws_pack_rows_probe(const std::vector<float>& x, int64_t nl, int dp, int64_t off,
+                                   const std::vector<float>& xsq, const std::vector<int32_t>& miss_row, int n_miss,
+                                   int q_max) {
+  const int64_t n = (int64_t)xsq.size();
+  DPSVM_CHECK(dp >= 16 && dp % 16 == 0 && nl >= 1 && off >= 0 && off + nl <= n && (int64_t)x.size() == nl * dp,
+              "ws_pack_rows_probe: x [nl][dp], dp a multiple of 16, the shard [off, off + nl) inside xsq's n rows");
+  DPSVM_CHECK(q_max >= 1 && q_max <= kWsMaxAll && n_miss >= 0 && n_miss <= q_max &&
+                  (int64_t)miss_row.size() >= n_miss && (int64_t)miss_row.size() <= kWsMaxAll,
+              "ws_pack_rows_probe: n_miss <= q_max <= 6144 rows, miss_row of at least n_miss entries");
+  for (int i = 0; i < n_miss; ++i)
+    DPSVM_CHECK(miss_row[i] >= 0 && miss_row[i] < n, "ws_pack_rows_probe: miss row out of range");
   Arena st;
   auto c = blank_ctrl();
-  c->outer = 1;  // this round builds parity 1; the previous union sits in parity 0
-  c->iter = iter;
-  c->uq[0] = (int32_t)prev_union.size();
-  for (size_t i = 0; i < prev_union.size(); ++i) c->uidx[0][i] = prev_union[i];
-  c->p_act = p_act;
-  for (int i = 0; i < kWsMaxAll; ++i) c->idx[1][i] = -1;
-  WsCtrl* dc = st.up_one(*c);
-  WsArgs a = single_rank_args();
-  a.cand = a.cand_out = st.up(cand, cand.size());
-  a.G = a.G_all = G;
-  a.blocks = blocks;
-  a.q_max = q_max;
-  a.n_new = n_new;
-  a.eps = eps;
-  a.max_iter = max_iter;
-  a.ctrl = dc;
-  a.sorted = st.alloc<uint64_t>((size_t)2 * kWsMaxGroups * kWsCand);
-  launch::ws_merge_multi(a, st.s);
-  const WsCtrl o = st.down(dc, 1)[0];
-  WsMergeProbe r;
-  r.done = o.done;
-  r.b_hi = o.b_hi;
-  r.b_lo = o.b_lo;
-  r.p_round = o.p_round;
-  if (o.done != kRunning) return r;
-  r.uidx.assign(o.uidx[1], o.uidx[1] + o.uq[1]);
-  r.qb.assign(o.qb[1], o.qb[1] + blocks);
-  r.idx.assign((size_t)blocks * q_max, -1);
-  for (int p = 0; p < blocks; ++p)
-    for (int la = 0; la < o.qb[1][p]; ++la) r.idx[(size_t)p * q_max + la] = o.idx[1][p * q_max + la];
+  c->n_miss = n_miss;
+  for (size_t i = 0; i < miss_row.size(); ++i) c->miss_row[i] = miss_row[i];
+  const WsCtrl* dc = st.up_one(*c);
+  const float* dx = st.up(x, x.size());
+  const float* dsq = st.up(xsq, xsq.size());
+  const float nan = std::numeric_limits<float>::quiet_NaN();
+  const size_t no = (size_t)q_max * dp;
+  float* out = st.up(std::vector<float>(no + q_max, nan), no + q_max);
+  launch::ws_pack_rows(dx, off, nl, dp, dsq, dc, q_max, out, out + no, st.s);
+  WsPackRowsProbe r;
+  r.out = st.down(out, no);
+  r.out_sq = st.down(out + no, (size_t)q_max);
   return r;
 }
 
@@ -380,7 +541,8 @@ struct MergeRound {
   WsArgs a{};
   MergeRound(Arena& st, int64_t n, const std::vector<uint64_t>& cand, const std::vector<int32_t>& prev_set,
              const std::vector<float>& f, const std::vector<float>& alpha, const std::vector<float>& y, int q_max,
-             int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer) {
+             int n_new, float eps, int64_t iter, int64_t max_iter, int nonfinite, int64_t outer,
+             const std::function<void(WsCtrl&)>& more = nullptr) {  // further fields of the record before the upload
     auto c = blank_ctrl();
     const int par = (int)(outer & 1);
     c->outer = outer;
@@ -390,6 +552,7 @@ struct MergeRound {
     c->q[par ^ 1] = (int32_t)prev_set.size();
     for (size_t i = 0; i < prev_set.size(); ++i) c->idx[par ^ 1][i] = prev_set[i];
     for (int i = 0; i < kWsMaxAll; ++i) c->idx[par][i] = -1;
+    if (more) more(*c);
     dc = st.up_one(*c);
     const float nan = std::numeric_limits<float>::quiet_NaN();
     float* sub = st.up(std::vector<float>((size_t)q_max * q_max + 3 * kWsMax, nan), (size_t)q_max * q_max + 3 * kWsMax);
@@ -461,6 +624,41 @@ WsGatherProbe ws_subgram_split_probe(const std::vector<float>& x, int64_t n, int
   DPSVM_CHECK(launch::ws_recompute_supported(m.a, sx.dp), "ws_subgram_split_probe: shape not supported");
   launch::ws_subgram_split(m.a, sx.xs, sx.xsh, sx.xsq, sx.dp, gamma, st.s);
   return m.result(st, outer);
+}
+
+WsMergeCacheProbe ws_merge_cache_probe(const std::vector<uint64_t>& cand, const std::vector<int32_t>& prev_set,
+                                       const std::vector<float>& f, const std::vector<float>& alpha,
+                                       const std::vector<float>& y, int q_max, int n_new, float eps, int64_t iter,
+                                       int64_t max_iter, int nonfinite, int64_t outer, int done, int64_t L, int hand,
+                                       const std::vector<int32_t>& slot_of, const std::vector<int32_t>& key_of,
+                                       const float* lines, int64_t ldl) {
+  const int64_t n = (int64_t)f.size();
+  check_merge_state(n, cand, prev_set, f, alpha, y, q_max, n_new, nonfinite);
+  check_cache_maps(n, L, hand, slot_of, key_of);
+  DPSVM_CHECK(outer >= 0 && done >= kRunning && done <= kCommFail, "ws_merge_cache_probe: outer >= 0, done a DoneCode");
+  DPSVM_CHECK(launch::ws_cache_supported(L, q_max), "ws_merge_cache_probe: L below ws_cache_min_lines(q_max)");
+  DPSVM_CHECK(lines == nullptr || ldl >= n, "ws_merge_cache_probe: lines must be [L][ldl >= n]");
+  Arena st;
+  MergeRound m(st, n, cand, prev_set, f, alpha, y, q_max, n_new, eps, iter, max_iter, nonfinite, outer,
+               [&](WsCtrl& c) {
+                 c.done = done;
+                 blank_cache_ctrl(c, hand);
+               });
+  WsArgs& a = m.a;
+  a.cache = 1;
+  a.L = (int32_t)L;
+  a.slot_of = st.up(slot_of, (size_t)n);
+  a.key_of = st.up(key_of, (size_t)L);
+  launch::ws_merge(a, st.s);  // ws_merge_kernel: one workgroup
+  if (lines != nullptr) {
+    a.gram = lines;
+    a.ldg = ldl;
+    launch::ws_gather(a, st.s);  // cache, one block: ws_gather_lines_kernel
+  }
+  WsMergeCacheProbe r;
+  r.round = m.result(st, outer);
+  r.cache = cache_state(st, st.down(m.dc, 1)[0], a, n);
+  return r;
 }
 
 WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, int d, const std::vector<float>& f,

@@ -443,6 +443,114 @@ def ws_fupdate_split(x, f, alpha, y, apply_idx, apply_coef, gamma: float, C_: fl
     return r
 
 
+def _cache_args(L, slot_of, key_of, lines):
+    """the cache maps as int32 arrays; lines: None or a float32 CUDA tensor [L][ldl] -> (address, ldl)"""
+    import numpy as np
+
+    so = np.ascontiguousarray(np.asarray(slot_of, dtype=np.int32)).reshape(-1)
+    ko = np.ascontiguousarray(np.asarray(key_of, dtype=np.int32)).reshape(-1)
+    if lines is None:
+        return so, ko, 0, 0
+    if not (lines.is_cuda and lines.dtype == torch.float32 and lines.dim() == 2 and lines.is_contiguous()
+            and lines.shape[0] == int(L)):
+        raise ValueError("lines must be a contiguous float32 CUDA tensor [L][ldl]")
+    torch.cuda.synchronize(lines.device)  # the probe works on a stream of its own
+    return so, ko, lines.data_ptr(), lines.shape[1]
+
+
+def _cache_result(r: dict) -> dict:
+    import numpy as np
+
+    for k in ("miss_row", "miss_line", "slot_of", "key_of"):
+        r[k] = np.asarray(r[k], dtype=np.int32)
+    return r
+
+
+def ws_merge_cache(cand, prev_set, f, alpha, y, q_max: int, n_new: int, eps: float, L: int, hand: int, slot_of,
+                   key_of, lines=None, iteration: int = 0, max_iter: int = 1 << 40, nonfinite: int = 0,
+                   outer: int = 1, done: int = 0) -> dict:
+    """One launch of the cache-mode one-block round's first kernel (ws_merge_kernel: the one-block merge of
+    ws_merge.hpp in one workgroup, then a line for every member — its cached line ``slot_of[row]``, or a victim from
+    the 512-line window after the CLOCK ``hand``) on the state ws_gather takes plus the cache: ``slot_of`` [n] and
+    ``key_of`` [L], mutual inverses (-1: none).  ``done``: the run's DoneCode when the launch starts.  ``lines``: a
+    float32 CUDA tensor [L][ldl >= n] of kernel rows; ws_gather_lines_kernel then gathers the sub-Gram from the
+    planned lines.  Returns ws_gather's fields (subg / aux stay NaN without lines) and n_miss, hand, rows_computed,
+    row_hits, the whole miss_row / miss_line arrays (-1 before the launch), slot_of and key_of after it.  Before the
+    launch n_miss holds kWsProbeMiss and the counters kWsProbeRowsComputed / kWsProbeRowHits."""
+    c, prev, f_, a_, y_ = _merge_round_args(cand, prev_set, f, alpha, y)
+    so, ko, ptr, ldl = _cache_args(L, slot_of, key_of, lines)
+    r = load().k_ws_merge_cache(c, prev, f_, a_, y_, int(q_max), int(n_new), float(eps), int(iteration),
+                                int(max_iter), int(nonfinite), int(outer), int(done), int(L), int(hand), so, ko,
+                                lines=ptr, ldl=ldl)
+    return _cache_result(_merge_round_result(r, q_max))
+
+
+def ws_merge_multi_cache(cand, blocks: int, q_max: int, n_new: int, eps: float, L: int, hand: int, slot_of, key_of,
+                         prev_union=(), p_act: int | None = None, iteration: int = 0, max_iter: int = 1 << 40,
+                         lines=None, f=None, alpha=None, y=None) -> dict:
+    """One launch of the multi-block merge in cache mode (ws_rank_merge_kernel, WsArgs::cache = 1): ws_merge_multi's
+    arguments plus the cache over n = len(slot_of) rows (every candidate and previous-union row below n).  Returns
+    ws_merge_multi's fields, ``line`` [blocks * q_max] (the members' lines at idx's positions, -1 unused) and the
+    cache state as ws_merge_cache.  ``lines`` (with f / alpha / y of n rows): ws_gather_multi_kernel then gathers
+    ``subg`` [blocks][q_max][q_max] and ``aux`` [3][blocks][192] (NaN before the launch)."""
+    import numpy as np
+
+    c = np.ascontiguousarray(np.asarray(cand, dtype=np.uint64).reshape(-1, 2, WS_CAND))
+    prev = np.asarray(list(prev_union), dtype=np.int32)
+    so, ko, ptr, ldl = _cache_args(L, slot_of, key_of, lines)
+    def f32(a):
+        return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float32)).reshape(-1)
+
+    r = load().k_ws_merge_multi_cache(c.reshape(-1), c.shape[0], int(blocks), int(blocks if p_act is None else p_act),
+                                      int(q_max), int(n_new), float(eps), prev, int(iteration), int(max_iter), int(L),
+                                      int(hand), so, ko, f=f32(f), alpha=f32(alpha), y=f32(y), lines=ptr, ldl=ldl)
+    r["line"] = np.asarray(r["line"], dtype=np.int32)
+    if lines is not None:
+        r["subg"] = r["subg"].reshape(blocks, q_max, q_max)
+        r["aux"] = r["aux"].reshape(3, blocks, -1)
+    return _cache_result(r)
+
+
+def ws_pack_rows(x, off: int, xsq, miss_row, n_miss: int, q_max: int) -> dict:
+    """One launch of ws_pack_rows_kernel (partitioned X, cache mode) on the shard ``x`` [nl][dp] (dp a multiple of
+    16) holding rows [off, off + nl) of a problem whose global norms are ``xsq`` [n]; ``miss_row``'s first n_miss
+    entries are the round's misses.  Returns ``out`` [q_max][dp] and ``out_sq`` [q_max], NaN before the launch."""
+    import numpy as np
+
+    xx = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+    r = load().k_ws_pack_rows(xx.reshape(-1), xx.shape[0], xx.shape[1], int(off),
+                              np.ascontiguousarray(np.asarray(xsq, dtype=np.float32)).reshape(-1),
+                              np.asarray(miss_row, dtype=np.int32).reshape(-1), int(n_miss), int(q_max))
+    r["out"] = r["out"].reshape(q_max, xx.shape[1])
+    return r
+
+
+def rbf_rows_miss(x: torch.Tensor, rows, gamma: float, m_max: int | None = None, off: int = 0, nl: int | None = None,
+                  out_lines=None, n_lines: int = 0, split: bool = False) -> torch.Tensor:
+    """The ws-cache row GEMM as a round calls it (gpu_engines.hip miss_rows): the launch sized by ``m_max`` >=
+    len(rows) while the device-side count is len(rows), the column operand the shard x[off : off + nl] with its
+    norms.  Returns the whole [n_lines][round_up(nl, 128)] array, NaN before the launch, pad columns included:
+    line out_lines[i] = K(x[rows[i]], x[off + j]), j < nl.  split=True: rbf_rows_split.hip."""
+    import numpy as np
+
+    rows = np.asarray([int(r) for r in rows], dtype=np.int32)
+    m = len(rows)
+    n = x.shape[0]
+    nl = n - off if nl is None else nl
+    xp, dp = _pad_rows_cols(x, row_mult=512)  # whole 256-column tiles of the shard stay inside
+    xsq = torch.zeros(xp.shape[0], device=x.device)
+    C = load()
+    C.k_row_sqnorm(xp.data_ptr(), xp.shape[0], dp, dp, xsq.data_ptr(), _stream(x))
+    out_lines = np.arange(m, dtype=np.int32) if out_lines is None else np.asarray(out_lines, dtype=np.int32)
+    n_lines = max(int(n_lines), int(out_lines.max()) + 1 if m else 1)
+    ld = (max(nl, 1) + 127) // 128 * 128
+    out = torch.full((n_lines, ld), float("nan"), device=x.device)
+    C.k_rbf_rows_miss(xp.data_ptr(), xsq.data_ptr(), xp.shape[0], n, dp, int(off), int(nl), rows,
+                      int(m if m_max is None else m_max), float(gamma), out.data_ptr(), n_lines, ld, out_lines,
+                      _stream(x), bool(split))
+    return out
+
+
 def holdout_decision(f, y, rows, b: float, dec, slot: int = 0):
     """One launch of holdout_decision_kernel (platt.hip): ``dec`` [slots][n] with
     dec[slot, i] = float32(float64(f[i]) + y[i] - b) for the rows i of ``rows``

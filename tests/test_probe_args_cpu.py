@@ -72,6 +72,115 @@ def test_one_block_merge_probes(K, C, probe):
         run(first, lists(C, 1, rows=(0, n)), [], f, alpha, y, *extra, 2, 2, 1e-3)
 
 
+def cache(n, L, pairs=()):
+    """slot_of [n] / key_of [L] with row r in line l for every (r, l)"""
+    s, k = np.full(n, -1, np.int32), np.full(L, -1, np.int32)
+    for r, ln in pairs:
+        s[r], k[ln] = ln, r
+    return s, k
+
+
+def test_ws_merge_cache(K, C):
+    n, L = 8, 520  # ws_cache_min_lines(2) = 516
+    f, alpha, y = state(n)
+
+    def run(L_=L, hand=0, maps=None, rows=(0, 1), prev=(), **kw):
+        s, k = cache(n, L_, [(2, 7)]) if maps is None else maps
+        return K.ws_merge_cache(lists(C, 1, rows=rows), list(prev), f, alpha, y, 2, 2, 1e-3, L_, hand, s, k, **kw)
+
+    with pytest.raises(RuntimeError, match="L below ws_cache_min_lines"):
+        run(L_=515)
+    for hand in (-1, L):
+        with pytest.raises(RuntimeError, match="the hand must be a line"):
+            run(hand=hand)
+    s, k = cache(n, L, [(2, 7)])
+    with pytest.raises(RuntimeError, match="not inverses"):  # the line holds another row
+        run(maps=(s, np.where(np.arange(L) == 7, 3, k).astype(np.int32)))
+    with pytest.raises(RuntimeError, match="not inverses"):  # a line claims a row that has no line
+        run(maps=(s, np.where(np.arange(L) == 9, 4, k).astype(np.int32)))
+    with pytest.raises(RuntimeError, match="slot_of entry out of range"):
+        run(maps=(np.where(np.arange(n) == 5, L, s).astype(np.int32), k))
+    with pytest.raises(RuntimeError, match="key_of entry out of range"):
+        run(maps=(s, np.where(np.arange(L) == 9, n, k).astype(np.int32)))
+    with pytest.raises(RuntimeError, match="slot_of of n rows, key_of of L lines"):
+        run(maps=(s[:-1], k))
+    with pytest.raises(RuntimeError, match="candidate row out of range"):
+        run(rows=(0, n))
+    with pytest.raises(RuntimeError, match="previous set longer than q_max"):
+        run(prev=(2, 3, 4))
+    with pytest.raises(RuntimeError, match="done a DoneCode"):
+        run(done=99)
+
+
+def test_ws_merge_multi_cache(K, C):
+    n, blocks, q_max = 64, 2, 4
+    L = 2 * blocks * q_max + 8192
+
+    def run(blocks_=blocks, q_=q_max, L_=L, rows=(0, 1), prev=(), maps=None):
+        s, k = cache(n, L_, [(2, 7)]) if maps is None else maps
+        return K.ws_merge_multi_cache(lists(C, 1, rows=rows), blocks_, q_, 2, 1e-3, L_, 0, s, k, prev_union=prev)
+
+    with pytest.raises(RuntimeError, match="<= 4096 union rows and L >="):
+        run(L_=L - 1)
+    with pytest.raises(RuntimeError, match="<= 4096 union rows and L >="):
+        run(blocks_=32, q_=192, L_=2 * 32 * 192 + 8192)
+    with pytest.raises(RuntimeError, match="2 <= blocks <= 128"):
+        run(blocks_=1)
+    with pytest.raises(RuntimeError, match="candidate row out of range"):
+        run(rows=(0, n))
+    with pytest.raises(RuntimeError, match="distinct, below n"):
+        run(prev=(3, n))
+    with pytest.raises(RuntimeError, match="distinct, below n"):
+        run(prev=(3, 5, 3))
+    s, k = cache(n, L, [(2, 7)])
+    with pytest.raises(RuntimeError, match="not inverses"):
+        run(maps=(np.where(np.arange(n) == 4, 7, s).astype(np.int32), k))
+
+
+def test_ws_pack_rows(K):
+    X, xsq = np.zeros((100, 32), np.float32), np.zeros(300, np.float32)
+    with pytest.raises(RuntimeError, match="miss row out of range"):
+        K.ws_pack_rows(X, 50, xsq, [300], 1, 192)
+    with pytest.raises(RuntimeError, match=r"the shard \[off, off \+ nl\) inside"):
+        K.ws_pack_rows(X, 201, xsq, [1], 1, 192)
+    with pytest.raises(RuntimeError, match="the shard"):  # dp no multiple of 16
+        K.ws_pack_rows(np.zeros((100, 20), np.float32), 50, xsq, [1], 1, 192)
+    with pytest.raises(RuntimeError, match="n_miss <= q_max"):
+        K.ws_pack_rows(X, 50, xsq, list(range(10)), 10, 8)
+    with pytest.raises(RuntimeError, match="n_miss <= q_max"):  # fewer rows listed than n_miss
+        K.ws_pack_rows(X, 50, xsq, [1, 2], 3, 192)
+
+
+def test_rbf_rows_miss(C):
+    """device addresses: nothing may be read before the checks pass (the addresses here are null)"""
+    def run(rows=(1, 2), out_lines=(0, 1), x_rows=1024, n=500, ld=16, off=0, nl=500, m_max=192, n_lines=4,
+            out_ld=512, split=False):
+        return C.k_rbf_rows_miss(0, 0, x_rows, n, ld, off, nl, np.asarray(rows, np.int32), m_max, 0.5, 0, n_lines,
+                                 out_ld, np.asarray(out_lines, np.int32), 0, split)
+
+    for split in (False, True):
+        with pytest.raises(RuntimeError, match="row out of range"):
+            run(rows=(1, 500), split=split)
+        with pytest.raises(RuntimeError, match="lines must be distinct"):
+            run(out_lines=(1, 1), split=split)
+        with pytest.raises(RuntimeError, match="lines must be distinct"):
+            run(out_lines=(1, 4), split=split)
+        with pytest.raises(RuntimeError, match="m <= m_max <= 6144"):
+            run(m_max=1, split=split)
+        with pytest.raises(RuntimeError, match="m <= m_max <= 6144"):
+            run(m_max=6145, split=split)
+        with pytest.raises(RuntimeError, match="the shard"):
+            run(off=400, nl=101, split=split)
+        with pytest.raises(RuntimeError, match="whole column tiles"):
+            run(x_rows=511, split=split)
+        with pytest.raises(RuntimeError, match="whole column tiles"):  # off + round_up(nl, 256) rows are read
+            run(x_rows=600, off=200, nl=300, split=split)
+        with pytest.raises(RuntimeError, match="out_ld >= nl"):
+            run(out_ld=499, split=split)
+        with pytest.raises(RuntimeError, match="ld a multiple of 16"):
+            run(ld=20, split=split)
+
+
 def test_ws_fupdate_split(K):
     n = 200
     f, alpha, y = state(n)

@@ -1,7 +1,9 @@
 """The Python surface of the kernel probes is frozen: every ``k_*`` function of the built module has the pybind11
-signature line (name, argument names, order, types, defaults, return type) and the two ``kWsProbe*`` constants the
-value that tests/data/probe_surface.json holds, recorded by bench/make_probe_surface_fixture.py on the build before
-the probes' host code was consolidated.  No name missing, none added."""
+signature line (name, argument names, order, types, defaults, return type) and every ``kWsProbe*`` constant the
+value that tests/data/probe_surface.json holds, recorded by bench/make_probe_surface_fixture.py: the entries of the
+build before the probes' host code was consolidated, unchanged since, plus those of the cache-mode probes
+(k_ws_merge_cache, k_ws_merge_multi_cache, k_ws_pack_rows, k_rbf_rows_miss and their three constants) as they were
+added.  No name missing, none added: a new probe is recorded in the fixture by the change that adds it."""
 import importlib.util
 import json
 import os

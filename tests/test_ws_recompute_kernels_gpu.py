@@ -195,8 +195,10 @@ def fup_apply(n, M, seed=0):
 
 
 def split_rows_of_gram(K, X, rows, gamma):  # noqa: F811
-    """Kb[k] = the split Gram's row rows[k] (rbf_rows_indexed, split: pinned
-    bit-identical to the split Gram by test_split_gemm_gpu.py)"""
+    """Kb[k] = the split Gram's row rows[k] (rbf_rows_indexed, split; d <= 64
+    here, so the small-K kernel: pinned bit-identical to the split Gram by
+    test_ws_cache_kernels_gpu.py::test_rbf_rows_miss_bit_identical_to_the_gram_rows;
+    test_split_gemm_gpu.py pins only the LDS-DMA kernels, d = 784)"""
     return K.rbf_rows_indexed(torch.from_numpy(X).cuda(), [int(r) for r in rows], gamma, split=True).cpu().numpy()
 
 

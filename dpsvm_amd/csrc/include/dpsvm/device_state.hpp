@@ -464,6 +464,23 @@ constexpr int64_t ws_xch_sub_words(int64_t P, int64_t q, int64_t q1) {
 constexpr int64_t ws_xch_words_multi(int64_t G_all, int64_t P1_all, int64_t ks, int64_t P, int64_t q, int64_t q1) {
   return ws_xch_cand_words_multi(G_all) + ws_xch_part_words(P1_all, ks) + ws_xch_sub_words(P, q, q1);
 }
+// The exchange region's layout in a rank's WsArgs (setup, and the sharded kernel probes): slot width, the
+// partials' and the sub-Gram rows' first words, the rows per parity — from blocks, G_all, world, p1G, ks, q_max.
+// Returns the words the layout spans for one-block rounds of q1 rows beside the P x q_max multi-block ones.
+inline int64_t ws_xch_set_layout(WsArgs& w, int64_t q1) {
+  if (w.blocks > 1) {  // ws_xch_words_multi: candidates (kWsCand keys a side), partials, sub-Gram rows
+    w.xcw = 4 * kWsCand;
+    w.xpart = ws_xch_cand_words_multi(w.G_all);
+    w.xsub = w.xpart + ws_xch_part_words((int64_t)w.world * w.p1G, w.ks);
+    w.xsub_rows = (int64_t)w.blocks * w.q_max;  // the one-block view: its own q_max (gpu_engines.hip)
+    return ws_xch_words_multi(w.G_all, (int64_t)w.world * w.p1G, w.ks, w.blocks, w.q_max, q1);
+  }
+  w.xcw = 4 * kWsCand1;  // ws_xch_words
+  w.xpart = 0;
+  w.xsub = 2 * (int64_t)w.G_all * 4 * kWsCand1;
+  w.xsub_rows = w.q_max;
+  return ws_xch_words(w.G_all, w.q_max);
+}
 constexpr int kStampRing = 4096;
 constexpr int kStampSlots = 12;
 

@@ -129,6 +129,17 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
                             // +1 / -1: the nu duals' class-masked kernels (one block, box clipping, scalar C) with
                             // this class as the round's (WsCtrl::nu_cls); 0: off
                             int nu_cls = 0);
+// ws_solve with WsArgs::direct_sub = 1 (the sub-Gram load of the 128 x 48 rounds): block p = the qb[p] first
+// rows of idx[p q_max ..] (global rows of gram [n][ldg >= n], distinct over the blocks; positions past qb[p] hold
+// any row or -1 and must not be read), f / alpha / y / row_C global [n], q_max <= 64.  The remaining arguments and
+// the result are ws_solve_probe's, with alpha the global [n] array and apply_idx global rows.
+WsSolveProbe ws_solve_direct_probe(const std::vector<float>& gram, int64_t n, int64_t ldg,
+                                   const std::vector<float>& f, const std::vector<float>& alpha,
+                                   const std::vector<float>& y, const std::vector<int32_t>& idx,
+                                   const std::vector<int32_t>& qb, int q_max, int blocks, int p_round, float C,
+                                   int clip, float eps, float rel, float eps_floor, float tau, float b_hi, float b_lo,
+                                   int inner_max, int64_t iter0, int64_t max_iter, int wss = 1,
+                                   const std::vector<float>& row_C = {});
 // ws_select: the f update of a round's alpha changes (apply rows: lines into
 // gram [L][ldg], coefficients) and the per-workgroup candidates.  blocks == 1:
 // the one-pass kernel; blocks > 1: pass 1 (d_f, line-search partials) and pass 2
@@ -288,6 +299,68 @@ WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, in
                                       const std::vector<float>& alpha, const std::vector<float>& y,
                                       const std::vector<int32_t>& apply_idx, const std::vector<float>& apply_coef,
                                       float gamma, float C, int done);
+// The sharded rounds: one stage of a round, launched once per rank r < world on one stream, rank r with the
+// arguments a rank of a world-rank run has — off / nl = shard_of(n, r, world), the geometry of
+// launch::ws_geometry(ceil(n / world), world), its own control record, f shard, copies of the global alpha / y /
+// dalpha and its Gram panel [L lines][ldg_r = round_up(nl, 4) + ldg_extra] holding columns [off, off + nl) of
+// gram [L][n], the padding columns NaN.  exchange = 0: the collectives form, every rank's buffers are returned for
+// the test to concatenate / add as the communicator would.  exchange = 1: the peer form — world receive buffers in
+// this process (allocated as the solver allocates one), xpeer[p] = buffer p on every rank, xrank = r; every rank's
+// producer runs first, then on the same stream every rank's consumer, so no poll ever waits:
+//   Select / Pass2 -> ws_xcollect_cand; Pass1 -> ws_xcollect_part; the gathers -> ws_solve.
+enum class WsShardStage : int {
+  Select = 0,      // the one-pass kernel (blocks == 1): apply list -> f shard, candidates
+  Pass1 = 1,       // ws_pass1_v4_kernel (blocks > 1): dfs, this rank's slots of part (prefilled kWsProbePart)
+  Pass2 = 2,       // pass 2 on `part` (all ranks' slots) and `dfs` ([ks][n] global columns)
+  Gather = 3,      // ws_gather_kernel (dense, blocks == 1): the merge of cand / prev_set, then the rows
+  GatherMulti = 4, // ws_gather_multi_kernel on idx / line / qb (cache: lines from WsCtrl::line)
+  GatherLines = 5, // ws_gather_lines_kernel (cache, blocks == 1) on idx / line, q = qb[0]
+};
+constexpr double kWsProbePart = -7777.0;
+constexpr int64_t kWsProbeXTimeout = 10000000;  // 0.1 s of s_memrealtime: the largest poll bound a probe takes
+struct WsShardIn {
+  int64_t n = 0, L = 0, ldg_extra = 0;  // gram [L][n]; dense stages: L == n
+  int world = 1, exchange = 0, cache = 0;
+  int blocks = 1, q_max = 0, p_round = 1, p_act = 1, ks = 1, ncand = 0;
+  int64_t outer = 1, xtimeout_ticks = kWsProbeXTimeout;
+  float C = 1.f;
+  std::vector<float> gram, f, alpha, y, dalpha, row_C;  // [n] each (row_C: or empty)
+  // Select / Pass1 / Pass2: the round's changes, block p's nab[p] rows (concatenated in block order)
+  std::vector<int32_t> apply_idx, apply_line, nab;
+  std::vector<float> apply_coef;
+  std::vector<double> part;  // Pass2: [world p1G][ks][2]
+  std::vector<float> dfs;    // Pass2: [ks][n]
+  // Gather: the lists [world G][2][kWsCand] and the previous set; n_new, eps, iter, max_iter of the merge
+  std::vector<uint64_t> cand;
+  std::vector<int32_t> prev_set;
+  int n_new = 1;
+  float eps = 1e-3f;
+  int64_t iter = 0, max_iter = (int64_t)1 << 40;
+  // GatherMulti / GatherLines: the set, block p's qb[p] first rows of idx[p q_max ..] and their lines
+  std::vector<int32_t> idx, line, qb;
+  // the peer form's ws_solve (ws_solve_probe's arguments)
+  int clip = 0, inner_max = 0, wss = 1;
+  float rel = 0.3f, eps_floor = 3e-4f, tau = 1e-12f, b_hi = 0.f, b_lo = 0.f;
+};
+struct WsShardRank {
+  int64_t off = 0, nl = 0, ldg = 0;
+  std::vector<float> f, alpha, dalpha, dfs;  // f [nl], alpha / dalpha [n], dfs [ks][nl]
+  std::vector<double> part;                  // [world p1G][ks][2]
+  std::vector<uint64_t> cand_out, cand;      // this rank's [G][2][kWsCand]; every rank's [world G][2][kWsCand]
+  float t = 0.f, b_hi = 0.f, b_lo = 0.f;
+  int p_act = 0, n_damped = 0, nonfinite = 0, done = 0, n_apply = 0, q = 0;
+  int64_t p1_round = 0, iter = 0, outer = 0;
+  std::vector<int32_t> idx, line;  // Gather: the merged set and its lines
+  std::vector<float> subg, aux;    // [blocks][q_max][q_max], [3][blocks][kWsMax] (NaN before the launch)
+  std::vector<int32_t> steps, apply_idx, nab;  // the peer form's solve, as WsSolveProbe
+  std::vector<float> apply_coef;
+};
+struct WsShardProbe {
+  int G = 0, rpt = 0, p1G = 0, uncached = 0;  // uncached: the receive buffers' memory (peer form)
+  int64_t xch_words = 0;
+  std::vector<WsShardRank> ranks;
+};
+WsShardProbe ws_shard_round_probe(WsShardStage stage, const WsShardIn& in);
 }  // namespace kernels
 
 }  // namespace dpsvm

@@ -9,6 +9,9 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <set>
+#include <string>
+
 #include "dpsvm/comm.hpp"
 #include "dpsvm/common.hpp"
 #include "dpsvm/device_state.hpp"
@@ -1062,6 +1065,109 @@ PYBIND11_MODULE(_C, m) {
         py::arg("p_round"), py::arg("C"), py::arg("clip"), py::arg("eps"), py::arg("rel"), py::arg("eps_floor"),
         py::arg("tau"), py::arg("b_hi"), py::arg("b_lo"), py::arg("inner_max"), py::arg("iter0"), py::arg("max_iter"),
         py::arg("wss"), py::arg("row_C") = py::none(), py::arg("diag") = false);
+  m.def("k_ws_solve_direct", [](const F32& gram, int64_t n, int64_t ldg, const F32& f, const F32& alpha, const F32& y,
+                                const I32& idx, const I32& qb, int q_max, int blocks, int p_round, float C, int clip,
+                                float eps, float rel, float eps_floor, float tau, float b_hi, float b_lo,
+                                int inner_max, int64_t iter0, int64_t max_iter, int wss, py::object row_C) {
+    const auto r = kernels::ws_solve_direct_probe(from_np(gram), n, ldg, from_np(f), from_np(alpha), from_np(y),
+                                                  from_np(idx), from_np(qb), q_max, blocks, p_round, C, clip, eps, rel,
+                                                  eps_floor, tau, b_hi, b_lo, inner_max, iter0, max_iter, wss,
+                                                  from_np_or_none<float>(row_C));
+    py::dict d;
+    d["alpha"] = to_np(r.alpha);
+    d["steps"] = r.steps;
+    d["apply_idx"] = r.apply_idx;
+    d["apply_coef"] = to_np(r.apply_coef);
+    d["nab"] = r.nab;
+    d["iter"] = r.iter;
+    d["outer"] = r.outer;
+    d["done"] = r.done;
+    d["p_act"] = r.p_act;
+    d["p1_round"] = r.p1_round;
+    return d;
+  }, py::arg("gram"), py::arg("n"), py::arg("ldg"), py::arg("f"), py::arg("alpha"), py::arg("y"), py::arg("idx"),
+        py::arg("qb"), py::arg("q_max"), py::arg("blocks"), py::arg("p_round"), py::arg("C"), py::arg("clip"),
+        py::arg("eps"), py::arg("rel"), py::arg("eps_floor"), py::arg("tau"), py::arg("b_hi"), py::arg("b_lo"),
+        py::arg("inner_max"), py::arg("iter0"), py::arg("max_iter"), py::arg("wss"), py::arg("row_C") = py::none());
+  // one stage of a sharded round, once per rank (kernel_probes.hpp WsShardIn: `state` holds its fields by name,
+  // arrays as numpy arrays; a field left out keeps its default)
+  m.def("k_ws_shard_round", [](int stage, int64_t n, int world, int exchange, const py::dict& state) {
+    kernels::WsShardIn in;
+    in.n = n;
+    in.world = world;
+    in.exchange = exchange;
+    auto num = [&](const char* k, auto& v) {
+      if (state.contains(k)) v = state[k].cast<std::decay_t<decltype(v)>>();
+    };
+    auto arr = [&](const char* k, auto& v) {
+      using T = typename std::decay_t<decltype(v)>::value_type;
+      if (state.contains(k) && !state[k].is_none()) v = from_np(state[k].cast<Arr<T>>());
+    };
+    num("L", in.L), num("ldg_extra", in.ldg_extra), num("cache", in.cache), num("blocks", in.blocks);
+    num("q_max", in.q_max), num("p_round", in.p_round), num("p_act", in.p_act), num("ks", in.ks);
+    num("ncand", in.ncand), num("outer", in.outer), num("xtimeout_ticks", in.xtimeout_ticks), num("C", in.C);
+    num("n_new", in.n_new), num("eps", in.eps), num("iter", in.iter), num("max_iter", in.max_iter);
+    num("clip", in.clip), num("inner_max", in.inner_max), num("wss", in.wss), num("rel", in.rel);
+    num("eps_floor", in.eps_floor), num("tau", in.tau), num("b_hi", in.b_hi), num("b_lo", in.b_lo);
+    arr("gram", in.gram), arr("f", in.f), arr("alpha", in.alpha), arr("y", in.y), arr("dalpha", in.dalpha);
+    arr("row_C", in.row_C), arr("apply_idx", in.apply_idx), arr("apply_line", in.apply_line), arr("nab", in.nab);
+    arr("apply_coef", in.apply_coef), arr("part", in.part), arr("dfs", in.dfs), arr("cand", in.cand);
+    arr("prev_set", in.prev_set), arr("idx", in.idx), arr("line", in.line), arr("qb", in.qb);
+    const std::set<std::string> known = {
+        "L", "ldg_extra", "cache", "blocks", "q_max", "p_round", "p_act", "ks", "ncand", "outer", "xtimeout_ticks", "C",
+        "n_new", "eps", "iter", "max_iter", "clip", "inner_max", "wss", "rel", "eps_floor", "tau", "b_hi", "b_lo",
+        "gram", "f", "alpha", "y", "dalpha", "row_C", "apply_idx", "apply_line", "nab", "apply_coef", "part", "dfs",
+        "cand", "prev_set", "idx", "line", "qb"};
+    for (auto kv : state)
+      if (!known.count(kv.first.cast<std::string>()))
+        throw py::value_error("k_ws_shard_round: unknown field " + kv.first.cast<std::string>());
+    const auto r = kernels::ws_shard_round_probe((kernels::WsShardStage)stage, in);
+    py::dict d;
+    d["G"] = r.G;
+    d["rpt"] = r.rpt;
+    d["p1G"] = r.p1G;
+    d["uncached"] = r.uncached;
+    d["xch_words"] = r.xch_words;
+    py::list ranks;
+    for (const auto& k : r.ranks) {
+      py::dict e;
+      e["off"] = k.off;
+      e["nl"] = k.nl;
+      e["ldg"] = k.ldg;
+      e["f"] = to_np(k.f);
+      e["alpha"] = to_np(k.alpha);
+      e["dalpha"] = to_np(k.dalpha);
+      e["dfs"] = to_np(k.dfs);
+      e["part"] = py::array_t<double>((py::ssize_t)k.part.size(), k.part.data());
+      e["cand_out"] = py::array_t<uint64_t>((py::ssize_t)k.cand_out.size(), k.cand_out.data());
+      e["cand"] = py::array_t<uint64_t>((py::ssize_t)k.cand.size(), k.cand.data());
+      e["t"] = k.t;
+      e["b_hi"] = k.b_hi;
+      e["b_lo"] = k.b_lo;
+      e["p_act"] = k.p_act;
+      e["n_damped"] = k.n_damped;
+      e["nonfinite"] = k.nonfinite;
+      e["done"] = k.done;
+      e["n_apply"] = k.n_apply;
+      e["q"] = k.q;
+      e["p1_round"] = k.p1_round;
+      e["iter"] = k.iter;
+      e["outer"] = k.outer;
+      e["idx"] = k.idx;
+      e["line"] = k.line;
+      e["subg"] = to_np(k.subg);
+      e["aux"] = to_np(k.aux);
+      e["steps"] = k.steps;
+      e["apply_idx"] = k.apply_idx;
+      e["apply_coef"] = to_np(k.apply_coef);
+      e["nab"] = k.nab;
+      ranks.append(e);
+    }
+    d["ranks"] = ranks;
+    return d;
+  }, py::arg("stage"), py::arg("n"), py::arg("world"), py::arg("exchange"), py::arg("state"));
+  m.attr("kWsProbePart") = kernels::kWsProbePart;
+  m.attr("kWsProbeXTimeout") = kernels::kWsProbeXTimeout;
   m.def("k_gram_rows_dot", [](const F32& Kt, int64_t nt, int64_t ld, int64_t n, const F32& coef, int64_t ldc, int k,
                               const F32& b, int reps) {
     kernels::GramDotProbe r;

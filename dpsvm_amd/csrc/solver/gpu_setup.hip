@@ -1043,16 +1043,7 @@ void alloc_round_buffers(GpuSolver::Impl& m, const SetupState& s) {
   if (m.xch) {
     w.xpeer = m.xpeer_d;
     w.xrank = m.rank;
-    if (w.blocks > 1) {  // ws_xch_words_multi: candidates (kWsCand keys a side), partials, sub-Gram rows
-      w.xcw = 4 * kWsCand;
-      w.xpart = ws_xch_cand_words_multi(w.G_all);
-      w.xsub = w.xpart + ws_xch_part_words((int64_t)w.world * w.p1G, w.ks);
-      w.xsub_rows = (int64_t)w.blocks * w.q_max;  // the one-block view: its own q_max (gpu_engines.hip)
-    } else {  // ws_xch_words
-      w.xcw = 4 * kWsCand1;
-      w.xsub = 2 * (int64_t)w.G_all * 4 * kWsCand1;
-      w.xsub_rows = w.q_max;
-    }
+    ws_xch_set_layout(w, ws_q);  // the region itself: setup_exchange, sized by the plan (ws_plan.hpp)
     w.xtimeout_ticks = (int64_t)(std::max(1e-6, m.p.xch_timeout_s) * 1e8);
   }
   if (w.cache && !m.replicated) {

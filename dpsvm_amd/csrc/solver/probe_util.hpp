@@ -47,12 +47,36 @@ class Arena {
     HIP_CHECK(hipMemsetAsync(d, 0, count * sizeof(T), s));
     return d;
   }
+  // max(count, 1) zeroed elements of a peer-exchange receive buffer, allocated as GpuSolver::Impl::setup_exchange
+  // allocates one: uncached device memory, plain device memory where that is refused (*uncached says which)
+  template <class T>
+  T* alloc_receive(size_t count, bool* uncached) {
+    count = std::max<size_t>(count, 1);
+    void* d = nullptr;
+    bufs_.push_back(nullptr);
+    *uncached = hipExtMallocWithFlags(&d, count * sizeof(T), hipDeviceMallocUncached) == hipSuccess;
+    if (!*uncached) {
+      (void)hipGetLastError();
+      HIP_CHECK(hipMalloc(&d, count * sizeof(T)));
+    }
+    bufs_.back() = d;
+    HIP_CHECK(hipMemset(d, 0, count * sizeof(T)));
+    HIP_CHECK(hipDeviceSynchronize());
+    return (T*)d;
+  }
   // count elements: the first min(n, count) of h, zeros behind them.  The copy has left the (pageable) host
   // memory when up returns — it synchronises the stream — so h may be a temporary.
+  // No byte is written twice: the zero fill covers only what lies behind the copy.
   template <class T>
   T* up(const T* h, size_t n, size_t count) {
-    T* d = alloc<T>(count);
-    if (n) HIP_CHECK(hipMemcpyAsync(d, h, std::min(n, count) * sizeof(T), hipMemcpyHostToDevice, s));
+    count = std::max<size_t>(count, 1);
+    n = std::min(n, count);
+    size_t tb = 0;
+    bufs_.push_back(nullptr);
+    T* d = gpu::dmalloc<T>(count, &tb);
+    bufs_.back() = d;
+    if (n < count) HIP_CHECK(hipMemsetAsync(d + n, 0, (count - n) * sizeof(T), s));
+    if (n) HIP_CHECK(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));
     return d;
   }

@@ -24,6 +24,11 @@
 //   ws_merge_multi_cache_probe  ws_rank_merge with WsArgs::cache: the multi-block merge and the line plan of its
 //                           union; with lines, ws_gather_multi reading WsCtrl::line
 //   ws_pack_rows_probe      ws_pack_rows: the misses' X rows packed for a partitioned X
+//   ws_solve_direct_probe   ws_solve with WsArgs::direct_sub: the blocks' sub-Grams straight from the resident Gram
+//                           (tests/test_ws_direct_kernels_gpu.py)
+//   ws_shard_round_probe    one stage of a round once per rank of a sharded run (off / nl of shard_of, own control
+//                           record, f shard and Gram panel), in the collectives or the peer-exchange form
+//                           (tests/test_ws_shard_kernels_gpu.py)
 // (tests/test_ws_kernels_gpu.py the first three, tests/test_ws_recompute_kernels_gpu.py the next three,
 // tests/test_ws_cache_kernels_gpu.py the last three and kernel_entry.hip's rbf_rows_miss.)  A
 // probe checks its arguments before it launches: a malformed call raises.
@@ -294,6 +299,50 @@ WsPackRowsProbe ws_pack_rows_probe(const std::vector<float>& x, int64_t nl, int 
   return r;
 }
 
+namespace {
+
+// the sub-problem's parameters in a launch's arguments
+void set_solve_args(WsArgs& a, int blocks, int q_max, float C, int clip, float eps, float rel, float eps_floor,
+                    float tau, int inner_max, int64_t max_iter, int wss) {
+  a.blocks = blocks;
+  a.q_max = q_max;
+  a.inner_max = inner_max;
+  a.rel_local = rel;
+  a.eps_floor = eps_floor;
+  a.C = C;
+  a.eps = eps;
+  a.tau = tau;
+  a.clip = clip;
+  a.max_iter = max_iter;
+  a.wss = wss;
+}
+
+// what one ws_solve launch left in the control record (alpha: the caller's)
+WsSolveProbe solve_result(const WsCtrl& o, int blocks, int q_max, int64_t iter0) {
+  WsSolveProbe r;
+  r.iter = o.iter;
+  r.outer = o.outer;
+  r.done = o.done;
+  r.p_act = o.p_act;
+  r.p1_round = o.p1_round;
+  if (blocks == 1) {
+    r.steps = {(int32_t)(o.iter - iter0)};
+    r.nab = {o.n_apply};
+    r.apply_idx.assign(o.apply_idx, o.apply_idx + o.n_apply);
+    r.apply_coef.assign(o.apply_coef, o.apply_coef + o.n_apply);
+  } else {
+    for (int p = 0; p < blocks; ++p) {
+      r.steps.push_back(o.inb[p]);
+      r.nab.push_back(o.nab[p]);
+      r.apply_idx.insert(r.apply_idx.end(), o.apply_idx + p * q_max, o.apply_idx + p * q_max + o.nab[p]);
+      r.apply_coef.insert(r.apply_coef.end(), o.apply_coef + p * q_max, o.apply_coef + p * q_max + o.nab[p]);
+    }
+  }
+  return r;
+}
+
+}  // namespace
+
 WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float>& f, const std::vector<float>& alpha,
                             const std::vector<float>& y, const std::vector<int32_t>& qb, int q_max, int blocks,
                             int p_round, float C, int clip, float eps, float rel, float eps_floor, float tau,
@@ -306,6 +355,7 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
               "ws_solve_probe: nu_cls is +1 / -1 and runs one block with box clipping and the scalar C");
   DPSVM_CHECK(blocks >= 1 && blocks <= kWsMaxBlocks && (int)qb.size() == blocks && q_max >= 2 && q_max <= kWsMax,
               "ws_solve_probe: 1 <= blocks <= 128, qb per block, q_max <= 192");
+  DPSVM_CHECK((int64_t)blocks * q_max <= kWsMaxAll, "ws_solve_probe: blocks x q_max <= 6144 (the control record's rows)");
   const size_t nq = (size_t)blocks * q_max;
   DPSVM_CHECK(K.size() == nq * q_max && f.size() == nq && alpha.size() == nq && y.size() == nq,
               "ws_solve_probe: K [P][q_max][q_max], f / alpha / y [P][q_max]");
@@ -344,43 +394,71 @@ WsSolveProbe ws_solve_probe(const std::vector<float>& K, const std::vector<float
   a.aux_stride = stride;
   a.alpha = st.up(alpha, nq);
   a.dalpha = st.alloc<float>(nq);
-  a.blocks = blocks;
-  a.q_max = q_max;
-  a.inner_max = inner_max;
-  a.rel_local = rel;
-  a.eps_floor = eps_floor;
-  a.C = C;
-  a.eps = eps;
-  a.tau = tau;
-  a.clip = clip;
-  a.max_iter = max_iter;
-  a.wss = wss;
+  set_solve_args(a, blocks, q_max, C, clip, eps, rel, eps_floor, tau, inner_max, max_iter, wss);
   if (!row_C.empty()) a.c_row = st.up(row_C, nq);  // row a of block p is global row p q_max + a
   a.diag = diag ? 1 : 0;
   a.nu_mode = nu_cls != 0 ? 1 : 0;
   a.ctrl = dc;
   launch::ws_solve(a, st.s);
-  const WsCtrl o = st.down(dc, 1)[0];
-  WsSolveProbe r;
+  WsSolveProbe r = solve_result(st.down(dc, 1)[0], blocks, q_max, iter0);
   r.alpha = st.down(a.alpha, nq);
-  r.iter = o.iter;
-  r.outer = o.outer;
-  r.done = o.done;
-  r.p_act = o.p_act;
-  r.p1_round = o.p1_round;
-  if (blocks == 1) {
-    r.steps = {(int32_t)(o.iter - iter0)};
-    r.nab = {o.n_apply};
-    r.apply_idx.assign(o.apply_idx, o.apply_idx + o.n_apply);
-    r.apply_coef.assign(o.apply_coef, o.apply_coef + o.n_apply);
-  } else {
-    for (int p = 0; p < blocks; ++p) {
-      r.steps.push_back(o.inb[p]);
-      r.nab.push_back(o.nab[p]);
-      r.apply_idx.insert(r.apply_idx.end(), o.apply_idx + p * q_max, o.apply_idx + p * q_max + o.nab[p]);
-      r.apply_coef.insert(r.apply_coef.end(), o.apply_coef + p * q_max, o.apply_coef + p * q_max + o.nab[p]);
+  return r;
+}
+
+WsSolveProbe ws_solve_direct_probe(const std::vector<float>& gram, int64_t n, int64_t ldg,
+                                   const std::vector<float>& f, const std::vector<float>& alpha,
+                                   const std::vector<float>& y, const std::vector<int32_t>& idx,
+                                   const std::vector<int32_t>& qb, int q_max, int blocks, int p_round, float C,
+                                   int clip, float eps, float rel, float eps_floor, float tau, float b_hi, float b_lo,
+                                   int inner_max, int64_t iter0, int64_t max_iter, int wss,
+                                   const std::vector<float>& row_C) {
+  DPSVM_CHECK(blocks >= 1 && blocks <= kWsMaxBlocks && (int)qb.size() == blocks && q_max >= 2 && q_max <= 64,
+              "ws_solve_direct_probe: 1 <= blocks <= 128, qb per block, 2 <= q_max <= 64");
+  DPSVM_CHECK(n >= 1 && n < ((int64_t)1 << 31) && ldg >= n && (int64_t)gram.size() == n * ldg,
+              "ws_solve_direct_probe: gram [n][ldg >= n]");
+  DPSVM_CHECK((int64_t)f.size() == n && (int64_t)alpha.size() == n && (int64_t)y.size() == n,
+              "ws_solve_direct_probe: f / alpha / y of n rows");
+  DPSVM_CHECK(row_C.empty() || (int64_t)row_C.size() == n, "ws_solve_direct_probe: row_C of n rows or empty");
+  DPSVM_CHECK((int64_t)blocks * q_max <= kWsMaxAll,
+              "ws_solve_direct_probe: blocks x q_max <= 6144 (the control record's rows)");
+  DPSVM_CHECK(idx.size() == (size_t)blocks * q_max, "ws_solve_direct_probe: idx [P][q_max]");
+  DPSVM_CHECK(blocks > 1 || p_round == 1, "ws_solve_direct_probe: one block means p_round 1");
+  std::vector<char> seen((size_t)n, 0);
+  for (int p = 0; p < blocks; ++p) {
+    DPSVM_CHECK(qb[p] >= 0 && qb[p] <= q_max, "ws_solve_direct_probe: qb[p] <= q_max");
+    for (int k = 0; k < q_max; ++k) {
+      const int64_t r = idx[(size_t)p * q_max + k];
+      DPSVM_CHECK(r >= -1 && r < n && (k >= qb[p] || r >= 0), "ws_solve_direct_probe: row out of range");
+      if (k < qb[p]) {  // two blocks committing one row's alpha would race
+        DPSVM_CHECK(!seen[r], "ws_solve_direct_probe: a row listed twice in the blocks");
+        seen[r] = 1;
+      }
     }
   }
+  Arena st;
+  auto c = blank_ctrl();
+  c->iter = iter0;
+  c->b_hi = b_hi;
+  c->b_lo = b_lo;
+  c->q[0] = qb[0];
+  c->p_round = c->p_act = p_round;
+  for (int p = 0; p < blocks; ++p) c->qb[0][p] = qb[p];
+  for (size_t i = 0; i < idx.size(); ++i) c->idx[0][i] = c->line[0][i] = idx[i];
+  WsArgs a = single_rank_args(n);
+  a.ctrl = st.up_one(*c);
+  a.gram = st.up(gram, gram.size());
+  a.ldg = ldg;
+  a.f = st.up(f, (size_t)n);
+  a.alpha = st.up(alpha, (size_t)n);
+  a.y = st.up(y, (size_t)n);
+  a.dalpha = st.alloc<float>((size_t)n);
+  if (!row_C.empty()) a.c_row = st.up(row_C, (size_t)n);
+  a.direct_sub = 1;  // subg / aux stay null: the branch must not read them
+  a.aux_stride = blocks * kWsMax;
+  set_solve_args(a, blocks, q_max, C, clip, eps, rel, eps_floor, tau, inner_max, max_iter, wss);
+  launch::ws_solve(a, st.s);
+  WsSolveProbe r = solve_result(st.down(a.ctrl, 1)[0], blocks, q_max, iter0);
+  r.alpha = st.down(a.alpha, (size_t)n);
   return r;
 }
 
@@ -726,6 +804,269 @@ WsFupdateProbe ws_fupdate_split_probe(const std::vector<float>& x, int64_t n, in
   r.G = G;
   r.rpt = rpt;
   return r;
+}
+
+namespace {
+
+// every argument of a sharded stage that an address is computed from, before any HIP call
+void check_shard_in(WsShardStage stage, const WsShardIn& in, int32_t G, int32_t rpt) {
+  const int64_t n = in.n;
+  const int W = in.world, P = in.blocks;
+  const bool sel = stage == WsShardStage::Select, p1 = stage == WsShardStage::Pass1, p2 = stage == WsShardStage::Pass2;
+  const bool g1 = stage == WsShardStage::Gather, gm = stage == WsShardStage::GatherMulti;
+  const bool gl = stage == WsShardStage::GatherLines;
+  DPSVM_CHECK(sel || p1 || p2 || g1 || gm || gl, "ws_shard_round_probe: stage is a WsShardStage");
+  // 32 ranks: pass 1 pushes its partials from lanes 2 p, 2 p + 1 < 64
+  DPSVM_CHECK(W >= 1 && W <= 32 && n >= W && n < ((int64_t)1 << 31),
+              "ws_shard_round_probe: 1 <= world <= 32 ranks of at least one row each");
+  DPSVM_CHECK(in.exchange == 0 || in.exchange == 1, "ws_shard_round_probe: exchange is 0 (collectives) or 1 (peer)");
+  DPSVM_CHECK(in.exchange == 0 || (in.xtimeout_ticks >= 1 && in.xtimeout_ticks <= kWsProbeXTimeout),
+              "ws_shard_round_probe: xtimeout_ticks in [1, 10^7] (0.1 s): a probe never waits longer");
+  DPSVM_CHECK(rpt <= kWsMaxRPT && (int64_t)G * W <= (int64_t)kWsMaxGroups * kWsListsPerThread,
+              "ws_shard_round_probe: too many rows");
+  DPSVM_CHECK(in.L >= 1 && in.L < ((int64_t)1 << 31) && (int64_t)in.gram.size() == in.L * n,
+              "ws_shard_round_probe: gram [L][n]");
+  DPSVM_CHECK(in.ldg_extra >= 0 && in.ldg_extra % 4 == 0, "ws_shard_round_probe: ldg_extra a multiple of 4");
+  DPSVM_CHECK((int64_t)in.f.size() == n && (int64_t)in.alpha.size() == n && (int64_t)in.y.size() == n &&
+                  (int64_t)in.dalpha.size() == n,
+              "ws_shard_round_probe: f / alpha / y / dalpha of n rows");
+  DPSVM_CHECK(in.row_C.empty() || (int64_t)in.row_C.size() == n, "ws_shard_round_probe: row_C of n rows or empty");
+  DPSVM_CHECK((sel || g1 || gl) ? P == 1 : (P >= 2 && P <= kWsMaxBlocks),
+              "ws_shard_round_probe: Select / Gather / GatherLines run one block, Pass1 / Pass2 / GatherMulti 2 .. 128");
+  DPSVM_CHECK(in.q_max >= 2 && in.q_max <= kWsMax && (int64_t)P * in.q_max <= kWsMaxAll,
+              "ws_shard_round_probe: 2 <= q_max <= 192, blocks x q_max <= 6144");
+  DPSVM_CHECK(in.cache == 0 || in.cache == 1, "ws_shard_round_probe: cache is 0 / 1");
+  DPSVM_CHECK(gl ? in.cache == 1 : (gm || in.cache == 0),
+              "ws_shard_round_probe: GatherLines is the cache form, only GatherMulti has both");
+  DPSVM_CHECK(!(g1 || gm || gl) || in.cache == 1 || in.L == n, "ws_shard_round_probe: a dense gather reads gram [n][n]");
+  DPSVM_CHECK(in.outer >= 0 && in.ks >= 1 && in.ks <= kWsMaxPass1Splits && in.ncand >= 0,
+              "ws_shard_round_probe: outer >= 0, 1 <= ks <= 16, ncand >= 0");
+  DPSVM_CHECK(in.p_round >= 1 && in.p_round <= P && in.p_act >= 1 && in.p_act <= P,
+              "ws_shard_round_probe: p_round / p_act in [1, blocks]");
+  if (sel || p1 || p2) {
+    DPSVM_CHECK((int)in.nab.size() == P, "ws_shard_round_probe: nab per block");
+    int64_t tot = 0;
+    for (int p = 0; p < P; ++p) {
+      DPSVM_CHECK(in.nab[p] >= 0 && in.nab[p] <= in.q_max, "ws_shard_round_probe: nab[p] <= q_max");
+      tot += in.nab[p];
+    }
+    DPSVM_CHECK(tot == (int64_t)in.apply_idx.size() && tot == (int64_t)in.apply_line.size() &&
+                    tot == (int64_t)in.apply_coef.size(),
+                "ws_shard_round_probe: sum(nab) apply rows, lines and coefficients");
+    for (int32_t l : in.apply_line) DPSVM_CHECK(l >= 0 && l < in.L, "ws_shard_round_probe: apply line out of range");
+    for (int32_t i : in.apply_idx) DPSVM_CHECK(i >= 0 && i < n, "ws_shard_round_probe: apply row out of range");
+  }
+  if (p2) {
+    const int64_t nl_max = (n + W - 1) / W;
+    DPSVM_CHECK((int64_t)in.part.size() == (int64_t)2 * W * ws_pass1_v4_groups(nl_max) * in.ks,
+                "ws_shard_round_probe: part [world p1G][ks][2]");
+    DPSVM_CHECK((int64_t)in.dfs.size() == in.ks * n, "ws_shard_round_probe: dfs [ks][n]");
+  }
+  if (g1) {
+    DPSVM_CHECK((int64_t)in.cand.size() == (int64_t)W * G * 2 * kWsCand,
+                "ws_shard_round_probe: cand [world G][2][kWsCand = 16]");
+    check_merge_state(n, in.cand, in.prev_set, in.f, in.alpha, in.y, in.q_max, in.n_new, 0);
+  }
+  if (gm || gl) {
+    DPSVM_CHECK((int)in.qb.size() == P && in.idx.size() == (size_t)P * in.q_max && in.line.size() == in.idx.size(),
+                "ws_shard_round_probe: qb per block, idx / line [blocks][q_max]");
+    std::vector<char> seen((size_t)n, 0);
+    for (int p = 0; p < P; ++p) {
+      DPSVM_CHECK(in.qb[p] >= 0 && in.qb[p] <= in.q_max, "ws_shard_round_probe: qb[p] <= q_max");
+      for (int k = 0; k < in.qb[p]; ++k) {
+        const int64_t r = in.idx[(size_t)p * in.q_max + k], l = in.line[(size_t)p * in.q_max + k];
+        DPSVM_CHECK(r >= 0 && r < n && l >= 0 && l < in.L, "ws_shard_round_probe: set row or line out of range");
+        DPSVM_CHECK(!seen[r], "ws_shard_round_probe: a row listed twice in the set");
+        seen[r] = 1;
+      }
+    }
+  }
+  if (in.exchange && (g1 || gm || gl))
+    DPSVM_CHECK(in.inner_max >= 0 && (in.clip == 0 || in.clip == 1) && (in.wss == 1 || in.wss == 2),
+                "ws_shard_round_probe: the peer form's solve: inner_max >= 0, clip 0 / 1, wss 1 / 2");
+}
+
+}  // namespace
+
+WsShardProbe ws_shard_round_probe(WsShardStage stage, const WsShardIn& in) {
+  const int64_t n = in.n;
+  const int W = in.world, P = in.blocks, q_max = in.q_max;
+  int32_t G = 0, rpt = 0;
+  const int64_t nl_max = W >= 1 ? (n + W - 1) / W : n;
+  launch::ws_geometry(nl_max, std::max(1, W), &G, &rpt);  // host arithmetic: as setup calls it
+  check_shard_in(stage, in, G, rpt);
+  const bool sel = stage == WsShardStage::Select, p1 = stage == WsShardStage::Pass1, p2 = stage == WsShardStage::Pass2;
+  const bool g1 = stage == WsShardStage::Gather, gm = stage == WsShardStage::GatherMulti;
+  const bool gather = !(sel || p1 || p2);
+  const int par = (int)(in.outer & 1), ks = in.ks;
+  const int p1G = P > 1 ? ws_pass1_v4_groups(nl_max) : G;
+  const size_t ncand = (size_t)W * G * 2 * kWsCand, npart = (size_t)2 * W * p1G * ks;
+  const size_t nsub = (size_t)P * q_max * q_max, naux = (size_t)3 * P * kWsMax;
+  const float nan = std::numeric_limits<float>::quiet_NaN();
+  Arena st;
+  WsShardProbe out;
+  out.G = G;
+  out.rpt = rpt;
+  out.p1G = p1G;
+  // the arguments every rank shares; the exchange region's layout from them
+  WsArgs base = single_rank_args(n);
+  base.world = W;
+  base.G = G;
+  base.rpt = rpt;
+  base.G_all = G * W;
+  base.ks = ks;
+  base.p1G = p1G;
+  base.ncand = in.ncand;
+  base.n_new = in.n_new;
+  base.cache = in.cache;
+  base.L = (int32_t)in.L;
+  base.aux_stride = P * kWsMax;
+  set_solve_args(base, P, q_max, in.C, in.clip, in.eps, in.rel, in.eps_floor, in.tau, in.inner_max, in.max_iter,
+                 in.wss);
+  if (in.exchange) {
+    out.xch_words = ws_xch_set_layout(base, q_max);
+    std::vector<uint64_t*> bufs((size_t)W);
+    bool uc = false;
+    for (int r = 0; r < W; ++r) bufs[r] = st.alloc_receive<uint64_t>((size_t)out.xch_words, &uc);
+    out.uncached = uc ? 1 : 0;
+    base.xpeer = st.up(bufs, (size_t)W);
+    base.xtimeout_ticks = in.xtimeout_ticks;
+  }
+  std::vector<WsArgs> args;
+  int64_t tot = 0;
+  for (int32_t v : in.nab) tot += v;
+  for (int r = 0; r < W; ++r) {
+    const Shard sh = shard_of(n, r, W);
+    WsArgs a = base;
+    a.nl = sh.size;
+    a.off = sh.offset;
+    a.rank = a.xrank = r;
+    // the panel: columns [off, off + nl) of every line, NaN behind them
+    a.ldg = (sh.size + 3) / 4 * 4 + in.ldg_extra;
+    std::vector<float> panel((size_t)in.L * a.ldg, nan);
+    for (int64_t l = 0; l < in.L; ++l)
+      std::copy(in.gram.begin() + l * n + sh.offset, in.gram.begin() + l * n + sh.offset + sh.size,
+                panel.begin() + l * a.ldg);
+    a.gram = st.up(panel, panel.size());
+    a.f = st.up(in.f.data() + sh.offset, (size_t)sh.size, (size_t)sh.size);
+    a.alpha = st.up(in.alpha, (size_t)n);
+    a.y = st.up(in.y, (size_t)n);
+    a.dalpha = st.up(in.dalpha, (size_t)n);
+    if (!in.row_C.empty()) a.c_row = st.up(in.row_C, (size_t)n);
+    uint64_t* cand = g1 ? st.up(in.cand, ncand) : st.up(std::vector<uint64_t>(ncand, kWsProbeKey), ncand);
+    a.cand = cand;
+    a.cand_out = cand + (size_t)r * G * 2 * kWsCand;
+    if (p2) {
+      std::vector<float> d((size_t)ks * sh.size);
+      for (int k = 0; k < ks; ++k)
+        std::copy(in.dfs.begin() + k * n + sh.offset, in.dfs.begin() + k * n + sh.offset + sh.size,
+                  d.begin() + k * sh.size);
+      a.dfs = st.up(d, d.size());
+      a.part = st.up(in.part, npart);
+    } else {
+      a.dfs = st.alloc<float>((size_t)ks * sh.size);
+      a.part = st.up(std::vector<double>(npart, kWsProbePart), npart);
+    }
+    if (gather) {
+      float* sub = st.up(std::vector<float>(nsub + naux, nan), nsub + naux);
+      a.subg = sub;
+      a.aux = sub + nsub;
+    }
+    auto c = blank_ctrl();
+    c->outer = in.outer;
+    c->iter = in.iter;
+    c->p_round = in.p_round;
+    c->p_act = in.p_act;
+    c->b_hi = in.b_hi;
+    c->b_lo = in.b_lo;
+    if (!gather) {
+      c->n_apply = (int32_t)tot;
+      int64_t at = 0;
+      for (int p = 0; p < P; ++p) {
+        c->nab[p] = in.nab[p];
+        const int b0 = P == 1 ? 0 : p * q_max;
+        for (int k = 0; k < in.nab[p]; ++k, ++at) {
+          c->apply_idx[b0 + k] = in.apply_idx[at];
+          c->apply_line[b0 + k] = in.apply_line[at];
+          c->apply_coef[b0 + k] = in.apply_coef[at];
+        }
+      }
+    } else if (g1) {  // as ws_gather_probe: the merge builds parity par from the previous set in the other
+      c->n_apply = kWsProbeApply;
+      c->q[par ^ 1] = (int32_t)in.prev_set.size();
+      for (size_t i = 0; i < in.prev_set.size(); ++i) c->idx[par ^ 1][i] = in.prev_set[i];
+      for (int i = 0; i < kWsMaxAll; ++i) c->idx[par][i] = -1;
+    } else {
+      int32_t q = 0;
+      for (int p = 0; p < P; ++p) {
+        c->qb[par][p] = in.qb[p];
+        q += in.qb[p];
+      }
+      c->q[par] = c->uq[par] = q;
+      for (size_t i = 0; i < in.idx.size(); ++i) {
+        c->idx[par][i] = in.idx[i];
+        c->line[par][i] = in.line[i];
+      }
+    }
+    a.ctrl = st.up_one(*c);
+    args.push_back(a);
+  }
+  // every rank's producer, then (peer form) every rank's consumer: a slot is full before anything polls it
+  for (const WsArgs& a : args) {
+    if (sel) launch::ws_select(a, st.s);
+    else if (p1 || p2) launch::ws_select_pass(a, p1 ? 1 : 2, st.s);
+    else launch::ws_gather(a, st.s);
+  }
+  if (in.exchange)
+    for (const WsArgs& a : args) {
+      if (sel || p2) launch::ws_xcollect_cand(a, st.s);
+      else if (p1) launch::ws_xcollect_part(a, st.s);
+      else launch::ws_solve(a, st.s);
+    }
+  for (const WsArgs& a : args) {
+    const WsCtrl o = st.down(a.ctrl, 1)[0];
+    WsShardRank r;
+    r.off = a.off;
+    r.nl = a.nl;
+    r.ldg = a.ldg;
+    r.f = st.down(a.f, (size_t)a.nl);
+    r.alpha = st.down(a.alpha, (size_t)n);
+    r.dalpha = st.down(a.dalpha, (size_t)n);
+    r.dfs = st.down(a.dfs, (size_t)ks * a.nl);
+    r.part = st.down(a.part, npart);
+    r.cand_out = st.down(a.cand_out, (size_t)G * 2 * kWsCand);
+    r.cand = st.down(a.cand, ncand);
+    r.t = o.t_last;
+    r.b_hi = o.b_hi;
+    r.b_lo = o.b_lo;
+    r.p_act = o.p_act;
+    r.n_damped = o.n_damped;
+    r.nonfinite = o.nonfinite;
+    r.done = o.done;
+    r.n_apply = o.n_apply;
+    r.p1_round = o.p1_round;
+    r.iter = o.iter;
+    r.outer = o.outer;
+    if (gather) {
+      r.q = o.q[par];
+      if (g1) {
+        const int q = std::max(0, std::min(r.q, (int)kWsMax));
+        r.idx.assign(o.idx[par], o.idx[par] + q);
+        r.line.assign(o.line[par], o.line[par] + q);
+      }
+      r.subg = st.down(a.subg, nsub);
+      r.aux = st.down(a.aux, naux);
+      if (in.exchange) {
+        const WsSolveProbe s = solve_result(o, P, q_max, in.iter);
+        r.steps = s.steps;
+        r.apply_idx = s.apply_idx;
+        r.apply_coef = s.apply_coef;
+        r.nab = s.nab;
+      }
+    }
+    out.ranks.push_back(std::move(r));
+  }
+  return out;
 }
 
 }  // namespace kernels

@@ -298,6 +298,79 @@ def ws_solve(K, f, alpha, y, qb, q_max: int, C_: float, clip: str = "independent
                              row_C=None if row_C is None else f32(row_C), diag=bool(diag))
 
 
+def ws_solve_direct(gram, f, alpha, y, idx, qb, q_max: int, C_: float, clip: str = "independent", eps: float = 1e-3,
+                    rel: float = 0.3, eps_floor: float = 3e-4, tau: float = 1e-12, b_hi: float = 0.0,
+                    b_lo: float = 0.0, inner_max: int = 768, p_round: int | None = None, iteration: int = 0,
+                    max_iter: int = 1 << 40, wss: int = 1, row_C=None) -> dict:
+    """One launch of ws_solve_kernel with WsArgs::direct_sub (the sub-Gram load of the 128 x 48 rounds): block p
+    solves the qb[p] first rows of ``idx`` [P][q_max] (global rows of ``gram`` [n][ldg >= n], distinct over the
+    blocks; the positions past qb[p] hold any row or -1), reading its sub-Gram's upper triangle straight from the
+    Gram and f / alpha / y / row_C by global row (all [n]); q_max <= 64.  The other arguments and the result are
+    ws_solve's, with ``alpha`` the global array after the solve and ``apply_idx`` global rows."""
+    import numpy as np
+
+    g = np.ascontiguousarray(np.asarray(gram, dtype=np.float32))
+    ix = np.ascontiguousarray(np.asarray(idx, dtype=np.int32)).reshape(-1)
+    P = len(qb)
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32)).reshape(-1)  # noqa: E731
+    return load().k_ws_solve_direct(g.reshape(-1), g.shape[0], g.shape[1], f32(f), f32(alpha), f32(y), ix,
+                                    np.asarray(qb, dtype=np.int32), int(q_max), P, P if p_round is None else p_round,
+                                    float(C_), 1 if clip == "box" else 0, float(eps), float(rel), float(eps_floor),
+                                    float(tau), float(b_hi), float(b_lo), int(inner_max), int(iteration),
+                                    int(max_iter), int(wss), row_C=None if row_C is None else f32(row_C))
+
+
+WS_SHARD_STAGES = {"select": 0, "pass1": 1, "pass2": 2, "gather": 3, "gather_multi": 4, "gather_lines": 5}
+_WS_SHARD_TYPES = {"gram": "f4", "f": "f4", "alpha": "f4", "y": "f4", "dalpha": "f4", "row_C": "f4", "apply_coef": "f4",
+                   "dfs": "f4", "part": "f8", "cand": "u8", "apply_idx": "i4", "apply_line": "i4", "nab": "i4",
+                   "prev_set": "i4", "idx": "i4", "line": "i4", "qb": "i4"}
+
+
+def ws_shard_round(stage: str, gram, f, alpha, y, world: int, exchange: str = "collectives", dalpha=None,
+                   **state) -> dict:
+    """One stage of a sharded working-set round, launched once per rank r < world on one stream: rank r runs with
+    off / nl = shard_of(n, r, world), the geometry of ws_geometry(ceil(n / world), world), its own control record,
+    f shard, copies of the global alpha / y / dalpha, and its panel of ``gram`` [L][n] — columns [off, off + nl) at
+    stride round_up(nl, 4) + ldg_extra, the padding NaN.  ``stage``: select (the one-pass kernel), pass1, pass2
+    (given ``part`` [world p1G][ks][2] and ``dfs`` [ks][n]), gather (ws_gather_kernel: ``cand`` [world G][2][16],
+    ``prev_set``), gather_multi (``idx`` / ``line`` [blocks][q_max], ``qb``; cache=1: the lines of ``line``),
+    gather_lines.  The selection stages take the round's changes as apply_idx / apply_line / apply_coef / nab.
+    ``exchange`` = "peer": world receive buffers in this process, every rank's producer first, then every rank's
+    consumer (ws_xcollect_cand after select / pass2, ws_xcollect_part after pass1, ws_solve after a gather, with
+    ws_solve's parameters C, clip, eps, rel, eps_floor, tau, b_hi, b_lo, inner_max, wss); xtimeout_ticks <= 10^7.
+    Further fields by name (kernel_probes.hpp WsShardIn): blocks, q_max, p_round, p_act, ks, ncand, outer, C,
+    row_C, n_new, eps, iter, max_iter, cache, ldg_extra.  Returns G, rpt, p1G, uncached, xch_words and ``ranks``: per
+    rank off, nl, f, alpha, dalpha, dfs [ks][nl], part, cand_out [G][2][16], cand [world G][2][16] (prefilled
+    kWsProbeKey), t, p_act, n_damped, p1_round, done, n_apply, and for the gathers q, idx, line, subg
+    [blocks][q_max][q_max], aux [3][blocks][192] (NaN before the launch) and, in the peer form, the solve's steps /
+    apply_idx / apply_coef / nab / iter / outer."""
+    import numpy as np
+
+    g = np.ascontiguousarray(np.asarray(gram, dtype=np.float32))
+    n = len(np.asarray(f).reshape(-1))
+    if g.ndim != 2 or g.shape[1] != n:
+        raise ValueError("gram must be (L, n)")
+    if exchange not in ("collectives", "peer"):
+        raise ValueError("exchange is 'collectives' or 'peer'")
+    st = dict(state, gram=g.reshape(-1), L=g.shape[0], f=f, alpha=alpha, y=y,
+              dalpha=np.zeros(n, np.float32) if dalpha is None else dalpha)
+    if "clip" in st and isinstance(st["clip"], str):
+        st["clip"] = 1 if st["clip"] == "box" else 0
+    for k, t in _WS_SHARD_TYPES.items():
+        if st.get(k) is not None:
+            st[k] = np.ascontiguousarray(np.asarray(st[k], dtype=t)).reshape(-1)
+    r = load().k_ws_shard_round(WS_SHARD_STAGES[stage], n, int(world), 1 if exchange == "peer" else 0, st)
+    blocks, q_max, G = int(st.get("blocks", 1)), int(st.get("q_max", 0)), r["G"]
+    for k in r["ranks"]:
+        k["cand_out"] = k["cand_out"].reshape(G, 2, WS_CAND)
+        k["cand"] = k["cand"].reshape(world * G, 2, WS_CAND)
+        k["dfs"] = k["dfs"].reshape(-1, k["nl"])
+        if len(k["subg"]):
+            k["subg"] = k["subg"].reshape(blocks, q_max, q_max)
+            k["aux"] = k["aux"].reshape(3, blocks, -1)
+    return r
+
+
 def gram_rows_dot(Kt, n: int, coef, b, reps: int = 0) -> dict:
     """Decisions from a rectangular Gram accumulated in fp64 and rounded once (gram_dot.hip):
     out[i, c] = float(sum_{j < n} Kt[i, j] coef[c, j] - b[c]) on ``Kt`` [nt][ld >= n] and ``coef`` [k][ldc >= n]

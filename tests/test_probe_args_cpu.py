@@ -42,8 +42,86 @@ def test_ws_solve(K):
     q = 4
     with pytest.raises(RuntimeError, match=r"qb\[p\] <= q_max"):
         K.ws_solve(np.eye(q), *state(q), [q + 1], q, 1.0)
+    with pytest.raises(RuntimeError, match="blocks x q_max <= 6144"):  # 128 x 64 rows overrun the control record
+        K.ws_solve(np.zeros((128, 64, 64), np.float32), *state(128 * 64), [2] * 128, 64, 1.0)
     with pytest.raises(RuntimeError, match="diag runs one block"):
         K.ws_solve(np.stack([np.eye(q)] * 2), *state(2 * q), [2, 2], q, 1.0, clip="box", diag=True)
+
+
+def test_ws_solve_direct(K):
+    n, q = 8, 4
+    gram = np.zeros((n, n), np.float32)
+    run = lambda idx, qb, q_max=q, g=gram: K.ws_solve_direct(g, *state(n), idx, qb, q_max, 1.0)  # noqa: E731
+    with pytest.raises(RuntimeError, match="2 <= q_max <= 64"):
+        run(np.zeros((1, 65), np.int32), [2], q_max=65)
+    with pytest.raises(RuntimeError, match=r"qb\[p\] <= q_max"):
+        run([[0, 1, 2, 3]], [q + 1])
+    with pytest.raises(RuntimeError, match="row out of range"):  # a row the load reads
+        run([[0, n, -1, -1]], [2])
+    with pytest.raises(RuntimeError, match="row out of range"):  # -1 inside the block's q rows
+        run([[0, -1, -1, -1]], [2])
+    with pytest.raises(RuntimeError, match="listed twice"):
+        run([[0, 1, -1, -1], [2, 1, -1, -1]], [2, 2])
+    with pytest.raises(RuntimeError, match=r"idx \[P\]\[q_max\]"):
+        run([[0, 1, 2]], [2])
+    with pytest.raises(RuntimeError, match="blocks x q_max <= 6144"):
+        run(np.zeros((128, 64), np.int32), [0] * 128, q_max=64)
+    with pytest.raises(RuntimeError, match=r"gram \[n\]\[ldg >= n\]"):
+        run([[0, 1, -1, -1]], [2], g=np.zeros((n, n - 1), np.float32))
+
+
+def shard(K, stage, n=8, W=2, exchange="collectives", **kw):
+    f, alpha, y = state(n)
+    args = dict(blocks=1, q_max=4, gram=np.zeros((n, n), np.float32))
+    args.update(kw)
+    return K.ws_shard_round(stage, args.pop("gram"), f, alpha, y, W, exchange=exchange, **args)
+
+
+def test_ws_shard_round(K, C):
+    apply = dict(apply_idx=[1], apply_line=[1], apply_coef=[0.5], nab=[1])
+    with pytest.raises(RuntimeError, match="1 <= world <= 32"):
+        shard(K, "select", W=33, n=40, **apply)
+    with pytest.raises(RuntimeError, match="at least one row each"):
+        shard(K, "select", W=9, **apply)
+    with pytest.raises(RuntimeError, match="apply line out of range"):
+        shard(K, "select", **dict(apply, apply_line=[8]))
+    with pytest.raises(RuntimeError, match="apply row out of range"):
+        shard(K, "select", **dict(apply, apply_idx=[8]))
+    with pytest.raises(RuntimeError, match="run one block"):
+        shard(K, "select", blocks=2, **dict(apply, nab=[1, 0]))
+    with pytest.raises(RuntimeError, match="run one block"):
+        shard(K, "pass1", **apply)
+    with pytest.raises(RuntimeError, match=r"nab\[p\] <= q_max"):
+        shard(K, "pass1", blocks=2, nab=[5, 0], apply_idx=[0] * 5, apply_line=[0] * 5, apply_coef=[0.5] * 5)
+    with pytest.raises(RuntimeError, match=r"part \[world p1G\]\[ks\]\[2\]"):
+        shard(K, "pass2", blocks=2, part=np.zeros(3), dfs=np.zeros(8), **dict(apply, nab=[1, 0]))
+    with pytest.raises(RuntimeError, match=r"dfs \[ks\]\[n\]"):
+        shard(K, "pass2", blocks=2, part=np.zeros(4), dfs=np.zeros(7), **dict(apply, nab=[1, 0]))
+    with pytest.raises(RuntimeError, match="ldg_extra a multiple of 4"):
+        shard(K, "select", ldg_extra=2, **apply)
+    with pytest.raises(RuntimeError, match=r"cand \[world G\]\[2\]"):
+        shard(K, "gather", cand=lists(C, 1), prev_set=[])
+    with pytest.raises(RuntimeError, match="candidate row out of range"):
+        shard(K, "gather", cand=lists(C, 2, rows=(0, 8)), prev_set=[])
+    sets = dict(idx=[[0, 1, -1, -1]], line=[[0, 1, -1, -1]], qb=[2], cache=1)
+    with pytest.raises(RuntimeError, match="set row or line out of range"):
+        shard(K, "gather_lines", **dict(sets, line=[[0, 8, -1, -1]]))
+    with pytest.raises(RuntimeError, match="set row or line out of range"):
+        shard(K, "gather_lines", **dict(sets, idx=[[0, -1, -1, -1]]))
+    with pytest.raises(RuntimeError, match="listed twice"):
+        shard(K, "gather_lines", **dict(sets, idx=[[1, 1, -1, -1]]))
+    with pytest.raises(RuntimeError, match="GatherLines is the cache form"):
+        shard(K, "gather_lines", **dict(sets, cache=0))
+    with pytest.raises(RuntimeError, match="a dense gather reads"):
+        shard(K, "gather_multi", blocks=2, gram=np.zeros((4, 8), np.float32), idx=np.zeros((2, 4)),
+              line=np.zeros((2, 4)), qb=[0, 0])
+    # the peer form never waits long: a poll bound above 0.1 s is refused, before any buffer is allocated
+    for ticks in (0, 10**7 + 1):
+        with pytest.raises(RuntimeError, match="xtimeout_ticks in"):
+            shard(K, "select", exchange="peer", xtimeout_ticks=ticks, **apply)
+    assert C.kWsProbeXTimeout == 10**7
+    with pytest.raises(ValueError, match="unknown field"):
+        shard(K, "select", q_maxx=4, **apply)
 
 
 def test_ws_select(K):
